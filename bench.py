@@ -7,8 +7,15 @@ exactly K timed steps between barrier + synchronize, MAX over ranks, rank 0 prin
 
 A "step" is one pass of the hot path over one batch of synthetic input: the K_layers-layer
 LightGCN message pass (normalised bipartite adjacency SpMM x embedding table, layer combine
-fused) over the whole graph — forward only for the headline `value`; fwd+bwd, InfoNCE and BPR
-rates are measured separately and reported under "extra".
+fused) over the whole graph — forward only for the headline `value`.
+
+A plain run does only what the headline line needs: build the workload, warm up, time the K steps
+and print the line (its `roofline` block comes from events around the timed launches).  `--full`
+adds everything else, each leg timed on its own: memory probes, the InfoNCE roofline, fwd+bwd,
+InfoNCE, BPR and training-step rates ("extra"), the CPU baseline, the cfg4 companion line, the
+community graphs, cfg5 and the GCL step (N > 1: the GCL step and the strong-scaling cfg4 line).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32; a
+fixed, seeded sample of the rows of a large output; see dump_outputs).
 
 Workloads:
   cfg2  U=1M  I=100K E=10M  (N=1.1M,  nnz=20M)   K=3 d=64   <- N=1 default (BASELINE configs[1])
@@ -260,6 +267,25 @@ def _event_ms(fn, reps, warm=1):
     return e0.elapsed_time(e1) / reps
 
 
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs in all
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every [rows, d] tensor of `arrays` (name -> tensor) as <outdir>/<name>.npy in float32.  The byte
+    budget is shared equally; a tensor over its share is cut to a sample of its rows drawn from SEED alone (sorted), so
+    runs with the same arguments dump the same rows and two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        row_bytes = 4 * (t.numel() // max(1, t.shape[0]))
+        if t.numel() * 4 > share:
+            keep = np.random.default_rng(SEED).choice(t.shape[0], share // row_bytes, replace=False)
+            t = t[torch.from_numpy(np.sort(keep)).to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
 def memory_probes(table, dev):
     """Measured ceilings of this box's memory system (gcr_probe_*): float4 copy / read over 1 GiB buffers
     (far past the 256 MiB Infinity Cache) and the 256-B row gather of the SpMM on `table` itself."""
@@ -317,7 +343,8 @@ def measure_propagation(ra, Fn, name, d, dev, steps, warmup):
     Fn.EVENT_SINK = events          # HIP events around every gcr_spmm_csr_f32 launch (same stream)
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        final = None        # only the last output is kept: each earlier one is released before the next step, as if discarded
+        final = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     Fn.EVENT_SINK = None
@@ -364,7 +391,7 @@ def measure_propagation(ra, Fn, name, d, dev, steps, warmup):
         roofline["traffic_source_digest"] = pmc["source_digest"]
     else:
         roofline["traffic_note"] = "no committed PMC capture matches these kernel sources (digest %s)" % spmm_source_digest()
-    res = {"name": name, "graph": graph, "x0": x0, "nnz": nnz, "n": n, "n_u": n_u, "n_i": n_i, "n_e": n_e,
+    res = {"name": name, "graph": graph, "x0": x0, "final": final, "nnz": nnz, "n": n, "n_u": n_u, "n_i": n_i, "n_e": n_e,
            "k_layers": k_layers, "elapsed": elapsed, "ms_per_step": 1e3 * elapsed / steps,
            "edges_per_s": nnz * k_layers * steps / elapsed, "roofline": roofline, "graph_build_s": round(t_build, 2)}
     return res
@@ -491,12 +518,19 @@ def main():
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = a cfg2-sized user block per rank; strong = the fixed workload graph over N ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps, also run every secondary leg (probes, rooflines, extra rates, CPU "
+                         "baseline, companion workloads); the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 48 MiB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-cfg4", action="store_true", help="skip the 10M x 1M / 100M-edge 1-GPU companion line")
     ap.add_argument("--gcl-full", action="store_true",
                     help="N > 1: run the GCL step leg on the benchmark graph itself (all-pairs user InfoNCE is O(U^2): minutes)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -527,10 +561,36 @@ def main():
     d = args.dim
     r = measure_propagation(ra, Fn, name, d, dev, args.steps, args.warmup)
     graph, x0, nnz, n, n_u, n_i, k_layers = r["graph"], r["x0"], r["nnz"], r["n"], r["n_u"], r["n_i"], r["k_layers"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"final_embeddings": r["final"]})
+    del r["final"]
     roofline = r["roofline"]
     extra = {"graph_build_s": r["graph_build_s"], "nnz": nnz, "n_nodes": n,
              "spmm_parts": graph.plan.n_parts, "spmm_split_rows": graph.plan.n_long}
-    # everything below is secondary: it must never cost the headline line
+    infonce_pairs_per_s = None
+    cpu = None
+    if args.full:
+        infonce_pairs_per_s, cpu = full_legs(args, ra, Fn, r, name, d, dev, roofline, extra)
+
+    line = {
+        "metric": "edges propagated/sec (LightGCN d=%d, %d-layer fwd message pass)" % (d, k_layers),
+        "value": r["edges_per_s"], "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic", "full": args.full,
+        "config": {"workload": f"{name}: LightGCN {k_layers}-layer d={d}, {n_u} users x {n_i} items / {r['n_e']} "
+                               f"interactions (nnz={nnz}), sym-normalised CSR, forward propagation + fused layer sum",
+                   "users": n_u, "items": n_i, "interactions": r["n_e"], "layers": k_layers, "dim": d},
+        "infonce_pairs_per_s": infonce_pairs_per_s,
+        "roofline": roofline, "roofline_infonce": roofline.get("infonce"), "cpu_baseline": cpu,
+        "dist_backend": None, "dist_world": 1, "extra": extra,
+    }
+    print(json.dumps(line))
+
+
+def full_legs(args, ra, Fn, r, name, d, dev, roofline, extra):
+    """--full on one GPU: every secondary leg after the headline steps, filling `roofline` and `extra` in place; returns
+    (InfoNCE pairs/s, CPU baseline).  Each leg is secondary: a failure is reported in the line, never costs it."""
+    graph, x0, nnz, n_u, n_i, k_layers = r["graph"], r["x0"], r["nnz"], r["n_u"], r["n_i"], r["k_layers"]
     try:
         roofline["probe"] = memory_probes(x0, dev)
     except Exception as e:      # noqa: BLE001
@@ -589,7 +649,7 @@ def main():
     # through the single-rank sharded path, and MHCN's 2-layer multi-channel pass forward and forward + backward
     if not args.no_extra and d == 64:
         try:
-            c5 = cfg5_measure(d, 5, 2, 0, 1, dev, ra)
+            c5, _ = cfg5_measure(d, 5, 2, 0, 1, dev, ra)
             extra["cfg5"] = {"workload": c5["config"]["workload"], "edges_per_s": c5["value"], "fwd_ms": c5["ms_per_step"],
                              "fwd_bwd_ms": c5["extra"]["fwd_bwd_ms"], "fwd_bwd_over_fwd": c5["extra"]["fwd_bwd_over_fwd"],
                              "frac_alg": c5["roofline"]["frac"]}
@@ -606,20 +666,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             extra["gcl_step"] = {"error": repr(e)[:300]}
         torch.cuda.empty_cache()
-
-    line = {
-        "metric": "edges propagated/sec (LightGCN d=%d, %d-layer fwd message pass)" % (d, k_layers),
-        "value": r["edges_per_s"], "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{name}: LightGCN {k_layers}-layer d={d}, {n_u} users x {n_i} items / {r['n_e']} "
-                               f"interactions (nnz={nnz}), sym-normalised CSR, forward propagation + fused layer sum",
-                   "users": n_u, "items": n_i, "interactions": r["n_e"], "layers": k_layers, "dim": d},
-        "infonce_pairs_per_s": infonce_pairs_per_s,
-        "roofline": roofline, "roofline_infonce": roofline.get("infonce"), "cpu_baseline": cpu,
-        "dist_backend": None, "dist_world": 1, "extra": extra,
-    }
-    print(json.dumps(line))
+    return infonce_pairs_per_s, cpu
 
 
 def _init_dist(dev):
@@ -636,7 +683,8 @@ def _init_dist(dev):
 
 
 def _timed_ranks(dist, dev, step, warmup, steps):
-    """W untimed + K timed steps between barrier + synchronize on both sides; MAX over ranks (seconds)."""
+    """W untimed + K timed steps between barrier + synchronize on both sides; (MAX over ranks in seconds, what the last
+    step returned)."""
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -644,13 +692,14 @@ def _timed_ranks(dist, dev, step, warmup, steps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        out = None          # only the last output is kept: each earlier one is released before the next step, as if discarded
+        out = step()
     torch.cuda.synchronize()
     dist.barrier()
     torch.cuda.synchronize()
     elapsed = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
     dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
-    return float(elapsed.item())
+    return float(elapsed.item()), out
 
 
 def build_sharded_bipartite(ra, gdist, dist, dev, rank, world, n_u_local, n_i, users, items):
@@ -730,7 +779,7 @@ def gcl_step_leg(ra, gdist, dist, dev, rank, world, d, full_graph=None):
         loss = ssl + sums[0] / bsz + 1e-4 * (sums[1] + sums[2] + sums[3]) / bsz
         loss.backward()
 
-    t = _timed_ranks(dist, dev, step, 1, 2)
+    t, _ = _timed_ranks(dist, dev, step, 1, 2)
     n_edges = torch.tensor([g.r_ui.nnz + g.r_iu.nnz], device=dev, dtype=torch.int64)
     dist.all_reduce(n_edges)
     u_tot, i_tot = n_u * world, g.items_padded
@@ -772,18 +821,21 @@ def main_sharded(args, rank, world, dev, ra):
             with torch.no_grad():
                 return gdist.sharded_propagate_raw(graph, x_u, x_i, WORKLOADS[wl_name]["layers"], 1.0)
 
-        elapsed = _timed_ranks(dist, dev, step, warmup, steps)
+        elapsed, final = _timed_ranks(dist, dev, step, warmup, steps)
         nnz_all = torch.tensor([nnz_local], device=dev, dtype=torch.int64)
         dist.all_reduce(nnz_all)
         return dict(users=users, items=items, graph=graph, n_u=n_u, n_u_total=n_u_total, n_i=n_i, n_e_total=n_e_total,
-                    nnz_all=int(nnz_all.item()), elapsed=elapsed, steps=steps)
+                    nnz_all=int(nnz_all.item()), elapsed=elapsed, steps=steps, final=final)
 
     leg = propagation_leg(name, args.scaling, args.steps, args.warmup)
     users, items, graph = leg["users"], leg["items"], leg["graph"]
     n_u, n_u_total, n_i, n_e_total, nnz_all, elapsed = (leg[k] for k in ("n_u", "n_u_total", "n_i", "n_e_total", "nnz_all",
                                                                          "elapsed"))
+    if args.dump_outputs and rank == 0:                           # rank 0's user block and item shard
+        dump_outputs(args.dump_outputs, {"user_embeddings": leg["final"][0], "item_embeddings": leg["final"][1]})
+    del leg["final"]
     gcl = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         try:
             full = (graph, users, items, k_layers) if args.gcl_full else None
             gcl = gcl_step_leg(ra, gdist, dist, dev, rank, world, d, full)
@@ -794,7 +846,7 @@ def main_sharded(args, rank, world, dev, ra):
     # to the weak-scaling headline whose N = 1 point is the single-GPU bench line
     cfg4_strong = None
     items_padded = graph.items_padded
-    if not (name == "cfg4" and args.scaling == "strong") and not args.no_cfg4 and d == 64:
+    if args.full and not (name == "cfg4" and args.scaling == "strong") and not args.no_cfg4 and d == 64:
         try:
             del users, items, graph
             leg.clear()
@@ -835,7 +887,7 @@ def main_sharded(args, rank, world, dev, ra):
                                        "no PMC capture exists for N > 1 (the 1-GPU line carries the counter-based fraction)",
                          "frac_alg": round(achieved / (HBM_PEAK_GBS * world), 4),
                          "collective_bytes_per_rank_per_layer": 2 * items_padded * d * 4 * (world - 1) // world},
-            "cpu_baseline": None, "dist_backend": dist.get_backend(), "dist_world": dist.get_world_size(),
+            "cpu_baseline": None, "dist_backend": dist.get_backend(), "dist_world": dist.get_world_size(), "full": args.full,
             "gcl_step": gcl, "cfg4_strong": cfg4_strong,
         }
         print(json.dumps(line))
@@ -846,20 +898,24 @@ CFG5 = dict(users=250_000, items=50_000, deg=(24, 16, 8), deg_r=10, layers=2)   
 
 
 def main_cfg5(args, rank, world, dev, ra):
-    line = cfg5_measure(args.dim, args.steps, args.warmup, rank, world, dev, ra)
+    line, final = cfg5_measure(args.dim, args.steps, args.warmup, rank, world, dev, ra, fwd_bwd=args.full)
     if rank == 0:
+        if args.dump_outputs:                                     # rank 0's outputs
+            dump_outputs(args.dump_outputs, {"user_embeddings": final[0], "item_embeddings": final[1]})
+        line["full"] = args.full
         print(json.dumps(line))
     import torch.distributed as dist
     if dist.is_initialized():
         dist.destroy_process_group()
 
 
-def cfg5_measure(d, steps, warmup, rank, world, dev, ra):
+def cfg5_measure(d, steps, warmup, rank, world, dev, ra, fwd_bwd=True):
     """BASELINE config 5: MHCN's layer loop (univariate/mhcn.py:422-466) with the three U x U channel operators
     row-sharded by user: per layer three all-gathers of [U, d] channel operands, each overlapped with the
     previous channel's dual-output SpMM on its own stream, plus the R^T / R item side (all-reduce of the partial
     item sums).  Synthetic operators: `deg` random columns per row and channel, row-normalised (the motif
-    adjacency of a real social graph comes from graph_ops.build_hyper_graphs)."""
+    adjacency of a real social graph comes from graph_ops.build_hyper_graphs).  fwd_bwd: also time forward + backward
+    (extra.fwd_bwd_ms).  Returns (rank 0's line or None, what the last timed forward returned)."""
     import torch.distributed as dist
     from recommendation_amd import distributed as gdist
     from recommendation_amd.mhcn import ShardedMHCNEncoder
@@ -893,9 +949,11 @@ def cfg5_measure(d, steps, warmup, rank, world, dev, ra):
         (fu.sum() + fi.sum() / world).backward()
         enc.allreduce_grads()
 
+    t_fb = None
     if world > 1:
-        elapsed = _timed_ranks(dist, dev, step, warmup, steps)
-        t_fb = _timed_ranks(dist, dev, step_fb, 1, 3) / 3
+        elapsed, final = _timed_ranks(dist, dev, step, warmup, steps)
+        if fwd_bwd:
+            t_fb = _timed_ranks(dist, dev, step_fb, 1, 3)[0] / 3
         nnz_all = torch.tensor([nnz_local], device=dev, dtype=torch.int64)
         dist.all_reduce(nnz_all)
         nnz_all = int(nnz_all.item())
@@ -905,16 +963,18 @@ def cfg5_measure(d, steps, warmup, rank, world, dev, ra):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            final = None    # only the last output is kept: each earlier one is released before the next step, as if discarded
+            final = step()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        step_fb()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(3):
+        if fwd_bwd:
             step_fb()
-        torch.cuda.synchronize()
-        t_fb = (time.perf_counter() - t0) / 3
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                step_fb()
+            torch.cuda.synchronize()
+            t_fb = (time.perf_counter() - t0) / 3
         nnz_all = nnz_local
     line = None
     if rank == 0:
@@ -936,9 +996,9 @@ def cfg5_measure(d, steps, warmup, rank, world, dev, ra):
                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
                          "frac": round(achieved / (HBM_PEAK_GBS * world), 4), "traffic": None},
             "cpu_baseline": None, "dist_backend": dist.get_backend() if dist.is_initialized() else None, "dist_world": world,
-            "extra": {"fwd_bwd_ms": 1e3 * t_fb, "fwd_bwd_over_fwd": round(t_fb * steps / elapsed, 3)},
+            "extra": {} if t_fb is None else {"fwd_bwd_ms": 1e3 * t_fb, "fwd_bwd_over_fwd": round(t_fb * steps / elapsed, 3)},
         }
-    return line
+    return line, final
 
 
 def bench_extra(ra, Fn, graph, x0, k_layers, nnz, dev, n_u, n_i):

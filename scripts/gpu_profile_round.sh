@@ -24,7 +24,7 @@ if [ "$WHAT" = "hbm" ] || [ "$WHAT" = "all" ]; then
       echo "pmc $wl $ro done"
     done
   done
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-extra > "$OUT/bench_kt.json" 2> "$OUT/bench_kt.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra > "$OUT/bench_kt.json" 2> "$OUT/bench_kt.err"
   echo "kernel trace bench done"
 fi
 if [ "$WHAT" = "nce" ] || [ "$WHAT" = "all" ]; then
@@ -41,7 +41,7 @@ if [ "$WHAT" = "nce" ] || [ "$WHAT" = "all" ]; then
   echo "bce pass done"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_kme" -- python3 "$R/profiles/kmeans_estep_probe.py" > "$OUT/kt_kme.log" 2>&1
   echo "k-means e_step pass done"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_cfg5" -- python3 "$R/bench.py" --workload cfg5 --steps 5 --warmup 2 > "$OUT/bench_cfg5_kt.json" 2> "$OUT/bench_cfg5_kt.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_cfg5" -- python3 "$R/bench.py" --full --workload cfg5 --steps 5 --warmup 2 > "$OUT/bench_cfg5_kt.json" 2> "$OUT/bench_cfg5_kt.err"
   echo "cfg5 pass done"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_gcl" -- python3 "$R/profiles/gcl_step_probe.py" > "$OUT/kt_gcl.log" 2>&1
   echo "gcl step pass done"
