@@ -3,7 +3,8 @@
   rank_topk            the U x I score matrix + masking + top-N of lightgcn.py:48-57, gcl.py:87-96,
                        ncl.py:253-264 on the GPU (gcr_score_rows_f32 + gcr_topk_masked_f32)
   test                 GraphRecommender.test  ncl.py:253-264  -> {user: [(item_name, score), ...]}
-  ranking_metrics      per-user hits / DCG / IDCG on the device (gcr_rank_metrics), means on the host
+  rank_metric_terms    per-user hits / DCG / IDCG on the device (gcr_rank_metrics)
+  ranking_metrics      ncl.py's metrics from those terms, means on the host
   ranking_evaluation   the reference's report lines (ncl.py:165-177) from {user: {item}} / {user: [(item, score)]}
 """
 from __future__ import annotations
@@ -88,14 +89,10 @@ def test(data, user_emb, item_emb, max_n):
             for k, u in enumerate(users)}
 
 
-def ranking_metrics(top_items, test_rowptr, test_items_sorted, cutoffs, n_test_total=None):
-    """Hit ratio / precision / recall / NDCG at every cut-off from the ranked lists, the per-user work on the
-    device (gcr_rank_metrics).  top_items int64 [Q, K] on the GPU (-1 = padding); (test_rowptr, test_items_sorted)
-    the CSR of each QUERY row's test items (ascending inside a row).  Users without a test item do not take part
-    (the reference only evaluates users of its test set).  Returns {n: {"Hit Ratio", "Precision", "Recall", "NDCG"}}
-    rounded to 5 decimals like the reference's report (ncl.py:133-177).
-    n_test_total: the Hit Ratio's denominator when it is not the query rows' own test items — `Metric.hit_ratio`
-    (ncl.py:143-145) divides by the test items of ALL users of `origin`, ranked or not."""
+def rank_metric_terms(top_items, test_rowptr, test_items_sorted, cutoffs):
+    """The per-user terms behind every metric definition, on the device (gcr_rank_metrics): returns (cut-offs int32 [C],
+    ascending; hits int32 [Q, C]; DCG float64 [Q, C]; IDCG float64 [Q, C]).  Row q counts the distinct test items of
+    query row q among its first n ranked items (-1 = padding) and sums 1 / log2(p + 2) over the hit positions p."""
     L = _lib.lib()
     dev = top_items.device
     q, k = top_items.shape
@@ -109,6 +106,19 @@ def ranking_metrics(top_items, test_rowptr, test_items_sorted, cutoffs, n_test_t
     _lib.check(L.gcr_rank_metrics(_lib.dptr(top_items.contiguous()), q, k, _lib.dptr(test_rowptr), _lib.dptr(test_items_sorted),
                                   _lib.dptr(cut), nc, _lib.dptr(hits), _lib.dptr(dcg), _lib.dptr(idcg), _lib.cur_stream(dev)),
                "gcr_rank_metrics")
+    return cut, hits, dcg, idcg
+
+
+def ranking_metrics(top_items, test_rowptr, test_items_sorted, cutoffs, n_test_total=None):
+    """Hit ratio / precision / recall / NDCG at every cut-off from the ranked lists, the per-user work on the
+    device (gcr_rank_metrics).  top_items int64 [Q, K] on the GPU (-1 = padding); (test_rowptr, test_items_sorted)
+    the CSR of each QUERY row's test items (ascending inside a row).  Users without a test item do not take part
+    (the reference only evaluates users of its test set).  Returns {n: {"Hit Ratio", "Precision", "Recall", "NDCG"}}
+    rounded to 5 decimals like the reference's report (ncl.py:133-177).
+    n_test_total: the Hit Ratio's denominator when it is not the query rows' own test items — `Metric.hit_ratio`
+    (ncl.py:143-145) divides by the test items of ALL users of `origin`, ranked or not."""
+    cut, hits, dcg, idcg = rank_metric_terms(top_items, test_rowptr, test_items_sorted, cutoffs)
+    test_rowptr = torch.as_tensor(test_rowptr, device=top_items.device, dtype=torch.int64)
     n_test = (test_rowptr[1:] - test_rowptr[:-1]).cpu().numpy().astype(np.float64)
     on = n_test > 0
     hits_h, dcg_h, idcg_h = hits.cpu().numpy()[on].astype(np.float64), dcg.cpu().numpy()[on], idcg.cpu().numpy()[on]
