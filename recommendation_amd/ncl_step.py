@@ -21,7 +21,11 @@ buffer or a separate add pass:
 
 Nothing in here synchronises with the host or depends on host-side values that change between steps, so the whole step
 can be captured in a hipGraph (`capture()`): batch indices live in static buffers, Adam's step count on the device.
-Checked against the autograd path by tests/test_ncl_step_gpu.py (same losses, same parameter update).
+Checked against the autograd path by tests/test_ncl_step_gpu.py (same losses, same parameter update), and, like the
+autograd path and the hipGraph replay, against ncl.py's own loop body run in float64 by tests/test_ncl_steps_gpu.py
+(tests/golden/ncl_steps.npz: six steps, three context-layer cases, every loss term and both final tables, also across a
+FusedAdam checkpoint).  The one deviation there is the e_step: fixed centroids instead of faiss k-means, each row still
+assigned to its nearest centroid of the current encoder output.
 """
 from __future__ import annotations
 

@@ -12,7 +12,9 @@ from . import _lib
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
         """capturable: keep the step count in device memory (gcr_adam_step_dev_f32), so that a step captured in a
-        hipGraph replays with the current bias corrections (torch.optim.Adam's flag of the same name)."""
+        hipGraph replays with the current bias corrections (torch.optim.Adam's flag of the same name).  A checkpoint
+        (`state_dict()` / `load_state_dict()`) resumes with either setting: the host count is synchronised on save and
+        the int64 device count rebuilt from it on load."""
         if lr < 0 or eps < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1) or weight_decay < 0:
             raise ValueError("invalid Adam hyper-parameters")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=bool(capturable)))
@@ -79,3 +81,23 @@ class FusedAdam(torch.optim.Optimizer):
     def state_dict(self):
         self.sync_step_counts()
         return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict, with the device step count rebuilt.  The base class casts every state
+        tensor but `step` to the parameter's dtype, which would turn a saved int64 `step_dev` into float32 (the kernel
+        reads 8 bytes of it).  So a capturable group gets a fresh int64 `step_dev` equal to the host `step` (which
+        `state_dict()` synchronised), on the parameter's device; a non-capturable group drops it, because a stale device
+        count would overwrite the host one at the next `state_dict()`.  Each group also keeps its own `capturable`
+        flag rather than the checkpoint's: the flag says how this optimiser runs (graph replay or not), not what it
+        computes, so a checkpoint resumes on either path."""
+        modes = [bool(g.get("capturable")) for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, capturable in zip(self.param_groups, modes):
+            group["capturable"] = capturable
+            for p in group["params"]:
+                st = self.state.get(p)
+                if not st:
+                    continue
+                st.pop("step_dev", None)
+                if capturable:
+                    st["step_dev"] = torch.full((1,), int(st["step"]), dtype=torch.int64, device=p.device)

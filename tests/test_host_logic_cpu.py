@@ -163,3 +163,54 @@ def test_encode_raw_ids_decides_from_the_whole_column():
     assert encode_raw_ids([1] * 100 + ["7"]) is None           # mixed after position 64: sorted() would raise
     assert encode_raw_ids(np.array([1, 2 ** 63 + 5], dtype=np.uint64)) is None
     assert encode_raw_ids([True, False]) is None
+
+
+def test_fused_adam_checkpoint_keeps_an_int64_device_step_count():
+    """FusedAdam(capturable=True) keeps Adam's step count in an int64 device tensor that gcr_adam_step_dev_f32 reads.
+    torch.optim.Optimizer.load_state_dict casts every state tensor but `step` to the parameter dtype, so without help
+    the count came back as float32 and the kernel read 8 bytes of a 4-byte value.  Round-trip state_dict() ->
+    torch.save / torch.load -> load_state_dict() in all three directions (state injected: no kernel runs)."""
+    import io
+    import torch
+    from recommendation_amd.optim import FusedAdam
+
+    def trained(capturable, steps):
+        p = torch.nn.Parameter(torch.zeros(4, 3))
+        q = torch.nn.Parameter(torch.zeros(2, 3))
+        opt = FusedAdam([p, q], lr=0.01, capturable=capturable)
+        for t in (p, q):
+            st = opt.state[t]
+            st["step"] = 0 if capturable else steps            # a graph replay advances the device count only
+            st["exp_avg"] = torch.full_like(t, 0.5)
+            st["exp_avg_sq"] = torch.full_like(t, 0.25)
+            if capturable:
+                st["step_dev"] = torch.full((1,), steps, dtype=torch.int64)
+        return opt
+
+    def resumed(src, capturable):
+        buf = io.BytesIO()
+        torch.save(src.state_dict(), buf)
+        buf.seek(0)
+        p, q = torch.nn.Parameter(torch.zeros(4, 3)), torch.nn.Parameter(torch.zeros(2, 3))
+        dst = FusedAdam([p, q], lr=0.01, capturable=capturable)
+        dst.load_state_dict(torch.load(buf, weights_only=True))
+        return dst, (p, q)
+
+    for src_cap, dst_cap in ((True, True), (True, False), (False, True)):
+        src = trained(src_cap, 7)
+        if src_cap:
+            assert all(st["step"] == 7 for st in src.state_dict()["state"].values())    # host count synchronised
+        dst, params = resumed(src, dst_cap)
+        case = (src_cap, dst_cap)
+        assert all(g["capturable"] == dst_cap for g in dst.param_groups), case
+        for t in params:
+            st = dst.state[t]
+            assert st["step"] == 7, case
+            assert st["exp_avg"].dtype == torch.float32 and float(st["exp_avg"][0, 0]) == 0.5, case
+            if dst_cap:
+                assert st["step_dev"].dtype == torch.int64 and st["step_dev"].device == t.device, case
+                assert st["step_dev"].tolist() == [7], case
+            else:
+                assert "step_dev" not in st, case
+        # a second checkpoint of the resumed optimiser carries the same count
+        assert all(st["step"] == 7 for st in dst.state_dict()["state"].values()), case
