@@ -18,6 +18,8 @@ How each reference function is reached:
     (nothing re-typed); LGConv itself stays "parity unpinned".
 
 Usage:  python oracle/gen_golden.py   (writes tests/golden/)
+        python oracle/gen_golden.py --f64 [--out DIR]   (float64 runs on the committed fp32 fixtures' inputs:
+        tests/golden/<family>_f64.npz, see gen_f64)
 """
 import ast
 import os
@@ -653,8 +655,469 @@ def gen_featmask():
     print("wrote featmask.npz: dropped columns", [int((out[f"y{k}"] == 0).all(0).sum()) for k in range(3)])
 
 
+# ==================================================================================================== float64 fixtures
+# `--f64` writes tests/golden/<family>_f64.npz: the same reference code the fp32 modes above run, reached the same way,
+# on the COMMITTED fp32 fixture's own inputs widened to float64, under torch.set_default_dtype(torch.float64) (tensors
+# the reference creates itself are float64 too).  Sparse operators are the reference's fp32 values widened (the kernels
+# consume fp32 values); discrete decisions (MHCN's permutations, BUIR's Bernoulli draw, SEPT-social's pseudo-labels) are
+# replayed from the fp32 fixture and checked against what the float64 run would decide.  Each family runs twice: in
+# float32, which must reproduce the committed fp32 arrays bit for bit (self-check), and in float64.
+#
+# Stored with every output key k: k (float64), k__scale = S, k__drift = max|fp32 golden - f64| / S.  S is max|f64| for
+# arrays; for a scalar loss that is a difference of larger terms it is the magnitude of the un-cancelled terms, from the
+# float64 run: every loss below is a (weighted) sum of per-row terms l_i = lse_i - pos_i >= 0 (log-softmax forms) or
+# softplus(neg_i - pos_i) >= 0 (log-sigmoid forms), so S = |L| + sum_i w_i (|pos_i| (+ |neg_i|)) >= sum_i w_i |lse_i|.
+# `ill_conditioned` lists the keys with 4 * drift > 1e-5 (the reference's own fp32 run misses 1e-5 there);
+# `dropped` lists fp32 output keys left out to keep the file under F64_SIZE_CAP.
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+F64_FAMILIES = ("propagation", "contrast", "bpr", "mhcn", "sept_social", "buir", "grace", "rownorm")
+F64_SIZE_CAP = 1066584                       # bytes: the largest fp32 fixture (contrast.npz)
+GRACE_F64_DROPPED = ((257, 0.5),)           # (m, tau) cases of grace.npz left out of grace_f64.npz (size cap)
+# The one fp32 output that the reference does not reproduce from run to run: the gradient of item_emb[neg_i] with a
+# [B, 3] index (lightgcn.py:102) is a multi-threaded scatter-add whose order varies (1 to 3 ulps of the element between
+# runs, and single-threaded differs again).  Its self-check allows 2^-20 of max|golden|; every other key is bit for bit.
+FP32_NOT_REPRODUCIBLE = {("bpr", "lgcn_block_n3_gi")}
+
+
+def _cos(a, b):
+    return (F.normalize(a, dim=1) * F.normalize(b, dim=1)).sum(1)
+
+
+def _f64_propagation(z, dt):
+    import directau, selfcf, sept  # noqa: E401
+    gb = np.load(os.path.join(GOLDEN, "graph_build.npz"))
+    train = [[u, i, 1.0] for u, i in zip(gb["train_user"].tolist(), gb["train_item"].tolist())]
+    test = [[train[k][0], train[(k * 7) % len(train)][1], 1.0] for k in range(0, 60, 3)] + [["999999", "888888", 1.0]]
+    x0, wgt, xs = (torch.from_numpy(z[k]).to(dt) for k in ("x0", "w", "xs"))
+    d = x0.shape[1]
+    out = {}
+    d_int = directau.Interaction({}, train, test)
+    for k_layers in (1, 2, 3):
+        enc = directau.LGCNEncoder(d_int, d, k_layers)
+        enc.sparse_norm_adj = enc.sparse_norm_adj.to(dt)
+        with torch.no_grad():
+            enc.embedding_dict["user_emb"].copy_(x0[: d_int.user_num])
+            enc.embedding_dict["item_emb"].copy_(x0[d_int.user_num:])
+        ue, ie, all_emb = enc()
+        final = torch.cat([ue, ie])
+        (final * wgt).sum().backward()
+        out[f"raw_mean_K{k_layers}"] = final.detach()
+        out[f"raw_last_K{k_layers}"] = all_emb[-1].detach()
+        out[f"raw_grad_K{k_layers}"] = torch.cat([enc.embedding_dict["user_emb"].grad, enc.embedding_dict["item_emb"].grad])
+    s_int = selfcf.Interaction({}, train, test)
+    ns = s_int.user_num + s_int.item_num
+    for k_layers in (2, 3):
+        enc = selfcf.LGCN_Encoder(s_int, d, k_layers)
+        enc.sparse_norm_adj = enc.sparse_norm_adj.to(dt)
+        with torch.no_grad():
+            enc.embedding_dict["user_emb"].copy_(xs[: s_int.user_num])
+            enc.embedding_dict["item_emb"].copy_(xs[s_int.user_num:])
+        ue, ie = enc()
+        final = torch.cat([ue, ie])
+        (final * wgt[:ns]).sum().backward()
+        out[f"norm_mean_K{k_layers}"] = final.detach()
+        out[f"norm_grad_K{k_layers}"] = torch.cat([enc.embedding_dict["user_emb"].grad, enc.embedding_dict["item_emb"].grad])
+    sp_int = sept.Interaction({}, train, test)
+    adj_t = sept.TFGraphInterface.convert_sparse_mat_to_tensor_inputs(sp_int.norm_adj).to(dt)
+    xr = x0.clone().requires_grad_(True)
+    fin = sept.SEPT.encoder(types.SimpleNamespace(n_layers=2), xr, adj_t)
+    (fin * wgt).sum().backward()
+    out["sept_mean_K2"], out["sept_grad_K2"] = fin.detach(), xr.grad
+    return out, {}
+
+
+def _f64_contrast(z, dt):
+    import gcl
+    ncl = load_defs(os.path.join(REF, "ncl.py"), {"InfoNCE", "bpr_loss", "l2_reg_loss"},
+                    {"NCLModel.ssl_layer_loss", "NCLModel.ProtoNCE_loss"})
+    s4r = load_defs(os.path.join(REF, "ssl4rec.py"), {"batch_softmax_loss", "InfoNCE", "l2_reg_loss"})
+    out, scale = {}, {}
+
+    def t(key):
+        return torch.from_numpy(z[key]).to(dt)
+
+    for m in (1, 7, 257, 1000):
+        z1, z2 = t(f"z1_{m}"), t(f"z2_{m}")
+        for temp in (0.1, 0.2, 0.5):
+            a, b = z1.clone().requires_grad_(True), z2.clone().requires_grad_(True)
+            loss = gcl.info_nce_loss(a, b, temp)
+            loss.backward()
+            key = f"gcl_loss_{m}_{temp}"
+            out[key] = loss.detach()
+            scale[key] = abs(loss.item()) + float(_cos(z1, z2).abs().mean()) / temp
+            if m in (7, 257) and temp == 0.2:
+                out[f"gcl_g1_{m}"], out[f"gcl_g2_{m}"] = a.grad, b.grad
+        for b_cos in (True, False):
+            v1, v2 = 0.3 * z1, 0.3 * z2
+            a, b = v1.clone().requires_grad_(True), v2.clone().requires_grad_(True)
+            loss = ncl["InfoNCE"](a, b, 0.2, b_cos)
+            loss.backward()
+            pos = float(((_cos(v1, v2) if b_cos else (v1 * v2).sum(1)) / 0.2).abs().mean())
+            out[f"ncl_infonce_{m}_{int(b_cos)}"] = loss.detach()
+            scale[f"ncl_infonce_{m}_{int(b_cos)}"] = abs(loss.item()) + pos
+            if m == 257:
+                out[f"ncl_infonce_g1_{m}_{int(b_cos)}"] = a.grad
+                out[f"ncl_infonce_g2_{m}_{int(b_cos)}"] = b.grad
+            loss = s4r["InfoNCE"](v1, v2, 0.2, b_cos)
+            out[f"s4r_infonce_{m}_{int(b_cos)}"] = loss
+            scale[f"s4r_infonce_{m}_{int(b_cos)}"] = abs(loss.item()) + pos
+        loss = s4r["batch_softmax_loss"](z1, z2, 0.2)
+        out[f"s4r_bsl_{m}"] = loss
+        scale[f"s4r_bsl_{m}"] = abs(loss.item()) + float(_cos(z1, z2).abs().mean()) / 0.2
+
+    nu = int(z["ncl_num_users"])
+    ctx, x0 = t("ncl_ctx"), t("ncl_x0")
+    uidx, iidx = z["ncl_uidx"].tolist(), z["ncl_iidx"].tolist()
+    temp, reg, alpha, proto_reg, bsz = (float(z["ncl_ssl_temp"]), float(z["ncl_ssl_reg"]), float(z["ncl_alpha"]),
+                                        float(z["ncl_proto_reg"]), int(z["ncl_bsz"]))
+    self_ = types.SimpleNamespace(
+        data=types.SimpleNamespace(user_num=nu, item_num=x0.shape[0] - nu), ssl_temp=temp, ssl_reg=reg, alpha=alpha,
+        proto_reg=proto_reg, batch_size=bsz, user_centroids=t("ncl_ucent"), item_centroids=t("ncl_icent"),
+        user_2cluster=torch.from_numpy(z["ncl_u2c"]), item_2cluster=torch.from_numpy(z["ncl_i2c"]))
+    ctx_r, x0_r = ctx.clone().requires_grad_(True), x0.clone().requires_grad_(True)
+    ssl = ncl["ssl_layer_loss"](self_, ctx_r, x0_r, uidx, iidx)
+    ssl.backward()
+    x0_p = x0.clone().requires_grad_(True)
+    proto = ncl["ProtoNCE_loss"](self_, x0_p, uidx, iidx)
+    proto.backward()
+    out.update(ncl_ssl=ssl.detach(), ncl_ssl_gctx=ctx_r.grad, ncl_ssl_gx0=x0_r.grad,
+               ncl_proto=proto.detach(), ncl_proto_gx0=x0_p.grad)
+    ui, ii = torch.tensor(uidx), torch.tensor(iidx) + nu
+    scale["ncl_ssl"] = abs(ssl.item()) + reg * (float(_cos(ctx[ui], x0[ui]).abs().sum())
+                                                + alpha * float(_cos(ctx[ii], x0[ii]).abs().sum())) / temp
+    pu = _cos(x0[ui], self_.user_centroids[self_.user_2cluster[ui]]).abs().mean()
+    pi = _cos(x0[ii], self_.item_centroids[self_.item_2cluster[ii - nu]]).abs().mean()
+    scale["ncl_proto"] = abs(proto.item()) + proto_reg * bsz * float(pu + pi) / temp
+    return out, scale
+
+
+def _f64_bpr(z, dt):
+    import directau, sept  # noqa: E401
+    ncl = load_defs(os.path.join(REF, "ncl.py"), {"bpr_loss", "l2_reg_loss"})
+    lgcn_code = load_stmts(os.path.join(REF, "lightgcn.py"), "train_model", 95, 118)
+    gcl_code = load_stmts(os.path.join(REF, "gcl.py"), "GCLTuner.run", 216, 223)
+    ui, pi, ni1, ni3 = (torch.from_numpy(z[k]) for k in ("u_idx", "i_idx", "j_idx", "j_idx3"))
+    out, scale = {}, {}
+    tabs = {"": (torch.from_numpy(z["user_tab"]).to(dt), torch.from_numpy(z["item_tab"]).to(dt)),
+            "_big": (torch.from_numpy(z["user_tab_big"]).to(dt), torch.from_numpy(z["item_tab_big"]).to(dt))}
+
+    def run(fn_loss, name, neg_idx, tab="", kind="bpr"):
+        ut, it = tabs[tab]
+        a, b = ut.clone().requires_grad_(True), it.clone().requires_grad_(True)
+        loss = fn_loss(a, b, neg_idx)
+        loss.backward()
+        out[f"{name}_loss"], out[f"{name}_gu"], out[f"{name}_gi"] = loss.detach(), a.grad, b.grad
+        s_pos = (ut[ui] * it[pi]).sum(1)
+        if kind == "bpr":       # softplus(neg - pos) per row, neg = the (mean) negative score
+            s_neg = (ut[ui].unsqueeze(1) * it[neg_idx.view(len(ui), -1)]).sum(-1).abs().mean(1)
+            scale[f"{name}_loss"] = abs(loss.item()) + float((s_pos.abs() + s_neg).mean())
+        elif kind == "bce":     # mean over [B, I] of softplus(s) - s y: the label-one entries cancel
+            scale[f"{name}_loss"] = abs(loss.item()) + float(s_pos.abs().sum()) / (len(ui) * it.shape[0])
+        else:                   # sums of squares: nothing cancels
+            scale[f"{name}_loss"] = abs(loss.item())
+
+    def lightgcn_block(loss_type):
+        def fn(a, b, nj, reg_weight=1e-4):
+            ns_ = {"torch": torch, "F": F, "user_emb": a, "item_emb": b, "pos_u": ui, "pos_i": pi, "neg_i": nj,
+                   "config": {"n_neg": 1 if nj.dim() == 1 else nj.shape[1], "loss_type": loss_type, "reg_weight": reg_weight}}
+            exec(lgcn_code, ns_)
+            return ns_["loss"]
+        return fn
+
+    def gcl_block(a, b, nj, reg_weight=1e-4):
+        ns_ = {"torch": torch, "F": F, "device": torch.device("cpu"), "user_z1": a, "item_z1": b, "users": ui,
+               "pos_items": pi, "neg_items": nj, "ssl_loss": torch.zeros(()), "config": {"reg_weight": reg_weight}}
+        exec(gcl_code, ns_)
+        return ns_["total_loss"]
+
+    run(lambda a, b, nj: ncl["bpr_loss"](a[ui], b[pi], b[nj]), "ncl_bpr", ni1)
+    run(lambda a, b, nj: sept.bpr_loss(a[ui], b[pi], b[nj]), "sept_bpr", ni1)
+    run(lambda a, b, nj: ncl["l2_reg_loss"](1e-4, a[ui], b[pi], b[nj]), "ncl_l2reg", ni1, kind="l2")
+    ut, it = tabs[""]
+    loss = directau.l2_reg_loss(1e-4, ut[ui], it[pi], it[ni1])
+    out["directau_l2reg_loss"], scale["directau_l2reg_loss"] = loss, abs(loss.item())
+    run(lightgcn_block("bpr"), "lgcn_block_n1", ni1)
+    run(lightgcn_block("bpr"), "lgcn_block_n3", ni3)
+    run(lightgcn_block("bce"), "lgcn_bce", ni1, kind="bce")
+    run(lightgcn_block("bce"), "lgcn_bce_big", ni1, tab="_big", kind="bce")
+    run(gcl_block, "gcl_block", ni1)
+    return out, scale
+
+
+def _f64_grace(z, dt):
+    from abc import ABC, abstractmethod
+    tree = ast.parse(open(os.path.join(REF, "univariate", "grace.py")).read())
+    names = {"_similarity", "Loss", "InfoNCE", "Sampler", "SameScaleSampler", "CrossScaleSampler", "get_sampler",
+             "add_extra_mask", "DualBranchContrast"}
+    wanted = [n for n in tree.body if isinstance(n, (ast.ClassDef, ast.FunctionDef)) and n.name in names]
+    assert {n.name for n in wanted} == names
+    ns = {"torch": torch, "F": F, "ABC": ABC, "abstractmethod": abstractmethod}
+    exec(compile(ast.Module(body=wanted, type_ignores=[]), "grace.py", "exec"), ns)
+    out, scale = {}, {}
+    for m in (7, 257):
+        h1, h2 = torch.from_numpy(z[f"h1_{m}"]).to(dt), torch.from_numpy(z[f"h2_{m}"]).to(dt)
+        for tau in (0.2, 0.5):
+            if dt == torch.float64 and (m, tau) in GRACE_F64_DROPPED:
+                continue
+            for intra in (0, 1):
+                for keep_sampler_mask in (0, 1):
+                    if keep_sampler_mask and not intra:
+                        continue
+                    t1, t2 = h1.clone().requires_grad_(True), h2.clone().requires_grad_(True)
+                    model = ns["DualBranchContrast"](loss=ns["InfoNCE"](tau=tau), mode="L2L", intraview_negs=bool(intra))
+                    extra = torch.ones(m, 2 * m) if keep_sampler_mask else None
+                    loss = model(h1=t1, h2=t2, extra_neg_mask=extra)
+                    loss.backward()
+                    key = f"{m}_{tau}_{intra}_{keep_sampler_mask}"
+                    out[f"loss_{key}"], out[f"g1_{key}"], out[f"g2_{key}"] = loss.detach(), t1.grad, t2.grad
+                    scale[f"loss_{key}"] = abs(loss.item()) + float(_cos(h1, h2).abs().mean()) / tau
+    return out, scale
+
+
+def _f64_rownorm(z, dt):
+    import scipy.sparse as sp
+    import selfcf
+    npdt = np.float32 if dt == torch.float32 else np.float64
+    a = sp.csr_matrix((z["val"].astype(npdt), (z["row"], z["col"])), shape=(int(z["n_rows"]), int(z["n_cols"])),
+                      dtype=npdt)
+    res = selfcf.Graph.normalize_graph_mat(a).tocsr()
+    res.sort_indices()
+    assert np.array_equal(res.indptr, z["indptr"]) and np.array_equal(res.indices, z["indices"])
+    return {"data": torch.from_numpy(res.data)}, {}
+
+
+def _sparse_to(t, dt, ref_csr):
+    """Torch sparse operator `t` as the reference built it (fp32 values), cast to dt; asserts that its values are the fp32
+    fixture's CSR data (`ref_csr`: indptr, indices, data), so that the float64 run sees the widened fixture operator."""
+    c = t.coalesce()
+    n_r = len(ref_csr[0]) - 1
+    import scipy.sparse as sp
+    got = sp.csr_matrix((c.values().numpy(), c.indices().numpy()), shape=(n_r, c.shape[1]))
+    got.sort_indices()
+    assert c.dtype == torch.float32
+    assert np.array_equal(got.indptr, ref_csr[0]) and np.array_equal(got.indices, ref_csr[1])
+    assert np.array_equal(got.data, ref_csr[2])
+    return t.to(dt)
+
+
+def _csr_of(z, name):
+    return z[f"{name}_indptr"], z[f"{name}_indices"], z[f"{name}_data"]
+
+
+def _f64_mhcn(z, dt):
+    import scipy.sparse as sp
+    path = os.path.join(REF, "univariate", "mhcn.py")
+    names = {"build_hyper_adj_mats", "self_gating", "self_supervised_gating", "channel_attention", "forward",
+             "hierarchical_self_supervision", "sparse_mx_to_torch_sparse_tensor"}
+    cls, ns = _lift_class_methods(path, "MHCN", names, top_level=("TFGraphInterface", "Graph"))
+    n_u, n_i = int(z["n_users"]), int(z["n_items"])
+    d = z["user_emb"].shape[1]
+    S = sp.csr_matrix((np.ones(len(z["S_row"]), dtype=np.float32), (z["S_row"], z["S_col"])), shape=(n_u, n_u),
+                      dtype=np.float32)
+    Y = sp.csr_matrix((np.ones(len(z["Y_row"]), dtype=np.float32), (z["Y_row"], z["Y_col"])), shape=(n_u, n_i),
+                      dtype=np.float32)
+    m = cls()
+    m.social_data = types.SimpleNamespace(get_social_mat=lambda: S)
+    m.data = types.SimpleNamespace(interaction_mat=Y, user_num=n_u, item_num=n_i)
+    H = [sp.csr_matrix(h) for h in m.build_hyper_adj_mats()]
+    R = ns["Graph"].normalize_graph_mat(Y)
+
+    def t(key):
+        return torch.from_numpy(z[key]).to(dt)
+
+    m.n_layers, m.n_channel, m.emb_size, m.ss_rate = int(z["n_layers"]), 4, d, float(z["ss_rate"])
+    m.user_embeddings = t("user_emb").requires_grad_(True)
+    m.item_embeddings = t("item_emb").requires_grad_(True)
+    m.gating_weights = {str(c): t(f"gw{c}") for c in (1, 2, 3, 4)}
+    m.gating_bias = {str(c): t(f"gb{c}") for c in (1, 2, 3, 4)}
+    m.sgating_weights = {str(c): t(f"sgw{c}") for c in (1, 2, 3, 4)}
+    m.sgating_bias = {str(c): t(f"sgb{c}") for c in (1, 2, 3, 4)}
+    m.attention, m.attention_mat = t("attention"), t("attention_mat")
+    m.H_s, m.H_j, m.H_p = (_sparse_to(m.sparse_mx_to_torch_sparse_tensor(h), dt, _csr_of(z, k))
+                           for h, k in zip(H, ("H_s", "H_j", "H_p")))
+    m.R = _sparse_to(m.sparse_mx_to_torch_sparse_tensor(R), dt, _csr_of(z, "R"))
+    # the self-supervision's torch.randperm draws, replayed from the fp32 fixture (they do not depend on values)
+    perms = [torch.from_numpy(p) for p in z["perms"]]
+    drawn = []
+    real_randperm = torch.randperm
+
+    def replay_randperm(n, **kw):
+        p = perms[len(drawn)]
+        assert p.numel() == n
+        drawn.append(p)
+        return p
+
+    torch.randperm = replay_randperm
+    try:
+        bu, bp, bn, ss_loss, fu, fi = m.forward(*(torch.from_numpy(z[k]) for k in ("u_idx", "v_idx", "j_idx")))
+    finally:
+        torch.randperm = real_randperm
+    assert len(drawn) == len(perms)
+    ((fu * t("wu")).sum() + (fi * t("wi")).sum() + ss_loss).backward()
+    # hierarchical_self_supervision (mhcn.py:480-505): sums of softplus(b - a) over the score pairs (a, b) =
+    # (pos, neg1), (neg1, neg2) and, global, (pos, neg1): S = |L| + ss_rate * sum (|a| + |b|)
+    mag = 0.0
+    with torch.no_grad():
+        for c, adj in enumerate((m.H_s, m.H_j, m.H_p)):
+            em = m.self_supervised_gating(fu, c + 1)
+            edge = torch.sparse.mm(adj, em)
+            p0, p1, p2 = perms[3 * c:3 * c + 3]
+            pos, neg1, neg2 = (em * edge).sum(1), (em[p0] * edge).sum(1), (edge[p1] * em).sum(1)
+            graph = edge.mean(0, keepdim=True)
+            gpos, gneg = (edge * graph).sum(1), (edge[p2] * graph).sum(1)
+            mag += float((pos.abs() + 2 * neg1.abs() + neg2.abs() + gpos.abs() + gneg.abs()).sum())
+    out = {"final_user": fu.detach(), "final_item": fi.detach(), "ss_loss": ss_loss.detach(), "batch_user": bu.detach(),
+           "batch_pos": bp.detach(), "batch_neg": bn.detach(), "grad_user": m.user_embeddings.grad,
+           "grad_item": m.item_embeddings.grad}
+    return out, {"ss_loss": abs(ss_loss.item()) + m.ss_rate * mag}
+
+
+def _f64_sept_social(z, dt):
+    import scipy.sparse as sp
+    from scipy.sparse import eye
+    path = os.path.join(REF, "univariate", "sept_social.py")
+    names = {"encoder", "social_encoder", "get_social_related_views", "label_prediction", "sampling",
+             "generate_pesudo_labels", "neighbor_discrimination"}
+    cls, ns = _lift_class_methods(path, "SEPT", names, extra_ns={"eye": eye}, top_level=("TFGraphInterface", "Graph"))
+    n_u, n_i, n_layers = int(z["n_users"]), int(z["n_items"]), int(z["n_layers"])
+    S = sp.csr_matrix((np.ones(len(z["S_row"]), dtype=np.float32), (z["S_row"], z["S_col"])), shape=(n_u, n_u),
+                      dtype=np.float32)
+    bi = S.multiply(S)
+    Y = sp.csr_matrix((np.ones(len(z["Y_row"]), dtype=np.float32), (z["Y_row"], z["Y_col"])), shape=(n_u, n_i),
+                      dtype=np.float32)
+    adj = sp.bmat([[None, Y], [Y.T, None]], format="csr", dtype=np.float32)
+    norm_adj = ns["Graph"].normalize_graph_mat(adj)
+    m = cls()
+    m.data = types.SimpleNamespace(user_num=n_u, item_num=n_i)
+    m.social_data = types.SimpleNamespace(normalize_graph_mat=ns["Graph"].normalize_graph_mat)
+    m.instance_cnt = 5
+    social_mat, sharing_mat = m.get_social_related_views(bi, Y)
+    to_t = ns["TFGraphInterface"].convert_sparse_mat_to_tensor
+    a_norm = _sparse_to(to_t(norm_adj), dt, _csr_of(z, "norm_adj"))
+    a_social = _sparse_to(to_t(social_mat), dt, _csr_of(z, "social"))
+    a_sharing = _sparse_to(to_t(sharing_mat), dt, _csr_of(z, "sharing"))
+    ego = torch.from_numpy(z["ego"]).to(dt).requires_grad_(True)
+    rec_u, rec_i = m.encoder(ego, a_norm, n_layers)
+    (torch.cat([rec_u, rec_i]) * torch.from_numpy(z["w"]).to(dt)).sum().backward()
+    users = ego.detach()[:n_u].clone().requires_grad_(True)
+    friend = m.social_encoder(users, a_social, n_layers)
+    sharing = m.social_encoder(users, a_sharing, n_layers)
+    u_idx = torch.from_numpy(z["u_idx"])
+    m.aug_user_embeddings = torch.from_numpy(z["aug_user"]).to(dt)
+    f_pos = m.generate_pesudo_labels(m.label_prediction(sharing.detach(), u_idx),
+                                     m.label_prediction(friend.detach(), u_idx))
+    fixture_pos = torch.from_numpy(z["positive"])
+    n_diff = int((f_pos != fixture_pos).any(1).sum())
+    if dt == torch.float64:
+        print(f"  sept_social: float64 pseudo-labels differ from the fp32 fixture's in {n_diff} of {len(f_pos)} rows"
+              + ("; the fixture's are used" if n_diff else ""))
+    emb_in = friend.detach().clone().requires_grad_(True)
+    loss = m.neighbor_discrimination(fixture_pos, emb_in, u_idx)
+    loss.backward()
+    # sept_social.py:408-420: sum over rows of lse(ttl) - lse(pos) >= 0 (the positives are a subset of the row):
+    # S = |L| + sum_i |lse_k(pos_ik / 0.1)|
+    with torch.no_grad():
+        uniq = torch.unique(u_idx)
+        e, aug = F.normalize(friend.detach()[uniq]), F.normalize(m.aug_user_embeddings[uniq])
+        lse_pos = torch.logsumexp((e.unsqueeze(1) * aug[fixture_pos]).sum(2) / 0.1, dim=1)
+    out = {"rec_user": rec_u.detach(), "rec_item": rec_i.detach(), "enc_grad": ego.grad,
+           "friend_view": friend.detach(), "sharing_view": sharing.detach(), "nd_loss": loss.detach(),
+           "nd_grad": emb_in.grad}
+    return out, {"nd_loss": abs(loss.item()) + float(lse_pos.abs().sum())}
+
+
+def _f64_buir(z, dt):
+    import buir
+    rng = np.random.default_rng(31)
+    data = buir.Interaction({}, seeded_triples(rng, 40, 30, 350, 0), [])
+    d, n_layers, rate = z["x"].shape[1], int(z["n_layers"]), float(z["rate"])
+    enc = buir.LGCN_Encoder(data, d, n_layers, rate, drop_flag=True)
+    idx = enc.sparse_norm_adj._indices().numpy()
+    assert np.array_equal(idx[0], z["adj_row"]) and np.array_equal(idx[1], z["adj_col"])
+    assert enc.sparse_norm_adj.dtype == torch.float32 and np.array_equal(enc.sparse_norm_adj._values().numpy(), z["adj_val"])
+    adj = enc.sparse_norm_adj.to(dt)
+    real_rand = torch.rand
+    drawn = []
+
+    def replay_rand(*a, **kw):                      # the fp32 fixture's Bernoulli draw, widened
+        drawn.append(a)
+        return torch.from_numpy(z["rand"]).to(torch.get_default_dtype())
+
+    torch.rand = replay_rand
+    try:
+        dropped = enc.sparse_dropout(adj, rate, enc.sparse_norm_adj._nnz())
+    finally:
+        torch.rand = real_rand
+    assert len(drawn) == 1
+    keep = np.floor(1 - rate + z["rand"].astype(np.float64 if dt == torch.float64 else np.float32)).astype(bool)
+    assert np.array_equal(keep, z["keep"])
+    x = torch.from_numpy(z["x"]).to(dt)
+    xr = x.clone().requires_grad_(True)
+    layers = [xr]
+    e = xr
+    for _ in range(n_layers):                      # buir.py:315-320 on the dropped operator
+        e = torch.sparse.mm(dropped, e)
+        layers.append(e)
+    final = torch.stack(layers, dim=1).mean(dim=1)
+    (final * torch.from_numpy(z["w"]).to(dt)).sum().backward()
+    dc = dropped.coalesce()
+    assert np.array_equal(dc.indices()[0].numpy(), z["dropped_row"]) and np.array_equal(dc.indices()[1].numpy(), z["dropped_col"])
+    return {"dropped_val": dc.values(), "final": final.detach(), "grad": xr.grad}, {}
+
+
+def gen_f64():
+    import io
+    import zipfile
+    for fam in F64_FAMILIES:
+        z = np.load(os.path.join(GOLDEN, f"{fam}.npz"))
+        run = globals()[f"_f64_{fam}"]
+        torch.manual_seed(0)
+        out32, _ = run(z, torch.float32)
+        for k, v in out32.items():                  # self-check: the fp32 path reproduces the committed arrays
+            assert v.dtype == torch.float32, (fam, k, v.dtype)
+            got, want = v.detach().numpy().astype(np.float64), z[k].astype(np.float64)
+            if got.shape != want.shape or not np.array_equal(got, want):
+                diff = np.abs(got - want).max() if got.shape == want.shape else f"shape {got.shape} vs {want.shape}"
+                if (fam, k) in FP32_NOT_REPRODUCIBLE and diff <= 2.0 ** -20 * np.abs(want).max():
+                    print(f"  fp32 self-check: {fam}.npz {k} differs by {diff:.3g} (thread-order-dependent scatter)")
+                    continue
+                sys.exit(f"fp32 self-check failed: {fam}.npz {k}: largest difference {diff}")
+        old = torch.get_default_dtype()
+        torch.set_default_dtype(torch.float64)
+        try:
+            torch.manual_seed(0)
+            out64, scales = run(z, torch.float64)
+        finally:
+            torch.set_default_dtype(old)
+        res, ill = {}, []
+        for k in sorted(out64):
+            v = out64[k].detach()
+            assert v.dtype == torch.float64, (fam, k, v.dtype)
+            v = v.numpy()
+            s = scales[k] if v.ndim == 0 else float(np.abs(v).max())
+            assert (k in scales) == (v.ndim == 0), (fam, k)
+            drift = float(np.abs(z[k].astype(np.float64) - v).max()) / s
+            res[k], res[f"{k}__scale"], res[f"{k}__drift"] = v, np.float64(s), np.float64(drift)
+            if 4 * drift > 1e-5:
+                ill.append(k)
+        dropped = sorted(set(out32) - set(out64))
+        res["ill_conditioned"] = np.array(ill, dtype=str).reshape(-1)
+        res["dropped"] = np.array(dropped, dtype=str).reshape(-1)
+        path = os.path.join(OUT, f"{fam}_f64.npz")
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **res)
+        assert buf.tell() <= F64_SIZE_CAP, (fam, buf.tell())
+        with open(path, "wb") as f:
+            f.write(buf.getvalue())
+        worst = max((float(res[f"{k}__drift"]), k) for k in out64)
+        print(f"wrote {fam}_f64.npz: {len(out64)} keys, {os.path.getsize(path)} bytes, largest drift {worst[0]:.2e} "
+              f"({worst[1]}), ill-conditioned {ill}, dropped {dropped}")
+        with zipfile.ZipFile(path) as zf:
+            assert zf.testzip() is None
+
+
 if __name__ == "__main__":
-    if "--out" in sys.argv:                        # write somewhere else (e.g. to diff a regeneration against tests/golden)
+    if "--out" in sys.argv:                       # write somewhere else (e.g. to diff a regeneration against tests/golden)
         OUT = sys.argv[sys.argv.index("--out") + 1]
         os.makedirs(OUT, exist_ok=True)
     if "--featmask" in sys.argv:
@@ -671,5 +1134,7 @@ if __name__ == "__main__":
         gen_rownorm()
     elif "--eval" in sys.argv:
         gen_eval()
+    elif "--f64" in sys.argv:
+        gen_f64()
     else:
         main()

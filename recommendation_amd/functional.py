@@ -1014,7 +1014,14 @@ def _infonce_bwd_raw(x, x_scale, y, y_scale, inv_tau, lse_x, w_x, lse_y, w_y, ex
 
 class _InfoNCEStats(torch.autograd.Function):
     """(a, b) -> row_lse [M], pos_logit [M] (and col_lse [N]) of S = inv_tau * ahat bhat^T, with the
-    flash-style HIP backward.  Every loss of the InfoNCE family is a few [M]-vector ops on top."""
+    flash-style HIP backward.  Every loss of the InfoNCE family is a few [M]-vector ops on top.
+
+    Diagonal positives (pos None, M = N >= 2, nothing excluded): the kernels run with the diagonal left out and the
+    positive's share is carried as q_i = 1 - p_ii = sigmoid(lse_ex_i - s_ii), which fp32 holds to its own relative
+    precision; lse = logaddexp(lse_ex, s_ii).  The backward then forms the diagonal's coefficient as a scalar,
+    (g_lse + g_col + g_pos) - g_lse q - g_col q_col, as autograd's (softmax - one-hot) does.  exp(s_ii - lse_i) - 1
+    from an lse stored in fp32 would carry an absolute error of ~ulp(lse) into p_ii - 1, which at p_ii -> 1 is all of
+    it (gcl.py:28-35 at small batches, ncl.py:125-130 with b_cos=False; tests/golden/contrast_f64.npz)."""
 
     @staticmethod
     def forward(ctx, a, b, pos, inv_tau, normalize, want_col, exd=False, grad_a=False):
@@ -1030,27 +1037,36 @@ class _InfoNCEStats(torch.autograd.Function):
         # 0.34-0.49 vs 0.62-0.89 ms at 20K x 20K; scripts/perf_infonce_sym.py)
         eng = _resolve_engine(unit_rows=normalize)   # once per problem: the backward runs on the same engine
         on_f32 = bool(eng & INFONCE_ENGINE_F32) or _lib.lib().gcr_infonce_engine(a_p.shape[1]) == 0
-        one_pass = want_col and normalize and inv_tau <= 40.0 and not COL_DETERMINISTIC and not exd and on_f32
+        diag = pos is None and not exd and a_p.shape[0] == b_p.shape[0] >= 2
+        kex = exd or diag                            # the kernels leave the diagonal out
+        one_pass = want_col and normalize and inv_tau <= 40.0 and not COL_DETERMINISTIC and not kex and on_f32
         o = None
         if FWD_O and not want_col and grad_a and a_p.shape[0] > 0 and \
                 infonce_fwd_o_supported(a_p.shape[1], eng):
-            lse, o = infonce_fwd_o_raw(a_p, sa, b_p, sb, inv_tau, exclude_diagonal=exd, engine_flag=eng)
+            lse, o = infonce_fwd_o_raw(a_p, sa, b_p, sb, inv_tau, exclude_diagonal=kex, engine_flag=eng)
             col = None
         elif one_pass:
             lse, col = infonce_lse_raw(a_p, sa, b_p, sb, inv_tau, col_bound=inv_tau * 1.0001, engine_flag=eng)
         else:
-            lse = infonce_lse_raw(a_p, sa, b_p, sb, inv_tau, exclude_diagonal=exd, engine_flag=eng)
-            col = infonce_lse_raw(b_p, sb, a_p, sa, inv_tau, exclude_diagonal=exd, engine_flag=eng) if want_col else None
+            lse = infonce_lse_raw(a_p, sa, b_p, sb, inv_tau, exclude_diagonal=kex, engine_flag=eng)
+            col = infonce_lse_raw(b_p, sb, a_p, sa, inv_tau, exclude_diagonal=kex, engine_flag=eng) if want_col else None
         pl = pos_logit_raw(a_p, sa, b_p, sb, pos, inv_tau)
-        ctx.save_for_backward(a_p, b_p, pos, sa, sb, lse, col, o)
-        ctx.inv_tau, ctx.d, ctx.exd, ctx.eng = inv_tau, a.shape[1], exd, eng
+        q = q_col = None
+        if diag:                                     # lse / col above leave out s_ii: put it back, keep 1 - p_ii
+            q = torch.sigmoid(lse - pl)
+            lse = torch.logaddexp(lse, pl)
+            if col is not None:
+                q_col = torch.sigmoid(col - pl)
+                col = torch.logaddexp(col, pl)
+        ctx.save_for_backward(a_p, b_p, pos, sa, sb, lse, col, o, q, q_col)
+        ctx.inv_tau, ctx.d, ctx.exd, ctx.eng, ctx.diag = inv_tau, a.shape[1], exd, eng, diag
         if want_col:
             return lse, pl, col
         return lse, pl
 
     @staticmethod
     def backward(ctx, g_lse, g_pos, g_col=None):
-        a, b, pos, sa, sb, lse, col, o = ctx.saved_tensors
+        a, b, pos, sa, sb, lse, col, o, q, q_col = ctx.saved_tensors
         L = _lib.lib()
         inv_tau = ctx.inv_tau
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
@@ -1058,15 +1074,28 @@ class _InfoNCEStats(torch.autograd.Function):
         g_col = g_col.contiguous().float() if (g_col is not None and col is not None) else None
         lse_r = lse if g_lse is not None else None
         col_r = col if g_col is not None else None
+        kex = ctx.exd or ctx.diag
         ga = gb = None
         stream = _lib.cur_stream(a.device)
         if need_a and o is not None:
             # flash-style forward kept o[i] = sum_j softmax_ij bhat_j: the softmax part of dL/dahat_i is one scale
-            ga = o * (g_lse * inv_tau).unsqueeze(1) if g_lse is not None else torch.zeros_like(o)
+            # (diagonal positives: o is the softmax over j != i, whose share of the full row is q)
+            w = g_lse * q if ctx.diag and g_lse is not None else g_lse
+            ga = o * (w * inv_tau).unsqueeze(1) if g_lse is not None else torch.zeros_like(o)
         elif need_a:
-            ga = _infonce_bwd_raw(a, sa, b, sb, inv_tau, lse_r, g_lse, col_r, g_col, ctx.exd, ctx.eng)
+            ga = _infonce_bwd_raw(a, sa, b, sb, inv_tau, lse_r, g_lse, col_r, g_col, kex, ctx.eng)
         if need_b:
-            gb = _infonce_bwd_raw(b, sb, a, sa, inv_tau, col_r, g_col, lse_r, g_lse, ctx.exd, ctx.eng)
+            gb = _infonce_bwd_raw(b, sb, a, sa, inv_tau, col_r, g_col, lse_r, g_lse, kex, ctx.eng)
+        if ctx.diag and (need_a or need_b):
+            # the diagonal, left out above: g_lse p_ii + g_col p^col_ii + g_pos with p_ii = 1 - q, the weights summed
+            # first (they cancel exactly where g_pos = -(g_lse + g_col): gcl.py:28-35, ncl.py:125-130)
+            total = torch.zeros_like(q) if g_pos is None else g_pos.contiguous().float()
+            corr = torch.zeros_like(q)
+            if g_lse is not None:
+                total, corr = total + g_lse, corr + g_lse * q
+            if g_col is not None:
+                total, corr = total + g_col, corr + g_col * q_col
+            g_pos = total - corr
         if g_pos is not None and (need_a or need_b):
             _lib.check(L.gcr_infonce_pos_bwd_f32(_lib.dptr(a), _lib.dptr(sa), _lib.dptr(b), _lib.dptr(sb), _lib.dptr(pos),
                                                  _lib.dptr(g_pos.contiguous().float()), a.shape[0], b.shape[0], a.shape[1],

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from f64_pins import pins
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,10 @@ def test_lightgcn_bce_golden(golden, engine, name, ukey, ikey):
     loss.backward()
     _close(ut.grad, b[f"{name}_gu"])
     _close(it.grad, b[f"{name}_gi"])
+    f64 = pins("bpr")                   # the reference's own float64 run (tests/f64_pins.py)
+    f64.check(f"{name}_loss", float(loss.detach()))
+    f64.check(f"{name}_gu", ut.grad)
+    f64.check(f"{name}_gi", it.grad)
 
 
 @pytest.mark.parametrize("engine", ENGINES)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from f64_pins import pins
 from oracle import oracle_c as C
 from oracle import oracle_np as O
 
@@ -44,6 +45,15 @@ def test_bpr_golden_value_and_grads(Fn, golden, variant, name):
     loss.backward()
     _close(ut.grad, b[f"{name}_gu"])
     _close(it.grad, b[f"{name}_gi"])
+    _pin64(name, loss, ut, it)
+
+
+def _pin64(name, loss, ut, it):
+    """The loss value and both gradients against the reference's own float64 run (tests/f64_pins.py)."""
+    f64 = pins("bpr")
+    f64.check(f"{name}_loss", float(loss.detach()))
+    f64.check(f"{name}_gu", ut.grad)
+    f64.check(f"{name}_gi", it.grad)
 
 
 @pytest.mark.parametrize("jkey,name", [("j_idx", "lgcn_block_n1"), ("j_idx3", "lgcn_block_n3")])
@@ -56,6 +66,7 @@ def test_lightgcn_loss_block(Fn, golden, jkey, name):
     loss.backward()
     _close(ut.grad, b[f"{name}_gu"])
     _close(it.grad, b[f"{name}_gi"])
+    _pin64(name, loss, ut, it)
 
 
 def test_gcl_loss_block_and_ncl_l2reg(Fn, golden):
@@ -68,6 +79,7 @@ def test_gcl_loss_block_and_ncl_l2reg(Fn, golden):
     loss.backward()
     _close(ut.grad, b["gcl_block_gu"])
     _close(it.grad, b["gcl_block_gi"])
+    _pin64("gcl_block", loss, ut, it)
     ut.grad = it.grad = None
     sums = Fn.bpr_sums(ut, it, b["u_idx"], b["i_idx"], b["j_idx"], Fn.BPR_NCL)
     l2 = 1e-4 * (sums[1].sqrt() + sums[2].sqrt() + sums[3].sqrt()) / n
@@ -75,6 +87,8 @@ def test_gcl_loss_block_and_ncl_l2reg(Fn, golden):
     l2.backward()
     _close(ut.grad, b["ncl_l2reg_gu"])
     _close(it.grad, b["ncl_l2reg_gi"])
+    _pin64("ncl_l2reg", l2, ut, it)
+    pins("bpr").check("directau_l2reg_loss", float(l2.detach()))
 
 
 @pytest.mark.parametrize("d", [64, 32, 128, 50])
@@ -186,6 +200,7 @@ def test_sorted_backward_matches_goldens(Fn, golden, monkeypatch, jkey, name, va
     loss.backward()
     _close(ut.grad, b[f"{name}_gu"])
     _close(it.grad, b[f"{name}_gi"])
+    _pin64(name, loss, ut, it)
 
 
 @pytest.mark.parametrize("d,n_neg", [(64, 1), (64, 2), (100, 1), (200, 3)])
@@ -258,6 +273,19 @@ def test_fused_ncl_rec_loss_equals_gathered_form(Fn, golden):
     for a, c in ((ut.grad, ut2.grad), (it.grad, it2.grad)):
         assert float((a - c).abs().max()) <= 2e-6 * float(c.abs().max())
     np.testing.assert_allclose(ut.grad.cpu().numpy(), b["ncl_bpr_gu"] + b["ncl_l2reg_gu"], rtol=2e-5, atol=2e-6 * np.abs(b["ncl_bpr_gu"]).max())
+    # each term against the reference's own float64 run; the fused gradient against the sum of the two float64
+    # gradients, under the same rule with the drift of the reference's summed fp32 gradients (S: max of the sum)
+    f64 = pins("bpr")
+    f64.check("ncl_bpr_loss", float(s[0] / n_b))
+    f64.check("ncl_l2reg_loss", float(l2))
+    for grad, key in ((ut.grad, "gu"), (it.grad, "gi")):
+        ref = f64.ref(f"ncl_bpr_{key}") + f64.ref(f"ncl_l2reg_{key}")
+        scale = float(np.abs(ref).max())
+        drift = float(np.abs(b[f"ncl_bpr_{key}"].astype(np.float64) + b[f"ncl_l2reg_{key}"] - ref).max()) / scale
+        err = float(np.abs(grad.cpu().double().numpy() - ref).max()) / scale
+        bound = max(4 * drift, 2.0 ** -20)
+        print(f"F64PIN bpr:ncl_bpr+ncl_l2reg_{key} err={err:.3e} bound={bound:.3e} ratio={err / bound:.3f}")
+        assert err <= bound and err <= 1e-5, (key, err, bound)
 
 
 @pytest.mark.gpu

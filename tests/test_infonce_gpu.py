@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from f64_pins import pins
 from oracle import oracle_c as C
 from oracle import oracle_np as O
 
@@ -106,25 +107,42 @@ def test_golden_loss_values(Ls, golden, m):
     """gcl.info_nce_loss, ncl.InfoNCE (= ssl4rec.InfoNCE), ssl4rec.batch_softmax_loss outputs."""
     c = golden("contrast.npz")
     z1, z2 = _t(c[f"z1_{m}"]), _t(c[f"z2_{m}"])
+    f64 = pins("contrast")              # the reference's own float64 run (tests/f64_pins.py)
     for temp in (0.1, 0.2, 0.5):
-        assert float(Ls.info_nce_loss(z1, z2, temp)) == pytest.approx(float(c[f"gcl_loss_{m}_{temp}"]), rel=1e-5, abs=2e-6)
+        got = float(Ls.info_nce_loss(z1, z2, temp))
+        assert got == pytest.approx(float(c[f"gcl_loss_{m}_{temp}"]), rel=1e-5, abs=2e-6)
+        f64.check(f"gcl_loss_{m}_{temp}", got)
     for b_cos in (True, False):
         got = float(Ls.InfoNCE(0.3 * z1, 0.3 * z2, 0.2, b_cos))
         assert got == pytest.approx(float(c[f"ncl_infonce_{m}_{int(b_cos)}"]), rel=1e-5, abs=2e-6)
-    assert float(Ls.batch_softmax_loss(z1, z2, 0.2)) == pytest.approx(float(c[f"s4r_bsl_{m}"]), rel=1e-5, abs=2e-6)
+        f64.check(f"ncl_infonce_{m}_{int(b_cos)}", got)
+        f64.check(f"s4r_infonce_{m}_{int(b_cos)}", got)
+    got = float(Ls.batch_softmax_loss(z1, z2, 0.2))
+    assert got == pytest.approx(float(c[f"s4r_bsl_{m}"]), rel=1e-5, abs=2e-6)
+    f64.check(f"s4r_bsl_{m}", got)
 
 
 @pytest.mark.parametrize("m", [7, 257])
 def test_golden_info_nce_loss_grads(Ls, golden, m):
+    """gcl.info_nce_loss gradients: the fp32 goldens at 2e-5, and the reference's float64 run under the bound rule of
+    tests/f64_pins.py.  At m = 7 the positive carries p_ii ~ 0.9 of its row's softmax: forming p_ii - 1 from an lse
+    stored in fp32 missed the bound by up to 1.24x on every engine, until the diagonal was carried as q = 1 - p_ii
+    (functional._InfoNCEStats)."""
     c = golden("contrast.npz")
     z1, z2 = _t(c[f"z1_{m}"], True), _t(c[f"z2_{m}"], True)
     Ls.info_nce_loss(z1, z2, 0.2).backward()
     _gclose(z1.grad, c[f"gcl_g1_{m}"])
     _gclose(z2.grad, c[f"gcl_g2_{m}"])
+    pins("contrast").check(f"gcl_g1_{m}", z1.grad)
+    pins("contrast").check(f"gcl_g2_{m}", z2.grad)
 
 
 @pytest.mark.parametrize("b_cos", [1, 0])
 def test_golden_ncl_infonce_grads(Ls, golden, b_cos):
+    """ncl.InfoNCE gradients at m = 257.  b_cos = False saturates the softmax (p_ii = 1 - 1e-11): its float64 keys are
+    ill-conditioned (the reference's own fp32 drift is 6.2e-5 / 6.9e-5 of max|f64|), and exp(s_ii - lse_i) - 1 with
+    lse_i ~ 29 stored in fp32 missed even that bound by up to 9.7x (~ulp(29) = 1.9e-6 absolute on p_ii); with the
+    diagonal carried as q = 1 - p_ii the HIP path is ~2.3e-6 here, below the reference's own drift."""
     c = golden("contrast.npz")
     z1, z2 = _t(0.3 * c["z1_257"], True), _t(0.3 * c["z2_257"], True)
     Ls.InfoNCE(z1, z2, 0.2, bool(b_cos)).backward()
@@ -134,6 +152,8 @@ def test_golden_ncl_infonce_grads(Ls, golden, b_cos):
     floor = 1e-8 if b_cos else 1e-5 * float(np.abs(0.3 * c["z2_257"]).max()) / (257 * 0.2)
     _gclose(z1.grad, c[f"ncl_infonce_g1_257_{b_cos}"], floor=floor)
     _gclose(z2.grad, c[f"ncl_infonce_g2_257_{b_cos}"], floor=floor)
+    pins("contrast").check(f"ncl_infonce_g1_257_{b_cos}", z1.grad)
+    pins("contrast").check(f"ncl_infonce_g2_257_{b_cos}", z2.grad)
 
 
 def test_golden_ncl_structure_and_prototype(Ls, golden, engine):
@@ -171,6 +191,10 @@ def test_golden_ncl_structure_and_prototype(Ls, golden, engine):
     # rounding of g (1e-6) shows up at ~1.6e-5 of the result on every engine (three bf16 planes: 7 of 5120 elements)
     gx = x64.grad.cpu().numpy()
     _gclose(x0.grad, gx, floor=5e-5 * np.abs(gx).max())
+    f64 = pins("contrast")
+    f64.check("ncl_ssl", float(ssl))
+    f64.check("ncl_ssl_gctx", ctx.grad)
+    f64.check("ncl_ssl_gx0", x0.grad)
     x0p = _t(c["ncl_x0"], True)
     proto = Ls.ProtoNCE_loss(x0p, c["ncl_uidx"], c["ncl_iidx"], nu, _t(c["ncl_ucent"]), _t(c["ncl_u2c"]),
                              _t(c["ncl_icent"]), _t(c["ncl_i2c"]), float(c["ncl_ssl_temp"]), float(c["ncl_proto_reg"]),
@@ -178,6 +202,8 @@ def test_golden_ncl_structure_and_prototype(Ls, golden, engine):
     assert float(proto) == pytest.approx(float(c["ncl_proto"]), rel=rel)
     proto.backward()
     _gclose(x0p.grad, c["ncl_proto_gx0"], floor=1e-13)
+    f64.check("ncl_proto", float(proto))
+    f64.check("ncl_proto_gx0", x0p.grad)
 
 
 @pytest.mark.parametrize("m,n,d,normalize,sym", [(64, 333, 64, True, False), (300, 300, 64, True, True),

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from f64_pins import pins
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +112,11 @@ def test_mhcn_forward_matches_reference(golden):
         ((fu * torch.from_numpy(z["wu"]).to(DEV)).sum() + (fi * torch.from_numpy(z["wi"]).to(DEV)).sum() + ss).backward()
         _close(enc.user_embeddings.grad, z["grad_user"], 2e-5)
         _close(enc.item_embeddings.grad, z["grad_item"], 2e-5)
+        f64 = pins("mhcn")              # the reference's own float64 run (tests/f64_pins.py)
+        for key, got in (("final_user", fu), ("final_item", fi), ("batch_user", bu), ("batch_pos", bp), ("batch_neg", bn),
+                         ("ss_loss", float(ss)), ("grad_user", enc.user_embeddings.grad),
+                         ("grad_item", enc.item_embeddings.grad)):
+            f64.check(key, got)
 
 
 def test_mhcn_raw_product_feeds_the_next_layer(golden):
@@ -136,8 +142,14 @@ def test_sept_social_encoder_and_neighbor_discrimination(golden):
     (final * torch.from_numpy(z["w"]).to(DEV)).sum().backward()
     _close(ego.grad, z["enc_grad"], 2e-5)
     users = ego.detach()[:n_u]
-    _close(sept_encoder(users, _graph(z, "social"), k, combine="sum"), z["friend_view"])
-    _close(sept_encoder(users, _graph(z, "sharing"), k, combine="sum"), z["sharing_view"])
+    friend = sept_encoder(users, _graph(z, "social"), k, combine="sum")
+    sharing = sept_encoder(users, _graph(z, "sharing"), k, combine="sum")
+    _close(friend, z["friend_view"])
+    _close(sharing, z["sharing_view"])
+    f64 = pins("sept_social")           # the reference's own float64 run (tests/f64_pins.py)
+    for key, got in (("rec_user", final[:n_u]), ("rec_item", final[n_u:]), ("enc_grad", ego.grad),
+                     ("friend_view", friend), ("sharing_view", sharing)):
+        f64.check(key, got)
     uniq = torch.unique(torch.from_numpy(z["u_idx"])).to(DEV)
     emb = torch.from_numpy(z["friend_view"]).to(DEV).requires_grad_(True)
     aug = torch.from_numpy(z["aug_user"]).to(DEV)
@@ -145,6 +157,12 @@ def test_sept_social_encoder_and_neighbor_discrimination(golden):
     assert float(loss) == pytest.approx(float(z["nd_loss"]), rel=1e-5)
     loss.backward()
     _close(emb.grad, z["nd_grad"], 2e-5)
+    # the float64 run fed the loss its own friend view, as the fp32 run did: here, the HIP path's
+    emb = friend.detach().clone().requires_grad_(True)
+    loss = losses.neighbor_discrimination(torch.from_numpy(z["positive"]).to(DEV), emb[uniq], aug[uniq], 0.1)
+    loss.backward()
+    f64.check("nd_loss", float(loss))
+    f64.check("nd_grad", emb.grad)
 
 
 def test_buir_sparse_dropout_masked_symmetric_backward(golden):
@@ -172,6 +190,8 @@ def test_buir_sparse_dropout_masked_symmetric_backward(golden):
     _close(final, z["final"])
     (final * torch.from_numpy(z["w"]).to(DEV)).sum().backward()
     _close(x.grad, z["grad"], 2e-5)
+    pins("buir").check("final", final)  # the reference's own float64 run (tests/f64_pins.py)
+    pins("buir").check("grad", x.grad)
     # a counter-based mask: edge_id = mirror gives the transposed mask without a gather
     m = g.mirror_perm()
     b1 = Fn.edge_mask_bits(g.nnz, 0.3, 5, DEV)

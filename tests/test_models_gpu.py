@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from f64_pins import pins
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +38,9 @@ def test_interaction_and_lgcn_encoder_match_reference(golden):
         gref = p[f"raw_grad_K{k}"]
         got = torch.cat([enc.embedding_dict["user_emb"].grad, enc.embedding_dict["item_emb"].grad]).cpu().numpy()
         np.testing.assert_allclose(got, gref, rtol=2e-5, atol=2e-5 * np.abs(gref).max())
+        pins("propagation").check(f"raw_mean_K{k}", final)
+        pins("propagation").check(f"raw_last_K{k}", all_emb[-1])
+        pins("propagation").check(f"raw_grad_K{k}", got)
 
 
 def test_lightgcn_module_cfg1():

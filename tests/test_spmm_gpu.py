@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from f64_pins import pins
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +123,10 @@ def test_golden_lgcn_encoder_raw_adjacency(ra, golden, k):
     close(layers[-1], p[f"raw_last_K{k}"].astype(np.float64), rt=2e-5)
     (final * torch.from_numpy(p["w"]).cuda()).sum().backward()
     close(x0.grad, p[f"raw_grad_K{k}"].astype(np.float64), rt=2e-5)
+    f64 = pins("propagation")           # the reference's own float64 run (tests/f64_pins.py)
+    f64.check(f"raw_mean_K{k}", final)
+    f64.check(f"raw_last_K{k}", layers[-1])
+    f64.check(f"raw_grad_K{k}", x0.grad)
 
 
 @pytest.mark.parametrize("k", [2, 3])
@@ -141,6 +146,8 @@ def test_golden_lgcn_encoder_normalised(ra, golden, k):
     close(final, p[f"norm_mean_K{k}"].astype(np.float64), rt=2e-5)
     (final * torch.from_numpy(p["w"][: xs.shape[0]]).cuda()).sum().backward()
     close(xs.grad, p[f"norm_grad_K{k}"].astype(np.float64), rt=2e-5)
+    pins("propagation").check(f"norm_mean_K{k}", final)
+    pins("propagation").check(f"norm_grad_K{k}", xs.grad)
 
 
 def test_golden_sept_encoder(ra, golden):
@@ -157,6 +164,8 @@ def test_golden_sept_encoder(ra, golden):
     close(final, p["sept_mean_K2"].astype(np.float64), rt=2e-5)
     (final * torch.from_numpy(p["w"]).cuda()).sum().backward()
     close(x0.grad, p["sept_grad_K2"].astype(np.float64), rt=5e-5)
+    pins("propagation").check("sept_mean_K2", final)
+    pins("propagation").check("sept_grad_K2", x0.grad)
 
 
 def test_cfg1_lightgcn_forward_sum_of_layers(ra):

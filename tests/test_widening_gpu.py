@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from f64_pins import pins
 from oracle import oracle_np as O
 
 pytestmark = pytest.mark.gpu
@@ -20,6 +21,7 @@ def test_row_normalised_operator_matches_reference(golden):
     assert np.array_equal(graph.rowptr.cpu().numpy(), g["indptr"])
     assert np.array_equal(graph.col.cpu().numpy().astype(np.int64), g["indices"])
     np.testing.assert_allclose(graph.val.cpu().numpy(), g["data"], rtol=3e-7)
+    pins("rownorm").check("data", graph.val)      # the reference's own float64 run (tests/f64_pins.py)
     rowsum = np.add.reduceat(np.append(g["data"], 0.0), g["indptr"][:-1])[np.diff(g["indptr"]) > 0]
     np.testing.assert_allclose(rowsum, 1.0, rtol=1e-6)                      # D^-1 A: rows sum to one
     rng = np.random.default_rng(0)
@@ -66,7 +68,8 @@ def test_neighbor_discrimination_matches_dense(b, k, d):
 @pytest.mark.parametrize("m", [7, 257])
 def test_grace_dual_branch_infonce_matches_reference(golden, monkeypatch, engine, m):
     """losses.grace_infonce_loss against the reference's own DualBranchContrast outputs (values and both
-    gradients), all three mask variants, both MFMA engines."""
+    gradients), all three mask variants, both MFMA engines; and against its float64 run (tests/f64_pins.py).  At
+    m = 7, tau = 0.2 the positive dominates its row (see test_infonce_gpu.py::test_golden_info_nce_loss_grads)."""
     from recommendation_amd.losses import grace_infonce_loss
     from recommendation_amd import functional as _Fn
     monkeypatch.setattr(_Fn, "INFONCE_ENGINE", engine)
@@ -81,6 +84,11 @@ def test_grace_dual_branch_infonce_matches_reference(golden, monkeypatch, engine
             loss.backward()
             for got, want in ((h1.grad, g[f"g1_{key}"]), (h2.grad, g[f"g2_{key}"])):
                 np.testing.assert_allclose(got.cpu().numpy(), want, rtol=1e-4, atol=1e-5 * np.abs(want).max() + 1e-9)
+            f64 = pins("grace")         # the reference's own float64 run (tests/f64_pins.py); m = 257, tau = 0.5 dropped
+            if f"loss_{key}" not in f64.dropped:
+                f64.check(f"loss_{key}", float(loss))
+                f64.check(f"g1_{key}", h1.grad)
+                f64.check(f"g2_{key}", h2.grad)
 
 
 @pytest.mark.parametrize("engine", ["auto", "b3", "f32"])
