@@ -685,6 +685,27 @@ int32_t gcr_gather_rows_f32(const float* table, const int64_t* idx, int64_t n, i
 int32_t gcr_scatter_add_rows_f32(const float* src, const int64_t* idx, int64_t n, int32_t d, int64_t n_rows, float* out,
                                  void* stream);
 
+/*
+ * Batch-row gather fused with V seeded dropout views (ssl4rec.py:192-196: `emb = initial_item[i]`, then two
+ * `nn.Dropout(p)` draws of it).  out [(1 + n_views) * n, d], stacked: block 0 is table[idx] with gcr_gather_rows_f32's
+ * contract (an id outside [0, n_rows) gives a zero row); block 1 + v is keep_v ? x * (1.0f / (1.0f - p)) : 0, nn.Dropout
+ * in training mode (p = 0: copies, p = 1: zeros).  Bit e = i * d + c of view v is bit e of the bitmap that
+ * gcr_edge_mask_bits draws for (n * d, p, seed + v) (same Philox stream and 24-bit grid, keep = u >= p); the kernel
+ * recomputes it, one Philox call per four columns when d % 4 == 0, and neither writes nor reads a mask buffer.
+ * keep_bits non-NULL ([n_views, ceil(n * d / 32)] words in that bit order; needs p < 1): those bits are used instead,
+ * which replays a recorded mask.  n_views in 1..4, any d >= 1 (16-B lanes when d % 4 == 0 and the pointers are 16-B
+ * aligned).
+ * Backward: grad_table[idx[i], c] += g_0[i, c] + 1 / (1 - p) * sum_v keep_v[i, c] * g_{1 + v}[i, c] for grad_out
+ * [(1 + n_views) * n, d], the masks regenerated from the same (p, seed) or read from the same keep_bits: ONE float
+ * atomic per element (256-B contiguous row segments), duplicate ids add up, ids outside [0, n_rows) are skipped
+ * (gcr_scatter_add_rows_f32's contract).  grad_table is accumulated into: the caller zeroes it.
+ */
+int32_t gcr_gather_dropout_f32(const float* table, const int64_t* idx, int64_t n, int32_t d, int64_t n_rows, float p,
+                               uint64_t seed, int32_t n_views, const uint32_t* keep_bits, float* out, void* stream);
+int32_t gcr_gather_dropout_bwd_f32(const float* grad_out, const int64_t* idx, int64_t n, int32_t d, int64_t n_rows,
+                                   float p, uint64_t seed, int32_t n_views, const uint32_t* keep_bits, float* grad_table,
+                                   void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Raw id -> dense id maps of graph ingest, on the device.
  *   order 0  dense id = rank of the key among the DISTINCT keys in ascending unsigned order

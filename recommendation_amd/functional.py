@@ -1374,3 +1374,50 @@ def gather_rows(table, idx):
         if lo < 0 or hi >= table.shape[0]:
             raise IndexError(f"gather_rows: index {lo if lo < 0 else hi} is out of bounds for a table of {table.shape[0]} rows")
     return _GatherRows.apply(table, idx)
+
+
+class _GatherDropoutViews(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, idx, p, seed, n_views, keep_bits):
+        table = table.contiguous()
+        n, d = idx.numel(), table.shape[1]
+        out = torch.empty((1 + n_views) * n, d, dtype=torch.float32, device=table.device)
+        _lib.check(_lib.lib().gcr_gather_dropout_f32(_lib.dptr(table), _lib.dptr(idx), n, d, table.shape[0], p, seed, n_views,
+                                                     _lib.dptr(keep_bits), _lib.dptr(out), _lib.cur_stream(table.device)),
+                   "gcr_gather_dropout_f32")
+        ctx.save_for_backward(idx, *(() if keep_bits is None else (keep_bits,)))      # no mask of its own: (p, seed)
+        ctx.args = (table.shape, p, seed, n_views)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, *bits = ctx.saved_tensors
+        shape, p, seed, n_views = ctx.args
+        gt = torch.zeros(shape, dtype=torch.float32, device=g.device)
+        g = g.contiguous()
+        _lib.check(_lib.lib().gcr_gather_dropout_bwd_f32(_lib.dptr(g), _lib.dptr(idx), idx.numel(), shape[1], shape[0], p, seed,
+                                                         n_views, _lib.dptr(bits[0] if bits else None), _lib.dptr(gt),
+                                                         _lib.cur_stream(g.device)), "gcr_gather_dropout_bwd_f32")
+        return gt, None, None, None, None, None
+
+
+def gather_dropout_views(table, idx, p, seed, n_views=2, keep_bits=None):
+    """`emb = table[idx]` and `n_views` training-mode `nn.Dropout(p)` draws of it (ssl4rec.py:192-196), stacked
+    [(1 + n_views) * n, d] in one kernel: rows [0, n) are `gather_rows(table, idx)` (same contract for ids outside the
+    table), rows [(1 + v) n, (2 + v) n) are view v, `keep_v ? emb * (1 / (1 - p)) : 0`.  Bit i * d + c of view v's mask is
+    that bit of `edge_mask_bits(n * d, p, seed + v)`; the kernel recomputes it and stores no mask, and the backward
+    regenerates it: one float atomic per table element for all 1 + n_views gradient blocks.  keep_bits (int32
+    [n_views, ceil(n * d / 32)], p < 1) replays recorded masks instead of drawing."""
+    _lib.require_cuda(table, keep_bits)
+    if table.dim() != 2 or table.dtype != torch.float32:
+        raise ValueError("table must be float32 [N, d]")
+    p, n_views = float(p), int(n_views)
+    if not (0.0 <= p <= 1.0) or not (1 <= n_views <= 4):
+        raise ValueError("p in [0, 1] and n_views in 1..4")
+    idx = _as_index(idx, table.device).reshape(-1)
+    if keep_bits is not None:
+        n_words = (idx.numel() * table.shape[1] + 31) // 32
+        if keep_bits.dtype != torch.int32 or tuple(keep_bits.shape) != (n_views, n_words) or p >= 1.0:
+            raise ValueError(f"keep_bits must be int32 [{n_views}, {n_words}] (and p < 1)")
+        keep_bits = keep_bits.contiguous()
+    return _GatherDropoutViews.apply(table, idx, p, int(seed) & (2 ** 64 - 1), n_views, keep_bits)
