@@ -672,6 +672,51 @@ int32_t gcr_spgemm_expand_f32(const int64_t* a_rowptr, const int32_t* a_col, con
                               const float* b_val, const int64_t* offset, int64_t* out_row, int64_t* out_col,
                               float* out_val, void* stream);
 
+/* One torch.optim.SGD step with momentum (directau.py:214: dampening 0, no nesterov): g = grad + weight_decay * p;
+ * buf = first_step ? g : momentum * buf + g; p -= lr * buf.  One streaming pass (reads p, g, buf; writes p, buf).
+ * momentum_buf may be NULL when momentum == 0 (plain SGD).  Pointers 16-B aligned. */
+int32_t gcr_sgd_momentum_step_f32(float* param, const float* grad, float* momentum_buf, int64_t n, float lr,
+                                  float momentum, float weight_decay, int32_t first_step, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DirectAU: alignment + uniformity over gathered, L2-normalised batch rows.
+ * --------------------------------------------------------------------------------------------- */
+/* bytes of workspace the DirectAU forward needs for `batch` rows of width d */
+int64_t gcr_directau_workspace_bytes(int64_t batch, int32_t d);
+
+/*
+ * replaces  user_emb[user_idx] / item_emb[pos_idx] / item_emb[neg_idx]  directau.py:222,
+ *           alignment  directau.py:245-246,  uniformity  directau.py:248-251  (F.normalize, torch.pdist, exp, mean),
+ *           the norms of l2_reg_loss  directau.py:35-36, 226.
+ * Sets: s = 0 rows user_tab[u_idx], s = 1 item_tab[i_idx], s = 2 item_tab[j_idx]; n_sets in 1..3 takes the first
+ * n_sets of them (1: uniformity of one tensor; 2: calculate_loss(u, i)).  An index pointer may be NULL: rows 0..batch-1
+ * of the table itself.  An id outside its table gives a zero row (gcr_gather_rows_f32's contract).
+ * With x^ = x / max(|x|, 1e-12) it writes, without a host read-back,
+ *   sums[8] = { A_pos = sum_b |x^_u[b] - x^_p[b]|^2, A_neg = sum_b |x^_u[b] - x^_n[b]|^2,
+ *               G_u, G_p, G_n with G_s = sum_{a<b} exp(-t |x^_s[a] - x^_s[b]|^2)   (pairs of POSITIONS: duplicate ids count),
+ *               Q_u, Q_p, Q_n with Q_s = sum_b |x_s[b]|^2 }          (entries of absent sets are 0)
+ * and for the backward inv_norm[3 * batch] = 1 / max(|x|, 1e-12), r[3 * batch]: r_s[a] = sum_b' e_ab and
+ * o[3 * batch, d]: o_s[a, :] = sum_b' e_ab x^_s[b, :]  (set-major; r and o both NULL: sums only).  sum_b' runs over the
+ * positions b != a that hold ANOTHER table row than a: a recurring row is a pair with e = 1 in G, but its gradient share
+ * e (x^_a - x^_b) is exactly 0, and leaving it out of r and o keeps r x^_a - o_a free of two large cancelling parts.
+ * Two launches; every output is bitwise reproducible (no float atomics).  d even, <= 512; batch >= 1; tables < 2^31 rows.
+ */
+int32_t gcr_directau_fwd_f32(const float* user_tab, const float* item_tab, int32_t d, const int64_t* u_idx,
+                             const int64_t* i_idx, const int64_t* j_idx, int64_t batch, int32_t n_sets, int64_t n_users,
+                             int64_t n_items, float t, float* sums, float* inv_norm, float* r, float* o, void* workspace,
+                             void* stream);
+
+/*
+ * Backward of the above (the autograd of directau.py:223-228 from the final tables down): g_sums[8] (device) is
+ * dL / d sums.  Per row of set s:  g^ = 2 g_A (x^_s - x^_other) - 2 t g_G (r x^ - o), then the normalize backward
+ * inv_norm (g^ - x^ <x^, g^>) plus 2 g_Q x, added to row idx of g_user_tab / g_item_tab (caller-zeroed; float atomics,
+ * duplicate ids add up, ids out of range are skipped).  One launch.
+ */
+int32_t gcr_directau_bwd_f32(const float* user_tab, const float* item_tab, int32_t d, const int64_t* u_idx,
+                             const int64_t* i_idx, const int64_t* j_idx, int64_t batch, int32_t n_sets, int64_t n_users,
+                             int64_t n_items, float t, const float* inv_norm, const float* r, const float* o,
+                             const float* g_sums, float* g_user_tab, float* g_item_tab, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

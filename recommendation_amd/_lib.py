@@ -109,6 +109,12 @@ SIGNATURES = {
                                     c_float, _P]),
     "gcr_adam_step_dev_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, _P,
                                         c_float, _P]),
+    "gcr_sgd_momentum_step_f32": (c_int32, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_int32, _P]),
+    "gcr_directau_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "gcr_directau_fwd_f32": (c_int32, [_P, _P, c_int32, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_float,
+                                       _P, _P, _P, _P, _P, _P]),
+    "gcr_directau_bwd_f32": (c_int32, [_P, _P, c_int32, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_float,
+                                       _P, _P, _P, _P, _P, _P, _P]),
     "gcr_mask_columns_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "gcr_spgemm_expand_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_csr_lookup_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P]),

@@ -63,6 +63,44 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float4* __restrict__ p, 
   }
 }
 
+// torch.optim.SGD(momentum, dampening = 0, nesterov = False): g = grad + wd p; buf = first ? g : mu buf + g; p -= lr buf
+__device__ __forceinline__ void sgd_point(float& p, float g, float* buf, float lr, float mu, float wd, bool first) {
+  g = fmaf(wd, p, g);
+  float step = g;
+  if (buf != nullptr) {
+    step = first ? g : fmaf(mu, *buf, g);
+    *buf = step;
+  }
+  p = fmaf(-lr, step, p);
+}
+
+__global__ __launch_bounds__(256) void sgd_momentum_step_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                                float4* __restrict__ buf, int64_t n4, int tail, float lr,
+                                                                float mu, float wd, int first) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    float4 pp = p[i];
+    const float4 gg = g[i];
+    float4 bb = (buf != nullptr && !first) ? buf[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float* bp = buf != nullptr ? &bb.x : nullptr;
+    sgd_point(pp.x, gg.x, bp, lr, mu, wd, first);
+    sgd_point(pp.y, gg.y, bp ? bp + 1 : nullptr, lr, mu, wd, first);
+    sgd_point(pp.z, gg.z, bp ? bp + 2 : nullptr, lr, mu, wd, first);
+    sgd_point(pp.w, gg.w, bp ? bp + 3 : nullptr, lr, mu, wd, first);
+    p[i] = pp;
+    if (buf != nullptr) buf[i] = bb;
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < tail) {        // the last n % 4 elements, one per thread
+    const int64_t i = 4 * n4 + threadIdx.x;
+    float* ps = reinterpret_cast<float*>(p);
+    float* bs = reinterpret_cast<float*>(buf);
+    float pv = ps[i];
+    float bv = (bs != nullptr && !first) ? bs[i] : 0.f;
+    sgd_point(pv, reinterpret_cast<const float*>(g)[i], bs != nullptr ? &bv : nullptr, lr, mu, wd, first);
+    ps[i] = pv;
+    if (bs != nullptr) bs[i] = bv;
+  }
+}
+
 __global__ __launch_bounds__(256) void mask_columns_kernel(const float* __restrict__ x, int64_t n, int d,
                                                            const uint32_t* __restrict__ keep_bits, float* __restrict__ out) {
   const int64_t total = n * (int64_t)d;
@@ -169,6 +207,18 @@ extern "C" int32_t gcr_adam_step_dev_f32(float* param, const float* grad, const 
   hipLaunchKernelGGL(adam_step_kernel, dim3(ops_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, (float4*)param,
                      (const float4*)grad, (const float4*)grad2, (const float4*)grad3, (float4*)exp_avg, (float4*)exp_avg_sq,
                      n / 4, (int)(n & 3), 0.f, beta1, beta2, eps, 0.f, weight_decay, grad_scale, step_dev, lr);
+  return GCR_LAUNCH_STATUS();
+}
+
+extern "C" int32_t gcr_sgd_momentum_step_f32(float* param, const float* grad, float* momentum_buf, int64_t n, float lr,
+                                             float momentum, float weight_decay, int32_t first_step, void* stream) {
+  GCR_CHECK_ARG(n >= 0 && lr >= 0.f && momentum >= 0.f && weight_decay >= 0.f);
+  if (n == 0) return GCR_OK;
+  GCR_CHECK_ARG(param && grad && (momentum_buf != nullptr || momentum == 0.f));
+  GCR_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0);
+  hipLaunchKernelGGL(sgd_momentum_step_kernel, dim3(ops_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (float4*)param, (const float4*)grad, (float4*)momentum_buf, n / 4, (int)(n & 3), lr, momentum,
+                     weight_decay, (int)(first_step != 0));
   return GCR_LAUNCH_STATUS();
 }
 

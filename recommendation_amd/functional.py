@@ -847,6 +847,100 @@ def bpr_sums(user_tab, item_tab, u_idx, i_idx, j_idx, variant=BPR_NCL):
 
 
 # ---------------------------------------------------------------------------------------------
+# DirectAU: alignment + uniformity sums (directau.py:240-251)
+# ---------------------------------------------------------------------------------------------
+AU_NATIVE_MAX_DIM = 512          # gcr_directau_fwd_f32 runs any multiple of 16 up to here as it is
+
+
+class _AuSums(torch.autograd.Function):
+    """sums = [A_pos, A_neg, G_u, G_p, G_n, Q_u, Q_p, Q_n] through gcr_directau_fwd/bwd_f32 (include/gcr.h); n_sets
+    1 / 2 / 3 takes the row sets u / u, p / u, p, n.  The forward keeps 1 / |x|, r and o, so the backward is one launch
+    that adds the row gradients straight into the table gradients."""
+
+    @staticmethod
+    def forward(ctx, user_tab, item_tab, u_idx, i_idx, j_idx, n_sets, t):
+        L = _lib.lib()
+        user_tab = user_tab.contiguous()
+        item_tab = None if item_tab is None else item_tab.contiguous()
+        batch = u_idx.numel() if u_idx is not None else user_tab.shape[0]
+        d, dev = user_tab.shape[1], user_tab.device
+        n_items = 0 if item_tab is None else item_tab.shape[0]
+        want_grad = ctx.needs_input_grad[0] or (item_tab is not None and ctx.needs_input_grad[1])
+        sums = torch.empty(8, dtype=torch.float32, device=dev)
+        inv = torch.empty(3 * batch, dtype=torch.float32, device=dev)
+        r = torch.empty(3 * batch, dtype=torch.float32, device=dev) if want_grad else None
+        o = torch.empty(3 * batch, d, dtype=torch.float32, device=dev) if want_grad else None
+        ws = torch.empty(int(L.gcr_directau_workspace_bytes(batch, d)) // 4, dtype=torch.float32, device=dev)
+        _lib.check(L.gcr_directau_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
+                                          _lib.dptr(j_idx), batch, n_sets, user_tab.shape[0], n_items, float(t),
+                                          _lib.dptr(sums), _lib.dptr(inv), _lib.dptr(r), _lib.dptr(o), _lib.dptr(ws),
+                                          _lib.cur_stream(dev)), "gcr_directau_fwd_f32")
+        if want_grad:
+            ctx.save_for_backward(user_tab, item_tab, u_idx, i_idx, j_idx, inv, r, o)
+            ctx.n_sets, ctx.t, ctx.batch = n_sets, float(t), batch
+            ctx.stacked = item_tab is not None and _halves_of_one_table(user_tab, item_tab)
+        ctx.mark_non_differentiable(*[k for k in (u_idx, i_idx, j_idx) if k is not None])
+        return sums
+
+    @staticmethod
+    def backward(ctx, g_sums):
+        user_tab, item_tab, u_idx, i_idx, j_idx, inv, r, o = ctx.saved_tensors
+        gs = g_sums.contiguous().to(torch.float32)
+        gi = None
+        if ctx.stacked:             # the halves of one stacked table: one gradient buffer (_SplitRows.backward hands it on)
+            gfull = torch.zeros(user_tab.shape[0] + item_tab.shape[0], user_tab.shape[1], dtype=torch.float32,
+                                device=user_tab.device)
+            gu, gi = gfull[: user_tab.shape[0]], gfull[user_tab.shape[0]:]
+        else:
+            gu = torch.zeros_like(user_tab)
+            if item_tab is not None:
+                gi = torch.zeros_like(item_tab)
+        _lib.check(_lib.lib().gcr_directau_bwd_f32(
+            _lib.dptr(user_tab), _lib.dptr(item_tab), user_tab.shape[1], _lib.dptr(u_idx), _lib.dptr(i_idx), _lib.dptr(j_idx),
+            ctx.batch, ctx.n_sets, user_tab.shape[0], 0 if item_tab is None else item_tab.shape[0], ctx.t, _lib.dptr(inv),
+            _lib.dptr(r), _lib.dptr(o), _lib.dptr(gs), _lib.dptr(gu), _lib.dptr(gi), _lib.cur_stream(user_tab.device)),
+            "gcr_directau_bwd_f32")
+        return gu, gi, None, None, None, None, None
+
+
+def _au_sums(user_tab, item_tab, u_idx, i_idx, j_idx, n_sets, t):
+    _lib.require_cuda(user_tab, item_tab)
+    tabs = [x for x in (user_tab, item_tab) if x is not None]
+    if any(x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] != user_tab.shape[1] for x in tabs):
+        raise ValueError("user_tab / item_tab must be float32 [*, d] with the same d")
+    dev = user_tab.device
+    idx = [None if k is None else _as_index(k, dev).reshape(-1) for k in (u_idx, i_idx, j_idx)]
+    sizes = [user_tab.shape[0], None if item_tab is None else item_tab.shape[0], None if item_tab is None else item_tab.shape[0]]
+    lens = {k.numel() if k is not None else sizes[s] for s, k in enumerate(idx[:n_sets])}
+    if len(lens) != 1 or min(lens) < 1:
+        raise ValueError("the row sets must have one common length >= 1 (an absent index vector stands for all rows of its table)")
+    d = user_tab.shape[1]
+    if d > AU_NATIVE_MAX_DIM:
+        raise ValueError(f"embedding dim must be <= {AU_NATIVE_MAX_DIM}")
+    if d % 16:
+        # other widths: zero columns up to the next multiple of 16 change neither a norm nor a distance.  This copies the
+        # WHOLE tables (and their gradients on the way back) every call and gives up the shared gradient buffer of a
+        # stacked table: fine for [B, d] inputs, a full-table pass per step for a large embedding table
+        pad = (0, 16 - d % 16)
+        user_tab = torch.nn.functional.pad(user_tab, pad)
+        item_tab = None if item_tab is None else torch.nn.functional.pad(item_tab, pad)
+    return _AuSums.apply(user_tab, item_tab, idx[0], idx[1], idx[2], int(n_sets), float(t))
+
+
+def au_sums(user_tab, item_tab, u_idx, i_idx, j_idx=None, t=2.0):
+    """The sums DirectAU's losses are made of (directau.py:222-226, 240-251), for the row sets u = user_tab[u_idx],
+    p = item_tab[i_idx] and — with j_idx — n = item_tab[j_idx], x^ = F.normalize(x, dim=-1).  Differentiable float32 [8]:
+        [A_pos = sum_b |u^_b - p^_b|^2, A_neg = sum_b |u^_b - n^_b|^2, G_u, G_p, G_n, Q_u, Q_p, Q_n],
+        G_s = sum over the pairs a < b of batch positions of exp(-t |x^_a - x^_b|^2),  Q_s = sum_b |x_b|^2
+    (entries of an absent set are 0).  An index vector may be None: all rows of the table, in order.  Gathers, normalise,
+    the all-pairs reduction and the norms are two launches, the backward one (gcr_directau_fwd_f32 / _bwd_f32); ids out
+    of range give zero rows and no gradient.  Widths that are a multiple of 16 up to 512 run as they are; any other
+    width up to 512 is zero-padded to the next multiple of 16, which copies both tables in full on every call (use a
+    multiple of 16 for a large embedding table)."""
+    return _au_sums(user_tab, item_tab, u_idx, i_idx, j_idx, 3 if j_idx is not None else 2, t)
+
+
+# ---------------------------------------------------------------------------------------------
 # negative sampler (N1) and edge-dropout bitmaps (A1)
 # ---------------------------------------------------------------------------------------------
 def neg_sample(user_rowptr, user_items_sorted, u_idx, n_negs, num_items, seed, offset=0, max_trials=101):

@@ -6,6 +6,7 @@ HIP kernels of libgcr (no M x N score matrix is ever materialised).
   batch_softmax_loss                      ssl4rec.py:25-30
   ssl_layer_loss, ProtoNCE_loss           ncl.py:358-375 (NCLModel methods; here plain functions
                                           taking what the methods read from `self`)
+  alignment, uniformity, directau_loss    directau.py:240-251 and the loss lines 223-226 of its training loop
   lightgcn_bce_loss                       lightgcn.py:109-113 (the `loss_type == "bce"` branch of train_model)
 """
 from __future__ import annotations
@@ -85,6 +86,42 @@ def bpr_loss_logsigmoid(user_emb, pos_emb, neg_emb):
 def l2_reg_loss(reg, *args):
     """ncl.py:122-123: reg * sum_x ||x||_F / rows(x) (tiny reductions; stays in torch)."""
     return reg * sum(torch.norm(x, p=2) / x.shape[0] for x in args)
+
+
+def _log_mean_pairs(g, rows, eps=1e-8):
+    """log(mean over the rows (rows - 1) / 2 pairs + 1e-8) of a pair sum G (directau.py:251; the 1e-8 inside the log)."""
+    return torch.log(g / (rows * (rows - 1) / 2.0) + eps)
+
+
+def alignment(x, y):
+    """directau.py:245-246: mean_b |normalize(x_b) - normalize(y_b)|^2 of two [B, d] tensors."""
+    if x.shape != y.shape:
+        raise ValueError("alignment needs two tensors of one shape")
+    return Fn.au_sums(x, y, None, None)[0] / x.shape[0]
+
+
+def uniformity(x, t=2):
+    """directau.py:248-251: log(mean(exp(-t pdist(normalize(x))^2)) + 1e-8) over the B (B - 1) / 2 row pairs; fewer than
+    two rows: 0.0, no gradient."""
+    if x.shape[0] < 2:
+        return torch.tensor(0.0, device=x.device)
+    return _log_mean_pairs(Fn._au_sums(x, None, None, None, None, 1, t)[2], x.shape[0])
+
+
+def directau_loss(user_tab, item_tab, u_idx, i_idx, j_idx, gamma, reg, batch_size, t=2):
+    """directau.py:222-226 from the two final tables and the batch's ids, every sum from ONE fused forward (`Fn.au_sums`):
+        pos_loss = calculate_loss(u, p),  neg_loss = calculate_loss(u, n),  calculate_loss = alignment + gamma *
+        (uniformity(a) + uniformity(b)) / 2,  l2 = l2_reg_loss(reg, u, p, n),  loss = pos_loss - neg_loss + l2 / batch_size.
+    Returns (pos_loss, neg_loss, l2, loss).  uniformity(u) is computed once and enters pos_loss and neg_loss alike: its
+    gradient coefficients add up to exactly 0, the value the reference's autograd reaches up to rounding."""
+    s = Fn.au_sums(user_tab, item_tab, u_idx, i_idx, j_idx, t)
+    rows = len(u_idx) if u_idx is not None else user_tab.shape[0]
+    unif = _log_mean_pairs(s[2:5], rows) if rows >= 2 else torch.zeros(3, device=s.device)
+    pos_loss = s[0] / rows + gamma * (unif[0] + unif[1]) / 2
+    neg_loss = s[1] / rows + gamma * (unif[0] + unif[2]) / 2
+    # ||x||_F = sqrt(Q); the clamp gives an all-zero set the zero gradient torch.norm has there
+    l2 = reg * torch.sqrt(s[5:8].clamp_min(1e-30)).sum() / rows
+    return pos_loss, neg_loss, l2, pos_loss - neg_loss + l2 / batch_size
 
 
 def lightgcn_bce_loss(user_emb, item_emb, pos_u, pos_i, engine=None):

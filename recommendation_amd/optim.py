@@ -1,7 +1,8 @@
 """Fused dense Adam on the embedding tables (the optimiser step on the other side of the hot path):
 `torch.optim.Adam(model.parameters(), lr=...)` of ncl.py:305, lightgcn.py:84, gcl.py:201 (with weight_decay) as ONE
 streaming HIP kernel per parameter (gcr_adam_step_f32): reads p, g, m, v and writes p, m, v once (28 B per element).
-Same update rule and defaults as torch.optim.Adam (no amsgrad, L2 weight_decay folded into the gradient)."""
+Same update rule and defaults as torch.optim.Adam (no amsgrad, L2 weight_decay folded into the gradient).
+`FusedSGD` is directau.py:214's `torch.optim.SGD(lr, momentum=0.9)` the same way (gcr_sgd_momentum_step_f32)."""
 from __future__ import annotations
 
 import torch
@@ -101,3 +102,48 @@ class FusedAdam(torch.optim.Optimizer):
                 st.pop("step_dev", None)
                 if capturable:
                     st["step_dev"] = torch.full((1,), int(st["step"]), dtype=torch.int64, device=p.device)
+
+
+class FusedSGD(torch.optim.Optimizer):
+    """`torch.optim.SGD(params, lr, momentum=0.9)` of directau.py:214 (dampening 0, no nesterov, L2 weight_decay folded
+    into the gradient) as ONE streaming HIP kernel per parameter (gcr_sgd_momentum_step_f32): buf = g on the first step,
+    buf = momentum * buf + g after it, p -= lr * buf.  The group keys and the state key (`momentum_buffer`) are
+    torch.optim.SGD's, so `state_dict()` / `load_state_dict()` pass between the two."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=0.0):
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError("invalid SGD hyper-parameters")
+        # torch.optim.SGD's own defaults for this torch version, so that the param_groups of the two carry the same keys
+        defaults = dict(torch.optim.SGD([torch.zeros(1)], lr=lr, momentum=momentum, weight_decay=weight_decay).defaults)
+        super().__init__(params, defaults)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        L = _lib.lib()
+        for group in self.param_groups:
+            mu = float(group["momentum"])
+            # a torch.optim.SGD state_dict can load these into the group: the kernel implements one setting of them
+            if group.get("nesterov") or group.get("dampening", 0) != 0 or group.get("maximize"):
+                raise ValueError("FusedSGD implements dampening = 0, nesterov = False, maximize = False only")
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                _lib.require_cuda(p, p.grad)
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise ValueError("FusedSGD needs contiguous float32 parameters")
+                st = self.state[p]
+                buf, first = None, False
+                if mu != 0.0:
+                    buf = st.get("momentum_buffer")
+                    first = buf is None
+                    if first:
+                        buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                g = p.grad.contiguous()
+                _lib.check(L.gcr_sgd_momentum_step_f32(_lib.dptr(p), _lib.dptr(g), _lib.dptr(buf), p.numel(),
+                                                       float(group["lr"]), mu, float(group["weight_decay"]), int(first),
+                                                       _lib.cur_stream(p.device)), "gcr_sgd_momentum_step_f32")
+        return loss
