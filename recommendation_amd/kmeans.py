@@ -89,7 +89,18 @@ def run_kmeans(x, k, niter=FAISS_NITER, seed=FAISS_SEED, init_centroids=None,
     with k' = min(k, max(2, n // 39)) exactly as ncl.py:350-351 clamps it (and, with return_info, a dict holding the
     device counter of re-seeded empty clusters).  assign_points=False skips the final search over all n points and
     returns None for the assignment (`assign_to_centroids` gives it later, for all rows or for a batch's rows only).
-    No host synchronisation."""
+    No host synchronisation.
+
+    Resolution.  On the default path (d in {32, 64} after padding, n_train * k <= IMAGE_SEARCH_MAX_PAIRS) the cluster sums
+    are 64-bit fixed point in units of 2^-e, max |x| * 2^e in [2^29, 2^30): every centroid element is the float64 mean of
+    its members within max|x| * 2^-28 + 2^-23 * |mean|, whatever the element's own size — a column a factor 2^28 below the
+    largest entry of the training set is not resolved.  For max |x| < 2^-96 (an all-zero set included) the unit stays at
+    2^-125 and the first term becomes 2^-125.  The float-sum paths (d > 64, or past the thresholds above) carry float32
+    accumulation error instead (1e-5 relative + 1e-5 absolute on inputs up to |x| = 16).  tests/test_kmeans_paths_gpu.py pins
+    every path to these bounds, one Lloyd step at a time.
+    Non-finite input (a NaN or an infinity anywhere in x) is UNDEFINED behaviour: centroids and assignment come back
+    without an error and mean nothing.  Refusing it would take a read-back of a device flag, and the e_step must not
+    synchronise with the host; callers that cannot vouch for their input check it themselves (`torch.isfinite(x).all()`)."""
     _lib.require_cuda(x)
     if x.dim() != 2 or x.dtype != torch.float32:
         raise ValueError("x must be float32 [n, d]")
@@ -127,8 +138,11 @@ def run_kmeans(x, k, niter=FAISS_NITER, seed=FAISS_SEED, init_centroids=None,
         image = torch.empty(int(L.gcr_kmeans_image_bytes(k, d)), dtype=torch.uint8, device=dev)
     incremental = image is not None and INCREMENTAL_UPDATE
     if incremental:
-        # fixed-point scale 2^e with max |x| * 2^e in [2^29, 2^30): exact in f32, computed on the device (no read-back)
-        e = 29.0 - torch.floor(torch.log2(xt.abs().max().clamp_min(1e-30)))
+        # fixed-point scale 2^e with max |x| * 2^e in [2^29, 2^30): exact in f32, computed on the device (no read-back).
+        # The floor 2^-96 under max |x| bounds e by 125, so 2^e and 2^-e stay finite normal float32 (with the former floor
+        # 1e-30 an all-zero set, or any max |x| < 2^-98, gave e > 127: 2^e = inf, 2^-e = 0, 0 * inf = NaN); below it the sums
+        # are kept in units of 2^-125.  max |x| < 2^128 gives e >= -98 by itself.
+        e = 29.0 - torch.floor(torch.log2(xt.abs().max().clamp_min(2.0 ** -96)))
         qscale = torch.stack([torch.exp2(e), torch.exp2(-e)]).to(torch.float32)
         sums_q = torch.zeros(copies, k, d, dtype=torch.int64, device=dev)
         counts_i = torch.zeros(copies, k, dtype=torch.int32, device=dev)
