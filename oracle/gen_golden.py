@@ -424,37 +424,120 @@ def _lift_class_methods(path, class_name, method_names, extra_ns=None, top_level
     return cls, ns
 
 
-def _csr_dict(prefix, m):
+def _csr_dict(prefix, m, ints=lambda a: np.asarray(a).astype(np.int64)):
     m = m.tocsr().astype(np.float32)
     m.sum_duplicates()
     m.sort_indices()
-    return {f"{prefix}_indptr": m.indptr.astype(np.int64), f"{prefix}_indices": m.indices.astype(np.int64),
-            f"{prefix}_data": m.data.astype(np.float32), f"{prefix}_shape": np.array(m.shape, dtype=np.int64)}
+    return {f"{prefix}_indptr": ints(m.indptr), f"{prefix}_indices": ints(m.indices),
+            f"{prefix}_data": m.data.astype(np.float32), f"{prefix}_shape": ints(np.array(m.shape))}
 
 
-def gen_mhcn():
-    """tests/golden/mhcn.npz: univariate/mhcn.py's own MHCN.build_hyper_adj_mats (:340-368), the channel layer
-    loop of MHCN.forward (:422-478: raw product fed forward, normalised copy summed) with self_gating /
-    channel_attention (:404-420) and hierarchical_self_supervision (:480-506), lifted from the AST (the module
-    imports tensorflow, which is absent) and run unchanged on a seeded social + interaction graph.  The
-    torch.randperm draws of the self-supervision are recorded so that the test can replay them."""
-    import scipy.sparse as sp
-    path = os.path.join(REF, "univariate", "mhcn.py")
-    names = {"build_hyper_adj_mats", "self_gating", "self_supervised_gating", "channel_attention", "forward",
-             "hierarchical_self_supervision", "sparse_mx_to_torch_sparse_tensor"}
-    cls, ns = _lift_class_methods(path, "MHCN", names, top_level=("TFGraphInterface", "Graph"))
-    rng = np.random.default_rng(77)
-    n_u, n_i, d, n_layers = 60, 45, 64, 2
-    # directed social relations with a good share of reciprocal pairs, so that every motif has members
+MHCN_METHODS = {"build_hyper_adj_mats", "self_gating", "self_supervised_gating", "channel_attention", "forward",
+                "hierarchical_self_supervision", "sparse_mx_to_torch_sparse_tensor"}
+
+
+def _mhcn_small_graph(rng, n_u, n_i):
+    """60-user recipe of mhcn.npz: directed social relations with a good share of reciprocal pairs, so that every motif
+    has members; every user has at least one item."""
     s_r, s_c = rng.integers(0, n_u, 420), rng.integers(0, n_u, 420)
     keep = s_r != s_c
     s_r, s_c = s_r[keep], s_c[keep]
     s_r, s_c = np.concatenate([s_r, s_c[:150]]), np.concatenate([s_c, s_r[:150]])
+    y_r = np.concatenate([np.arange(n_u), rng.integers(0, n_u, 500)])
+    y_c = np.concatenate([rng.integers(0, n_i, n_u), rng.integers(0, n_i, 500)])
+    return s_r, s_c, y_r, y_c
+
+
+def _mhcn_wide_graph(rng, n_u, n_i):
+    """Recipe of mhcn_wide.npz: a social graph dense enough for the motif operators to have long rows (targets drawn with
+    a heavy-tailed popularity: hubs), a third of the relations reciprocal, a heavy-tailed item count per user (a few
+    power users: long H_p rows), and 24 users without any relation and with two items each (empty rows of H_s, H_j and
+    H_p: H_p keeps co-purchase counts above 3 only)."""
+    loners = rng.choice(n_u, 24, replace=False)
+    social = np.setdiff1d(np.arange(n_u), loners)
+    pop = 1.0 / (np.arange(social.size) + 4.0) ** 0.9
+    pop = pop[rng.permutation(social.size)]
+    n_s = 14 * n_u
+    s_r = social[rng.integers(0, social.size, n_s)]
+    s_c = social[rng.choice(social.size, n_s, p=pop / pop.sum())]
+    keep = s_r != s_c
+    s_r, s_c = s_r[keep], s_c[keep]
+    n_b = s_r.size // 3
+    s_r, s_c = np.concatenate([s_r, s_c[:n_b]]), np.concatenate([s_c, s_r[:n_b]])
+    item_pop = 1.0 / (np.arange(n_i) + 8.0) ** 0.7
+    item_pop = item_pop[rng.permutation(n_i)] / item_pop.sum()
+    count = np.minimum(2 + rng.geometric(0.16, n_u), n_i // 2)
+    count[rng.choice(social, 6, replace=False)] = n_i // 2          # power users
+    count[loners] = 2
+    y_r = np.repeat(np.arange(n_u), count)
+    y_c = np.concatenate([rng.choice(n_i, k, replace=False, p=item_pop) for k in count])
+    return s_r, s_c, y_r, y_c
+
+
+def _narrow(a):
+    """Integer array in the narrowest signed type that holds its values."""
+    a = np.asarray(a)
+    for dt in (np.int8, np.int16, np.int32):
+        if a.size == 0 or (a.min() >= np.iinfo(dt).min and a.max() <= np.iinfo(dt).max):
+            return a.astype(dt)
+    return a.astype(np.int64)
+
+
+MHCN_DENSE = [(f"{p}{c}", attr, str(c)) for c in (1, 2, 3, 4) for p, attr in
+              (("gw", "gating_weights"), ("gb", "gating_bias"), ("sgw", "sgating_weights"), ("sgb", "sgating_bias"))] + \
+             [("attention", "attention", None), ("attention_mat", "attention_mat", None)]
+
+
+def _mhcn_params(m):
+    """(fixture key, leaf tensor) of every parameter of the lifted MHCN: user, item, then MHCN_DENSE's order."""
+    out = [("user", m.user_embeddings), ("item", m.item_embeddings)]
+    for key, attr, c in MHCN_DENSE:
+        out.append((key, getattr(m, attr) if c is None else getattr(m, attr)[c]))
+    return out
+
+
+def _mhcn_backward(m, fu, fi, ss_loss, wu, wi, prop_only):
+    """Gradients of the fixture's loss sum(fu * wu) + sum(fi * wi) + ss_loss w.r.t. every parameter as grad_<key> (a
+    parameter the loss does not reach has none: sgating of channel 4), and, with prop_only, of the same loss without
+    ss_loss as prop_grad_<key> (the loss of a caller of the layer loop alone)."""
+    params = _mhcn_params(m)
+    out = {}
+    prop = (fu * wu).sum() + (fi * wi).sum()
+    if prop_only:
+        gs = torch.autograd.grad(prop, [p for _, p in params], retain_graph=True, allow_unused=True)
+        out.update({f"prop_grad_{k}": g for (k, _), g in zip(params, gs) if g is not None})
+    (prop + ss_loss).backward()
+    out.update({f"grad_{k}": p.grad for k, p in params if p.grad is not None})
+    return out
+
+
+def gen_mhcn(name="mhcn", wide=False):
+    """tests/golden/mhcn.npz: univariate/mhcn.py's own MHCN.build_hyper_adj_mats (:340-368), the channel layer
+    loop of MHCN.forward (:422-478: raw product fed forward, normalised copy summed) with self_gating /
+    channel_attention (:404-420) and hierarchical_self_supervision (:480-506), lifted from the AST (the module
+    imports tensorflow, which is absent) and run unchanged on a seeded social + interaction graph.  The
+    torch.randperm draws of the self-supervision are recorded so that the test can replay them.  Every parameter is a
+    leaf: the reference's own gradient of each is stored (grad_<key>; ss_grad_channels: the channels whose
+    self-supervised gating the loss reaches).
+
+    tests/golden/mhcn_wide.npz (wide): the same at 775 users, 203 items, d = 32: ceil(775 / 256) = 4 workgroups of the
+    row-split backward kernels (194, 194, 194 and 193 rows: an odd count); narrow integer types; also the gradients
+    of the loss without ss_loss (prop_grad_<key>)."""
+    import scipy.sparse as sp
+    path = os.path.join(REF, "univariate", "mhcn.py")
+    cls, ns = _lift_class_methods(path, "MHCN", MHCN_METHODS, top_level=("TFGraphInterface", "Graph"))
+    if wide:
+        rng, seed = np.random.default_rng(78), 8
+        n_u, n_i, d, n_layers = 775, 203, 32, 2
+        s_r, s_c, y_r, y_c = _mhcn_wide_graph(rng, n_u, n_i)
+        assert -(-n_u // 256) >= 3 and n_u % 256 and n_i % 16
+    else:
+        rng, seed = np.random.default_rng(77), 7
+        n_u, n_i, d, n_layers = 60, 45, 64, 2
+        s_r, s_c, y_r, y_c = _mhcn_small_graph(rng, n_u, n_i)
     pairs = np.unique(np.stack([s_r, s_c], 1), axis=0)
     s_r, s_c = pairs[:, 0], pairs[:, 1]
     S = sp.csr_matrix((np.ones(len(s_r), dtype=np.float32), (s_r, s_c)), shape=(n_u, n_u), dtype=np.float32)
-    y_r = np.concatenate([np.arange(n_u), rng.integers(0, n_u, 500)])
-    y_c = np.concatenate([rng.integers(0, n_i, n_u), rng.integers(0, n_i, 500)])
     ypairs = np.unique(np.stack([y_r, y_c], 1), axis=0)
     y_r, y_c = ypairs[:, 0], ypairs[:, 1]
     Y = sp.csr_matrix((np.ones(len(y_r), dtype=np.float32), (y_r, y_c)), shape=(n_u, n_i), dtype=np.float32)
@@ -464,21 +547,29 @@ def gen_mhcn():
     m.data = types.SimpleNamespace(interaction_mat=Y, user_num=n_u, item_num=n_i)
     H = m.build_hyper_adj_mats()
     H = [sp.csr_matrix(h) for h in H]
+    if wide:                                     # what the fixture is for: empty rows, real rows, a split-worthy one
+        for hname, h in zip(("H_s", "H_j", "H_p"), H):
+            per_row = np.diff(h.indptr)
+            assert (h.data != 0).all(), hname
+            assert (per_row == 0).any() and per_row[per_row > 0].mean() >= 4 and per_row.max() >= 64, (hname, per_row.max())
     R = ns["Graph"].normalize_graph_mat(Y)
-    g = torch.Generator().manual_seed(7)
+    g = torch.Generator().manual_seed(seed)
 
     def xav(*shape):
         t = torch.empty(*shape)
         torch.nn.init.xavier_uniform_(t, generator=g)
-        return t
+        return t.requires_grad_(True)
+
+    def bias():
+        return (0.05 * torch.randn(1, d, generator=g)).requires_grad_(True)
 
     m.n_layers, m.n_channel, m.emb_size, m.ss_rate = n_layers, 4, d, 0.01
-    m.user_embeddings = xav(n_u, d).requires_grad_(True)
-    m.item_embeddings = xav(n_i, d).requires_grad_(True)
+    m.user_embeddings = xav(n_u, d)
+    m.item_embeddings = xav(n_i, d)
     m.gating_weights = {str(c + 1): xav(d, d) for c in range(4)}
-    m.gating_bias = {str(c + 1): 0.05 * torch.randn(1, d, generator=g) for c in range(4)}
+    m.gating_bias = {str(c + 1): bias() for c in range(4)}
     m.sgating_weights = {str(c + 1): xav(d, d) for c in range(4)}
-    m.sgating_bias = {str(c + 1): 0.05 * torch.randn(1, d, generator=g) for c in range(4)}
+    m.sgating_bias = {str(c + 1): bias() for c in range(4)}
     m.attention = xav(1, d)
     m.attention_mat = xav(d, d)
     m.H_s, m.H_j, m.H_p = (m.sparse_mx_to_torch_sparse_tensor(h) for h in H)
@@ -503,24 +594,25 @@ def gen_mhcn():
         torch.randperm = real_randperm
     wu = torch.randn(n_u, d, generator=g)
     wi = torch.randn(n_i, d, generator=g)
-    ((fu * wu).sum() + (fi * wi).sum() + ss_loss).backward()
-    out = {"S_row": s_r.astype(np.int64), "S_col": s_c.astype(np.int64), "Y_row": y_r.astype(np.int64),
-           "Y_col": y_c.astype(np.int64), "n_users": n_u, "n_items": n_i, "n_layers": n_layers, "ss_rate": 0.01,
+    grads = _mhcn_backward(m, fu, fi, ss_loss, wu, wi, prop_only=wide)
+    ints = _narrow if wide else (lambda a: np.asarray(a).astype(np.int64))
+    out = {"S_row": ints(s_r), "S_col": ints(s_c), "Y_row": ints(y_r),
+           "Y_col": ints(y_c), "n_users": n_u, "n_items": n_i, "n_layers": n_layers, "ss_rate": 0.01,
            "user_emb": m.user_embeddings.detach().numpy(), "item_emb": m.item_embeddings.detach().numpy(),
-           "attention": m.attention.numpy(), "attention_mat": m.attention_mat.numpy(),
-           "u_idx": u_idx.numpy(), "v_idx": v_idx.numpy(), "j_idx": j_idx.numpy(),
-           "perms": np.stack(perms), "wu": wu.numpy(), "wi": wi.numpy(),
+           "u_idx": ints(u_idx.numpy()), "v_idx": ints(v_idx.numpy()), "j_idx": ints(j_idx.numpy()),
+           "perms": ints(np.stack(perms)), "wu": wu.numpy(), "wi": wi.numpy(),
            "final_user": fu.detach().numpy(), "final_item": fi.detach().numpy(), "ss_loss": np.float32(ss_loss.item()),
-           "batch_user": bu.detach().numpy(), "batch_pos": bp.detach().numpy(), "batch_neg": bn.detach().numpy(),
-           "grad_user": m.user_embeddings.grad.numpy(), "grad_item": m.item_embeddings.grad.numpy()}
-    for c in range(4):
-        out[f"gw{c + 1}"], out[f"gb{c + 1}"] = m.gating_weights[str(c + 1)].numpy(), m.gating_bias[str(c + 1)].numpy()
-        out[f"sgw{c + 1}"], out[f"sgb{c + 1}"] = m.sgating_weights[str(c + 1)].numpy(), m.sgating_bias[str(c + 1)].numpy()
-    for name, h in zip(("H_s", "H_j", "H_p"), H):
-        out.update(_csr_dict(name, h))
-    out.update(_csr_dict("R", sp.csr_matrix(R)))
-    np.savez_compressed(os.path.join(OUT, "mhcn.npz"), **out)
-    print("wrote mhcn.npz: nnz", [h.nnz for h in H], "ss_loss", float(ss_loss), "perms", len(perms))
+           "batch_user": bu.detach().numpy(), "batch_pos": bp.detach().numpy(), "batch_neg": bn.detach().numpy()}
+    for key, p in _mhcn_params(m)[2:]:
+        out[key] = p.detach().numpy()
+    out.update({k: v.numpy() for k, v in grads.items()})
+    out["ss_grad_channels"] = np.array([c for c in (1, 2, 3, 4) if f"grad_sgw{c}" in grads], dtype=np.int8 if wide else np.int64)
+    for hname, h in zip(("H_s", "H_j", "H_p"), H):
+        out.update(_csr_dict(hname, h, ints))
+    out.update(_csr_dict("R", sp.csr_matrix(R), ints))
+    np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **out)
+    print(f"wrote {name}.npz:", os.path.getsize(os.path.join(OUT, f"{name}.npz")), "bytes, nnz", [h.nnz for h in H],
+          "longest rows", [int(np.diff(h.indptr).max()) for h in H], "ss_loss", float(ss_loss), "perms", len(perms))
 
 
 def gen_sept_social():
@@ -670,7 +762,7 @@ def gen_featmask():
 # `ill_conditioned` lists the keys with 4 * drift > 1e-5 (the reference's own fp32 run misses 1e-5 there);
 # `dropped` lists fp32 output keys left out to keep the file under F64_SIZE_CAP.
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
-F64_FAMILIES = ("propagation", "contrast", "bpr", "mhcn", "sept_social", "buir", "grace", "rownorm")
+F64_FAMILIES = ("propagation", "contrast", "bpr", "mhcn", "mhcn_wide", "sept_social", "buir", "grace", "rownorm")
 F64_SIZE_CAP = 1066584                       # bytes: the largest fp32 fixture (contrast.npz)
 GRACE_F64_DROPPED = ((257, 0.5),)           # (m, tau) cases of grace.npz left out of grace_f64.npz (size cap)
 # The one fp32 output that the reference does not reproduce from run to run: the gradient of item_emb[neg_i] with a
@@ -907,9 +999,7 @@ def _csr_of(z, name):
 def _f64_mhcn(z, dt):
     import scipy.sparse as sp
     path = os.path.join(REF, "univariate", "mhcn.py")
-    names = {"build_hyper_adj_mats", "self_gating", "self_supervised_gating", "channel_attention", "forward",
-             "hierarchical_self_supervision", "sparse_mx_to_torch_sparse_tensor"}
-    cls, ns = _lift_class_methods(path, "MHCN", names, top_level=("TFGraphInterface", "Graph"))
+    cls, ns = _lift_class_methods(path, "MHCN", MHCN_METHODS, top_level=("TFGraphInterface", "Graph"))
     n_u, n_i = int(z["n_users"]), int(z["n_items"])
     d = z["user_emb"].shape[1]
     S = sp.csr_matrix((np.ones(len(z["S_row"]), dtype=np.float32), (z["S_row"], z["S_col"])), shape=(n_u, n_u),
@@ -925,19 +1015,21 @@ def _f64_mhcn(z, dt):
     def t(key):
         return torch.from_numpy(z[key]).to(dt)
 
+    def leaf(key):
+        return t(key).requires_grad_(True)
+
     m.n_layers, m.n_channel, m.emb_size, m.ss_rate = int(z["n_layers"]), 4, d, float(z["ss_rate"])
-    m.user_embeddings = t("user_emb").requires_grad_(True)
-    m.item_embeddings = t("item_emb").requires_grad_(True)
-    m.gating_weights = {str(c): t(f"gw{c}") for c in (1, 2, 3, 4)}
-    m.gating_bias = {str(c): t(f"gb{c}") for c in (1, 2, 3, 4)}
-    m.sgating_weights = {str(c): t(f"sgw{c}") for c in (1, 2, 3, 4)}
-    m.sgating_bias = {str(c): t(f"sgb{c}") for c in (1, 2, 3, 4)}
-    m.attention, m.attention_mat = t("attention"), t("attention_mat")
+    m.user_embeddings, m.item_embeddings = leaf("user_emb"), leaf("item_emb")
+    m.gating_weights = {str(c): leaf(f"gw{c}") for c in (1, 2, 3, 4)}
+    m.gating_bias = {str(c): leaf(f"gb{c}") for c in (1, 2, 3, 4)}
+    m.sgating_weights = {str(c): leaf(f"sgw{c}") for c in (1, 2, 3, 4)}
+    m.sgating_bias = {str(c): leaf(f"sgb{c}") for c in (1, 2, 3, 4)}
+    m.attention, m.attention_mat = leaf("attention"), leaf("attention_mat")
     m.H_s, m.H_j, m.H_p = (_sparse_to(m.sparse_mx_to_torch_sparse_tensor(h), dt, _csr_of(z, k))
                            for h, k in zip(H, ("H_s", "H_j", "H_p")))
     m.R = _sparse_to(m.sparse_mx_to_torch_sparse_tensor(R), dt, _csr_of(z, "R"))
     # the self-supervision's torch.randperm draws, replayed from the fp32 fixture (they do not depend on values)
-    perms = [torch.from_numpy(p) for p in z["perms"]]
+    perms = [torch.from_numpy(p.astype(np.int64)) for p in z["perms"]]
     drawn = []
     real_randperm = torch.randperm
 
@@ -949,11 +1041,12 @@ def _f64_mhcn(z, dt):
 
     torch.randperm = replay_randperm
     try:
-        bu, bp, bn, ss_loss, fu, fi = m.forward(*(torch.from_numpy(z[k]) for k in ("u_idx", "v_idx", "j_idx")))
+        bu, bp, bn, ss_loss, fu, fi = m.forward(*(torch.from_numpy(z[k].astype(np.int64)) for k in ("u_idx", "v_idx", "j_idx")))
     finally:
         torch.randperm = real_randperm
     assert len(drawn) == len(perms)
-    ((fu * t("wu")).sum() + (fi * t("wi")).sum() + ss_loss).backward()
+    grads = _mhcn_backward(m, fu, fi, ss_loss, t("wu"), t("wi"), prop_only="prop_grad_user" in z.files)
+    assert [c for c in (1, 2, 3, 4) if f"grad_sgw{c}" in grads] == z["ss_grad_channels"].tolist()
     # hierarchical_self_supervision (mhcn.py:480-505): sums of softplus(b - a) over the score pairs (a, b) =
     # (pos, neg1), (neg1, neg2) and, global, (pos, neg1): S = |L| + ss_rate * sum (|a| + |b|)
     mag = 0.0
@@ -967,9 +1060,11 @@ def _f64_mhcn(z, dt):
             gpos, gneg = (edge * graph).sum(1), (edge[p2] * graph).sum(1)
             mag += float((pos.abs() + 2 * neg1.abs() + neg2.abs() + gpos.abs() + gneg.abs()).sum())
     out = {"final_user": fu.detach(), "final_item": fi.detach(), "ss_loss": ss_loss.detach(), "batch_user": bu.detach(),
-           "batch_pos": bp.detach(), "batch_neg": bn.detach(), "grad_user": m.user_embeddings.grad,
-           "grad_item": m.item_embeddings.grad}
+           "batch_pos": bp.detach(), "batch_neg": bn.detach(), **grads}
     return out, {"ss_loss": abs(ss_loss.item()) + m.ss_rate * mag}
+
+
+_f64_mhcn_wide = _f64_mhcn                    # the same run on mhcn_wide.npz (+ the prop_grad_* keys it holds)
 
 
 def _f64_sept_social(z, dt):
@@ -1124,6 +1219,7 @@ if __name__ == "__main__":
         gen_featmask()
     elif "--mhcn" in sys.argv:
         gen_mhcn()
+        gen_mhcn("mhcn_wide", wide=True)
     elif "--sept-social" in sys.argv:
         gen_sept_social()
     elif "--buir" in sys.argv:

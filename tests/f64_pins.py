@@ -17,7 +17,7 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FLOOR = 2.0 ** -20
 NORTH_STAR = 1e-5
-FAMILIES = ("propagation", "contrast", "bpr", "mhcn", "sept_social", "buir", "grace", "rownorm")
+FAMILIES = ("propagation", "contrast", "bpr", "mhcn", "mhcn_wide", "sept_social", "buir", "grace", "rownorm")
 _cache = {}
 
 

@@ -175,7 +175,12 @@ def test_two_ranks_one_gpu_match_single_process(backend, overlap):
 
 
 # --------------------------------------------------------------------------- BASELINE config 5 (MHCN channels)
-def _mhcn_worker(rank, world, port, out):
+# beside the default problem (101 users, d = 16: the torch expression of the channel mix), one at d = 32 with 301 user
+# rows per rank: the fused _ChannelMix, the dual_acc launches and two workgroups of every row-split backward kernel
+MHCN_D32 = dict(n_users=601, n_items=203, d=32, nnz=(5400, 4200, 2400, 3600))
+
+
+def _mhcn_worker(rank, world, port, out, sizes):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
@@ -187,15 +192,16 @@ def _mhcn_worker(rank, world, port, out):
         def make_graph(row, col, val, n_rows, n_cols):
             return ra.CsrGraph.from_coo(row, col, val, n_rows, n_cols, dev)
 
-        out[rank] = C.run_rank(rank, world, dev, make_graph, HipOps)
+        out[rank] = C.run_rank(rank, world, dev, make_graph, HipOps, **sizes)
     finally:
         dist.destroy_process_group()
 
 
-def test_sharded_mhcn_two_ranks_one_gpu():
+def _sharded_mhcn_two_ranks(sizes):
     """Config 5 with the real HIP kernels (dual-output SpMM on the row blocks of H_s / H_j / H_p, three streams,
-    per-channel all-gather / reduce-scatter over gloo): values and gradients == the single-process float64
-    restatement of univariate/mhcn.py:422-466."""
+    per-channel all-gather / reduce-scatter over gloo): values and the gradient of every parameter == the
+    single-process float64 restatement of univariate/mhcn.py:422-466 (itself pinned to the reference's float64 run:
+    test_oracle_golden.py::test_sharded_mhcn_oracle_matches_reference_run)."""
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import mhcn_sharded_common as C
@@ -204,14 +210,24 @@ def test_sharded_mhcn_two_ranks_one_gpu():
     with ctx.Manager() as mgr:
         out = mgr.dict()
         port = _free_port()
-        procs = [ctx.Process(target=_mhcn_worker, args=(r, world, port, out)) for r in range(world)]
+        procs = [ctx.Process(target=_mhcn_worker, args=(r, world, port, out, sizes)) for r in range(world)]
         for p in procs:
             p.start()
         for p in procs:
             p.join(300)
             assert p.exitcode == 0
         res = {r: out[r] for r in range(world)}
-    C.check(res, world, 2e-5)
+    C.check(res, world, 2e-5, **sizes)
+
+
+def test_sharded_mhcn_two_ranks_one_gpu():
+    _sharded_mhcn_two_ranks({})
+
+
+def test_sharded_mhcn_two_ranks_one_gpu_fused_channel_mix():
+    """The same at d = 32, where gcr_channel_mix_supported holds: the fused _ChannelMix with its `extra` term and the
+    running sums through the dual_acc launches, inside the sharded encoder."""
+    _sharded_mhcn_two_ranks(MHCN_D32)
 
 
 # --------------------------------------------------------------------------- the real `nccl` (RCCL) backend, one rank

@@ -330,6 +330,28 @@ def test_mhcn_motif_adjacency_and_layer_loop(golden):
     pin64("mhcn", "ss_loss", float(z["ss_rate"]) * ss)
 
 
+def test_sharded_mhcn_oracle_matches_reference_run(golden):
+    """tests/mhcn_sharded_common.reference (the oracle of the sharded-encoder tests, a restatement written here) fed the
+    775-user fixture's inputs: final embeddings and every gradient propagate() produces == the reference's own float64
+    run of the layer loop with the loss sum(fu * wu) + sum(fi * wi) (mhcn_wide_f64.npz: final_*, prop_grad_*)."""
+    import mhcn_sharded_common as C
+    z = golden("mhcn_wide.npz")
+    p = {"user": z["user_emb"], "item": z["item_emb"], "att": z["attention"], "att_mat": z["attention_mat"],
+         "wu": z["wu"], "wi": z["wi"]}
+    for c in range(4):
+        p[f"gw{c}"], p[f"gb{c}"] = z[f"gw{c + 1}"], z[f"gb{c + 1}"]
+    fu, fi, g = C.reference([_dense(z, n) for n in ("H_s", "H_j", "H_p")], _dense(z, "R"), p, int(z["n_layers"]))
+    pin64("mhcn_wide", "final_user", fu)
+    pin64("mhcn_wide", "final_item", fi)
+    fixture_key = {"att": "attention", "att_mat": "attention_mat"}
+    fixture_key.update({f"g{q}{c}": f"g{q}{c + 1}" for c in range(4) for q in "wb"})
+    assert set(g) == set(C.GRAD_KEYS)
+    for k in C.GRAD_KEYS:
+        pin64("mhcn_wide", f"prop_grad_{fixture_key.get(k, k)}", g[k])
+    assert {k for k in pins("mhcn_wide").keys if k.startswith("prop_grad_")} == \
+        {f"prop_grad_{fixture_key.get(k, k)}" for k in C.GRAD_KEYS}
+
+
 def test_sept_social_encoder_and_neighbor_discrimination(golden):
     """univariate/sept_social.py:370-385 (sum of row-normalised layers) and :408-420."""
     z = golden("sept_social.npz")
