@@ -15,16 +15,29 @@
 //     tails) is scalar and divergence-free;
 //   * UNR (16 at d <= 64) gathers are issued back to back before the first FMA to keep >= 4 KiB per
 //     wave in flight; at 8 waves/SIMD that is >= 128 KiB per CU;
+//   * a row end does not drain that pipeline: acc_in of the next rows of a whole-row partition is loaded BEFORE a batch's
+//     gathers are issued and held in a short register queue, so the combine at the flush waits with a counted vmcnt on a
+//     load that is older than every gather still in flight (it used to load at the flush and wait vmcnt(0): all remaining
+//     gathers, all earlier stores and one fresh HBM round trip per row, 1.1 M times per cfg2 layer);
 //   * long rows: chunk partial sums go to a workspace and are added in chunk order by
 //     spmm_long_rows (deterministic; no float atomics).
 #include "gcr_common.h"
 
 namespace {
 
-// gathers in flight per wave before the first FMA: interleaved A/B on MI355X (scripts/perf_spmm_ab.py)
+// gathers in flight per wave before the first FMA: interleaved A/B on MI355X (scripts/perf_spmm_ab.py, round 1)
 // 4 -> 0.647 ms, 8 -> 0.612 ms, 16 -> 0.598 ms per cfg2 layer (cfg4: 7.52 / 7.06 / 6.91 ms)
 template <int NV>
 constexpr int unroll_for() { return NV == 1 ? 16 : 8; }
+
+// rows of acc_in a whole-row partition holds in registers ahead of their flush (one VGPR each at d <= 64; a batch of 16
+// gathers ends 1.6 rows on average at the mean degree 10 of the user rows).  Interleaved A/B, ms per cfg2 / cfg4 layer:
+// 2 rows 0.6534 / 7.136 against the parent's 0.6655 / 7.457.  With the next block's col / val loaded early as well (a
+// variant that did not stay) 4 rows were slower than 2, 0.658 / 7.14 against 0.645 / 7.00: the refill is scalar work in
+// front of every batch.  None for d > 64 (NV registers per row) and none for the ACC2 form (two addends per row; that
+// instantiation has no registers to spare at 8 waves per SIMD).
+template <int NV, bool ACC2>
+constexpr int acc_queue_for() { return (NV == 1 && !ACC2) ? 2 : 0; }
 
 struct Epilogue {
   float val_scale;
@@ -42,8 +55,16 @@ struct Epilogue {
 
 // ACC2: the second-addend form is its own instantiation — read unconditionally, its pointer and scale cost the hot
 // instantiation 9 SGPRs (96 -> 105), which is one wave per SIMD of occupancy and 4 % of the cfg2 layer time
+// have_pre: `pre` already holds acc_in[row] (loaded a gather batch ago by the caller's queue), so the combine below issues
+// no load and waits for none.  The two arms are kept apart on purpose: a load in one arm of a diamond makes the wait at
+// the join a vmcnt(0) for both.
 template <int NV, bool D64, bool ACC2>
-__device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d, int lane, float (&acc)[NV]) {
+__device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d, int lane, float (&acc)[NV],
+                                          bool have_pre, const float (&pre)[NV]) {
+  // No contraction anywhere in the epilogue: `acc * val_scale` and the add of acc_in stay two roundings in both arms.  The
+  // parent build never contracted here (its ISA has v_mul, v_add, v_mul; the replay test reproduced it bit for bit), so
+  // this pins what it did, the row normalise below included (its fmaf is explicit and stays one).
+#pragma clang fp contract(off)
   float yv[NV];
 #pragma unroll
   for (int v = 0; v < NV; ++v) yv[v] = acc[v] * ep.val_scale;
@@ -66,12 +87,25 @@ __device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d
     if (ep.inv_norm_out != nullptr && lane == 0) ep.inv_norm_out[row] = inv;
   }
   const int64_t base = row * (int64_t)d;
+  if (ep.y != nullptr) {
 #pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    const int c = lane + 64 * v;
-    if (D64 || c < d) {
-      if (ep.y != nullptr) ep.y[base + c] = yv[v];
-      if (ep.acc_out != nullptr) {
+    for (int v = 0; v < NV; ++v) {
+      const int c = lane + 64 * v;
+      if (D64 || c < d) ep.y[base + c] = yv[v];
+    }
+  }
+  if (ep.acc_out == nullptr) return;
+  if (have_pre) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int c = lane + 64 * v;
+      if (D64 || c < d) ep.acc_out[base + c] = (pre[v] + yv[v]) * ep.acc_scale;
+    }
+  } else {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int c = lane + 64 * v;
+      if (D64 || c < d) {
         float prev = ep.acc_in != nullptr ? ep.acc_in[base + c] : 0.f;
         if (ACC2) prev = fmaf(ep.acc_in2[base + c], ep.acc_in2_scale, prev);
         ep.acc_out[base + c] = (prev + yv[v]) * ep.acc_scale;
@@ -85,7 +119,13 @@ __device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d
 // whose incoming gradient has a few thousand non-zero rows of a million (the NCL step: DESIGN 4.5) reads the CSR and
 // writes its output, but gathers almost nothing.
 template <int NV, bool D64, bool HAS_VAL, bool MASKED, int UNR, bool ACC2, bool COLMASK = false>
-__global__ __launch_bounds__(256) void spmm_parts(const int64_t* __restrict__ desc, int64_t n_parts,
+// amdgpu_num_sgpr(96): the queued forms' extra scalar state pushes the allocator past the 102 SGPRs that 8 waves per
+// SIMD allow (it takes all 106 when nothing stops it: 7 waves, DESIGN 4.1 puts that at 4 %); capped, the few coldest
+// scalars live in VGPR lanes instead (v_writelane / v_readlane outside the gather batches) and every d <= 128
+// instantiation keeps 8 waves.  The attribute takes a literal only, so it also covers the ACC2 forms, which keep the
+// parent's schedule: they move 2-19 cold scalars to VGPR lanes at unchanged occupancy (not timed separately).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void spmm_parts(const int64_t* __restrict__ desc,
+                                                  int64_t n_parts,
                                                   const int64_t* __restrict__ rowptr,
                                                   const int32_t* __restrict__ col,
                                                   const float* __restrict__ val,
@@ -118,30 +158,81 @@ __global__ __launch_bounds__(256) void spmm_parts(const int64_t* __restrict__ de
     cur_end = gcr_readlane_i(ends_v, 0);
   }
 
+  // acc_in of rows cur .. cur + nq - 1, loaded ahead of their flush: the rows of a whole-row partition are consecutive,
+  // so their addresses are known from the start.  refill() runs at a fixed point, BEFORE a batch of gathers is issued:
+  // by the time the first of those gathers has been consumed every queue entry has landed (loads return in order), so
+  // neither the combine at a row end nor the shift of the queue waits for anything a gather was not already waited for.
+  // In place (acc_in == acc_out) stays correct: a row is read before this wave, its only writer, stores it.
+  constexpr int PQ = acc_queue_for<NV, ACC2>();
+  float q[PQ > 0 ? PQ : 1][NV];
+  int nq = 0;
+  // rows this partition may prefetch: none for chunks, y-only launches and acc_in == NULL (no new loads there)
+  const int qrows = (PQ > 0 && whole_rows && ep.acc_in != nullptr && ep.acc_out != nullptr) ? nrows : 0;
+  auto refill = [&]() {
+    if (PQ == 0) return;
+#pragma unroll
+    for (int k = 0; k < PQ; ++k) {
+      if (k >= nq && cur + k < qrows) {
+        const float* ap = ep.acc_in + ((int64_t)row0 + cur + k) * d;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) q[k][v] = (D64 || lane + 64 * v < d) ? ap[lane + 64 * v] : 0.f;
+      }
+    }
+    nq = max(nq, min(PQ, qrows - cur));
+  };
+
   auto flush = [&]() {
-    store_row<NV, D64, ACC2>(ep, (int64_t)row0 + cur, d, lane, acc);
+    // fewer queued rows than row ends in one batch (degree-1 runs), or nothing to prefetch: store_row loads at the flush
+    const bool pre = PQ > 0 && nq > 0;
+    store_row<NV, D64, ACC2>(ep, (int64_t)row0 + cur, d, lane, acc, pre, q[0]);
+    if (pre) {
+#pragma unroll
+      for (int k = 0; k + 1 < PQ; ++k)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) q[k][v] = q[k + 1][v];
+      --nq;
+    }
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = 0.f;
     ++cur;
     cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
   };
 
+  // column id, value and edge-mask word of the 64 non-zeros of block b, one per lane
+  auto load_block = [&](int b, int& cv_o, float& vv_o, uint32_t& kw_o) {
+    cv_o = 0;
+    vv_o = 0.f;
+    kw_o = 0u;
+    if (lane < n - b) {
+      const int64_t e = nnz0 + b + lane;
+      cv_o = col[e];
+      vv_o = HAS_VAL ? val[e] : 1.0f;
+      if (MASKED && !COLMASK) kw_o = keep_bits[e >> 5];
+    }
+  };
+
+  // the next block's words are loaded after this block's last FMA.  Loading them before this block's gathers was measured:
+  // +1.2 % on cfg4 on top of the queue, but inside the noise margin on cfg2, so it did not stay (EXPERIMENTS.md)
+  int cv_n;
+  float vv_n;
+  uint32_t kw_n;
+  load_block(0, cv_n, vv_n, kw_n);
   for (int b = 0; b < n; b += 64) {
     const int m = min(64, n - b);
-    int cv = 0;
-    float vv = 0.f;
+    const int cv = cv_n;
+    const float vv = vv_n;
+    const uint32_t kw = kw_n;
     bool keep = lane < m;
-    if (keep) {
-      const int64_t e = nnz0 + b + lane;
-      cv = col[e];
-      vv = HAS_VAL ? val[e] : 1.0f;
-      if (MASKED && !COLMASK) keep = (keep_bits[e >> 5] >> (e & 31)) & 1u;
-      if (COLMASK) keep = (keep_bits[cv >> 5] >> (cv & 31)) & 1u;
+    if (MASKED && !COLMASK) keep = keep && ((kw >> ((nnz0 + b + lane) & 31)) & 1u);
+    if (COLMASK) {
+      if (keep) keep = (keep_bits[cv >> 5] >> (cv & 31)) & 1u;
     }
     unsigned long long todo = (MASKED || COLMASK) ? __ballot(keep) : (m == 64 ? ~0ull : ((1ull << m) - 1ull));
     int cnt = __builtin_popcountll(todo);
 
-    while (cnt >= UNR) {
+    // one batch: UNR gathers issued back to back, then consumed in order with the row ends between them
+    auto batch = [&]() {
+      refill();
       int js[UNR];
       float xr[UNR][NV];
 #pragma unroll
@@ -161,8 +252,12 @@ __global__ __launch_bounds__(256) void spmm_parts(const int64_t* __restrict__ de
 #pragma unroll
         for (int v = 0; v < NV; ++v) acc[v] = fmaf(w, xr[u][v], acc[v]);
       }
+    };
+    while (cnt >= UNR) {
+      batch();
       cnt -= UNR;
     }
+    if (cnt > 0) refill();
     while (cnt > 0) {
       const int j = __builtin_ctzll(todo);
       todo &= todo - 1ull;
@@ -178,10 +273,14 @@ __global__ __launch_bounds__(256) void spmm_parts(const int64_t* __restrict__ de
       for (int v = 0; v < NV; ++v) acc[v] = fmaf(w, xr[v], acc[v]);
       --cnt;
     }
+    if (b + 64 < n) load_block(b + 64, cv_n, vv_n, kw_n);
   }
 
   if (whole_rows) {
-    while (cur < nrows) flush();
+    while (cur < nrows) {
+      if (nq == 0) refill();
+      flush();
+    }
   } else {
     const int64_t base = slot * (int64_t)d;
 #pragma unroll
@@ -233,7 +332,7 @@ __global__ __launch_bounds__(256) void spmm_long_rows(const int32_t* __restrict_
     for (int w = 0; w < 3; ++w)
 #pragma unroll
       for (int v = 0; v < NV; ++v) acc[v] += red[w][v * 64 + lane];
-    store_row<NV, D64, ACC2>(ep, (int64_t)long_row[i], d, lane, acc);
+    store_row<NV, D64, ACC2>(ep, (int64_t)long_row[i], d, lane, acc, false, acc);
   }
 }
 

@@ -1,0 +1,139 @@
+"""Interleaved A/B of the SpMM layer between builds of libgcr, in ONE process on one GPU.
+
+    scripts/build_ab.sh <parent-rev> libgcr_base          # the parent's library -> build/libgcr_base.so
+    python scripts/perf_spmm_ab.py --lib build/libgcr_base.so --lib recommendation_amd/libgcr.so --workload cfg2
+
+Every --lib is opened with ctypes next to the others (the first one is the base).  The workload graph (bench.py's
+generator and seed) is built once through the package; then `gcr_spmm_csr_acc2_f32` of each library is timed in turn with
+the arguments of the Horner layer of functional.lightgcn_propagate (x = the previous layer's output, acc_in = x0, one
+acc_out, no y; --acc2 adds the second addend of the Horner backward): warm-up first, then --alternations rounds of
+--launches launches per library between two HIP events.
+Prints ms per layer for every alternation, the mean and the spread (max - min) per library, and whether each library's
+output is torch.equal to the base's.  A build "beats" the base when its mean is lower by more than three times the
+larger of the two spreads.
+
+The measurement runs in a child process under a time limit of its own (--timeout seconds); the parent never touches the
+GPU and stops at the first failure."""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def child(args):
+    import torch
+    import bench
+    import recommendation_amd as ra
+    from recommendation_amd import _lib
+
+    dev = "cuda:0"
+    wl = bench.WORKLOADS[args.workload]
+    n_u, n_i = wl["users"], wl["items"]
+    users, items = bench.synth_interactions_device(n_u, n_i, wl["edges"], bench.SEED, dev)
+    graph = ra.CsrGraph.bipartite_sym_norm(users, items, n_u, n_i, dev)
+    del users, items
+    n, d = n_u + n_i, args.d
+    x0 = torch.empty(n, d, device=dev)
+    torch.nn.init.xavier_uniform_(x0, generator=torch.Generator(device=dev).manual_seed(0))
+    p, ws = graph.plan, graph.workspace(d)
+    res, argt = _lib.SIGNATURES["gcr_spmm_csr_acc2_f32"]
+    libs = []
+    for path in args.lib:
+        h = ctypes.CDLL(os.path.abspath(path))
+        fn = h.gcr_spmm_csr_acc2_f32
+        fn.restype, fn.argtypes = res, argt
+        libs.append((path, fn))
+    stream = _lib.cur_stream(torch.device(dev))
+
+    # --acc2: the Horner backward's form, a second addend with its own scale (the ACC2 instantiation of the kernel)
+    in2 = torch.randn(n, d, device=dev, generator=torch.Generator(device=dev).manual_seed(1)) if args.acc2 else None
+    in2_scale = 0.25 if args.acc2 else 0.0
+
+    def launch(fn, x, out):
+        _lib.check(fn(_lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
+                      _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), None, 1.0, _lib.dptr(x), d, None,
+                      _lib.dptr(x0), _lib.dptr(in2), in2_scale, _lib.dptr(out), 1.0, 0, None, _lib.dptr(ws), graph.n_rows,
+                      graph.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
+
+    z = torch.empty_like(x0)
+    launch(libs[0][1], x0, z)                      # layer 1 of the base: the input of the timed (second) layer
+    outs = [torch.empty_like(x0) for _ in libs]
+    for (_, fn), out in zip(libs, outs):
+        for _ in range(args.warmup):
+            launch(fn, z, out)
+    torch.cuda.synchronize()
+    ms = [[] for _ in libs]
+    for _ in range(args.alternations):
+        for k, ((_, fn), out) in enumerate(zip(libs, outs)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                launch(fn, z, out)
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / args.launches)
+    report = {"workload": args.workload, "acc2": bool(args.acc2), "d": d, "nnz": graph.nnz, "n_parts": p.n_parts, "n_long": p.n_long,
+              "alternations": args.alternations, "launches": args.launches, "libs": []}
+    for k, (path, _) in enumerate(libs):
+        m = sum(ms[k]) / len(ms[k])
+        ent = {"lib": path, "ms_per_layer": [round(v, 5) for v in ms[k]], "mean": round(m, 5),
+               "spread": round(max(ms[k]) - min(ms[k]), 5), "equal_to_base": bool(torch.equal(outs[k], outs[0]))}
+        if k:
+            base = report["libs"][0]
+            margin = 3 * max(base["spread"], ent["spread"])
+            ent["gain_ms"] = round(base["mean"] - m, 5)
+            ent["gain_pct"] = round(100 * (base["mean"] - m) / base["mean"], 2)
+            ent["beats_base"] = bool(base["mean"] - m > margin)
+        report["libs"].append(ent)
+        print(f"{path}: " + " ".join(f"{v:.4f}" for v in ms[k]) + f" | mean {m:.4f} ms spread {ent['spread']:.4f}"
+              + (f" | {ent['gain_pct']:+.2f} % vs base, beats base: {ent['beats_base']}, equal: {ent['equal_to_base']}" if k else ""))
+    print(json.dumps(report))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--lib", action="append", required=True, help="library path; give it at least twice, the base first")
+    ap.add_argument("--workload", action="append", choices=["cfg1", "cfg2", "cfg4"], help="default: cfg2")
+    ap.add_argument("--d", type=int, default=64)
+    ap.add_argument("--alternations", type=int, default=5)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--acc2", action="store_true", help="time the second-addend form (acc_in2 given) instead")
+    ap.add_argument("--timeout", type=int, default=300, help="seconds per workload (child process)")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if len(args.lib) < 2:
+        ap.error("need at least two --lib")
+    if args.alternations < 5 or args.launches < 20:
+        ap.error("at least 5 alternations of at least 20 launches")
+    for path in args.lib:
+        if not os.path.exists(path):
+            ap.error(f"{path} does not exist")
+    if args.child:
+        args.workload = args.workload[0]
+        return child(args)
+    for wl in args.workload or ["cfg2"]:
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--workload", wl, "--d", str(args.d),
+               "--alternations", str(args.alternations), "--launches", str(args.launches), "--warmup", str(args.warmup)]
+        for path in args.lib:
+            cmd += ["--lib", path]
+        if args.acc2:
+            cmd.append("--acc2")
+        try:
+            rc = subprocess.run(cmd, timeout=args.timeout).returncode
+        except subprocess.TimeoutExpired:
+            print(f"{wl}: no result within {args.timeout} s; stopping", file=sys.stderr)
+            return 124
+        if rc != 0:
+            print(f"{wl}: child exited with {rc}; stopping", file=sys.stderr)
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
