@@ -45,6 +45,13 @@ int32_t gcr_spmm_plan_size_host(const int64_t* rowptr_host, int64_t n_rows, int3
                                 int64_t* n_parts, int64_t* n_long_rows, int64_t* n_slots);
 int32_t gcr_spmm_plan_fill_host(const int64_t* rowptr_host, int64_t n_rows, int32_t nnz_per_part,
                                 int64_t* desc_host, int32_t* long_row_host, int32_t* long_slot0_host);
+/* The same walk with `skip_host` (one byte per row, may be NULL): a row whose byte is set gets no partition and no
+ * long-row entry -- another plan computes it (the hub rows of the windowed companion, gcr_spmm_hub_reduce_f32). */
+int32_t gcr_spmm_plan_size_skip_host(const int64_t* rowptr_host, int64_t n_rows, int32_t nnz_per_part,
+                                     const uint8_t* skip_host, int64_t* n_parts, int64_t* n_long_rows, int64_t* n_slots);
+int32_t gcr_spmm_plan_fill_skip_host(const int64_t* rowptr_host, int64_t n_rows, int32_t nnz_per_part,
+                                     const uint8_t* skip_host, int64_t* desc_host, int32_t* long_row_host,
+                                     int32_t* long_slot0_host);
 
 /* flags for gcr_spmm_csr_f32 */
 #define GCR_SPMM_ROW_L2NORM 1u /* y <- y / max(||y||_2, 1e-12) per row (sept.py:224, sept_social.py:373-374) */
@@ -92,6 +99,17 @@ int32_t gcr_spmm_csr_acc2_f32(const int64_t* desc, int64_t n_parts,
                               float* acc_out, float acc_scale,
                               uint32_t flags, float* inv_norm_out, float* partials,
                               int64_t n_rows, int64_t n_cols, const uint32_t* col_active_bits, void* stream);
+/*
+ * Reduction of the windowed companion of the heaviest rows (one-off plan: recommendation_amd/graph.py HubPlan).
+ * partials [n_windows * n_hub, d] holds H x, H = the hub rows cut by column window (row w * n_hub + h = the non-zeros of
+ * hub row h with a column in window w; computed by gcr_spmm_csr_f32 on H, y only, val_scale 1).  For every hub row:
+ *   s_v = sum of partials[(v + 4 k) * n_hub + h], k = 0, 1, ... in that order (v = 0..3);  r = ((s_0 + s_1) + s_2) + s_3
+ *   y[hub_row[h]] = val_scale * r;  acc_out[hub_row[h]] = (acc_in[hub_row[h]] + y) * acc_scale   (as gcr_spmm_csr_f32)
+ * Deterministic: the order is fixed by the plan, no float atomics.
+ */
+int32_t gcr_spmm_hub_reduce_f32(const int32_t* hub_row, int64_t n_hub, int32_t n_windows, const float* partials,
+                                int32_t d, float val_scale, float* y, const float* acc_in, float* acc_out,
+                                float acc_scale, int64_t n_rows, void* stream);
 /* bits[idx[i] >> 5] |= 1 << (idx[i] & 31) for every idx[i] in [0, n_bits) (atomic OR; the caller zeroes `bits`). */
 int32_t gcr_bitmap_set(const int64_t* idx, int64_t n, int64_t n_bits, uint32_t* bits, void* stream);
 

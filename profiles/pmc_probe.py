@@ -63,8 +63,19 @@ with torch.no_grad():
     for _ in range(2):
         Fn.lightgcn_propagate(graph, x0, wl["layers"], combine="sum")
 torch.cuda.synchronize()
+# kernels per layer: with the windowed companion of the hub rows (graph.HubPlan) a layer is the companion's spmm_parts
+# (+ spmm_long_rows for its split segments), spmm_hub_rows and the main plan's spmm_parts (+ spmm_long_rows)
+hub = graph.hub if graph.hub is not None and graph.hub.eligible(64) else None
+if hub is None:
+    per = {"spmm_parts": 1, "spmm_long_rows": int(graph.plan.n_long > 0), "spmm_hub_rows": 0}
+else:
+    per = {"spmm_parts": 2, "spmm_long_rows": int(hub.H.plan.n_long > 0) + int(hub.main.n_long > 0), "spmm_hub_rows": 1}
 info = {"workload": name, "nnz": graph.nnz, "n": n, "layers": wl["layers"], "d": 64, "cal_rows": n_cal,
         "cal_parts": cal_parts, "parts": graph.plan.n_parts, "long_rows": graph.plan.n_long,
+        "dispatches_per_launch": per,
+        "hub": None if hub is None else {"window_rows": hub.window_rows, "windows": hub.n_windows, "n_hub": hub.n_hub,
+                                         "hub_nnz": hub.hub_nnz, "min_degree": hub.min_degree,
+                                         "companion_parts": hub.H.plan.n_parts, "main_parts": hub.main.n_parts},
         "source_digest": bench.spmm_source_digest()}
 os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
 with open(os.path.join(ROOT, "gpurun_out", f"pmc_probe_{name}.json"), "w") as f:

@@ -118,40 +118,48 @@ for wl in ("cfg2", "cfg4", "cfg2c_before", "cfg2c_after", "cfg4c_before", "cfg4c
         continue
     info = json.load(open(info_path))
     rows = []
+    kname = lambda k: ("spmm_parts" if "spmm_parts" in k else "spmm_hub_rows" if "spmm_hub_rows" in k else "spmm_long_rows")  # noqa: E731
     for kind, path in (("fetch", fetch), ("write", write)):
         k = 0
         for r in csv.DictReader(open(path)):
             if "spmm_" in r["Kernel_Name"]:
                 k += 1
-                name = "spmm_parts" if "spmm_parts" in r["Kernel_Name"] else "spmm_long_rows"
-                rows.append([kind, k, name, r["Grid_Size"], r["Counter_Name"], r["Counter_Value"]])
+                rows.append([kind, k, kname(r["Kernel_Name"]), r["Grid_Size"], r["Counter_Name"], r["Counter_Value"]])
     with open(os.path.join(here, f"{tag}_{wl}_pmc_hbm.csv"), "w") as f:
         w = csv.writer(f)
         w.writerow(["pass", "dispatch", "kernel", "grid", "counter", "value_KB"])
         w.writerows(rows)
-    f_parts = [float(r[5]) for r in rows if r[0] == "fetch" and r[2] == "spmm_parts"]
-    w_parts = [float(r[5]) for r in rows if r[0] == "write" and r[2] == "spmm_parts"]
-    f_long = [float(r[5]) for r in rows if r[0] == "fetch" and r[2] == "spmm_long_rows"]
-    w_long = [float(r[5]) for r in rows if r[0] == "write" and r[2] == "spmm_long_rows"]
+    pick = lambda kind, name: [float(r[5]) for r in rows if r[0] == kind and r[2] == name]  # noqa: E731
+    f_parts, w_parts = pick("fetch", "spmm_parts"), pick("write", "spmm_parts")
     # dispatch order: 3 calibration launches, [the renumbering's own subspace-iteration launches], then the measured
-    # 2 forward passes x K layers — always the LAST 2 K dispatches
+    # 2 forward passes x K layers -- always the LAST dispatches.  A layer is one spmm_parts + one spmm_long_rows, or, with
+    # the windowed companion of the hub rows (graph.HubPlan), the companion's spmm_parts (+ spmm_long_rows for its split
+    # segments), spmm_hub_rows and the main plan's spmm_parts (+ spmm_long_rows): the probe says how many of each.
     n_meas = 2 * int(info.get("layers", 3))
-    cal_f, lay_f, lay_w = f_parts[:3], f_parts[-n_meas:], w_parts[-n_meas:]
-    f_long, w_long = f_long[-n_meas:], w_long[-n_meas:]
+    per = info.get("dispatches_per_launch", {"spmm_parts": 1, "spmm_long_rows": 1, "spmm_hub_rows": 0})
+    last = lambda v, name: v[len(v) - n_meas * int(per[name]):] if per[name] else []  # noqa: E731
+    cal_f = f_parts[:3]
+    lay_f, lay_w = last(f_parts, "spmm_parts"), last(w_parts, "spmm_parts")
+    f_long, w_long = last(pick("fetch", "spmm_long_rows"), "spmm_long_rows"), last(pick("write", "spmm_long_rows"), "spmm_long_rows")
+    f_hub, w_hub = last(pick("fetch", "spmm_hub_rows"), "spmm_hub_rows"), last(pick("write", "spmm_hub_rows"), "spmm_hub_rows")
     nc = info["cal_rows"]
     expected_read_kb = (nc * 256 + nc * 8 + nc * 8 + info["cal_parts"] * 32) / 1024
     cal_ratio = (sum(cal_f) / len(cal_f)) / expected_read_kb
-    avg = lambda v: sum(v) / len(v) if v else 0.0        # noqa: E731
-    # one gcr_spmm_csr_f32 launch = spmm_parts + spmm_long_rows (the split rows' partial sums)
-    bytes_per_launch = (2.0 * (avg(lay_f) + avg(f_long)) + avg(lay_w) + avg(w_long)) * 1024
+    assert len(lay_f) == n_meas * int(per["spmm_parts"]), "fewer spmm_parts dispatches than the probe launched"
+    avg = lambda v: sum(v) / n_meas if v else 0.0        # per layer: a layer may be several dispatches  # noqa: E731
+    # one layer = every spmm_* kernel functional.spmm_into launches for it
+    bytes_per_launch = (2.0 * (avg(lay_f) + avg(f_long) + avg(f_hub)) + avg(lay_w) + avg(w_long) + avg(w_hub)) * 1024
     traffic[wl] = {
-        "kernel": "spmm_parts + spmm_long_rows (one gcr_spmm_csr_f32 launch, Horner layer: reads x0, writes one array)",
+        "kernel": "every spmm_* kernel of one functional.spmm_into call (Horner layer: reads x0, writes one array)",
+        "dispatches_per_launch": per,
+        "hub_rows_fetch_kb_avg": avg(f_hub), "hub_rows_write_kb_avg": avg(w_hub),
         "fetch_size_kb_avg": avg(lay_f), "write_size_kb_avg": avg(lay_w),
         "long_rows_fetch_kb_avg": avg(f_long), "long_rows_write_kb_avg": avg(w_long),
         "fetch_correction": 2.0, "dispatches_averaged": len(lay_f),
+        "parts_fetch_kb_by_dispatch": lay_f[: int(per["spmm_parts"])],
         "calibration": {"graph": "diagonal N=%d d=64" % nc, "expected_read_kb": expected_read_kb,
                         "fetch_size_kb": avg(cal_f), "ratio": cal_ratio,
-                        "expected_write_kb": nc * 256 / 1024, "write_size_kb": avg(w_parts[:3])},
+                        "expected_write_kb": nc * 256 / 1024, "write_size_kb": sum(w_parts[:3]) / 3},
         "bytes_per_launch": bytes_per_launch,
         "nnz": info["nnz"], "n": info["n"],
         "source_digest": info["source_digest"], "git_sha": sha, "git_dirty_at_summarise": dirty,

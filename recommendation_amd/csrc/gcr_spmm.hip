@@ -336,6 +336,51 @@ __global__ __launch_bounds__(256) void spmm_long_rows(const int32_t* __restrict_
   }
 }
 
+// The windowed companion's reduction (graph.py HubPlan): hub row h was multiplied window by window into
+// partials[w * n_hub + h] (a `spmm_parts` launch on the companion CSR, y only).  One 4-wave block per hub row: wave v adds
+// the partials of windows v, v+4, ... in window order (4 loads in flight), the four wave sums are combined through LDS in
+// wave order, then the common epilogue with the launch's real scales.  The order is fixed by the plan: no float atomics.
+template <int NV, bool D64>
+__global__ __launch_bounds__(256) void spmm_hub_rows(const int32_t* __restrict__ hub_row, int64_t n_hub, int n_win,
+                                                     const float* __restrict__ partials, int d, Epilogue ep) {
+  __shared__ float red[3][NV * 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int64_t h = blockIdx.x;
+  float acc[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc[v] = 0.f;
+  int w = wave;
+  for (; w + 12 < n_win; w += 16) {
+    float t[4][NV];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        t[u][v] = (D64 || lane + 64 * v < d) ? partials[((int64_t)(w + 4 * u) * n_hub + h) * d + lane + 64 * v] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) acc[v] += t[u][v];
+  }
+  for (; w < n_win; w += 4)
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      if (D64 || lane + 64 * v < d) acc[v] += partials[((int64_t)w * n_hub + h) * d + lane + 64 * v];
+  if (wave > 0) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) red[wave - 1][v * 64 + lane] = acc[v];
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) acc[v] += red[k][v * 64 + lane];
+    store_row<NV, D64, false>(ep, (int64_t)hub_row[h], d, lane, acc, false, acc);
+  }
+}
+
 __global__ void csr_validate_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                     int64_t n_rows, int64_t n_cols, int64_t nnz,
                                     unsigned long long* __restrict__ n_errors) {
@@ -484,6 +529,32 @@ extern "C" int32_t gcr_spmm_csr_dual_acc_f32(const int64_t* desc, int64_t n_part
   hipStream_t s = (hipStream_t)stream;
 #define GCR_GO(NV, D64) \
   return launch_spmm<NV, D64>(desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, keep_bits, x, d, ep, partials, s)
+  if (d == 64) GCR_GO(1, true);
+  if (d <= 64) GCR_GO(1, false);
+  if (d <= 128) GCR_GO(2, false);
+  if (d <= 192) GCR_GO(3, false);
+  GCR_GO(4, false);
+#undef GCR_GO
+}
+
+// out[hub_row[h]] = epilogue(sum over the n_windows window partials of hub row h): see spmm_hub_rows.
+extern "C" int32_t gcr_spmm_hub_reduce_f32(const int32_t* hub_row, int64_t n_hub, int32_t n_windows, const float* partials,
+                                           int32_t d, float val_scale, float* y, const float* acc_in, float* acc_out,
+                                           float acc_scale, int64_t n_rows, void* stream) {
+  GCR_CHECK_ARG(n_hub >= 0 && n_windows >= 1 && n_rows >= 0 && n_rows < (1ll << 31));
+  GCR_CHECK_ARG(n_hub <= n_rows && n_hub * (int64_t)n_windows < (1ll << 31));
+  GCR_CHECK_ARG(d >= 1 && d <= 256);
+  if (n_hub == 0) return GCR_OK;
+  GCR_CHECK_ARG(hub_row != nullptr && partials != nullptr);
+  GCR_CHECK_ARG(y != nullptr || acc_out != nullptr);
+  Epilogue ep{val_scale, y, acc_in, acc_out, acc_scale, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
+  hipStream_t s = (hipStream_t)stream;
+#define GCR_GO(NV, D64)                                                                                              \
+  do {                                                                                                               \
+    hipLaunchKernelGGL((spmm_hub_rows<NV, D64>), dim3((unsigned)n_hub), dim3(256), 0, s, hub_row, n_hub, n_windows,  \
+                       partials, d, ep);                                                                             \
+    return GCR_LAUNCH_STATUS();                                                                                      \
+  } while (0)
   if (d == 64) GCR_GO(1, true);
   if (d <= 64) GCR_GO(1, false);
   if (d <= 128) GCR_GO(2, false);

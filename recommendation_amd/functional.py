@@ -56,6 +56,21 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
     if sink is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
+    # the heaviest rows by column window (graph.HubPlan): plain launches only -- a mask is a predicate per stored non-zero
+    # of the classic order, the second addend and the row normalise have instantiations of their own
+    hub = graph.hub
+    if (hub is not None and keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm
+            and inv_norm_out is None and hub.eligible(d)):
+        L, H, stream = _lib.lib(), hub.H, _lib.cur_stream(x.device)
+        part = hub.partials(d)
+        _lib.check(L.gcr_spmm_csr_acc2_f32(
+            _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0), H.plan.n_long,
+            _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d, _lib.dptr(part), None, None,
+            0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
+        _lib.check(L.gcr_spmm_hub_reduce_f32(
+            _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
+            _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
+        p = hub.main                      # every other row: the classic walk with the hub rows skipped
     rc = _lib.lib().gcr_spmm_csr_acc2_f32(
         _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
         _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(keep_bits), float(val_scale),

@@ -22,6 +22,17 @@ from . import _lib
 # 512 -> 0.617, 1024 -> 0.631 per cfg2 layer; cfg4 7.97 / 7.22 / 6.87 / 6.70 / 6.67 ms
 DEFAULT_NNZ_PER_PART = 512
 
+# The windowed companion of the heaviest ("hub") rows (HubPlan); measurements in EXPERIMENTS.md "SpMM: hub rows by column
+# window".  Fabric bytes fetched per gathered non-zero of the hub rows fall from 264 (classic plan) to 61-103 at windows of
+# 2048-8192 rows, least at 64 non-zeros per partition -- but the layer is fastest at 128 (fewer, longer partitions), and
+# faster still at 16384-row windows, where twice as many rows are hubs (the 8 W bound halves) and a segment is twice as
+# long: interleaved A/B, ms per cfg2 layer against the parent's 0.6616: 8192:128 0.6150, 16384:128 0.6021, 16384:256
+# 0.5996, 32768:128 0.5989, 65536:256 0.6303; cfg4 7.305 -> 6.681 / 6.276 / 6.223 at 8192 / 16384 / 32768.
+HUB_WINDOW_ROWS = 16384
+HUB_NNZ_PER_PART = 128
+HUB_MIN_TABLE_BYTES = 16 << 20        # the gathered table is at least 4 x one XCD's 4 MiB L2, or the rows hit anyway
+HUB_MAX_WINDOW_BYTES = 4 << 20        # one window of the table is at most one XCD's L2 (d <= 64 at the default window)
+
 
 def _np_i64(a):
     if isinstance(a, torch.Tensor):
@@ -32,24 +43,31 @@ def _np_i64(a):
 class SpmmPlan:
     """Host-built partition list for gcr_spmm_csr_f32 (include/gcr.h)."""
 
-    def __init__(self, rowptr_host: np.ndarray, device, nnz_per_part=DEFAULT_NNZ_PER_PART, row_group=None):
+    def __init__(self, rowptr_host: np.ndarray, device, nnz_per_part=DEFAULT_NNZ_PER_PART, row_group=None, skip=None):
         """row_group (optional int array [n_rows]): a locality group per row (reorder.locality_permutation's labels on the
         re-numbered operator).  The partitions are then laid out so that each group runs on ONE XCD, group after group
         (reorder.xcd_grouped_order), and its rows stay in that XCD's L2 between the gathers that share them; without it
-        the partitions keep row order and consecutive workgroups alternate over the XCDs."""
+        the partitions keep row order and consecutive workgroups alternate over the XCDs.
+        skip (optional bool / uint8 array [n_rows]): rows that get no partition and no long-row entry (HubPlan's)."""
         L = _lib.lib()
         rowptr_host = np.ascontiguousarray(rowptr_host, dtype=np.int64)
         n_rows = rowptr_host.size - 1
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            if skip.shape != (n_rows,):
+                raise ValueError("skip must have one entry per row")
+        skip_p = None if skip is None else skip.ctypes.data
         sizes = (ctypes.c_int64 * 3)()
         p = ctypes.addressof(sizes)
-        _lib.check(L.gcr_spmm_plan_size_host(rowptr_host.ctypes.data, n_rows, nnz_per_part, p, p + 8, p + 16),
-                   "gcr_spmm_plan_size_host")
+        _lib.check(L.gcr_spmm_plan_size_skip_host(rowptr_host.ctypes.data, n_rows, nnz_per_part, skip_p, p, p + 8, p + 16),
+                   "gcr_spmm_plan_size_skip_host")
         self.n_parts, self.n_long, self.n_slots = int(sizes[0]), int(sizes[1]), int(sizes[2])
         desc = np.empty((max(self.n_parts, 1), 4), dtype=np.int64)
         long_row = np.zeros(max(self.n_long, 1), dtype=np.int32)
         long_slot0 = np.zeros(self.n_long + 1, dtype=np.int32)
-        _lib.check(L.gcr_spmm_plan_fill_host(rowptr_host.ctypes.data, n_rows, nnz_per_part, desc.ctypes.data,
-                                             long_row.ctypes.data, long_slot0.ctypes.data), "gcr_spmm_plan_fill_host")
+        _lib.check(L.gcr_spmm_plan_fill_skip_host(rowptr_host.ctypes.data, n_rows, nnz_per_part, skip_p, desc.ctypes.data,
+                                                  long_row.ctypes.data, long_slot0.ctypes.data),
+                   "gcr_spmm_plan_fill_skip_host")
         self.nnz_per_part = nnz_per_part
         self.grouped = row_group is not None and self.n_parts > 0
         if self.grouped:
@@ -67,11 +85,97 @@ class SpmmPlan:
         self.long_slot0 = torch.from_numpy(long_slot0).to(device)
 
 
+class HubPlan:
+    """Windowed companion of a graph's heaviest rows: their gathers are made to hit in L2.
+
+    A hub row (degree > max(nnz_per_part, 8 W), W = ceil(n_cols / window_rows) column windows) spans the whole gathered
+    table, and so do the 512-non-zero chunks the classic plan cuts it into: nothing two chunks gather is still in an XCD's
+    4 MiB L2 when the other needs it, although all hub rows share the same columns.  Here the hub rows are cut by column
+    window instead.  The companion CSR `H` has W x n_hub rows; row w * n_hub + h holds the non-zeros of hub row h whose
+    column lies in window w, in stored order (`col` / `val` copied window-major).  `H` gets an ordinary whole-row plan with
+    small partitions whose descriptors are laid out per XCD window after window (reorder.xcd_grouped_order), so the waves
+    resident on one XCD gather from two or three windows of the table at a time.  A launch is then
+      1. partials[W n_hub, d] = H x            gcr_spmm_csr_f32 on H, y only, val_scale 1
+      2. out[hub rows] = epilogue(sum of a row's window partials in window order)      gcr_spmm_hub_reduce_f32
+      3. every other row: the classic walk with the hub rows skipped (`main`)          gcr_spmm_csr_f32
+    on one stream.  The 8 W bound keeps the partial traffic (W x 2 x 4 d bytes per hub row) under a quarter of the row's
+    gathers.  `build` returns None when the graph has no hub rows or a hub row's columns are not sorted."""
+
+    @classmethod
+    def build(cls, graph, window_rows, min_degree=None, nnz_per_part=HUB_NNZ_PER_PART, forced=False):
+        window_rows = int(window_rows)
+        if window_rows < 1:
+            raise ValueError("hub_window_rows must be positive")
+        n_win = -(-graph.n_cols // window_rows)
+        thr = max(nnz_per_part, 8 * n_win) if min_degree is None else int(min_degree)
+        deg_host = np.diff(graph.rowptr_host)
+        hub_host = np.flatnonzero(deg_host > thr)
+        n_hub = int(hub_host.size)
+        if n_hub == 0 or n_win * n_hub >= (1 << 31):
+            return None
+        dev = graph.device
+        hub = torch.from_numpy(hub_host).to(dev)
+        hdeg = torch.from_numpy(deg_host[hub_host]).to(dev)
+        hub_nnz = int(deg_host[hub_host].sum())
+        hoff = torch.cumsum(hdeg, 0) - hdeg
+        hid = torch.repeat_interleave(torch.arange(n_hub, device=dev), hdeg)            # hub index of every hub non-zero
+        e = graph.rowptr[hub][hid] + (torch.arange(hub_nnz, device=dev) - hoff[hid])    # its position in col / val
+        c = graph.col[e].to(torch.int64)
+        if not bool(((c[1:] >= c[:-1]) | (hid[1:] != hid[:-1])).all()):
+            return None                                                                  # unsorted hub row: classic plan
+        # segment boundaries: a search of every hub row's sorted columns for the window edges, [n_hub, W + 1]
+        pad = n_win * window_rows
+        edges = (torch.arange(n_hub, device=dev)[:, None] * pad + torch.arange(n_win + 1, device=dev)[None, :] * window_rows)
+        bounds = torch.searchsorted(hid * pad + c, edges.reshape(-1)).view(n_hub, n_win + 1)
+        del c, edges
+        seg_len = (bounds[:, 1:] - bounds[:, :-1]).t().reshape(-1)                       # of row w * n_hub + h
+        rp = torch.zeros(n_win * n_hub + 1, dtype=torch.int64, device=dev)
+        rp[1:] = torch.cumsum(seg_len, 0)
+        row_of = torch.repeat_interleave(torch.arange(n_win * n_hub, device=dev), seg_len)
+        src = bounds[:, :-1].t().reshape(-1)[row_of] + (torch.arange(hub_nnz, device=dev) - rp[row_of])
+        del row_of, hid
+        e = e[src]
+        self = cls()
+        self.window_rows, self.n_windows, self.n_hub, self.min_degree, self.forced = window_rows, n_win, n_hub, thr, bool(forced)
+        self.hub_nnz = hub_nnz
+        self.hub_row_host = hub_host
+        self.hub_row = hub.to(torch.int32)
+        self.bounds = bounds
+        group = np.repeat(np.arange(n_win, dtype=np.int64), n_hub)                       # window id of every row of H
+        self.H = CsrGraph(rp, graph.col[e], None if graph.val is None else graph.val[e], n_win * n_hub, graph.n_cols, dev,
+                          nnz_per_part=nnz_per_part, validate=False, row_group=group, hub_window_rows=0)
+        skip = np.zeros(graph.n_rows, dtype=np.uint8)
+        skip[hub_host] = 1
+        self.main = SpmmPlan(graph.rowptr_host, dev, graph.plan.nnz_per_part, skip=skip)
+        self._partials = {}
+        return self
+
+    def eligible(self, d: int) -> bool:
+        """Size conditions of a launch with d columns; a plan forced through the constructor keyword waives them."""
+        if self.forced:
+            return True
+        return self.H.n_cols * 4 * d >= HUB_MIN_TABLE_BYTES and self.window_rows * 4 * d <= HUB_MAX_WINDOW_BYTES
+
+    def partials(self, d: int):
+        """fp32 [W * n_hub, d] window partial sums, one per (d, stream)."""
+        key = (d, torch.cuda.current_stream(self.H.device).cuda_stream)
+        ws = self._partials.get(key)
+        if ws is None:
+            ws = torch.empty(self.n_windows * self.n_hub, d, dtype=torch.float32, device=self.H.device)
+            self._partials[key] = ws
+        return ws
+
+
 class CsrGraph:
     """A sparse operator A [n_rows, n_cols] resident on one GPU, ready for `functional.spmm`."""
 
     def __init__(self, rowptr, col, val, n_rows, n_cols, device, symmetric=False,
-                 nnz_per_part=DEFAULT_NNZ_PER_PART, validate=True, transpose=None, row_group=None):
+                 nnz_per_part=DEFAULT_NNZ_PER_PART, validate=True, transpose=None, row_group=None,
+                 hub_window_rows=None, hub_min_degree=None):
+        """hub_window_rows: None = the windowed companion of the hub rows (HubPlan) is built with HUB_WINDOW_ROWS when the
+        table is large enough for it to matter and used by the launches whose sizes qualify; an int > 0 forces it with that
+        window at any size; 0 disables it.  hub_min_degree: None = max(HUB_NNZ_PER_PART, 8 W); an int = rows with a larger
+        degree are hubs.  A graph with a `row_group` (XCD-grouped classic plan) keeps the classic plan."""
         rowptr_host = _np_i64(rowptr)
         if rowptr_host.size != n_rows + 1:
             raise ValueError("rowptr must have n_rows + 1 entries")
@@ -90,6 +194,14 @@ class CsrGraph:
         self._workspaces = {}
         if validate and self.device.type == "cuda":
             self.validate()
+        self._hub_kw = dict(hub_window_rows=hub_window_rows, hub_min_degree=hub_min_degree)
+        self.hub = None
+        if hub_window_rows is None:
+            # not worth a look unless some launch (d <= 256) could qualify
+            if row_group is None and self.n_cols * 4 * 256 >= HUB_MIN_TABLE_BYTES:
+                self.hub = HubPlan.build(self, HUB_WINDOW_ROWS, hub_min_degree)
+        elif int(hub_window_rows) > 0:
+            self.hub = HubPlan.build(self, hub_window_rows, hub_min_degree, forced=True)
 
     # -- checks ---------------------------------------------------------------------------
     def validate(self):
@@ -122,7 +234,7 @@ class CsrGraph:
             rp, c, v, perm = coo_to_csr_device(self.col.to(torch.int64), rows, self.val, self.n_cols, self.n_rows,
                                                self.device, want_perm=True)
             self._t = CsrGraph(rp, c, v, self.n_cols, self.n_rows, self.device, symmetric=False,
-                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self)
+                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self, **self._hub_kw)
             self._t.perm_from_transpose = perm     # non-zero e of A^T is non-zero perm[e] of A (shared edge masks)
         if self._t is None:
             col_host = self.col.cpu().numpy().astype(np.int64)
@@ -130,7 +242,7 @@ class CsrGraph:
             val_host = None if self.val is None else self.val.cpu().numpy()
             rp, c, v, _ = _coo_to_csr_host(col_host, rows, val_host, self.n_cols)
             self._t = CsrGraph(rp, c, v, self.n_cols, self.n_rows, self.device, symmetric=False,
-                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self)
+                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self, **self._hub_kw)
         return self._t
 
     def row_degrees(self):
@@ -150,6 +262,7 @@ class CsrGraph:
         g = copy.copy(self)
         g.val = val.contiguous()
         g._t = None
+        g.hub = None                       # the companion holds a copy of the old values: this view runs the classic plan
         return g
 
     def user_major_edges(self, n_users):
@@ -181,7 +294,8 @@ class CsrGraph:
             nnz = int(rp[-1])
             blk = CsrGraph(rp, torch.zeros(nnz, dtype=torch.int32, device=self.device),
                            torch.zeros(nnz, dtype=torch.float32, device=self.device), n_users, n_items, self.device,
-                           symmetric=False, nnz_per_part=self.plan.nnz_per_part, validate=False)
+                           symmetric=False, nnz_per_part=self.plan.nnz_per_part, validate=False,
+                           hub_window_rows=0)           # the caller rewrites col / val every step
             cache[key] = blk
         return blk
 

@@ -1,0 +1,170 @@
+"""Bit-for-bit pin of a windowed SpMM launch (graph.HubPlan, forced through the CsrGraph keyword at a size a test can
+afford) and of everything that must NOT change with it.
+
+The expected bits come from the replay of tests/test_spmm_pipeline_gpu.py extended to the new order
+(tests/spmm_window_common.py): the segment sums of the companion from 0 in stored order with the float32 fma of
+tests/test_spmm_order_cpu.py, the window partials of a hub row summed per wave (windows v, v+4, ...), the four wave sums as
+((s0 + s1) + s2) + s3, then `* val_scale`, then `(acc_in + y) * acc_scale`; every other row as the classic plan computes it.
+The float64 oracle stays beside it at that test's 1e-5.  Masked, second-addend and row-normalised launches do not take the
+windowed plan: on a graph built with the keyword they must give the bits of the same launch on a graph built without."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle_np as O
+from spmm_window_common import F32, HUB_MIN_DEGREE, N_COLS, WINDOW_ROWS, make_matrix, replay_plan, replay_windowed
+
+pytestmark = pytest.mark.gpu
+
+
+def _bits_equal(got_t, want, what):
+    got = got_t.cpu().numpy()
+    same = got.view(np.uint32) == want.view(np.uint32)
+    assert same.all(), f"{what}: {int((~same).sum())} of {same.size} words differ, first at {np.argwhere(~same)[0]}"
+
+
+def _epilogue(raw, val_scale, acc_in, acc_scale):
+    y = raw * F32(val_scale)
+    prev = np.zeros_like(y) if acc_in is None else acc_in
+    return y, (prev + y) * F32(acc_scale)
+
+
+def _near_oracle(got_t, ref, extra=0.0):
+    np.testing.assert_allclose(got_t.cpu().numpy(), ref, rtol=1e-5, atol=1e-5 * max(np.abs(ref).max(), extra, 1e-30))
+
+
+@pytest.mark.parametrize("has_val", [True, False], ids=["val", "ones"])
+@pytest.mark.parametrize("d", [64, 48, 128])
+@pytest.mark.parametrize("kind", ["base", "empty_window", "one_hub", "dup"])
+def test_windowed_order_is_pinned(kind, d, has_val):
+    import recommendation_amd as ra
+    from recommendation_amd import functional as Fn
+    rowptr, col, val, _ = make_matrix(kind)
+    n_rows = rowptr.size - 1
+    rng = np.random.default_rng(17 * d + int(has_val) + sum(map(ord, kind)))
+    w = val if has_val else np.ones(col.size, F32)
+    x = rng.standard_normal((N_COLS, d)).astype(F32)
+    acc_in = rng.standard_normal((n_rows, d)).astype(F32)
+    g = ra.CsrGraph(rowptr, col, val if has_val else None, n_rows, N_COLS, "cuda", hub_window_rows=WINDOW_ROWS,
+                    hub_min_degree=HUB_MIN_DEGREE)
+    plain = ra.CsrGraph(rowptr, col, val if has_val else None, n_rows, N_COLS, "cuda")
+    assert g.hub is not None and g.hub.eligible(d) and plain.hub is None
+    if kind == "dup":
+        assert g.hub.H.plan.n_long > 0                      # segments longer than a partition of the companion
+    if kind == "one_hub":
+        assert g.hub.n_hub == 1
+    dev = lambda a: torch.from_numpy(a).cuda()
+    empty = lambda: torch.full((n_rows, d), float("nan"), device="cuda")
+    xt, a_in = dev(x), dev(acc_in)
+
+    raw = replay_windowed(g, rowptr, col, w, x)
+    ref64 = O.spmm_csr(rowptr, col, w, x, keep=None, scale=1.0)
+    # rows that are not hubs: bit for bit the classic plan's
+    classic, cov = replay_plan(rowptr, col, w, x, plain.plan.desc_host, plain.plan.long_row.cpu().numpy()[: plain.plan.n_long],
+                               plain.plan.long_slot0.cpu().numpy(), n_rows)
+    assert cov.all()
+    others = np.setdiff1d(np.arange(n_rows), g.hub.hub_row_host)
+    assert np.array_equal(raw[others].view(np.uint32), classic[others].view(np.uint32))
+
+    y = empty()
+    Fn.spmm_into(g, xt, y=y)                                                            # y only
+    _bits_equal(y, _epilogue(raw, 1.0, None, 1.0)[0], "y only")
+    _near_oracle(y, ref64)
+    y_plain = empty()
+    Fn.spmm_into(plain, xt, y=y_plain)
+    assert torch.equal(y[dev(others)], y_plain[dev(others)])
+    out = empty()
+    Fn.spmm_into(g, xt, acc_in=a_in, acc_out=out)                                       # acc_out only (the Horner layer)
+    _bits_equal(out, _epilogue(raw, 1.0, acc_in, 1.0)[1], "acc_out only")
+    _near_oracle(out, acc_in + ref64, np.abs(acc_in).max())
+    y, out = empty(), empty()
+    Fn.spmm_into(g, xt, y=y, acc_in=a_in, acc_out=out, acc_scale=0.25, val_scale=1.0 / 0.65)     # y + acc_out, both scales
+    ey, eo = _epilogue(raw, 1.0 / 0.65, acc_in, 0.25)
+    _bits_equal(y, ey, "y of y + acc_out")
+    _bits_equal(out, eo, "acc_out of y + acc_out")
+    _near_oracle(y, ref64 / 0.65)
+    inplace = a_in.clone()
+    Fn.spmm_into(g, xt, acc_in=inplace, acc_out=inplace, acc_scale=0.5)                 # in place
+    _bits_equal(inplace, _epilogue(raw, 1.0, acc_in, 0.5)[1], "in place")
+    out = empty()
+    Fn.spmm_into(g, xt, acc_in=None, acc_out=out, acc_scale=3.0, val_scale=0.7)         # acc_in = None
+    _bits_equal(out, _epilogue(raw, 0.7, None, 3.0)[1], "acc_in None")
+
+    # -- launches that fall back to the classic plan: the bits of a graph built without the keyword -----------------------
+    def both(**kw):
+        res = []
+        for graph in (g, plain):
+            o = {k: empty() for k in ("y", "acc_out")}
+            Fn.spmm_into(graph, xt, y=o["y"], acc_in=a_in, acc_out=o["acc_out"], **kw)
+            res.append(o)
+        assert torch.equal(res[0]["y"], res[1]["y"]) and torch.equal(res[0]["acc_out"], res[1]["acc_out"]), sorted(kw)
+
+    both(keep_bits=Fn.pack_bits(dev(rng.random(col.size) >= 0.35)), val_scale=1.0 / 0.65)
+    active = np.sort(rng.choice(N_COLS, 90, replace=False)).astype(np.int64)
+    xs = torch.zeros_like(xt)
+    xs[dev(active)] = xt[dev(active)]
+    res = []
+    for graph in (g, plain):
+        o = empty()
+        Fn.spmm_into(graph, xs, acc_in=a_in, acc_out=o, col_active_bits=Fn.active_rows_bitmap(dev(active), N_COLS))
+        res.append(o)
+    assert torch.equal(res[0], res[1])
+    both(acc_in2=dev(rng.standard_normal((n_rows, d)).astype(F32)), acc_in2_scale=1.0 / 3.0, acc_scale=0.25)
+    res = []
+    for graph in (g, plain):
+        o, inv = empty(), torch.empty(n_rows, device="cuda")
+        Fn.spmm_into(graph, xt, y=o, l2norm=True, inv_norm_out=inv)
+        res.append((o, inv))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+
+
+def _bipartite(n_u, n_i, edges, **kw):
+    import recommendation_amd as ra
+    u, i = O.synthetic_interactions(n_u, n_i, edges, seed=5)
+    return u, i, ra.CsrGraph.bipartite_sym_norm(u, i, n_u, n_i, "cuda", **kw)
+
+
+@pytest.mark.parametrize("combine", ["mean", "sum"])
+def test_propagate_twice_is_bitwise_equal_and_near_the_oracle(combine):
+    from recommendation_amd import functional as Fn
+    n_u, n_i, k, d = 600, 100, 3, 64
+    u, i, g = _bipartite(n_u, n_i, 6000, hub_window_rows=WINDOW_ROWS, hub_min_degree=HUB_MIN_DEGREE)
+    assert g.hub is not None and g.hub.n_hub > 1 and g.t is g
+    x0 = torch.randn(n_u + n_i, d, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+    with torch.no_grad():
+        a = Fn.lightgcn_propagate(g, x0, k, combine=combine)
+        b = Fn.lightgcn_propagate(g, x0, k, combine=combine)
+        fa, la = Fn.lightgcn_propagate(g, x0, k, combine=combine, return_layers=True)
+        fb, lb = Fn.lightgcn_propagate(g, x0, k, combine=combine, return_layers=True)
+    assert torch.equal(a, b) and torch.equal(fa, fb) and all(torch.equal(p, q) for p, q in zip(la, lb))
+    rowptr, col, val = O.norm_adj_csr(u, i, n_u, n_i)
+    ref, _ = O.lgcn_encoder_forward(rowptr, col, val, x0.cpu().numpy(), k, combine=combine)
+    for got in (a, fa):
+        assert np.abs(got.cpu().numpy() - ref).max() <= 1e-5 * np.abs(ref).max()
+
+
+@pytest.mark.parametrize("symmetric", [True, False], ids=["symmetric", "own_transpose"])
+def test_backward_matches_the_classic_graph(symmetric):
+    import recommendation_amd as ra
+    from recommendation_amd import functional as Fn
+    n_u, n_i, k, d = 600, 100, 2, 64
+    u, i, g = _bipartite(n_u, n_i, 6000, hub_window_rows=WINDOW_ROWS, hub_min_degree=HUB_MIN_DEGREE)
+    _, _, plain = _bipartite(n_u, n_i, 6000)
+    if not symmetric:
+        # the same operator without the symmetry promise: the backward builds A^T through the constructor, keyword included
+        g = ra.CsrGraph(g.rowptr, g.col, g.val, g.n_rows, g.n_cols, "cuda", hub_window_rows=WINDOW_ROWS,
+                        hub_min_degree=HUB_MIN_DEGREE)
+        assert g.t is not g and g.t.hub is not None and g.t.hub.window_rows == WINDOW_ROWS
+    assert plain.hub is None
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    x0 = torch.randn(n_u + n_i, d, device="cuda", generator=gen)
+    wgt = torch.randn(n_u + n_i, d, device="cuda", generator=gen)
+    grads, outs = [], []
+    for graph in (g, plain):
+        x = x0.clone().requires_grad_(True)
+        final, layers = Fn.lightgcn_propagate(graph, x, k, combine="mean", return_layers=True)
+        ((final * wgt).sum() + (layers[1] * wgt).sum() * 0.5).backward()
+        grads.append(x.grad)
+        outs.append(final.detach())
+    for got, ref in ((outs[0], outs[1]), (grads[0], grads[1])):
+        assert float((got - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
