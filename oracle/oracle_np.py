@@ -139,6 +139,39 @@ def gcn_norm_weights(edge_index, num_nodes):
     return (dis[src] * dis[dst]).astype(np.float32)
 
 
+def coo_sums_f64(index, val, n):
+    """Degrees straight from the COO entries, in float64: out[k] = sum of val over the entries whose `index` is k
+    (val None = ones) -- the `rowsum = np.array(adj_mat.sum(1))` of selfcf.py:243 before any device code has seen it."""
+    index = np.asarray(index, dtype=np.int64)
+    w = None if val is None else np.asarray(val, dtype=F64)
+    return np.bincount(index, weights=w, minlength=n).astype(F64)
+
+
+def sym_norm_values_f64(rows, cols, val, rowsum, colsum=None):
+    """selfcf.py:240-249 / lightgcn.py:17,25 in float64, one value per stored non-zero (rows[e], cols[e], val[e]):
+    d = sum^-1/2 with inf -> 0 ; out[e] = d_row[rows[e]] * val[e] * d_col[cols[e]].  `colsum` None = the square symmetric
+    case (column scale = row scale); given = the rectangular D_r^-1/2 A D_c^-1/2."""
+    def dinv(s):
+        s = np.asarray(s, dtype=F64)
+        with np.errstate(divide="ignore"):
+            d = np.power(s, -0.5)
+        d[np.isinf(d)] = 0.0
+        return d
+    dr = dinv(rowsum)
+    dc = dr if colsum is None else dinv(colsum)
+    return dr[np.asarray(rows)] * np.asarray(val, dtype=F64) * dc[np.asarray(cols)]
+
+
+def row_norm_values_f64(rows, val, rowsum):
+    """selfcf.py:250-254 (= ncl.py:37-41) in float64: out[e] = val[e] / rowsum[rows[e]], with 1/0 -> 0 (a row whose
+    entries cancel to exactly 0 comes out all zeros, never inf or NaN)."""
+    rowsum = np.asarray(rowsum, dtype=F64)
+    with np.errstate(divide="ignore"):
+        rinv = 1.0 / rowsum
+    rinv[np.isinf(rinv)] = 0.0
+    return np.asarray(val, dtype=F64) * rinv[np.asarray(rows)]
+
+
 # --------------------------------------------------------------------------
 # propagation (S1-S3)
 # --------------------------------------------------------------------------
@@ -515,6 +548,20 @@ def edge_keep_mask(nnz, pe, seed, first_edge=0):
     r = np.stack(r, 1)[np.arange(nnz), (e & np.uint64(3)).astype(np.int64)]
     u = (r >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
     return u >= np.float32(pe)
+
+
+def edge_keep_exact(nnz, n_keep, seed):
+    """sept.py:55-61 `np.random.choice(idx, int(len(idx) * (1 - drop_rate)), replace=False)` with a counter RNG: edge e
+    gets the 64-bit key (x << 32) | y of philox(ctr=(e lo, e hi, 1, STREAM_EDGE), key=seed); the edges are sorted by key,
+    stably ascending (ties keep edge order), and the first n_keep of them are kept.  Returns bool [nnz]."""
+    e = np.arange(nnz, dtype=np.uint64)
+    k0, k1 = np.uint32(seed & 0xFFFFFFFF), np.uint32((seed >> 32) & 0xFFFFFFFF)
+    x, y, _, _ = philox4x32_10((e & _MASK32).astype(np.uint32), (e >> np.uint64(32)).astype(np.uint32),
+                               np.full(nnz, 1, np.uint32), np.full(nnz, STREAM_EDGE, np.uint32), k0, k1)
+    key = (x.astype(np.uint64) << np.uint64(32)) | y.astype(np.uint64)
+    keep = np.zeros(nnz, dtype=bool)
+    keep[np.argsort(key, kind="stable")[:n_keep]] = True
+    return keep
 
 
 # --------------------------------------------------------------------------

@@ -247,6 +247,64 @@ def test_augmentation_contract(golden):
     assert np.array_equal(keep[1000:2000], O.edge_keep_mask(1000, 0.3, seed=7, first_edge=1000))
 
 
+def test_float64_normalisations_from_the_coo(golden):
+    """O.sym_norm_values_f64 / O.row_norm_values_f64 with degrees taken from the COO (O.coo_sums_f64) against the reference's
+    own fp32 outputs (graph_build.npz `norm_data`, rownorm.npz `data`) at fp32 resolution, the row normalisation also
+    against the reference's float64 run; the rectangular form with both sums equal to the row sums is the square one."""
+    g = golden("graph_build.npz")
+    umap, imap, uid, iid = _maps(g["train_user"], g["train_item"], O.id_maps_first_seen)
+    n = len(umap) + len(imap)
+    row, col = np.concatenate([uid, iid + len(umap)]), np.concatenate([iid + len(umap), uid])
+    rowptr, c, v = O.coalesce_csr(row, col, np.ones(row.size, np.float32), n)
+    rows = np.repeat(np.arange(n), np.diff(rowptr))
+    assert np.array_equal(rowptr, g["norm_indptr"]) and np.array_equal(c.astype(np.int64), g["norm_indices"])
+    deg = O.coo_sums_f64(row, None, n)
+    assert np.array_equal(deg, np.bincount(rows, weights=v, minlength=n))
+    val = O.sym_norm_values_f64(rows, c, v, deg)
+    np.testing.assert_allclose(val, g["norm_data"], rtol=3e-7, atol=0)
+    assert np.array_equal(val, O.sym_norm_values_f64(rows, c, v, deg, O.coo_sums_f64(col, None, n)))
+    # an isolated node: d = 0, not inf
+    assert np.array_equal(O.sym_norm_values_f64([0, 1], [1, 0], [1.0, 1.0], [0.0, 4.0]), [0.0, 0.0])
+    z = golden("rownorm.npz")
+    n_rows = int(z["n_rows"])
+    rowptr, c, v = O.coalesce_csr(z["row"], z["col"], z["val"], n_rows)
+    assert np.array_equal(rowptr, z["indptr"]) and np.array_equal(c.astype(np.int64), z["indices"])
+    rows = np.repeat(np.arange(n_rows), np.diff(rowptr))
+    uniq, inv = np.unique(z["row"].astype(np.int64) * int(z["n_cols"]) + z["col"], return_inverse=True)
+    v64 = np.bincount(inv, weights=z["val"].astype(np.float64))           # duplicates summed in float64, (row, col) order
+    np.testing.assert_allclose(v64, v, rtol=2e-7, atol=0)
+    val = O.row_norm_values_f64(rows, v64, O.coo_sums_f64(z["row"], z["val"], n_rows))
+    np.testing.assert_allclose(val, z["data"], rtol=3e-7, atol=0)
+    pin64("rownorm", "data", val)
+    # a row that cancels to exactly 0 comes out 0, a negative sum keeps the signs flipped
+    assert np.array_equal(O.row_norm_values_f64([0, 0, 1, 1], [2.0, -2.0, 1.0, -3.0], [0.0, -2.0]), [0.0, 0.0, -0.5, 1.5])
+
+
+def test_edge_keep_exact_count_and_order(golden):
+    """O.edge_keep_exact keeps exactly n_keep edges (sept.py:55-61, golden 'sept_kept' = int(nnz (1 - rate))), nested in
+    n_keep (a prefix of one sorted order), and depends on the seed."""
+    a = golden("augment.npz")
+    nnz, rate = int(a["sept_nnz"]), float(a["sept_rate"])
+    keep = O.edge_keep_exact(nnz, int(nnz * (1 - rate)), 7)
+    assert keep.dtype == bool and keep.shape == (nnz,) and int(keep.sum()) == int(a["sept_kept"])
+    for n, k in ((1, 0), (1, 1), (33, 32), (1000, 250), (1000, 1000)):
+        m = O.edge_keep_exact(n, k, 11)
+        assert int(m.sum()) == k
+        if k:
+            assert not (O.edge_keep_exact(n, k - 1, 11) & ~m).any()
+    assert not np.array_equal(O.edge_keep_exact(1000, 500, 1), O.edge_keep_exact(1000, 500, 2))
+    assert abs(O.edge_keep_exact(100_000, 30_000, 5)[:50_000].mean() - 0.3) < 0.01
+    # the order itself, restated with Python integers: key(e) = (x << 32) | y of philox(ctr = (e, 0, 1, 'EDGE'), key = seed)
+    seed = 7 + (1 << 40)
+    keys = []
+    for e in range(9):
+        x, y, _, _ = O.philox4x32_10([e], [0], [1], [O.STREAM_EDGE], seed & 0xFFFFFFFF, seed >> 32)
+        keys.append((int(x[0]) << 32) | int(y[0]))
+    order = sorted(range(9), key=lambda e: (keys[e], e))
+    for k in range(10):
+        assert np.flatnonzero(O.edge_keep_exact(9, k, seed)).tolist() == sorted(order[:k])
+
+
 def test_philox_known_answer():
     """Random123 known-answer vectors for philox4x32-10."""
     out = O.philox4x32_10([0], [0], [0], [0], 0, 0)
