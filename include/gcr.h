@@ -438,6 +438,30 @@ int32_t gcr_channel_mix_bwd_f32(const float* g, const float* e1, const float* e2
                                 const float* score, float extra_scale, int64_t n, int32_t d, float* d_e1, float* d_e2,
                                 float* d_e3, float* d_extra, float* d_v, void* workspace, void* stream);
 
+/* MHCN's hierarchical mutual-information loss (univariate/mhcn.py:496-505) for row-major em [n, d], edge = H em [n, d]
+ * (the caller's SpMM) and three row permutations p0, p1, p2 (int64 [n]):
+ *   pos = <em_r, edge_r>   neg1 = <em[p0 r], edge_r>   neg2 = <edge[p1 r], em_r>
+ *   g = mean_r edge_r      gpos = <edge_r, g>          gneg = <edge[p2 r], g>
+ *   loss = sum_r sp(neg1 - pos) + sp(neg2 - neg1) + sp(gneg - gpos),  sp(x) = log(1 + e^x) = -log(sigmoid(-x)), finite
+ *   for any x (the reference's fp32 log(sigmoid(x)) is -inf at x = -100).
+ * replaces  row_shuffle / row_column_shuffle (x[perm] copies), score x 5, -log(sigmoid(.)) x 3, torch.mean   mhcn.py:481-505
+ *           and in the backward one index_put_(accumulate=True) per x[perm].
+ * Forward (two launches): loss [1]; coef [3, n] = (a, b, c) = -sigmoid of the three differences; gvec [2, d] = (g, dg)
+ * with dg = sum_r c_r (edge_r - edge[p2 r]).  Backward (two launches: the three inverse permutations, one pull per row):
+ *   d_em_r   = a_r edge_r - b_r edge[p1 r] + (b - a)_{q0 r} edge_{q0 r}                                    q_k = p_k^-1
+ *   d_edge_r = a_r em_r + (b_r - a_r) em[p0 r] - b_{q1 r} em_{q1 r} + (c_r - c_{q2 r}) g + dg / n
+ * times the upstream scalar g_out [1] (device).  Cross-row sums are fixed-order partial sums in double and every output
+ * row has one writer: bitwise reproducible, no float atomics.  An index outside [0, n) reads as a zero row.
+ * d in {32, 64, 128, 256} (gcr_mim_supported; GCR_EUNSUPPORTED otherwise); n = 0 launches nothing.  Both calls take a
+ * workspace of gcr_mim_workspace_bytes(n, d) bytes. */
+int32_t gcr_mim_supported(int32_t d);
+int64_t gcr_mim_workspace_bytes(int64_t n, int32_t d);
+int32_t gcr_mim_fwd_f32(const float* em, const float* edge, const int64_t* p0, const int64_t* p1, const int64_t* p2, int64_t n,
+                        int32_t d, float* loss, float* coef, float* gvec, void* workspace, void* stream);
+int32_t gcr_mim_bwd_f32(const float* em, const float* edge, const int64_t* p0, const int64_t* p1, const int64_t* p2, int64_t n,
+                        int32_t d, const float* coef, const float* gvec, const float* g_out, float* d_em, float* d_edge,
+                        void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * BCE-with-logits over the all-pairs score matrix — the `loss_type == "bce"` branch of LightGCN's training step:
  *   scores = torch.matmul(user_vecs, item_emb.t()); labels = one-hot at pos_i;                 lightgcn.py:110-112

@@ -79,6 +79,10 @@ SIGNATURES = {
     "gcr_channel_mix_fwd_f32": (c_int32, [_P, _P, _P, _P, _P, c_float, c_int64, c_int32, _P, _P, _P]),
     "gcr_channel_mix_bwd_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "gcr_channel_mix_bwd_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_float, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "gcr_mim_supported": (c_int32, [c_int32]),
+    "gcr_mim_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "gcr_mim_fwd_f32": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P]),
+    "gcr_mim_bwd_f32": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_bce_fwd_o_supported": (c_int32, [c_int32, c_uint32]),
     "gcr_bce_fwd_workspace_bytes": (c_int64, [c_int64, c_int64, c_int32]),
     "gcr_bce_fwd_f32": (c_int32, [_P, c_int64, _P, c_int64, c_int32, _P, _P, _P, c_uint32, _P]),

@@ -414,6 +414,72 @@ def channel_mix(e1, e2, e3, v, extra=None, extra_scale=0.0):
     return _ChannelMix.apply(e1, e2, e3, v, extra, float(extra_scale))
 
 
+class _MimLoss(torch.autograd.Function):
+    """mhcn.py:496-505 from em, edge = H em and three row permutations: two launches forward (gcr_mim_fwd_f32), two
+    backward (gcr_mim_bwd_f32); saves the [3, n] sigmoid coefficients and (g, dg), never a gathered copy."""
+
+    @staticmethod
+    def forward(ctx, em, edge, p0, p1, p2):
+        L = _lib.lib()
+        em, edge = em.contiguous(), edge.contiguous()
+        n, d = em.shape
+        dev = em.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty(3, n, dtype=torch.float32, device=dev)
+        gvec = torch.empty(2, d, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(int(L.gcr_mim_workspace_bytes(n, d)), 8) // 8, dtype=torch.float64, device=dev)
+        _lib.check(L.gcr_mim_fwd_f32(_lib.dptr(em), _lib.dptr(edge), _lib.dptr(p0), _lib.dptr(p1), _lib.dptr(p2), n, d,
+                                     _lib.dptr(loss), _lib.dptr(coef), _lib.dptr(gvec), _lib.dptr(ws), _lib.cur_stream(dev)),
+                   "gcr_mim_fwd_f32")
+        ctx.save_for_backward(em, edge, p0, p1, p2, coef, gvec)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        em, edge, p0, p1, p2, coef, gvec = ctx.saved_tensors
+        L = _lib.lib()
+        n, d = em.shape
+        g = g.to(torch.float32).contiguous()
+        d_em, d_edge = torch.empty_like(em), torch.empty_like(edge)
+        ws = torch.empty(max(int(L.gcr_mim_workspace_bytes(n, d)), 8) // 8, dtype=torch.float64, device=em.device)
+        _lib.check(L.gcr_mim_bwd_f32(_lib.dptr(em), _lib.dptr(edge), _lib.dptr(p0), _lib.dptr(p1), _lib.dptr(p2), n, d,
+                                     _lib.dptr(coef), _lib.dptr(gvec), _lib.dptr(g), _lib.dptr(d_em), _lib.dptr(d_edge),
+                                     _lib.dptr(ws), _lib.cur_stream(em.device)), "gcr_mim_bwd_f32")
+        return d_em, d_edge, None, None, None
+
+
+def mim_supported(em):
+    """True when `mim_loss` runs these rows: float32 [n, d] on the GPU with d in {32, 64, 128, 256}."""
+    return bool(em.is_cuda and em.dim() == 2 and em.dtype == torch.float32 and _lib.lib().gcr_mim_supported(em.shape[1]))
+
+
+def mim_loss(em, edge, perms=None):
+    """The hierarchical mutual-information loss of mhcn.py:496-505 (local + global) for em [n, d] and edge = H em [n, d]
+    (the caller's `spmm`; the gradient reaches em through it a second time): `-log(sigmoid(x))` as a softplus that is
+    finite at any x, the loss and both gradients bitwise reproducible.  perms: the three row permutations of
+    row_shuffle / row_column_shuffle x 2 (int64 [n]); given ones are checked to be permutations on the host before any
+    launch (ValueError), None draws them on the device.  Widths other than 32 / 64 / 128 / 256 raise (`mim_supported`)."""
+    _lib.require_cuda(em, edge)
+    if em.dim() != 2 or edge.shape != em.shape or em.dtype != torch.float32 or edge.dtype != torch.float32:
+        raise ValueError("em and edge must be float32 [n, d] of the same shape")
+    n, dev = em.shape[0], em.device
+    if perms is None:
+        perms = [torch.randperm(n, device=dev) for _ in range(3)]
+    else:
+        if len(perms) != 3:
+            raise ValueError("perms must hold three row permutations")
+        perms = [torch.as_tensor(p).to(device=dev, dtype=torch.int64).contiguous() for p in perms]
+        rows = torch.arange(n, device=dev)
+        for k, p in enumerate(perms):
+            if p.shape != (n,) or not torch.equal(torch.sort(p).values, rows):
+                raise ValueError(f"perms[{k}] is not a permutation of the {n} rows")
+    if not _lib.lib().gcr_mim_supported(em.shape[1]):
+        raise _lib.GcrError(f"mim_loss: unsupported width {em.shape[1]} (32, 64, 128 or 256)")
+    if n == 0:
+        return (em.sum() + edge.sum()) * 0.0
+    return _MimLoss.apply(em, edge, *perms)
+
+
 class _NormProp(torch.autograd.Function):
     """One SEPT layer: y = normalize(A x) row-wise (sept.py:223-224); saves y and 1/||Ax||."""
 

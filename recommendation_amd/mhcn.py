@@ -4,21 +4,45 @@
                                                  R [U x I]: the RAW product feeds the next layer, its row-
                                                  normalised copy is appended and summed (gcr_spmm_csr_dual_f32),
                                                  the five launches on separate HIP streams
-  hierarchical_self_supervision mhcn.py:480-506  edge embeddings = one more SpMM per channel
+  hierarchical_self_supervision mhcn.py:480-506  edge embeddings = one more SpMM per channel, then the fused loss
+                                                 functional.mim_loss (gcr_mim_fwd_f32 / gcr_mim_bwd_f32)
   self_gating / channel_attention mhcn.py:404-420 dense [U, d] x [d, d] products: plain library GEMMs (torch)
 
 The operators are CsrGraph handles (graph.py); `build_hyper_graphs` makes them from the social and
 interaction lists (motif adjacency, mhcn.py:340-368, on the device: graph_ops.py).
+
+MHCNModel is the reference's model class (mhcn.py:316-555) on these pieces:
+
+    MHCNModel(conf, train_set, test_set, social_data).train()  ->  {'Hit Ratio': .., 'Precision': .., 'Recall': .., 'NDCG': ..}
+
+    Interaction (sorted ids)                   mhcn.py:219-268   encoders.Interaction
+    Relation.__initialize (pair filter)        mhcn.py:102-108   social_pairs
+    build_hyper_adj_mats, normalize_graph_mat  mhcn.py:340-368,401  graph_ops.build_hyper_graphs
+    build (xavier, zero biases)                mhcn.py:370-402   MHCNEncoder.__init__
+    forward, bpr_loss, the 20 norms, Adam      mhcn.py:528-539   MHCNModel.train_step: propagate, self_supervision,
+                                                                 losses.bpr_gather_loss (BPR_NCL), optim.FusedAdam
+    next_batch_pairwise                        mhcn.py:13-31     sampler.next_batch_pairwise (gcr_neg_sample)
+    train_model, save, predict, evaluate       mhcn.py:508-555   MHCNModel.train / save / predict / test / evaluate
+The tuner (mhcn.py:558-), the prints and a sharded model are out of scope.
 """
 from __future__ import annotations
+
+import types
 
 import torch
 import torch.nn as nn
 
 from . import functional as Fn
+from . import losses as Ls
 from .distributed import _hip_dual, _hip_spmm_t
-from .encoders import multi_stream_spmm
+from .encoders import Interaction, multi_stream_spmm
+from .evaluate import ranking_evaluation, test as rank_test
 from .graph import CsrGraph
+from .graph_ops import build_hyper_graphs
+from .optim import FusedAdam
+from .sampler import next_batch_pairwise
+
+MAX_TRIALS = 1 << 20          # mhcn.py:26-30 retries until a negative is found (as directau.py's sampler)
 
 
 class MHCNEncoder(nn.Module):
@@ -96,7 +120,15 @@ class MHCNEncoder(nn.Module):
 
     def hierarchical_self_supervision(self, em, adj: CsrGraph, perms=None):
         """mhcn.py:480-506.  perms: the three row permutations the reference draws with torch.randperm
-        (row_shuffle, row_column_shuffle x 2); None draws them on the device."""
+        (row_shuffle, row_column_shuffle x 2); None draws them on the device.  Rows on the GPU of a width the kernel
+        family has (32 / 64 / 128 / 256) take `Fn.mim_loss` around the one SpMM; others the torch composition."""
+        if Fn.mim_supported(em):
+            return Fn.mim_loss(em, Fn.spmm(adj, em), perms)
+        return self.hierarchical_self_supervision_composed(em, adj, perms)
+
+    @staticmethod
+    def hierarchical_self_supervision_composed(em, adj: CsrGraph, perms=None):
+        """The same loss as a chain of torch expressions around the SpMM, written as the reference writes it."""
         n = em.shape[0]
         if perms is None:
             perms = [torch.randperm(n, device=em.device) for _ in range(3)]
@@ -110,15 +142,21 @@ class MHCNEncoder(nn.Module):
         neg1 = (edge[perms[2]] * graph).sum(1)
         return (-torch.log(torch.sigmoid(pos - neg1))).sum() + local
 
-    def forward(self, u_idx, v_idx, neg_idx, perms=None):
-        """Same 6-tuple as mhcn.py:422-478: batch user / positive / negative rows, ss_loss, final embeddings.
-        perms: optional 9 row permutations (3 per channel) replaying the reference's randperm draws."""
-        final_user, final_item = self.propagate()
+    def self_supervision(self, final_user, perms=None):
+        """ss_rate * the three channels' hierarchical losses on the self-supervised gates of `final_user`
+        (mhcn.py:470-473).  perms: optional 9 row permutations (3 per channel)."""
         ss = 0
         for c, adj in enumerate((self.H_s, self.H_j, self.H_p)):
             p = None if perms is None else perms[3 * c:3 * c + 3]
             ss = ss + self.hierarchical_self_supervision(self.self_supervised_gating(final_user, c + 1), adj, p)
-        return final_user[u_idx], final_item[v_idx], final_item[neg_idx], self.ss_rate * ss, final_user, final_item
+        return self.ss_rate * ss
+
+    def forward(self, u_idx, v_idx, neg_idx, perms=None):
+        """Same 6-tuple as mhcn.py:422-478: batch user / positive / negative rows, ss_loss, final embeddings.
+        perms: optional 9 row permutations (3 per channel) replaying the reference's randperm draws."""
+        final_user, final_item = self.propagate()
+        ss = self.self_supervision(final_user, perms)
+        return final_user[u_idx], final_item[v_idx], final_item[neg_idx], ss, final_user, final_item
 
 
 class HipOps:
@@ -204,3 +242,129 @@ class ShardedMHCNEncoder(MHCNEncoder):
 
     def forward(self, *a, **kw):
         raise NotImplementedError("the sharded encoder provides propagate(); the per-batch losses are the caller's")
+
+
+def social_pairs(social_data, user):
+    """`Relation.__initialize` (mhcn.py:102-108): the (follower, followee) pairs whose two users both occur in the
+    training set, as dense ids in list order — a repeated pair stays repeated (it sums to 2 in S, mhcn.py:121)."""
+    kept = [(user[p[0]], user[p[1]]) for p in social_data if p[0] in user and p[1] in user]
+    rows, cols = zip(*kept) if kept else ((), ())
+    return torch.tensor(rows, dtype=torch.int64), torch.tensor(cols, dtype=torch.int64)
+
+
+class MHCNModel:
+    def __init__(self, conf, train_set, test_set, social_data=None, device=None, seed=0):
+        """conf: the reference's keys (mhcn.py:316-327) — conf['MHCN']['n_layer' | 'ss_rate'], `emb_size` (64),
+        `batch_size` (2048), `lr` (1e-3), `reg_lambda` (1e-4), `max.epoch`, `item.ranking.topN` ([10, 20, 30, 50]).
+        social_data: [follower, followee, weight] triples.  seed: initial weights, batch order and negatives are functions
+        of it (the reference never seeds its generators)."""
+        self.config, self.seed = conf, int(seed)
+        args = conf["MHCN"]
+        self.n_layers, self.ss_rate = int(args["n_layer"]), float(args["ss_rate"])
+        self.emb_size = conf.get("emb_size", 64)
+        self.batch_size = conf.get("batch_size", 2048)
+        self.lRate = conf.get("lr", 0.001)
+        self.reg = conf.get("reg_lambda", 0.0001)
+        self.maxEpoch = int(conf["max.epoch"])
+        self.topN = [int(n) for n in conf.get("item.ranking.topN", [10, 20, 30, 50])]
+        self.max_N = max(self.topN)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if hasattr(train_set, "graphs"):                    # prepared operators (`from_graphs`)
+            self.data = train_set
+            graphs = train_set.graphs
+        else:
+            self.data = Interaction(conf, train_set, test_set, device=self.device)
+            s_row, s_col = social_pairs(social_data or [], self.data.user)
+            self.social_pairs = (s_row, s_col)
+            graphs = build_hyper_graphs(s_row, s_col, self.data.uid_dev, self.data.iid_dev, self.data.user_num,
+                                        self.data.item_num, self.device)
+        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
+            torch.manual_seed(self.seed)              # initial weights: a function of `seed`, the caller's RNG untouched
+            self.model = MHCNEncoder(*graphs, emb_size=self.emb_size, n_layers=self.n_layers, ss_rate=self.ss_rate)
+        self.optimizer = FusedAdam(list(self.model.parameters()), lr=self.lRate)
+        self.bestPerformance = []
+
+    @classmethod
+    def from_graphs(cls, conf, h_s, h_j, h_p, r, **kw):
+        """MHCNModel over operators that already live on the device (row-normalised H_s, H_j, H_p [U, U] and R [U, I]):
+        what the training step reads from the data object without the Python id maps (scripts/perf_mhcn_step.py)."""
+        data = types.SimpleNamespace(user_num=r.n_rows, item_num=r.n_cols, device=r.device, graphs=(h_s, h_j, h_p, r),
+                                     test_set={}, training_set_u={}, user={}, item={})
+        return cls(conf, data, None, None, device=r.device, **kw)
+
+    def losses(self, u, i, j, perms=None):
+        """mhcn.py:528-535 on the HIP path: (rec_loss, reg_loss, ss_loss, total_loss), differentiable, no host sync; keeps
+        the forward's final embeddings (detached) as the reference keeps `self.final_*_embeddings`."""
+        m = self.model
+        final_user, final_item = m.propagate()
+        ss_loss = m.self_supervision(final_user, perms)
+        rec_loss = Ls.bpr_gather_loss(final_user, final_item, u, i, j, Fn.BPR_NCL)[0]
+        reg_loss = 0
+        for _, param in m.named_parameters():         # the norm, not its square; its gradient at a zero bias is 0
+            reg_loss = reg_loss + self.reg * torch.norm(param, 2)
+        self.final_user_embeddings, self.final_item_embeddings = final_user.detach(), final_item.detach()
+        return rec_loss, reg_loss, ss_loss, rec_loss + reg_loss + ss_loss
+
+    def train_step(self, batch, perms=None):
+        """One body of mhcn.py:528-539 for batch = (user_idx, pos_idx, neg_idx): losses, zero_grad, backward, Adam step.
+        perms: optional 9 row permutations replaying the self-supervision's randperm draws.  Returns the detached terms
+        (rec_loss, reg_loss, ss_loss, total_loss)."""
+        dev = self.device
+        u, i, j = (torch.as_tensor(t, device=dev, dtype=torch.int64).contiguous() for t in batch)
+        if perms is not None:
+            perms = [torch.as_tensor(p, device=dev, dtype=torch.int64) for p in perms]
+        self.optimizer.zero_grad(set_to_none=True)
+        out = self.losses(u, i, j, perms)
+        out[3].backward()
+        self.optimizer.step()
+        return tuple(t.detach() for t in out)
+
+    def train_epoch(self, epoch):
+        self.model.train()
+        for batch in next_batch_pairwise(self.data, self.batch_size, seed=self.seed, epoch=epoch, max_trials=MAX_TRIALS):
+            self.train_step(batch)
+
+    def train(self):
+        """mhcn.py:508-518 with its quirks: the embeddings evaluated after an epoch are the ones the LAST batch's forward
+        produced, before that batch's update (they are not re-encoded), and `save()` runs once after the loop, so the
+        "best" tables are the last epoch's."""
+        for epoch in range(self.maxEpoch):
+            self.train_epoch(epoch)
+            self.U, self.V = self.final_user_embeddings.contiguous(), self.final_item_embeddings.contiguous()
+            self.fast_evaluation(epoch)
+        self.save()
+        self.U, self.V = self.best_user_emb, self.best_item_emb
+        return self.evaluate()
+
+    def save(self):
+        self.best_user_emb = self.final_user_embeddings.contiguous()
+        self.best_item_emb = self.final_item_embeddings.contiguous()
+
+    def _final(self):
+        if not hasattr(self, "U"):                          # never trained: the current parameters' forward
+            with torch.no_grad():
+                fu, fi = self.model.propagate()
+            self.U, self.V = fu.contiguous(), fi.contiguous()
+        return self.U, self.V
+
+    def predict(self, u):
+        """mhcn.py:546-548: V @ U[u], the scores of every item for raw user id u."""
+        U, V = self._final()
+        return torch.matmul(V, U[self.data.get_user_id(u)]).cpu().numpy()
+
+    def test(self):
+        U, V = self._final()
+        return rank_test(self.data, U, V, self.max_N)
+
+    def fast_evaluation(self, epoch):
+        """mhcn.py:306-312: the four metrics at max_N; bestPerformance follows Recall."""
+        lines = ranking_evaluation(self.data.test_set, self.test(), [self.max_N], device=self.device)
+        performance = {k: float(v) for m in lines[1:] for k, v in [m.strip().split(":")]}
+        if not self.bestPerformance or performance.get("Recall", 0) > self.bestPerformance[1].get("Recall", 0):
+            self.bestPerformance = [epoch + 1, performance]
+        return performance
+
+    def evaluate(self):
+        """mhcn.py:550-555: every cut-off's metrics flattened into one dict, so the last cut-off's four remain."""
+        metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN, device=self.device)
+        return {k: float(v) for m in metrics[1:] if ":" in m for k, v in [m.strip().split(":", 1)]}
