@@ -110,6 +110,17 @@ int32_t gcr_spmm_csr_acc2_f32(const int64_t* desc, int64_t n_parts,
 int32_t gcr_spmm_hub_reduce_f32(const int32_t* hub_row, int64_t n_hub, int32_t n_windows, const float* partials,
                                 int32_t d, float val_scale, float* y, const float* acc_in, float* acc_out,
                                 float acc_scale, int64_t n_rows, void* stream);
+/*
+ * Step 1 of a windowed launch for d <= 64: y = H x for the companion H with its plan (the arguments of gcr_spmm_csr_f32 on
+ * H with y only, val_scale 1 and no mask), one wave per partition as there, by a kernel without the epilogue that gathers
+ * what is left of a 64-non-zero block in batches instead of one row at a time; the companion's own split segments are then
+ * summed from `partials` in chunk order as gcr_spmm_csr_f32 does.  Every word written equals that launch's, bit for bit.
+ * d > 64: GCR_EUNSUPPORTED (the caller keeps gcr_spmm_csr_f32 on H).
+ */
+int32_t gcr_spmm_hub_parts_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0,
+                               int64_t n_long_rows, const int64_t* rowptr, const int32_t* col, const float* val,
+                               const float* x, int32_t d, float* y, float* partials, int64_t n_rows, int64_t n_cols,
+                               void* stream);
 /* bits[idx[i] >> 5] |= 1 << (idx[i] & 31) for every idx[i] in [0, n_bits) (atomic OR; the caller zeroes `bits`). */
 int32_t gcr_bitmap_set(const int64_t* idx, int64_t n, int64_t n_bits, uint32_t* bits, void* stream);
 

@@ -63,8 +63,9 @@ with torch.no_grad():
     for _ in range(2):
         Fn.lightgcn_propagate(graph, x0, wl["layers"], combine="sum")
 torch.cuda.synchronize()
-# kernels per layer: with the windowed companion of the hub rows (graph.HubPlan) a layer is the companion's spmm_parts
-# (+ spmm_long_rows for its split segments), spmm_hub_rows and the main plan's spmm_parts (+ spmm_long_rows)
+# kernels per layer: with the windowed companion of the hub rows (graph.HubPlan) a layer is the companion's spmm_hub_parts
+# (counted as a spmm_parts dispatch, which it was; + spmm_long_rows for its split segments), spmm_hub_rows and the main
+# plan's spmm_parts (+ spmm_long_rows)
 hub = graph.hub if graph.hub is not None and graph.hub.eligible(64) else None
 if hub is None:
     per = {"spmm_parts": 1, "spmm_long_rows": int(graph.plan.n_long > 0), "spmm_hub_rows": 0}

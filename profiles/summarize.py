@@ -118,7 +118,11 @@ for wl in ("cfg2", "cfg4", "cfg2c_before", "cfg2c_after", "cfg4c_before", "cfg4c
         continue
     info = json.load(open(info_path))
     rows = []
-    kname = lambda k: ("spmm_parts" if "spmm_parts" in k else "spmm_hub_rows" if "spmm_hub_rows" in k else "spmm_long_rows")  # noqa: E731
+    # the CSV keeps every kernel's own name; `slot` maps the companion's launch (`spmm_hub_parts` at d <= 64, a second
+    # `spmm_parts` at wider d and before) to the place it has in the probe's dispatch count and in
+    # parts_fetch_kb_by_dispatch (companion first, main second)
+    kname = lambda k: next(n for n in ("spmm_hub_parts", "spmm_parts", "spmm_hub_rows", "spmm_long_rows") if n in k)  # noqa: E731
+    slot = lambda n: "spmm_parts" if n == "spmm_hub_parts" else n  # noqa: E731
     for kind, path in (("fetch", fetch), ("write", write)):
         k = 0
         for r in csv.DictReader(open(path)):
@@ -129,7 +133,7 @@ for wl in ("cfg2", "cfg4", "cfg2c_before", "cfg2c_after", "cfg4c_before", "cfg4c
         w = csv.writer(f)
         w.writerow(["pass", "dispatch", "kernel", "grid", "counter", "value_KB"])
         w.writerows(rows)
-    pick = lambda kind, name: [float(r[5]) for r in rows if r[0] == kind and r[2] == name]  # noqa: E731
+    pick = lambda kind, name: [float(r[5]) for r in rows if r[0] == kind and slot(r[2]) == name]  # noqa: E731
     f_parts, w_parts = pick("fetch", "spmm_parts"), pick("write", "spmm_parts")
     # dispatch order: 3 calibration launches, [the renumbering's own subspace-iteration launches], then the measured
     # 2 forward passes x K layers -- always the LAST dispatches.  A layer is one spmm_parts + one spmm_long_rows, or, with

@@ -23,6 +23,8 @@
 //     spmm_long_rows (deterministic; no float atomics).
 #include "gcr_common.h"
 
+#include <type_traits>
+
 namespace {
 
 // gathers in flight per wave before the first FMA: interleaved A/B on MI355X (scripts/perf_spmm_ab.py, round 1)
@@ -381,6 +383,107 @@ __global__ __launch_bounds__(256) void spmm_hub_rows(const int32_t* __restrict__
   }
 }
 
+// The windowed companion's own kernel (graph.py HubPlan, step 1 of a windowed launch: partials = H x, nothing else), d <= 64.
+// One wave per partition in the hardware's dispatch order, as `spmm_parts`, and the words it writes are those of
+// `spmm_parts` on H with y only: one fmaf per non-zero from 0 in stored order, a whole-row partition stores its rows (empty
+// ones zeros), a chunk partition its slot.  What differs is the partition body.  No mask, no epilogue, no acc_in queue: a
+// row's sum is stored as it stands (`spmm_parts` multiplied it by a val_scale of 1.0).  The next 64-non-zero block's col /
+// val are loaded before this block's gathers.  And what is left of a block below a full batch of 16 goes out in batches of
+// 8, 4, 2 and 1 instead of one gather at a time: the companion's partitions average 96 non-zeros, so 7-8 of a partition's
+// gathers were such single round trips beside the six batches that carried the rest, and that is where its waves waited
+// (EXPERIMENTS.md "SpMM: spmm_hub_parts, the companion's own kernel").
+template <bool D64, bool HAS_VAL>
+__global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict__ desc, int64_t n_parts,
+                                                      const int64_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ col, const float* __restrict__ val,
+                                                      const float* __restrict__ x, int d, float* __restrict__ y,
+                                                      float* __restrict__ partials) {
+  constexpr int UNR = 16;
+  const int lane = threadIdx.x & 63;
+  const int64_t part = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (part >= n_parts) return;
+  const int64_t nnz0 = desc[4 * part + 0];
+  const int n = (int)(desc[4 * part + 1] - nnz0);
+  const int64_t rowinfo = desc[4 * part + 2];
+  const int64_t slot = desc[4 * part + 3];
+  const int row0 = (int)(rowinfo & 0xffffffffll);
+  const int nrows = (int)(rowinfo >> 32);
+  const bool whole_rows = slot < 0;
+
+  // local end offsets of the (<= 64) rows of a whole-row partition, one per lane
+  int ends_v = 0x7fffffff;
+  if (whole_rows && lane < nrows) ends_v = (int)(rowptr[row0 + lane + 1] - nnz0);
+  int cur = 0;
+  int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
+
+  float acc = 0.f;
+  auto flush = [&]() {
+    if (D64 || lane < d) y[((int64_t)row0 + cur) * d + lane] = acc;
+    acc = 0.f;
+    ++cur;
+    cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
+  };
+  // column id and value of the 64 non-zeros of block b, one per lane
+  auto load_block = [&](int b, int& cv_o, float& vv_o) {
+    cv_o = 0;
+    vv_o = 0.f;
+    if (lane < n - b) {
+      const int64_t e = nnz0 + b + lane;
+      cv_o = col[e];
+      vv_o = HAS_VAL ? val[e] : 1.0f;
+    }
+  };
+
+  int cv, cv_n = 0;
+  float vv, vv_n = 0.f;
+  load_block(0, cv, vv);
+  for (int b = 0; b < n; b += 64) {
+    const int m = min(64, n - b);
+    if (b + 64 < n) load_block(b + 64, cv_n, vv_n);
+    // B gathers issued back to back, then consumed in stored order with the row ends between them
+    auto batch = [&](auto bc, int jb) {
+      constexpr int B = decltype(bc)::value;
+      float xr[B];
+#pragma unroll
+      for (int u = 0; u < B; ++u) {
+        const float* xp = x + (int64_t)gcr_readlane_i(cv, jb + u) * d;
+        xr[u] = (D64 || lane < d) ? xp[lane] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < B; ++u) {
+        if (whole_rows) {
+          while (b + jb + u >= cur_end) flush();
+        }
+        const float w = HAS_VAL ? gcr_readlane_f(vv, jb + u) : 1.0f;
+        acc = fmaf(w, xr[u], acc);
+      }
+    };
+    int j = 0;
+    while (m - j >= UNR) {
+      batch(std::integral_constant<int, UNR>{}, j);
+      j += UNR;
+    }
+#define GCR_HUB_TAIL(B)                           \
+  if (m - j >= B) {                               \
+    batch(std::integral_constant<int, B>{}, j);   \
+    j += B;                                       \
+  }
+    GCR_HUB_TAIL(8)
+    GCR_HUB_TAIL(4)
+    GCR_HUB_TAIL(2)
+    GCR_HUB_TAIL(1)
+#undef GCR_HUB_TAIL
+    cv = cv_n;
+    vv = vv_n;
+  }
+
+  if (whole_rows) {
+    while (cur < nrows) flush();
+  } else {
+    if (D64 || lane < d) partials[slot * (int64_t)d + lane] = acc;
+  }
+}
+
 __global__ void csr_validate_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                     int64_t n_rows, int64_t n_cols, int64_t nnz,
                                     unsigned long long* __restrict__ n_errors) {
@@ -561,6 +664,46 @@ extern "C" int32_t gcr_spmm_hub_reduce_f32(const int32_t* hub_row, int64_t n_hub
   if (d <= 192) GCR_GO(3, false);
   GCR_GO(4, false);
 #undef GCR_GO
+}
+
+// Step 1 of a windowed launch (graph.py HubPlan) for d <= 64: y[H rows] = H x by `spmm_hub_parts`, then the companion's own
+// split segments through `spmm_long_rows`, exactly as gcr_spmm_csr_f32 on H with y only would have run them.
+extern "C" int32_t gcr_spmm_hub_parts_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
+                                          const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
+                                          const int32_t* col, const float* val, const float* x, int32_t d, float* y,
+                                          float* partials, int64_t n_rows, int64_t n_cols, void* stream) {
+  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
+  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
+  GCR_CHECK_ARG(d >= 1 && d <= 256);
+  if (d > 64) return GCR_EUNSUPPORTED;
+  if (n_rows == 0 || n_parts == 0) return GCR_OK;
+  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && col != nullptr && x != nullptr && y != nullptr);
+  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
+  const unsigned blocks = (unsigned)((n_parts + 3) / 4);
+  hipStream_t s = (hipStream_t)stream;
+#define GCR_HUB(D64, HV) \
+  hipLaunchKernelGGL((spmm_hub_parts<D64, HV>), dim3(blocks), dim3(256), 0, s, desc, n_parts, rowptr, col, val, x, d, y, partials)
+  if (d == 64) {
+    if (val != nullptr) GCR_HUB(true, true);
+    else GCR_HUB(true, false);
+  } else {
+    if (val != nullptr) GCR_HUB(false, true);
+    else GCR_HUB(false, false);
+  }
+#undef GCR_HUB
+  int32_t st = GCR_LAUNCH_STATUS();
+  if (st != GCR_OK) return st;
+  if (n_long_rows > 0) {
+    Epilogue ep{1.0f, y, nullptr, nullptr, 1.0f, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
+    if (d == 64)
+      hipLaunchKernelGGL((spmm_long_rows<1, true, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
+                         long_slot0, n_long_rows, partials, d, ep);
+    else
+      hipLaunchKernelGGL((spmm_long_rows<1, false, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
+                         long_slot0, n_long_rows, partials, d, ep);
+    return GCR_LAUNCH_STATUS();
+  }
+  return GCR_OK;
 }
 
 extern "C" int32_t gcr_csr_validate(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_cols,

@@ -11,6 +11,7 @@ from . import _lib
 from .graph import CsrGraph
 
 SPMM_ROW_L2NORM = 1
+HUB_PARTS_MAX_D = 64       # gcr_spmm_hub_parts_f32 holds one register per lane and row; wider launches keep spmm_parts on H
 
 # bench.py sets this to a list to receive a (start, end) HIP event pair per gcr_spmm_csr_f32
 # launch, recorded on the stream the kernel is launched on
@@ -63,10 +64,17 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
             and inv_norm_out is None and hub.eligible(d)):
         L, H, stream = _lib.lib(), hub.H, _lib.cur_stream(x.device)
         part = hub.partials(d)
-        _lib.check(L.gcr_spmm_csr_acc2_f32(
-            _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0), H.plan.n_long,
-            _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d, _lib.dptr(part), None, None,
-            0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
+        if d <= HUB_PARTS_MAX_D:          # the companion's own kernel: the same words, the tail of a block gathered in batches
+            _lib.check(L.gcr_spmm_hub_parts_f32(
+                _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0),
+                H.plan.n_long, _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(x), d, _lib.dptr(part),
+                _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, stream), "gcr_spmm_hub_parts_f32")
+        else:
+            _lib.check(L.gcr_spmm_csr_acc2_f32(
+                _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0),
+                H.plan.n_long, _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d,
+                _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None,
+                stream), "gcr_spmm_csr_acc2_f32")
         _lib.check(L.gcr_spmm_hub_reduce_f32(
             _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
             _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")

@@ -95,7 +95,9 @@ class HubPlan:
     column lies in window w, in stored order (`col` / `val` copied window-major).  `H` gets an ordinary whole-row plan with
     small partitions whose descriptors are laid out per XCD window after window (reorder.xcd_grouped_order), so the waves
     resident on one XCD gather from two or three windows of the table at a time.  A launch is then
-      1. partials[W n_hub, d] = H x            gcr_spmm_csr_f32 on H, y only, val_scale 1
+      1. partials[W n_hub, d] = H x            gcr_spmm_hub_parts_f32 at d <= 64 (the same partitions, one wave each, by a
+                                               kernel without the epilogue that gathers the tail of a block in batches);
+                                               gcr_spmm_csr_f32 on H, y only, val_scale 1 at wider d (the same bits)
       2. out[hub rows] = epilogue(sum of a row's window partials in window order)      gcr_spmm_hub_reduce_f32
       3. every other row: the classic walk with the hub rows skipped (`main`)          gcr_spmm_csr_f32
     on one stream.  The 8 W bound keeps the partial traffic (W x 2 x 4 d bytes per hub row) under a quarter of the row's

@@ -16,7 +16,8 @@ A library that exports gcr_spmm_hub_reduce_f32 runs the layer as functional.spmm
 companion of the hub rows, their reduction, then the main plan (graph.HubPlan) -- three launches between the same two events.
 Its hub rows are summed in another order than the base's, so `equal_to_base` is false there and the largest difference
 relative to the largest output is printed beside it.  --hub-config WINDOW_ROWS:NNZ_PER_PART[:MIN_DEGREE] (repeatable) times
-that library once per companion layout instead of the graph's own.
+that library once per companion layout instead of the graph's own.  A library that also exports gcr_spmm_hub_parts_f32
+runs the companion (d <= 64) through it, as functional.spmm_into does.
 
 The measurement runs in a child process under a time limit of its own (--timeout seconds); the parent never touches the
 GPU and stops at the first failure."""
@@ -49,23 +50,27 @@ def child(args):
     p, ws = graph.plan, graph.workspace(d)
     res, argt = _lib.SIGNATURES["gcr_spmm_csr_acc2_f32"]
     from recommendation_amd.graph import HubPlan
-    libs = []
+    libs, plans = [], {}
     for path in args.lib:
         h = ctypes.CDLL(os.path.abspath(path))
         fn = h.gcr_spmm_csr_acc2_f32
         fn.restype, fn.argtypes = res, argt
         red = getattr(h, "gcr_spmm_hub_reduce_f32", None)
         if red is None or args.acc2:                       # the second-addend form never takes the windowed plan
-            libs.append((path, fn, None, None))
+            libs.append((path, fn, None, None, None))
             continue
         red.restype, red.argtypes = _lib.SIGNATURES["gcr_spmm_hub_reduce_f32"]
+        own = getattr(h, "gcr_spmm_hub_parts_f32", None) if d <= 64 else None
+        if own is not None:
+            own.restype, own.argtypes = _lib.SIGNATURES["gcr_spmm_hub_parts_f32"]
         if not args.hub_config:
             hub = graph.hub if graph.hub is not None and graph.hub.eligible(d) else None
-            libs.append((path, fn, red, hub))
+            libs.append((path, fn, red, hub, own))
         for cfg in args.hub_config or []:
             wr, npp, *mind = (int(v) for v in cfg.split(":"))
-            libs.append((f"{path} [hub {cfg}]", fn, red,
-                         HubPlan.build(graph, wr, min_degree=mind[0] if mind else None, nnz_per_part=npp, forced=True)))
+            if cfg not in plans:                           # one companion per layout, shared by the libraries
+                plans[cfg] = HubPlan.build(graph, wr, min_degree=mind[0] if mind else None, nnz_per_part=npp, forced=True)
+            libs.append((f"{path} [hub {cfg}]", fn, red, plans[cfg], own))
     stream = _lib.cur_stream(torch.device(dev))
 
     # --acc2: the Horner backward's form, a second addend with its own scale (the ACC2 instantiation of the kernel)
@@ -73,14 +78,19 @@ def child(args):
     in2_scale = 0.25 if args.acc2 else 0.0
 
     def launch(lib, x, out):
-        _, fn, red, hub = lib
+        _, fn, red, hub, own = lib
         q = p
         if hub is not None:
             H, hp, part = hub.H, hub.H.plan, hub.partials(d)
-            _lib.check(fn(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
-                          _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d, _lib.dptr(part),
-                          None, None, 0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None, stream),
-                       "gcr_spmm_csr_acc2_f32")
+            if own is not None:
+                _lib.check(own(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
+                               _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(x), d, _lib.dptr(part),
+                               _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, stream), "gcr_spmm_hub_parts_f32")
+            else:
+                _lib.check(fn(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
+                              _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d,
+                              _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows,
+                              H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
             _lib.check(red(_lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, 1.0, None, _lib.dptr(x0),
                            _lib.dptr(out), 1.0, graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
             q = hub.main
@@ -108,7 +118,7 @@ def child(args):
             ms[k].append(e0.elapsed_time(e1) / args.launches)
     report = {"workload": args.workload, "acc2": bool(args.acc2), "d": d, "nnz": graph.nnz, "n_parts": p.n_parts, "n_long": p.n_long,
               "alternations": args.alternations, "launches": args.launches, "libs": []}
-    for k, (path, _, _, hub) in enumerate(libs):
+    for k, (path, _, _, hub, _) in enumerate(libs):
         m = sum(ms[k]) / len(ms[k])
         ent = {"lib": path, "ms_per_layer": [round(v, 5) for v in ms[k]], "mean": round(m, 5),
                "spread": round(max(ms[k]) - min(ms[k]), 5), "equal_to_base": bool(torch.equal(outs[k], outs[0])),
