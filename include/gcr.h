@@ -121,6 +121,18 @@ int32_t gcr_spmm_hub_parts_f32(const int64_t* desc, int64_t n_parts, const int32
                                int64_t n_long_rows, const int64_t* rowptr, const int32_t* col, const float* val,
                                const float* x, int32_t d, float* y, float* partials, int64_t n_rows, int64_t n_cols,
                                void* stream);
+/*
+ * The plain launch for d <= 64: the arguments of gcr_spmm_csr_f32 without keep_bits, flags and inv_norm_out, by a kernel
+ * of its own for exactly that form (no mask, no second addend, no row normalise): y = val_scale * A x and / or
+ * acc_out = (acc_in + y) * acc_scale (acc_in may be NULL or equal acc_out), the same partitions, one wave each, split rows
+ * summed from `partials` in chunk order.  Only the schedule of a partition differs (the next 64 non-zeros' col / val are
+ * loaded ahead of the gathers; what is left below a batch of 16 is gathered in batches): every word written equals
+ * gcr_spmm_csr_f32's, bit for bit.  d > 64: GCR_EUNSUPPORTED (the caller keeps gcr_spmm_csr_f32).
+ */
+int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0,
+                          int64_t n_long_rows, const int64_t* rowptr, const int32_t* col, const float* val,
+                          float val_scale, const float* x, int32_t d, float* y, const float* acc_in, float* acc_out,
+                          float acc_scale, float* partials, int64_t n_rows, int64_t n_cols, void* stream);
 /* bits[idx[i] >> 5] |= 1 << (idx[i] & 31) for every idx[i] in [0, n_bits) (atomic OR; the caller zeroes `bits`). */
 int32_t gcr_bitmap_set(const int64_t* idx, int64_t n, int64_t n_bits, uint32_t* bits, void* stream);
 

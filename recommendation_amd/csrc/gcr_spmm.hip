@@ -484,6 +484,162 @@ __global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict_
   }
 }
 
+// The plain launch's own kernel (gcr_spmm_rows_f32), d <= 64: what `spmm_parts<1, D64, HAS_VAL, false, 16, false>` is used
+// for and nothing else.  No edge or column mask, no second addend, no row normalise, no second output; the epilogue is
+// y = acc * val_scale and / or acc_out = (acc_in + y) * acc_scale with store_row's two roundings.  One wave per partition in
+// the hardware's dispatch order, one fmaf per non-zero from 0 in stored order, whole-row partitions store their rows and
+// chunk partitions their slot: every word written equals `spmm_parts`'s.  What differs is the schedule of a partition:
+//   * a block that has a successor is a block of exactly 64 non-zeros, and it has a path of its own: the successor's col /
+//     val are loaded BEFORE its four batches of gathers and are back with the first of them, so the copy at its end waits
+//     for nothing the last batch's last FMA has not waited for (the generic kernel loads them after that FMA: one exposed
+//     round trip per block);
+//   * what the last block holds below a full batch of 16 goes out in batches of 8, 4, 2 and 1, as in `spmm_hub_parts`,
+//     instead of one gather, one wait at a time;
+//   * the two-entry acc_in queue of `spmm_parts` is kept as it is: refilled in front of a batch's gathers, so the combine
+//     at a row end waits for nothing younger than a gather it has already waited for.
+// 52 VGPRs / 82 SGPRs at d = 64 with values, 8 waves per SIMD without an SGPR cap and without lane spills (`spmm_parts`: 63
+// / 94 capped, 18 scalars in VGPR lanes).  Measurements: EXPERIMENTS.md "SpMM: spmm_rows".
+template <bool D64, bool HAS_VAL>
+__global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ desc, int64_t n_parts,
+                                                 const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                 const float* __restrict__ val, const float* __restrict__ x, int d,
+                                                 float val_scale, float* y, const float* acc_in, float* acc_out,
+                                                 float acc_scale, float* __restrict__ partials) {
+  constexpr int UNR = 16;
+  const int lane = threadIdx.x & 63;
+  const int64_t part = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+  if (part >= n_parts) return;
+  const int64_t nnz0 = desc[4 * part + 0];
+  const int n = (int)(desc[4 * part + 1] - nnz0);
+  const int64_t rowinfo = desc[4 * part + 2];
+  const int64_t slot = desc[4 * part + 3];
+  const int row0 = (int)(rowinfo & 0xffffffffll);
+  const int nrows = (int)(rowinfo >> 32);
+  const bool whole_rows = slot < 0;
+  const bool on = D64 || lane < d;
+
+  // local end offsets of the (<= 64) rows of a whole-row partition, one per lane
+  int ends_v = 0x7fffffff;
+  if (whole_rows && lane < nrows) ends_v = (int)(rowptr[row0 + lane + 1] - nnz0);
+  int cur = 0;
+  int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
+
+  // acc_in of rows cur and cur + 1, loaded ahead of their flush (see spmm_parts): none for chunks, y-only launches and
+  // acc_in == NULL.  In place (acc_in == acc_out) stays correct: a row is read before this wave, its only writer, stores it.
+  float q0 = 0.f, q1 = 0.f;
+  int nq = 0;
+  const int qrows = (whole_rows && acc_in != nullptr && acc_out != nullptr) ? nrows : 0;
+  auto refill = [&]() {
+    if (nq < 1 && cur < qrows) q0 = on ? acc_in[((int64_t)row0 + cur) * d + lane] : 0.f;
+    if (nq < 2 && cur + 1 < qrows) q1 = on ? acc_in[((int64_t)row0 + cur + 1) * d + lane] : 0.f;
+    nq = max(nq, min(2, qrows - cur));
+  };
+
+  float acc = 0.f;
+  auto flush = [&]() {
+    // two roundings, as store_row: `acc * val_scale`, then the add of acc_in, never contracted
+#pragma clang fp contract(off)
+    const float yv = acc * val_scale;
+    const int64_t base = ((int64_t)row0 + cur) * d + lane;
+    if (y != nullptr) {
+      if (on) y[base] = yv;
+    }
+    if (acc_out != nullptr) {
+      if (nq > 0) {
+        if (on) acc_out[base] = (q0 + yv) * acc_scale;
+        q0 = q1;
+        --nq;
+      } else {
+        // fewer queued rows than row ends in one batch (degree-1 runs), or nothing to prefetch: load at the flush
+        if (on) {
+          const float prev = acc_in != nullptr ? acc_in[base] : 0.f;
+          acc_out[base] = (prev + yv) * acc_scale;
+        }
+      }
+    }
+    acc = 0.f;
+    ++cur;
+    cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
+  };
+  // column id and value of the 64 non-zeros of block b, one per lane
+  auto load_block = [&](int b, int& cv_o, float& vv_o) {
+    cv_o = 0;
+    vv_o = 0.f;
+    if (lane < n - b) {
+      const int64_t e = nnz0 + b + lane;
+      cv_o = col[e];
+      vv_o = HAS_VAL ? val[e] : 1.0f;
+    }
+  };
+
+  int cv, cv_n = 0;
+  float vv, vv_n = 0.f;
+  load_block(0, cv, vv);
+  // The first block's words are waited for here, once, and not at the first v_readlane of the batch loop: that wait would
+  // sit behind refill() in the loop body and hold every batch of the block until the acc_in it has just asked for is back.
+  asm volatile("" ::"v"(cv), "v"(vv));
+  for (int b = 0; b < n; b += 64) {
+    // B gathers issued back to back, then consumed in stored order with the row ends between them
+    auto batch = [&](auto bc, int jb) {
+      constexpr int B = decltype(bc)::value;
+      float xr[B];
+#pragma unroll
+      for (int u = 0; u < B; ++u) {
+        const float* xp = x + (int64_t)gcr_readlane_i(cv, jb + u) * d;
+        xr[u] = on ? xp[lane] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < B; ++u) {
+        if (whole_rows) {
+          while (b + jb + u >= cur_end) flush();
+        }
+        const float w = HAS_VAL ? gcr_readlane_f(vv, jb + u) : 1.0f;
+        acc = fmaf(w, xr[u], acc);
+      }
+    };
+    if (b + 64 < n) {
+      // 64 non-zeros and a successor
+      load_block(b + 64, cv_n, vv_n);
+      int j = 0;
+      do {
+        refill();
+        batch(std::integral_constant<int, UNR>{}, j);
+        j += UNR;
+      } while (j < 64);
+      cv = cv_n;
+      vv = vv_n;
+    } else {
+      const int m = n - b;
+      int j = 0;
+      while (m - j >= UNR) {
+        refill();
+        batch(std::integral_constant<int, UNR>{}, j);
+        j += UNR;
+      }
+#define GCR_ROWS_TAIL(B)                          \
+  if (m - j >= B) {                               \
+    refill();                                     \
+    batch(std::integral_constant<int, B>{}, j);   \
+    j += B;                                       \
+  }
+      GCR_ROWS_TAIL(8)
+      GCR_ROWS_TAIL(4)
+      GCR_ROWS_TAIL(2)
+      GCR_ROWS_TAIL(1)
+#undef GCR_ROWS_TAIL
+    }
+  }
+
+  if (whole_rows) {
+    while (cur < nrows) {
+      if (nq == 0) refill();
+      flush();
+    }
+  } else {
+    if (on) partials[slot * (int64_t)d + lane] = acc;
+  }
+}
+
 __global__ void csr_validate_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                     int64_t n_rows, int64_t n_cols, int64_t nnz,
                                     unsigned long long* __restrict__ n_errors) {
@@ -695,6 +851,50 @@ extern "C" int32_t gcr_spmm_hub_parts_f32(const int64_t* desc, int64_t n_parts, 
   if (st != GCR_OK) return st;
   if (n_long_rows > 0) {
     Epilogue ep{1.0f, y, nullptr, nullptr, 1.0f, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
+    if (d == 64)
+      hipLaunchKernelGGL((spmm_long_rows<1, true, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
+                         long_slot0, n_long_rows, partials, d, ep);
+    else
+      hipLaunchKernelGGL((spmm_long_rows<1, false, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
+                         long_slot0, n_long_rows, partials, d, ep);
+    return GCR_LAUNCH_STATUS();
+  }
+  return GCR_OK;
+}
+
+// The plain launch at d <= 64 (no mask, no second addend, no row normalise): `spmm_rows` on the partitions, then the split
+// rows through `spmm_long_rows` with the same epilogue, exactly as gcr_spmm_csr_f32 runs them.  Every word written equals
+// that launch's.  d > 64: GCR_EUNSUPPORTED (the caller keeps gcr_spmm_csr_f32).
+extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
+                                     const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
+                                     const int32_t* col, const float* val, float val_scale, const float* x, int32_t d,
+                                     float* y, const float* acc_in, float* acc_out, float acc_scale, float* partials,
+                                     int64_t n_rows, int64_t n_cols, void* stream) {
+  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
+  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
+  GCR_CHECK_ARG(d >= 1 && d <= 256);
+  if (d > 64) return GCR_EUNSUPPORTED;
+  if (n_rows == 0 || n_parts == 0) return GCR_OK;
+  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && x != nullptr);
+  GCR_CHECK_ARG(y != nullptr || acc_out != nullptr);
+  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
+  const unsigned blocks = (unsigned)((n_parts + 3) / 4);
+  hipStream_t s = (hipStream_t)stream;
+#define GCR_ROWS(D64, HV)                                                                                              \
+  hipLaunchKernelGGL((spmm_rows<D64, HV>), dim3(blocks), dim3(256), 0, s, desc, n_parts, rowptr, col, val, x, d, val_scale, \
+                     y, acc_in, acc_out, acc_scale, partials)
+  if (d == 64) {
+    if (val != nullptr) GCR_ROWS(true, true);
+    else GCR_ROWS(true, false);
+  } else {
+    if (val != nullptr) GCR_ROWS(false, true);
+    else GCR_ROWS(false, false);
+  }
+#undef GCR_ROWS
+  int32_t st = GCR_LAUNCH_STATUS();
+  if (st != GCR_OK) return st;
+  if (n_long_rows > 0) {
+    Epilogue ep{val_scale, y, acc_in, acc_out, acc_scale, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
     if (d == 64)
       hipLaunchKernelGGL((spmm_long_rows<1, true, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
                          long_slot0, n_long_rows, partials, d, ep);

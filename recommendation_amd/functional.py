@@ -11,6 +11,7 @@ from . import _lib
 from .graph import CsrGraph
 
 SPMM_ROW_L2NORM = 1
+ROWS_MAX_D = 64            # gcr_spmm_rows_f32, the plain launch's own kernel, likewise; wider launches keep gcr_spmm_csr_acc2_f32
 HUB_PARTS_MAX_D = 64       # gcr_spmm_hub_parts_f32 holds one register per lane and row; wider launches keep spmm_parts on H
 
 # bench.py sets this to a list to receive a (start, end) HIP event pair per gcr_spmm_csr_f32
@@ -79,6 +80,17 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
             _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
             _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
         p = hub.main                      # every other row: the classic walk with the hub rows skipped
+    if (keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm and inv_norm_out is None
+            and d <= ROWS_MAX_D):         # the plain launch's own kernel: the same words on another schedule
+        _lib.check(_lib.lib().gcr_spmm_rows_f32(
+            _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
+            _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), float(val_scale), _lib.dptr(x), d,
+            _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), _lib.dptr(ws), graph.n_rows, graph.n_cols,
+            _lib.cur_stream(x.device)), "gcr_spmm_rows_f32")
+        if sink is not None:
+            ev1.record()
+            sink.append((ev0, ev1))
+        return y if y is not None else acc_out
     rc = _lib.lib().gcr_spmm_csr_acc2_f32(
         _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
         _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(keep_bits), float(val_scale),

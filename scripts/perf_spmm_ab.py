@@ -17,7 +17,9 @@ companion of the hub rows, their reduction, then the main plan (graph.HubPlan) -
 Its hub rows are summed in another order than the base's, so `equal_to_base` is false there and the largest difference
 relative to the largest output is printed beside it.  --hub-config WINDOW_ROWS:NNZ_PER_PART[:MIN_DEGREE] (repeatable) times
 that library once per companion layout instead of the graph's own.  A library that also exports gcr_spmm_hub_parts_f32
-runs the companion (d <= 64) through it, as functional.spmm_into does.
+runs the companion (d <= 64) through it, as functional.spmm_into does.  A library that exports gcr_spmm_rows_f32 runs the
+main launch (d <= 64, not --acc2) through it, again as functional.spmm_into does; its words are the generic launch's, so
+`equal_to_base` must hold against a base with the same plan.
 
 The measurement runs in a child process under a time limit of its own (--timeout seconds); the parent never touches the
 GPU and stops at the first failure."""
@@ -55,9 +57,12 @@ def child(args):
         h = ctypes.CDLL(os.path.abspath(path))
         fn = h.gcr_spmm_csr_acc2_f32
         fn.restype, fn.argtypes = res, argt
+        rows = getattr(h, "gcr_spmm_rows_f32", None) if d <= 64 and not args.acc2 else None
+        if rows is not None:
+            rows.restype, rows.argtypes = _lib.SIGNATURES["gcr_spmm_rows_f32"]
         red = getattr(h, "gcr_spmm_hub_reduce_f32", None)
         if red is None or args.acc2:                       # the second-addend form never takes the windowed plan
-            libs.append((path, fn, None, None, None))
+            libs.append((path, fn, None, None, None, rows))
             continue
         red.restype, red.argtypes = _lib.SIGNATURES["gcr_spmm_hub_reduce_f32"]
         own = getattr(h, "gcr_spmm_hub_parts_f32", None) if d <= 64 else None
@@ -65,12 +70,12 @@ def child(args):
             own.restype, own.argtypes = _lib.SIGNATURES["gcr_spmm_hub_parts_f32"]
         if not args.hub_config:
             hub = graph.hub if graph.hub is not None and graph.hub.eligible(d) else None
-            libs.append((path, fn, red, hub, own))
+            libs.append((path, fn, red, hub, own, rows))
         for cfg in args.hub_config or []:
             wr, npp, *mind = (int(v) for v in cfg.split(":"))
             if cfg not in plans:                           # one companion per layout, shared by the libraries
                 plans[cfg] = HubPlan.build(graph, wr, min_degree=mind[0] if mind else None, nnz_per_part=npp, forced=True)
-            libs.append((f"{path} [hub {cfg}]", fn, red, plans[cfg], own))
+            libs.append((f"{path} [hub {cfg}]", fn, red, plans[cfg], own, rows))
     stream = _lib.cur_stream(torch.device(dev))
 
     # --acc2: the Horner backward's form, a second addend with its own scale (the ACC2 instantiation of the kernel)
@@ -78,7 +83,7 @@ def child(args):
     in2_scale = 0.25 if args.acc2 else 0.0
 
     def launch(lib, x, out):
-        _, fn, red, hub, own = lib
+        _, fn, red, hub, own, rows = lib
         q = p
         if hub is not None:
             H, hp, part = hub.H, hub.H.plan, hub.partials(d)
@@ -94,6 +99,12 @@ def child(args):
             _lib.check(red(_lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, 1.0, None, _lib.dptr(x0),
                            _lib.dptr(out), 1.0, graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
             q = hub.main
+        if rows is not None:
+            _lib.check(rows(_lib.dptr(q.desc), q.n_parts, _lib.dptr(q.long_row), _lib.dptr(q.long_slot0), q.n_long,
+                            _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), 1.0, _lib.dptr(x), d, None,
+                            _lib.dptr(x0), _lib.dptr(out), 1.0, _lib.dptr(ws), graph.n_rows, graph.n_cols, stream),
+                       "gcr_spmm_rows_f32")
+            return
         _lib.check(fn(_lib.dptr(q.desc), q.n_parts, _lib.dptr(q.long_row), _lib.dptr(q.long_slot0), q.n_long,
                       _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), None, 1.0, _lib.dptr(x), d, None,
                       _lib.dptr(x0), _lib.dptr(in2), in2_scale, _lib.dptr(out), 1.0, 0, None, _lib.dptr(ws), graph.n_rows,
@@ -118,11 +129,12 @@ def child(args):
             ms[k].append(e0.elapsed_time(e1) / args.launches)
     report = {"workload": args.workload, "acc2": bool(args.acc2), "d": d, "nnz": graph.nnz, "n_parts": p.n_parts, "n_long": p.n_long,
               "alternations": args.alternations, "launches": args.launches, "libs": []}
-    for k, (path, _, _, hub, _) in enumerate(libs):
+    for k, (path, _, _, hub, _, rows) in enumerate(libs):
         m = sum(ms[k]) / len(ms[k])
         ent = {"lib": path, "ms_per_layer": [round(v, 5) for v in ms[k]], "mean": round(m, 5),
                "spread": round(max(ms[k]) - min(ms[k]), 5), "equal_to_base": bool(torch.equal(outs[k], outs[0])),
                "max_diff_over_max": float((outs[k] - outs[0]).abs().max() / outs[0].abs().max()),
+               "main_entry": "gcr_spmm_csr_acc2_f32" if rows is None else "gcr_spmm_rows_f32",
                "windowed": None if hub is None else {"window_rows": hub.window_rows, "windows": hub.n_windows,
                                                       "n_hub": hub.n_hub, "hub_nnz": hub.hub_nnz,
                                                       "nnz_per_part": hub.H.plan.nnz_per_part}}

@@ -1,0 +1,219 @@
+"""The plain launch's own kernel (gcr_spmm_rows_f32: `spmm_rows`, d <= 64, no mask, no second addend, no row normalise)
+against the generic launch it replaces (gcr_spmm_csr_acc2_f32: `spmm_parts`).
+
+Both run the same partitions, one wave each, one fmaf per non-zero from 0 in stored order and the same two-rounding
+epilogue; only the schedule of a partition differs (the next block's col / val loaded ahead of the gathers, batched tails).
+So every word either launch writes must be equal, bit for bit: outputs and the split rows' workspace, each filled with NaN
+before the launch, so that a row nobody wrote shows.  A second launch must repeat the first.  A subset is also held to the
+float64 oracle at the bar of tests/test_spmm_pipeline_gpu.py.
+
+The matrices are the smallest at which each mechanism can go wrong (<= 1 000 rows, 700 columns): every row degree around
+the batch sizes 1 / 2 / 4 / 8 / 16 and the 64-non-zero block, empty rows at either end of a partition and in runs, runs of
+degree-1 rows longer than the acc_in queue, rows straddling every block boundary of a partition, a partition of exactly 64
+rows, one of exactly 512 non-zeros, a one-partition graph, partition counts that are no multiple of the 4 waves of a
+workgroup, and rows above a partition's 512 (or 64) non-zeros, which go through chunks and `spmm_long_rows`."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle_np as O
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+N_COLS = 700
+QUEUE = 2          # rows of acc_in the kernel holds ahead of their flush
+
+
+def _degrees(kind):
+    """(row degrees, non-zeros per partition)"""
+    if kind == "ladder":
+        deg = [0, 0, 0]                                                  # a partition that starts with empty rows
+        for k in (7, 8, 9, 15, 16, 17, 31, 33, 63, 64, 65, 127, 128, 129):
+            deg += [k, 0] if k % 2 else [k]                              # an empty row after every odd one
+        deg += [1] * (8 * QUEUE + 5)                                     # many row ends in one batch of 16
+        deg += [0] * (QUEUE + 3) + [2] + [0] * (QUEUE + 3)               # runs of empty rows around one short row
+        deg += [600, 1, 1, 513, 1500, 3]                                 # rows above 512: chunks + spmm_long_rows
+        deg += [10, 9, 11, 12, 8, 13, 7, 10] * 6                         # the mean-degree-10 regime of the user rows
+        deg += [5, 0, 0]                                                 # ... and one that ends with empty rows
+        return deg, 512
+    if kind == "straddle":
+        return [9] * 130, 512            # 56 rows = 504 non-zeros per partition: a row across each of its 7 block boundaries
+    if kind == "rows64":
+        return [3] * 64 + [5] * 64 + [1] * 64 + [2] * 30, 512           # the row limit closes the partitions, not the non-zeros
+    if kind == "nnz512":
+        return [64] * 8 + [100, 100, 100, 100, 112] + [500, 12], 512    # partitions of exactly 512 non-zeros
+    if kind == "one_part":
+        return [3, 0, 20, 1, 0], 512
+    if kind == "small_parts":
+        # 64 non-zeros per partition: every block is a partition's last one; chunked rows next to whole-row partitions
+        return [0, 5, 64, 1, 63, 65, 0, 0, 30, 34, 7, 200, 1, 1, 1, 1, 64 * 9 + 1, 16, 48, 0], 64
+    raise ValueError(kind)
+
+
+KINDS = ["ladder", "straddle", "rows64", "nnz512", "one_part", "small_parts"]
+
+
+class _Case:
+    def __init__(self, kind, d, has_val):
+        import recommendation_amd as ra
+        deg, L = _degrees(kind)
+        deg = np.asarray(deg, dtype=np.int64)
+        rng = np.random.default_rng(sum(map(ord, kind)) * 11 + 17 * d + int(has_val))
+        self.kind, self.d, self.L, self.n_rows = kind, d, L, deg.size
+        self.rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+        self.nnz = int(self.rowptr[-1])
+        self.col = rng.integers(0, N_COLS, self.nnz).astype(np.int32)
+        self.val = rng.standard_normal(self.nnz).astype(F32) if has_val else None
+        self.w = self.val if has_val else np.ones(self.nnz, F32)
+        self.x = rng.standard_normal((N_COLS, d)).astype(F32)
+        self.acc_in = rng.standard_normal((self.n_rows, d)).astype(F32)
+        self.g = ra.CsrGraph(self.rowptr, self.col, self.val, self.n_rows, N_COLS, "cuda", nnz_per_part=L, hub_window_rows=0)
+        self.xt = torch.from_numpy(self.x).cuda()
+        self.acc_t = torch.from_numpy(self.acc_in).cuda()
+
+    def launch(self, entry, y, acc_in, acc_out, val_scale, acc_scale):
+        """One raw launch of `entry` ('rows' | 'parts') on NaN-filled split-row workspace; returns a copy of the workspace."""
+        from recommendation_amd import _lib
+        g, p, d = self.g, self.g.plan, self.d
+        ws = g.workspace(d)
+        if ws is not None:
+            ws.fill_(float("nan"))
+        L, s = _lib.lib(), _lib.cur_stream(self.xt.device)
+        head = (_lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long, _lib.dptr(g.rowptr),
+                _lib.dptr(g.col), _lib.dptr(g.val))
+        if entry == "rows":
+            rc = L.gcr_spmm_rows_f32(*head, float(val_scale), _lib.dptr(self.xt), d, _lib.dptr(y), _lib.dptr(acc_in),
+                                     _lib.dptr(acc_out), float(acc_scale), _lib.dptr(ws), g.n_rows, g.n_cols, s)
+        else:
+            rc = L.gcr_spmm_csr_acc2_f32(*head, None, float(val_scale), _lib.dptr(self.xt), d, _lib.dptr(y), _lib.dptr(acc_in),
+                                         None, 0.0, _lib.dptr(acc_out), float(acc_scale), 0, None, _lib.dptr(ws), g.n_rows,
+                                         g.n_cols, None, s)
+        assert rc == 0, f"{entry}: status {rc}"
+        torch.cuda.synchronize()
+        return None if ws is None else ws.clone()
+
+
+def _same_words(a, b, what):
+    if a is None and b is None:
+        return
+    same = a.view(torch.int32) == b.view(torch.int32)
+    assert bool(same.all()), f"{what}: {int((~same).sum())} of {same.numel()} words differ, first at {same.logical_not().nonzero()[0].tolist()}"
+
+
+# (name, y?, acc_out?, acc_in: None | 'given' | 'inplace', val_scale, acc_scale)
+FORMS = [
+    ("y", True, False, None, 1.0, 1.0),
+    ("y_scaled", True, False, None, 1.0 / 0.65, 1.0),
+    ("acc", False, True, "given", 1.0, 1.0),
+    ("acc_scaled", False, True, "given", 0.75, 0.25),
+    ("both", True, True, "given", 1.0 / 0.65, 1.0 / 3.0),
+    ("acc_null_in", False, True, None, -1.5, 0.5),
+    ("both_null_in", True, True, None, 1.0, 1.0),
+    ("inplace", False, True, "inplace", 1.0, 0.5),
+    ("both_inplace", True, True, "inplace", 0.3, 1.0),
+]
+
+
+def _run(c, entry, form):
+    _, has_y, has_acc, acc_in, val_scale, acc_scale = form
+    nan = float("nan")
+    y = torch.full((c.n_rows, c.d), nan, device="cuda") if has_y else None
+    out = ain = None
+    if has_acc:
+        if acc_in == "inplace":
+            out = ain = c.acc_t.clone()
+        else:
+            out = torch.full((c.n_rows, c.d), nan, device="cuda")
+            ain = c.acc_t if acc_in == "given" else None
+    ws = c.launch(entry, y, ain, out, val_scale, acc_scale)
+    return y, out, ws
+
+
+def _check_geometry(c):
+    desc = c.g.plan.desc_host
+    n = (desc[:, 1] - desc[:, 0]).tolist()
+    rows = [(int(r) >> 32) if s < 0 else 1 for r, s in zip(desc[:, 2].tolist(), desc[:, 3].tolist())]
+    whole = (desc[:, 3] < 0).tolist()
+    if c.kind == "ladder":
+        assert c.g.plan.n_long == 3 and len(n) % 4 != 0 and len(n) > 4
+    elif c.kind == "straddle":
+        assert n[0] == 504 and rows[0] == 56 and len(n) % 4 != 0
+    elif c.kind == "rows64":
+        assert rows[:3] == [64, 64, 64] and n[:3] == [192, 320, 64]
+    elif c.kind == "nnz512":
+        assert n[:3] == [512, 512, 512] and all(whole[:3])
+    elif c.kind == "one_part":
+        assert len(n) == 1
+    elif c.kind == "small_parts":
+        assert max(n) == 64 and c.g.plan.n_long == 3 and len(n) % 4 != 0
+
+
+@pytest.mark.parametrize("has_val", [True, False], ids=["val", "ones"])
+@pytest.mark.parametrize("d", [64, 48, 4])
+@pytest.mark.parametrize("kind", KINDS)
+def test_every_word_equals_the_generic_launch(kind, d, has_val):
+    c = _Case(kind, d, has_val)
+    _check_geometry(c)
+    ref64 = None
+    if d == 64 and has_val:
+        ref64 = O.spmm_csr(c.rowptr, c.col, c.w, c.x, keep=None, scale=1.0)
+    for form in FORMS:
+        name = form[0]
+        y0, out0, ws0 = _run(c, "parts", form)
+        y1, out1, ws1 = _run(c, "rows", form)
+        y2, out2, ws2 = _run(c, "rows", form)
+        for got, want, again, what in ((y1, y0, y2, "y"), (out1, out0, out2, "acc_out")):
+            if want is None:
+                assert got is None
+                continue
+            assert not bool(torch.isnan(want).any()), f"{name}: the generic launch left a word of {what} unwritten"
+            _same_words(got, want, f"{kind} {name} {what}")
+            _same_words(again, got, f"{kind} {name} {what}, second launch")
+        _same_words(ws1, ws0, f"{kind} {name} workspace")
+        _same_words(ws2, ws1, f"{kind} {name} workspace, second launch")
+        if ref64 is not None:
+            _, _, _, acc_in, val_scale, acc_scale = form
+            yref = ref64 * val_scale
+            prev = 0.0 if acc_in is None else c.acc_in
+            amax = 0.0 if acc_in is None else np.abs(c.acc_in).max()
+            for got, ref, extra in ((y1, yref, 0.0), (out1, (prev + yref) * acc_scale, amax)):
+                if got is not None:
+                    np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=1e-5,
+                                               atol=1e-5 * max(np.abs(ref).max(), extra, 1e-30))
+
+
+def test_spmm_into_takes_the_new_entry_and_wider_launches_do_not():
+    from recommendation_amd import _lib
+    from recommendation_amd import functional as Fn
+    c = _Case("ladder", 64, True)
+    L = _lib.lib()
+    calls = []
+    real = L.gcr_spmm_rows_f32
+
+    def counted(*a):
+        calls.append(a[10])                                          # d
+        return real(*a)
+
+    L.gcr_spmm_rows_f32 = counted
+    try:
+        y = Fn.spmm_into(c.g, c.xt, y=torch.empty(c.n_rows, 64, device="cuda"))
+        assert calls == [64]
+        keep = torch.full(((c.nnz + 31) // 32,), -1, dtype=torch.int32, device="cuda")
+        ym = Fn.spmm_into(c.g, c.xt, y=torch.empty(c.n_rows, 64, device="cuda"), keep_bits=keep)
+        assert calls == [64], "a masked launch belongs to the generic kernel"
+        _same_words(ym, y, "all-ones mask")
+        x128 = torch.randn(N_COLS, 128, device="cuda", generator=torch.Generator(device="cuda").manual_seed(3))
+        Fn.spmm_into(c.g, x128, y=torch.empty(c.n_rows, 128, device="cuda"))
+        assert calls == [64], "d > 64 belongs to the generic kernel"
+    finally:
+        L.gcr_spmm_rows_f32 = real
+    # called directly, a wider launch is refused before anything is launched
+    out = torch.full((c.n_rows, 128), 7.0, device="cuda")
+    g, p = c.g, c.g.plan
+    rc = L.gcr_spmm_rows_f32(_lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
+                             _lib.dptr(g.rowptr), _lib.dptr(g.col), _lib.dptr(g.val), 1.0, _lib.dptr(x128), 128, _lib.dptr(out),
+                             None, None, 1.0, _lib.dptr(g.workspace(128)), g.n_rows, g.n_cols, _lib.cur_stream(out.device))
+    assert rc == -2                                                  # GCR_EUNSUPPORTED
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()), "a refused call launched something"
