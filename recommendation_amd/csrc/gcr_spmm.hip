@@ -21,6 +21,14 @@
 //     gathers, all earlier stores and one fresh HBM round trip per row, 1.1 M times per cfg2 layer);
 //   * long rows: chunk partial sums go to a workspace and are added in chunk order by
 //     spmm_long_rows (deterministic; no float atomics).
+//
+// Kernels: `spmm_parts` is the generic walk (every width, mask and epilogue) and the reference the bit-for-bit tests compare
+// the others against.  The other four are shells around two shared pieces:
+//   * `walk_partition`, one wave's walk over a partition at d <= 64 on a tighter schedule, with a row sink for what happens
+//     at a row end: `spmm_hub_parts` stores the sum (the windowed companion), `spmm_rows` combines it with acc_in through
+//     a two-entry queue (the plain launch);
+//   * `sum_partials`, the fixed-order 4-wave sum of partial rows: `spmm_long_rows` over the chunks of a split row,
+//     `spmm_hub_rows` over the windows of a hub row, either followed by store_row.
 #include "gcr_common.h"
 
 #include <type_traits>
@@ -291,220 +299,91 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void spmm
   }
 }
 
-// one 4-wave block per long row: wave w adds chunk partials w, w+4, ... (4 loads in flight each),
-// the four wave sums are combined through LDS in wave order, then the common epilogue.  The order
-// of additions is fixed by the plan, so the result stays bitwise reproducible.  (One wave per row
-// took 24 us per cfg2 layer — hub rows have ~100 chunks — i.e. 3 % of the layer.)
+// The sum of `count` partial rows p0, p0 + stride, ... (stride in floats) by one 4-wave block: wave w adds partials w,
+// w+4, ... (4 loads in flight), the four wave sums are combined through LDS in wave order.  Returns whether this wave
+// holds the sum in `acc`.  The order of additions is fixed by the plan — per wave in steps of 16 with the four loads of a
+// step added in order, the remainder in steps of 4, then ((w0 + w1) + w2) + w3 — so the result stays bitwise
+// reproducible: no float atomics.  (One wave per row took 24 us per cfg2 layer — hub rows have ~100 chunks — i.e. 3 % of
+// the layer.)
+template <int NV, bool D64>
+__device__ __forceinline__ bool sum_partials(const float* __restrict__ p0, int64_t stride, int count, int d,
+                                             float (&acc)[NV]) {
+  __shared__ float red[3][NV * 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) acc[v] = 0.f;
+  int k = wave;
+  for (; k + 12 < count; k += 16) {
+    float t[4][NV];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        t[u][v] = (D64 || lane + 64 * v < d) ? p0[(int64_t)(k + 4 * u) * stride + lane + 64 * v] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int v = 0; v < NV; ++v) acc[v] += t[u][v];
+  }
+  for (; k < count; k += 4)
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      if (D64 || lane + 64 * v < d) acc[v] += p0[(int64_t)k * stride + lane + 64 * v];
+  if (wave > 0) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) red[wave - 1][v * 64 + lane] = acc[v];
+  }
+  __syncthreads();
+  if (wave > 0) return false;
+#pragma unroll
+  for (int w = 0; w < 3; ++w)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] += red[w][v * 64 + lane];
+  return true;
+}
+
+// one block per long row: its chunk partials, slots s0 .. s1 - 1 of the workspace, in chunk order, then the common epilogue
 template <int NV, bool D64, bool ACC2>
 __global__ __launch_bounds__(256) void spmm_long_rows(const int32_t* __restrict__ long_row,
                                                       const int32_t* __restrict__ long_slot0, int64_t n_long,
                                                       const float* __restrict__ partials, int d, Epilogue ep) {
-  __shared__ float red[3][NV * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
   const int64_t i = blockIdx.x;
   const int s0 = long_slot0[i], s1 = long_slot0[i + 1];
   float acc[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) acc[v] = 0.f;
-  int s = s0 + wave;
-  for (; s + 12 < s1; s += 16) {
-    float t[4][NV];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        t[u][v] = (D64 || lane + 64 * v < d) ? partials[(int64_t)(s + 4 * u) * d + lane + 64 * v] : 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] += t[u][v];
-  }
-  for (; s < s1; s += 4)
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-      if (D64 || lane + 64 * v < d) acc[v] += partials[(int64_t)s * d + lane + 64 * v];
-  if (wave > 0) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) red[wave - 1][v * 64 + lane] = acc[v];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 0; w < 3; ++w)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] += red[w][v * 64 + lane];
-    store_row<NV, D64, ACC2>(ep, (int64_t)long_row[i], d, lane, acc, false, acc);
-  }
+  if (sum_partials<NV, D64>(partials + (int64_t)s0 * d, d, s1 - s0, d, acc))
+    store_row<NV, D64, ACC2>(ep, (int64_t)long_row[i], d, threadIdx.x & 63, acc, false, acc);
 }
 
-// The windowed companion's reduction (graph.py HubPlan): hub row h was multiplied window by window into
-// partials[w * n_hub + h] (a `spmm_parts` launch on the companion CSR, y only).  One 4-wave block per hub row: wave v adds
-// the partials of windows v, v+4, ... in window order (4 loads in flight), the four wave sums are combined through LDS in
-// wave order, then the common epilogue with the launch's real scales.  The order is fixed by the plan: no float atomics.
+// The windowed companion's reduction (graph.py HubPlan), one block per hub row: hub row h was multiplied window by window
+// into partials[w * n_hub + h]; they are added in window order, then the common epilogue with the launch's real scales.
 template <int NV, bool D64>
 __global__ __launch_bounds__(256) void spmm_hub_rows(const int32_t* __restrict__ hub_row, int64_t n_hub, int n_win,
                                                      const float* __restrict__ partials, int d, Epilogue ep) {
-  __shared__ float red[3][NV * 64];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
   const int64_t h = blockIdx.x;
   float acc[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) acc[v] = 0.f;
-  int w = wave;
-  for (; w + 12 < n_win; w += 16) {
-    float t[4][NV];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        t[u][v] = (D64 || lane + 64 * v < d) ? partials[((int64_t)(w + 4 * u) * n_hub + h) * d + lane + 64 * v] : 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] += t[u][v];
-  }
-  for (; w < n_win; w += 4)
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-      if (D64 || lane + 64 * v < d) acc[v] += partials[((int64_t)w * n_hub + h) * d + lane + 64 * v];
-  if (wave > 0) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) red[wave - 1][v * 64 + lane] = acc[v];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] += red[k][v * 64 + lane];
-    store_row<NV, D64, false>(ep, (int64_t)hub_row[h], d, lane, acc, false, acc);
-  }
+  if (sum_partials<NV, D64>(partials + h * d, n_hub * d, n_win, d, acc))
+    store_row<NV, D64, false>(ep, (int64_t)hub_row[h], d, threadIdx.x & 63, acc, false, acc);
 }
 
-// The windowed companion's own kernel (graph.py HubPlan, step 1 of a windowed launch: partials = H x, nothing else), d <= 64.
-// One wave per partition in the hardware's dispatch order, as `spmm_parts`, and the words it writes are those of
-// `spmm_parts` on H with y only: one fmaf per non-zero from 0 in stored order, a whole-row partition stores its rows (empty
-// ones zeros), a chunk partition its slot.  What differs is the partition body.  No mask, no epilogue, no acc_in queue: a
-// row's sum is stored as it stands (`spmm_parts` multiplied it by a val_scale of 1.0).  The next 64-non-zero block's col /
-// val are loaded before this block's gathers.  And what is left of a block below a full batch of 16 goes out in batches of
-// 8, 4, 2 and 1 instead of one gather at a time: the companion's partitions average 96 non-zeros, so 7-8 of a partition's
-// gathers were such single round trips beside the six batches that carried the rest, and that is where its waves waited
-// (EXPERIMENTS.md "SpMM: spmm_hub_parts, the companion's own kernel").
-template <bool D64, bool HAS_VAL>
-__global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict__ desc, int64_t n_parts,
-                                                      const int64_t* __restrict__ rowptr,
-                                                      const int32_t* __restrict__ col, const float* __restrict__ val,
-                                                      const float* __restrict__ x, int d, float* __restrict__ y,
-                                                      float* __restrict__ partials) {
-  constexpr int UNR = 16;
-  const int lane = threadIdx.x & 63;
-  const int64_t part = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
-  if (part >= n_parts) return;
-  const int64_t nnz0 = desc[4 * part + 0];
-  const int n = (int)(desc[4 * part + 1] - nnz0);
-  const int64_t rowinfo = desc[4 * part + 2];
-  const int64_t slot = desc[4 * part + 3];
-  const int row0 = (int)(rowinfo & 0xffffffffll);
-  const int nrows = (int)(rowinfo >> 32);
-  const bool whole_rows = slot < 0;
-
-  // local end offsets of the (<= 64) rows of a whole-row partition, one per lane
-  int ends_v = 0x7fffffff;
-  if (whole_rows && lane < nrows) ends_v = (int)(rowptr[row0 + lane + 1] - nnz0);
-  int cur = 0;
-  int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
-
-  float acc = 0.f;
-  auto flush = [&]() {
-    if (D64 || lane < d) y[((int64_t)row0 + cur) * d + lane] = acc;
-    acc = 0.f;
-    ++cur;
-    cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
-  };
-  // column id and value of the 64 non-zeros of block b, one per lane
-  auto load_block = [&](int b, int& cv_o, float& vv_o) {
-    cv_o = 0;
-    vv_o = 0.f;
-    if (lane < n - b) {
-      const int64_t e = nnz0 + b + lane;
-      cv_o = col[e];
-      vv_o = HAS_VAL ? val[e] : 1.0f;
-    }
-  };
-
-  int cv, cv_n = 0;
-  float vv, vv_n = 0.f;
-  load_block(0, cv, vv);
-  for (int b = 0; b < n; b += 64) {
-    const int m = min(64, n - b);
-    if (b + 64 < n) load_block(b + 64, cv_n, vv_n);
-    // B gathers issued back to back, then consumed in stored order with the row ends between them
-    auto batch = [&](auto bc, int jb) {
-      constexpr int B = decltype(bc)::value;
-      float xr[B];
-#pragma unroll
-      for (int u = 0; u < B; ++u) {
-        const float* xp = x + (int64_t)gcr_readlane_i(cv, jb + u) * d;
-        xr[u] = (D64 || lane < d) ? xp[lane] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < B; ++u) {
-        if (whole_rows) {
-          while (b + jb + u >= cur_end) flush();
-        }
-        const float w = HAS_VAL ? gcr_readlane_f(vv, jb + u) : 1.0f;
-        acc = fmaf(w, xr[u], acc);
-      }
-    };
-    int j = 0;
-    while (m - j >= UNR) {
-      batch(std::integral_constant<int, UNR>{}, j);
-      j += UNR;
-    }
-#define GCR_HUB_TAIL(B)                           \
-  if (m - j >= B) {                               \
-    batch(std::integral_constant<int, B>{}, j);   \
-    j += B;                                       \
-  }
-    GCR_HUB_TAIL(8)
-    GCR_HUB_TAIL(4)
-    GCR_HUB_TAIL(2)
-    GCR_HUB_TAIL(1)
-#undef GCR_HUB_TAIL
-    cv = cv_n;
-    vv = vv_n;
-  }
-
-  if (whole_rows) {
-    while (cur < nrows) flush();
-  } else {
-    if (D64 || lane < d) partials[slot * (int64_t)d + lane] = acc;
-  }
-}
-
-// The plain launch's own kernel (gcr_spmm_rows_f32), d <= 64: what `spmm_parts<1, D64, HAS_VAL, false, 16, false>` is used
-// for and nothing else.  No edge or column mask, no second addend, no row normalise, no second output; the epilogue is
-// y = acc * val_scale and / or acc_out = (acc_in + y) * acc_scale with store_row's two roundings.  One wave per partition in
-// the hardware's dispatch order, one fmaf per non-zero from 0 in stored order, whole-row partitions store their rows and
-// chunk partitions their slot: every word written equals `spmm_parts`'s.  What differs is the schedule of a partition:
-//   * a block that has a successor is a block of exactly 64 non-zeros, and it has a path of its own: the successor's col /
-//     val are loaded BEFORE its four batches of gathers and are back with the first of them, so the copy at its end waits
-//     for nothing the last batch's last FMA has not waited for (the generic kernel loads them after that FMA: one exposed
-//     round trip per block);
-//   * what the last block holds below a full batch of 16 goes out in batches of 8, 4, 2 and 1, as in `spmm_hub_parts`,
-//     instead of one gather, one wait at a time;
-//   * the two-entry acc_in queue of `spmm_parts` is kept as it is: refilled in front of a batch's gathers, so the combine
-//     at a row end waits for nothing younger than a gather it has already waited for.
-// 52 VGPRs / 82 SGPRs at d = 64 with values, 8 waves per SIMD without an SGPR cap and without lane spills (`spmm_parts`: 63
-// / 94 capped, 18 scalars in VGPR lanes).  Measurements: EXPERIMENTS.md "SpMM: spmm_rows".
-template <bool D64, bool HAS_VAL>
-__global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ desc, int64_t n_parts,
-                                                 const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                 const float* __restrict__ val, const float* __restrict__ x, int d,
-                                                 float val_scale, float* y, const float* acc_in, float* acc_out,
-                                                 float acc_scale, float* __restrict__ partials) {
+// One wave's walk over its partition at d <= 64 (one accumulator register per lane), shared by the two kernels below.  One
+// wave per partition in the hardware's dispatch order and one fmaf per non-zero from 0 in stored order, as `spmm_parts`; a
+// whole-row partition hands every row's sum to its row sink (empty rows zeros), a chunk partition stores its slot.  What
+// differs from `spmm_parts` is the schedule:
+//   * the successor's col / val are loaded BEFORE a block's gathers and are back with the first of them, so the copy at the
+//     block's end waits for nothing the last batch's last FMA has not waited for (the generic kernel loads them after that
+//     FMA: one exposed round trip per block);
+//   * what a block holds below a full batch of 16 goes out in batches of 8, 4, 2 and 1 instead of one gather, one wait at a
+//     time: the companion's partitions average 96 non-zeros, so 7-8 of a partition's gathers were such single round trips
+//     beside the six batches that carried the rest, and that is where its waves waited (EXPERIMENTS.md "SpMM:
+//     spmm_hub_parts, the companion's own kernel").
+// What happens at a row end is the sink's: sink.refill(row, n) runs in front of every batch of gathers (the next n rows to
+// end are row, row + 1, ...; n = 0 in a chunk), sink.flush(row, acc) at every row end.
+template <bool D64, bool HAS_VAL, class Sink>
+__device__ __forceinline__ void walk_partition(const int64_t* __restrict__ desc, int64_t n_parts,
+                                               const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                               const float* __restrict__ val, const float* __restrict__ x, int d,
+                                               float* __restrict__ partials, Sink& sink) {
   constexpr int UNR = 16;
   const int lane = threadIdx.x & 63;
   const int64_t part = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
@@ -524,39 +403,10 @@ __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ des
   int cur = 0;
   int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
 
-  // acc_in of rows cur and cur + 1, loaded ahead of their flush (see spmm_parts): none for chunks, y-only launches and
-  // acc_in == NULL.  In place (acc_in == acc_out) stays correct: a row is read before this wave, its only writer, stores it.
-  float q0 = 0.f, q1 = 0.f;
-  int nq = 0;
-  const int qrows = (whole_rows && acc_in != nullptr && acc_out != nullptr) ? nrows : 0;
-  auto refill = [&]() {
-    if (nq < 1 && cur < qrows) q0 = on ? acc_in[((int64_t)row0 + cur) * d + lane] : 0.f;
-    if (nq < 2 && cur + 1 < qrows) q1 = on ? acc_in[((int64_t)row0 + cur + 1) * d + lane] : 0.f;
-    nq = max(nq, min(2, qrows - cur));
-  };
-
   float acc = 0.f;
+  auto refill = [&]() { sink.refill((int64_t)row0 + cur, whole_rows ? nrows - cur : 0); };
   auto flush = [&]() {
-    // two roundings, as store_row: `acc * val_scale`, then the add of acc_in, never contracted
-#pragma clang fp contract(off)
-    const float yv = acc * val_scale;
-    const int64_t base = ((int64_t)row0 + cur) * d + lane;
-    if (y != nullptr) {
-      if (on) y[base] = yv;
-    }
-    if (acc_out != nullptr) {
-      if (nq > 0) {
-        if (on) acc_out[base] = (q0 + yv) * acc_scale;
-        q0 = q1;
-        --nq;
-      } else {
-        // fewer queued rows than row ends in one batch (degree-1 runs), or nothing to prefetch: load at the flush
-        if (on) {
-          const float prev = acc_in != nullptr ? acc_in[base] : 0.f;
-          acc_out[base] = (prev + yv) * acc_scale;
-        }
-      }
-    }
+    sink.flush((int64_t)row0 + cur, acc);
     acc = 0.f;
     ++cur;
     cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
@@ -575,13 +425,20 @@ __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ des
   int cv, cv_n = 0;
   float vv, vv_n = 0.f;
   load_block(0, cv, vv);
-  // The first block's words are waited for here, once, and not at the first v_readlane of the batch loop: that wait would
-  // sit behind refill() in the loop body and hold every batch of the block until the acc_in it has just asked for is back.
-  asm volatile("" ::"v"(cv), "v"(vv));
+  if (Sink::queued) {
+    // The first block's words are waited for here, once, and not at the first v_readlane of the batch loop: that wait would
+    // sit behind refill() in the loop body and hold every batch of the block until the acc_in it has just asked for is back.
+    asm volatile("" ::"v"(cv), "v"(vv));
+  }
   for (int b = 0; b < n; b += 64) {
-    // B gathers issued back to back, then consumed in stored order with the row ends between them
-    auto batch = [&](auto bc, int jb) {
+    const bool more = b + 64 < n;
+    if (more) load_block(b + 64, cv_n, vv_n);
+    const int m = more ? 64 : n - b;
+    // B gathers from non-zero jb of the block on, issued back to back, then consumed in stored order with the row ends
+    // between them; returns B
+    auto batch = [&](auto bc, const int jb) {
       constexpr int B = decltype(bc)::value;
+      refill();
       float xr[B];
 #pragma unroll
       for (int u = 0; u < B; ++u) {
@@ -596,48 +453,118 @@ __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ des
         const float w = HAS_VAL ? gcr_readlane_f(vv, jb + u) : 1.0f;
         acc = fmaf(w, xr[u], acc);
       }
+      return B;
     };
-    if (b + 64 < n) {
-      // 64 non-zeros and a successor
-      load_block(b + 64, cv_n, vv_n);
-      int j = 0;
-      do {
-        refill();
-        batch(std::integral_constant<int, UNR>{}, j);
-        j += UNR;
-      } while (j < 64);
+    // One loop for every block.  `spmm_rows` used to have a second path for blocks with a successor (always 64 non-zeros,
+    // four full batches); this loop measured level with it on cfg2 and cfg4, so that path is gone (EXPERIMENTS.md "SpMM: one
+    // partition walk, one partial reducer").
+    int j = 0;
+    while (m - j >= UNR) j += batch(std::integral_constant<int, UNR>{}, j);
+    if (m - j >= 8) j += batch(std::integral_constant<int, 8>{}, j);
+    if (m - j >= 4) j += batch(std::integral_constant<int, 4>{}, j);
+    if (m - j >= 2) j += batch(std::integral_constant<int, 2>{}, j);
+    if (m - j >= 1) j += batch(std::integral_constant<int, 1>{}, j);
+    if (more) {
       cv = cv_n;
       vv = vv_n;
-    } else {
-      const int m = n - b;
-      int j = 0;
-      while (m - j >= UNR) {
-        refill();
-        batch(std::integral_constant<int, UNR>{}, j);
-        j += UNR;
-      }
-#define GCR_ROWS_TAIL(B)                          \
-  if (m - j >= B) {                               \
-    refill();                                     \
-    batch(std::integral_constant<int, B>{}, j);   \
-    j += B;                                       \
-  }
-      GCR_ROWS_TAIL(8)
-      GCR_ROWS_TAIL(4)
-      GCR_ROWS_TAIL(2)
-      GCR_ROWS_TAIL(1)
-#undef GCR_ROWS_TAIL
     }
   }
 
   if (whole_rows) {
     while (cur < nrows) {
-      if (nq == 0) refill();
+      refill();
       flush();
     }
   } else {
     if (on) partials[slot * (int64_t)d + lane] = acc;
   }
+}
+
+// Row sink of the windowed companion: no epilogue and no acc_in, a row's sum is stored as it stands (`spmm_parts` multiplied
+// it by a val_scale of 1.0).
+template <bool D64>
+struct StoreSink {
+  static constexpr bool queued = false;
+  float* __restrict__ y;
+  int d, lane;
+  __device__ __forceinline__ void refill(int64_t, int) {}
+  __device__ __forceinline__ void flush(int64_t row, float acc) {
+    if (D64 || lane < d) y[row * d + lane] = acc;
+  }
+};
+
+// Row sink of the plain launch: y = acc * val_scale and / or acc_out = (acc_in + y) * acc_scale with store_row's two
+// roundings, and the two-entry acc_in queue of `spmm_parts`: acc_in of the next two rows to end is loaded in front of a
+// batch's gathers, so the combine at a row end waits for nothing younger than a gather it has already waited for.  Nothing
+// is queued for chunks (n = 0), y-only launches and acc_in == NULL.  In place (acc_in == acc_out) stays correct: a row is
+// read before this wave, its only writer, stores it.
+template <bool D64>
+struct CombineSink {
+  static constexpr bool queued = true;
+  float val_scale, acc_scale;
+  float* y;
+  const float* acc_in;
+  float* acc_out;
+  int d, lane;
+  float q0 = 0.f, q1 = 0.f;
+  int nq = 0;
+  const bool queues = acc_in != nullptr && acc_out != nullptr;
+  __device__ __forceinline__ void refill(int64_t row, int n) {
+    const bool on = D64 || lane < d;
+    if (!queues) n = 0;
+    if (nq < 1 && 0 < n) q0 = on ? acc_in[row * d + lane] : 0.f;
+    if (nq < 2 && 1 < n) q1 = on ? acc_in[(row + 1) * d + lane] : 0.f;
+    nq = max(nq, min(2, n));
+  }
+  __device__ __forceinline__ void flush(int64_t row, float acc) {
+    // two roundings, as store_row: `acc * val_scale`, then the add of acc_in, never contracted
+#pragma clang fp contract(off)
+    const bool on = D64 || lane < d;
+    const float yv = acc * val_scale;
+    const int64_t base = row * d + lane;
+    if (y != nullptr) {
+      if (on) y[base] = yv;
+    }
+    if (acc_out != nullptr) {
+      if (nq > 0) {
+        if (on) acc_out[base] = (q0 + yv) * acc_scale;
+        q0 = q1;
+        --nq;
+      } else {
+        // fewer queued rows than row ends in one batch (degree-1 runs), or nothing to prefetch: load at the flush
+        if (on) {
+          const float prev = acc_in != nullptr ? acc_in[base] : 0.f;
+          acc_out[base] = (prev + yv) * acc_scale;
+        }
+      }
+    }
+  }
+};
+
+// The windowed companion's own kernel (graph.py HubPlan, step 1 of a windowed launch: partials = H x, nothing else), d <= 64:
+// the words it writes are those of `spmm_parts` on H with y only.  No mask, no epilogue, no acc_in queue.
+template <bool D64, bool HAS_VAL>
+__global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict__ desc, int64_t n_parts,
+                                                      const int64_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ col, const float* __restrict__ val,
+                                                      const float* __restrict__ x, int d, float* __restrict__ y,
+                                                      float* __restrict__ partials) {
+  StoreSink<D64> sink{y, d, (int)(threadIdx.x & 63)};
+  walk_partition<D64, HAS_VAL>(desc, n_parts, rowptr, col, val, x, d, partials, sink);
+}
+
+// The plain launch's own kernel (gcr_spmm_rows_f32), d <= 64: what `spmm_parts<1, D64, HAS_VAL, false, 16, false>` is used
+// for and nothing else.  No edge or column mask, no second addend, no row normalise, no second output; every word written
+// equals `spmm_parts`'s.  52 VGPRs / 81 SGPRs at d = 64 with values, 8 waves per SIMD without an SGPR cap and without lane
+// spills (`spmm_parts`: 63 / 94 capped, 18 scalars in VGPR lanes).  Measurements: EXPERIMENTS.md "SpMM: spmm_rows".
+template <bool D64, bool HAS_VAL>
+__global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ desc, int64_t n_parts,
+                                                 const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                 const float* __restrict__ val, const float* __restrict__ x, int d,
+                                                 float val_scale, float* y, const float* acc_in, float* acc_out,
+                                                 float acc_scale, float* __restrict__ partials) {
+  CombineSink<D64> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
+  walk_partition<D64, HAS_VAL>(desc, n_parts, rowptr, col, val, x, d, partials, sink);
 }
 
 __global__ void csr_validate_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -653,52 +580,105 @@ __global__ void csr_validate_kernel(const int64_t* __restrict__ rowptr, const in
   if (bad) atomicAdd(n_errors, bad);
 }
 
-template <int NV, bool D64, bool ACC2>
-int32_t launch_spmm_a(const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0,
-                    int64_t n_long, const int64_t* rowptr, const int32_t* col, const float* val,
-                    const uint32_t* keep_bits, const float* x, int d, const Epilogue& ep, float* partials,
-                    hipStream_t stream) {
-  const unsigned blocks = (unsigned)((n_parts + 3) / 4);
-  if (blocks > 0) {
-#define GCR_SPMM_LAUNCH(HV, MK)                                                                             \
-  hipLaunchKernelGGL((spmm_parts<NV, D64, HV, MK, unroll_for<NV>(), ACC2>), dim3(blocks), dim3(256), 0, stream, desc, n_parts, \
-                     rowptr, col, val, keep_bits, x, d, ep, partials)
-    if (ep.col_bits != nullptr) {
-      if (val != nullptr)
-        hipLaunchKernelGGL((spmm_parts<NV, D64, true, false, unroll_for<NV>(), ACC2, true>), dim3(blocks), dim3(256), 0,
-                           stream, desc, n_parts, rowptr, col, val, ep.col_bits, x, d, ep, partials);
-      else
-        hipLaunchKernelGGL((spmm_parts<NV, D64, false, false, unroll_for<NV>(), ACC2, true>), dim3(blocks), dim3(256), 0,
-                           stream, desc, n_parts, rowptr, col, val, ep.col_bits, x, d, ep, partials);
-    } else if (val != nullptr) {
-      if (keep_bits != nullptr) GCR_SPMM_LAUNCH(true, true);
-      else GCR_SPMM_LAUNCH(true, false);
-    } else {
-      if (keep_bits != nullptr) GCR_SPMM_LAUNCH(false, true);
-      else GCR_SPMM_LAUNCH(false, false);
-    }
-#undef GCR_SPMM_LAUNCH
-    int32_t st = GCR_LAUNCH_STATUS();
-    if (st != GCR_OK) return st;
-  }
-  if (n_long > 0) {
-    hipLaunchKernelGGL((spmm_long_rows<NV, D64, ACC2>), dim3((unsigned)n_long), dim3(256), 0, stream,
-                       long_row, long_slot0, n_long, partials, d, ep);
-    return GCR_LAUNCH_STATUS();
-  }
-  return GCR_OK;
+// the plan head every SpMM entry point takes (gcr_spmm_plan_*), the CSR it was made for and the split rows' workspace
+struct Plan {
+  const int64_t* desc;
+  int64_t n_parts;
+  const int32_t* long_row;
+  const int32_t* long_slot0;
+  int64_t n_long;
+  const int64_t* rowptr;
+  const int32_t* col;
+  const float* val;
+  float* partials;
+};
+
+// What every plan-taking entry point checks first.  GCR_LAUNCH: go on to the entry's own conditions and launch; anything
+// else is the entry's answer — a width above max_d (the entry's own kernel) is GCR_EUNSUPPORTED and an empty plan GCR_OK,
+// both before any pointer is looked at.
+constexpr int32_t GCR_LAUNCH = 1;
+int32_t check_plan(const Plan& p, int64_t n_rows, int64_t n_cols, int d, int max_d) {
+  GCR_CHECK_ARG(p.n_parts >= 0 && p.n_long >= 0 && n_rows >= 0 && n_cols >= 0);
+  GCR_CHECK_ARG(p.n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
+  GCR_CHECK_ARG(d >= 1 && d <= 256);
+  if (d > max_d) return GCR_EUNSUPPORTED;
+  if (n_rows == 0 || p.n_parts == 0) return GCR_OK;
+  GCR_CHECK_ARG(p.desc != nullptr && p.rowptr != nullptr);
+  GCR_CHECK_ARG(p.n_long == 0 || (p.long_row != nullptr && p.long_slot0 != nullptr && p.partials != nullptr));
+  return GCR_LAUNCH;
 }
 
-template <int NV, bool D64>
-int32_t launch_spmm(const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0,
-                    int64_t n_long, const int64_t* rowptr, const int32_t* col, const float* val,
-                    const uint32_t* keep_bits, const float* x, int d, const Epilogue& ep, float* partials,
+// the epilogue of a plain launch; the normalising and second-addend entries set their own fields on top
+Epilogue make_epilogue(float val_scale, float* y, const float* acc_in, float* acc_out, float acc_scale) {
+  return Epilogue{val_scale, y, acc_in, acc_out, acc_scale};   // every later field zero / NULL
+}
+
+// the one place a width picks its registers per lane: f(integral_constant<int, NV>, bool_constant<D64>)
+template <class F>
+int32_t dispatch_d(int d, F f) {
+  if (d == 64) return f(std::integral_constant<int, 1>{}, std::true_type{});
+  if (d <= 64) return f(std::integral_constant<int, 1>{}, std::false_type{});
+  if (d <= 128) return f(std::integral_constant<int, 2>{}, std::false_type{});
+  if (d <= 192) return f(std::integral_constant<int, 3>{}, std::false_type{});
+  return f(std::integral_constant<int, 4>{}, std::false_type{});
+}
+
+// the split rows of a plan, after the launch that wrote their chunk partials
+template <int NV, bool D64, bool ACC2>
+int32_t launch_long_rows(const Plan& p, int d, const Epilogue& ep, hipStream_t stream) {
+  if (p.n_long == 0) return GCR_OK;
+  hipLaunchKernelGGL((spmm_long_rows<NV, D64, ACC2>), dim3((unsigned)p.n_long), dim3(256), 0, stream, p.long_row,
+                     p.long_slot0, p.n_long, p.partials, d, ep);
+  return GCR_LAUNCH_STATUS();
+}
+
+template <int NV, bool D64, bool ACC2>
+int32_t launch_spmm(const Plan& p, const uint32_t* keep_bits, const float* x, int d, const Epilogue& ep,
                     hipStream_t stream) {
-  if (ep.acc_in2 != nullptr)
-    return launch_spmm_a<NV, D64, true>(desc, n_parts, long_row, long_slot0, n_long, rowptr, col, val, keep_bits, x, d, ep,
-                                        partials, stream);
-  return launch_spmm_a<NV, D64, false>(desc, n_parts, long_row, long_slot0, n_long, rowptr, col, val, keep_bits, x, d, ep,
-                                       partials, stream);
+  const unsigned blocks = (unsigned)((p.n_parts + 3) / 4);
+#define GCR_SPMM_LAUNCH(HV, MK, CM, BITS)                                                                          \
+  hipLaunchKernelGGL((spmm_parts<NV, D64, HV, MK, unroll_for<NV>(), ACC2, CM>), dim3(blocks), dim3(256), 0, stream, \
+                     p.desc, p.n_parts, p.rowptr, p.col, p.val, BITS, x, d, ep, p.partials)
+  if (ep.col_bits != nullptr) {
+    if (p.val != nullptr) GCR_SPMM_LAUNCH(true, false, true, ep.col_bits);
+    else GCR_SPMM_LAUNCH(false, false, true, ep.col_bits);
+  } else if (p.val != nullptr) {
+    if (keep_bits != nullptr) GCR_SPMM_LAUNCH(true, true, false, keep_bits);
+    else GCR_SPMM_LAUNCH(true, false, false, keep_bits);
+  } else {
+    if (keep_bits != nullptr) GCR_SPMM_LAUNCH(false, true, false, keep_bits);
+    else GCR_SPMM_LAUNCH(false, false, false, keep_bits);
+  }
+#undef GCR_SPMM_LAUNCH
+  const int32_t st = GCR_LAUNCH_STATUS();
+  if (st != GCR_OK) return st;
+  return launch_long_rows<NV, D64, ACC2>(p, d, ep, stream);
+}
+
+// every entry point that runs `spmm_parts`: the instantiation by width and by whether the combine has a second addend
+int32_t launch_spmm_d(const Plan& p, const uint32_t* keep_bits, const float* x, int d, const Epilogue& ep, void* stream) {
+  return dispatch_d(d, [&](auto nv, auto d64) {
+    constexpr int NV = decltype(nv)::value;
+    constexpr bool D64 = decltype(d64)::value;
+    if (ep.acc_in2 != nullptr) return launch_spmm<NV, D64, true>(p, keep_bits, x, d, ep, (hipStream_t)stream);
+    return launch_spmm<NV, D64, false>(p, keep_bits, x, d, ep, (hipStream_t)stream);
+  });
+}
+
+// The two entry points with a kernel of their own at d <= 64: `launch` starts its <D64, HAS_VAL> instantiation on the
+// partitions, then the split rows go through `spmm_long_rows` with epilogue `ep`, exactly as gcr_spmm_csr_f32 runs them.
+template <class Launch>
+int32_t launch_walk(const Plan& p, int d, const Epilogue& ep, hipStream_t stream, Launch launch) {
+  const dim3 blocks((unsigned)((p.n_parts + 3) / 4));
+  auto go = [&](auto d64) {
+    constexpr bool D64 = decltype(d64)::value;
+    if (p.val != nullptr) launch(d64, std::true_type{}, blocks);
+    else launch(d64, std::false_type{}, blocks);
+    const int32_t st = GCR_LAUNCH_STATUS();
+    if (st != GCR_OK) return st;
+    return launch_long_rows<1, D64, false>(p, d, ep, stream);
+  };
+  return d == 64 ? go(std::true_type{}) : go(std::false_type{});
 }
 
 }  // namespace
@@ -710,26 +690,20 @@ extern "C" int32_t gcr_spmm_csr_acc2_f32(const int64_t* desc, int64_t n_parts, c
                                          const float* acc_in2, float acc_in2_scale, float* acc_out, float acc_scale,
                                          uint32_t flags, float* inv_norm_out, float* partials, int64_t n_rows,
                                          int64_t n_cols, const uint32_t* col_active_bits, void* stream) {
-  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
-  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
-  GCR_CHECK_ARG(d >= 1 && d <= 256);
-  if (n_rows == 0 || n_parts == 0) return GCR_OK;
-  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && x != nullptr);
-  GCR_CHECK_ARG(y != nullptr || acc_out != nullptr);
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  const int32_t st = check_plan(p, n_rows, n_cols, d, 256);
+  if (st != GCR_LAUNCH) return st;
+  GCR_CHECK_ARG(x != nullptr && (y != nullptr || acc_out != nullptr));
   GCR_CHECK_ARG(acc_in2 == nullptr || acc_out != nullptr);
   GCR_CHECK_ARG(col_active_bits == nullptr || keep_bits == nullptr);       // one predicate per launch
-  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
   GCR_CHECK_ARG((flags & ~GCR_SPMM_ROW_L2NORM) == 0);
-  Epilogue ep{val_scale, y, acc_in, acc_out, acc_scale, flags, inv_norm_out, nullptr, acc_in2, acc_in2_scale, col_active_bits};
-  hipStream_t s = (hipStream_t)stream;
-#define GCR_GO(NV, D64) \
-  return launch_spmm<NV, D64>(desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, keep_bits, x, d, ep, partials, s)
-  if (d == 64) GCR_GO(1, true);
-  if (d <= 64) GCR_GO(1, false);
-  if (d <= 128) GCR_GO(2, false);
-  if (d <= 192) GCR_GO(3, false);
-  GCR_GO(4, false);
-#undef GCR_GO
+  Epilogue ep = make_epilogue(val_scale, y, acc_in, acc_out, acc_scale);
+  ep.flags = flags;
+  ep.inv_norm_out = inv_norm_out;
+  ep.acc_in2 = acc_in2;
+  ep.acc_in2_scale = acc_in2_scale;
+  ep.col_bits = col_active_bits;
+  return launch_spmm_d(p, keep_bits, x, d, ep, stream);
 }
 
 extern "C" int32_t gcr_spmm_csr_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
@@ -749,23 +723,16 @@ extern "C" int32_t gcr_spmm_csr_dual_f32(const int64_t* desc, int64_t n_parts, c
                                          float val_scale, const float* x, int32_t d, float* y_raw, float* y_norm,
                                          float* inv_norm_out, float* partials, int64_t n_rows, int64_t n_cols,
                                          void* stream) {
-  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
-  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
-  GCR_CHECK_ARG(d >= 1 && d <= 256);
-  if (n_rows == 0 || n_parts == 0) return GCR_OK;
-  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && x != nullptr && y_raw != nullptr && y_norm != nullptr);
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  const int32_t st = check_plan(p, n_rows, n_cols, d, 256);
+  if (st != GCR_LAUNCH) return st;
+  GCR_CHECK_ARG(x != nullptr && y_raw != nullptr && y_norm != nullptr);
   GCR_CHECK_ARG(y_raw != y_norm);
-  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
-  Epilogue ep{val_scale, y_norm, nullptr, nullptr, 1.0f, GCR_SPMM_ROW_L2NORM, inv_norm_out, y_raw, nullptr, 0.f, nullptr};
-  hipStream_t s = (hipStream_t)stream;
-#define GCR_GO(NV, D64) \
-  return launch_spmm<NV, D64>(desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, keep_bits, x, d, ep, partials, s)
-  if (d == 64) GCR_GO(1, true);
-  if (d <= 64) GCR_GO(1, false);
-  if (d <= 128) GCR_GO(2, false);
-  if (d <= 192) GCR_GO(3, false);
-  GCR_GO(4, false);
-#undef GCR_GO
+  Epilogue ep = make_epilogue(val_scale, y_norm, nullptr, nullptr, 1.0f);
+  ep.flags = GCR_SPMM_ROW_L2NORM;
+  ep.inv_norm_out = inv_norm_out;
+  ep.y_raw = y_raw;
+  return launch_spmm_d(p, keep_bits, x, d, ep, stream);
 }
 
 // The dual launch with the layer-list accumulation folded in (mhcn.py:440-457 appends the normalised product of every layer
@@ -777,23 +744,16 @@ extern "C" int32_t gcr_spmm_csr_dual_acc_f32(const int64_t* desc, int64_t n_part
                                              float val_scale, const float* x, int32_t d, float* y_raw, float* y_norm,
                                              const float* acc_in, float* acc_out, float* inv_norm_out, float* partials,
                                              int64_t n_rows, int64_t n_cols, void* stream) {
-  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
-  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
-  GCR_CHECK_ARG(d >= 1 && d <= 256);
-  if (n_rows == 0 || n_parts == 0) return GCR_OK;
-  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && x != nullptr && y_raw != nullptr && acc_out != nullptr);
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  const int32_t st = check_plan(p, n_rows, n_cols, d, 256);
+  if (st != GCR_LAUNCH) return st;
+  GCR_CHECK_ARG(x != nullptr && y_raw != nullptr && acc_out != nullptr);
   GCR_CHECK_ARG(y_raw != y_norm && y_raw != acc_out && (y_norm != nullptr || inv_norm_out != nullptr));
-  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
-  Epilogue ep{val_scale, y_norm, acc_in, acc_out, 1.0f, GCR_SPMM_ROW_L2NORM, inv_norm_out, y_raw, nullptr, 0.f, nullptr};
-  hipStream_t s = (hipStream_t)stream;
-#define GCR_GO(NV, D64) \
-  return launch_spmm<NV, D64>(desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, keep_bits, x, d, ep, partials, s)
-  if (d == 64) GCR_GO(1, true);
-  if (d <= 64) GCR_GO(1, false);
-  if (d <= 128) GCR_GO(2, false);
-  if (d <= 192) GCR_GO(3, false);
-  GCR_GO(4, false);
-#undef GCR_GO
+  Epilogue ep = make_epilogue(val_scale, y_norm, acc_in, acc_out, 1.0f);
+  ep.flags = GCR_SPMM_ROW_L2NORM;
+  ep.inv_norm_out = inv_norm_out;
+  ep.y_raw = y_raw;
+  return launch_spmm_d(p, keep_bits, x, d, ep, stream);
 }
 
 // out[hub_row[h]] = epilogue(sum over the n_windows window partials of hub row h): see spmm_hub_rows.
@@ -806,20 +766,12 @@ extern "C" int32_t gcr_spmm_hub_reduce_f32(const int32_t* hub_row, int64_t n_hub
   if (n_hub == 0) return GCR_OK;
   GCR_CHECK_ARG(hub_row != nullptr && partials != nullptr);
   GCR_CHECK_ARG(y != nullptr || acc_out != nullptr);
-  Epilogue ep{val_scale, y, acc_in, acc_out, acc_scale, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
-  hipStream_t s = (hipStream_t)stream;
-#define GCR_GO(NV, D64)                                                                                              \
-  do {                                                                                                               \
-    hipLaunchKernelGGL((spmm_hub_rows<NV, D64>), dim3((unsigned)n_hub), dim3(256), 0, s, hub_row, n_hub, n_windows,  \
-                       partials, d, ep);                                                                             \
-    return GCR_LAUNCH_STATUS();                                                                                      \
-  } while (0)
-  if (d == 64) GCR_GO(1, true);
-  if (d <= 64) GCR_GO(1, false);
-  if (d <= 128) GCR_GO(2, false);
-  if (d <= 192) GCR_GO(3, false);
-  GCR_GO(4, false);
-#undef GCR_GO
+  const Epilogue ep = make_epilogue(val_scale, y, acc_in, acc_out, acc_scale);
+  return dispatch_d(d, [&](auto nv, auto d64) {
+    hipLaunchKernelGGL((spmm_hub_rows<decltype(nv)::value, decltype(d64)::value>), dim3((unsigned)n_hub), dim3(256), 0,
+                       (hipStream_t)stream, hub_row, n_hub, n_windows, partials, d, ep);
+    return GCR_LAUNCH_STATUS();
+  });
 }
 
 // Step 1 of a windowed launch (graph.py HubPlan) for d <= 64: y[H rows] = H x by `spmm_hub_parts`, then the companion's own
@@ -828,38 +780,15 @@ extern "C" int32_t gcr_spmm_hub_parts_f32(const int64_t* desc, int64_t n_parts, 
                                           const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
                                           const int32_t* col, const float* val, const float* x, int32_t d, float* y,
                                           float* partials, int64_t n_rows, int64_t n_cols, void* stream) {
-  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
-  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
-  GCR_CHECK_ARG(d >= 1 && d <= 256);
-  if (d > 64) return GCR_EUNSUPPORTED;
-  if (n_rows == 0 || n_parts == 0) return GCR_OK;
-  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && col != nullptr && x != nullptr && y != nullptr);
-  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
-  const unsigned blocks = (unsigned)((n_parts + 3) / 4);
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  const int32_t st = check_plan(p, n_rows, n_cols, d, 64);
+  if (st != GCR_LAUNCH) return st;
+  GCR_CHECK_ARG(col != nullptr && x != nullptr && y != nullptr);
   hipStream_t s = (hipStream_t)stream;
-#define GCR_HUB(D64, HV) \
-  hipLaunchKernelGGL((spmm_hub_parts<D64, HV>), dim3(blocks), dim3(256), 0, s, desc, n_parts, rowptr, col, val, x, d, y, partials)
-  if (d == 64) {
-    if (val != nullptr) GCR_HUB(true, true);
-    else GCR_HUB(true, false);
-  } else {
-    if (val != nullptr) GCR_HUB(false, true);
-    else GCR_HUB(false, false);
-  }
-#undef GCR_HUB
-  int32_t st = GCR_LAUNCH_STATUS();
-  if (st != GCR_OK) return st;
-  if (n_long_rows > 0) {
-    Epilogue ep{1.0f, y, nullptr, nullptr, 1.0f, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
-    if (d == 64)
-      hipLaunchKernelGGL((spmm_long_rows<1, true, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
-                         long_slot0, n_long_rows, partials, d, ep);
-    else
-      hipLaunchKernelGGL((spmm_long_rows<1, false, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
-                         long_slot0, n_long_rows, partials, d, ep);
-    return GCR_LAUNCH_STATUS();
-  }
-  return GCR_OK;
+  return launch_walk(p, d, make_epilogue(1.0f, y, nullptr, nullptr, 1.0f), s, [&](auto d64, auto hv, dim3 blocks) {
+    hipLaunchKernelGGL((spmm_hub_parts<decltype(d64)::value, decltype(hv)::value>), blocks, dim3(256), 0, s, desc, n_parts,
+                       rowptr, col, val, x, d, y, partials);
+  });
 }
 
 // The plain launch at d <= 64 (no mask, no second addend, no row normalise): `spmm_rows` on the partitions, then the split
@@ -870,40 +799,17 @@ extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const
                                      const int32_t* col, const float* val, float val_scale, const float* x, int32_t d,
                                      float* y, const float* acc_in, float* acc_out, float acc_scale, float* partials,
                                      int64_t n_rows, int64_t n_cols, void* stream) {
-  GCR_CHECK_ARG(n_parts >= 0 && n_long_rows >= 0 && n_rows >= 0 && n_cols >= 0);
-  GCR_CHECK_ARG(n_parts < (1ll << 31) - 4 && n_rows < (1ll << 31) && n_cols < (1ll << 31));
-  GCR_CHECK_ARG(d >= 1 && d <= 256);
-  if (d > 64) return GCR_EUNSUPPORTED;
-  if (n_rows == 0 || n_parts == 0) return GCR_OK;
-  GCR_CHECK_ARG(desc != nullptr && rowptr != nullptr && x != nullptr);
-  GCR_CHECK_ARG(y != nullptr || acc_out != nullptr);
-  GCR_CHECK_ARG(n_long_rows == 0 || (long_row != nullptr && long_slot0 != nullptr && partials != nullptr));
-  const unsigned blocks = (unsigned)((n_parts + 3) / 4);
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  const int32_t st = check_plan(p, n_rows, n_cols, d, 64);
+  if (st != GCR_LAUNCH) return st;
+  GCR_CHECK_ARG(x != nullptr && (y != nullptr || acc_out != nullptr));
   hipStream_t s = (hipStream_t)stream;
-#define GCR_ROWS(D64, HV)                                                                                              \
-  hipLaunchKernelGGL((spmm_rows<D64, HV>), dim3(blocks), dim3(256), 0, s, desc, n_parts, rowptr, col, val, x, d, val_scale, \
-                     y, acc_in, acc_out, acc_scale, partials)
-  if (d == 64) {
-    if (val != nullptr) GCR_ROWS(true, true);
-    else GCR_ROWS(true, false);
-  } else {
-    if (val != nullptr) GCR_ROWS(false, true);
-    else GCR_ROWS(false, false);
-  }
-#undef GCR_ROWS
-  int32_t st = GCR_LAUNCH_STATUS();
-  if (st != GCR_OK) return st;
-  if (n_long_rows > 0) {
-    Epilogue ep{val_scale, y, acc_in, acc_out, acc_scale, 0u, nullptr, nullptr, nullptr, 0.f, nullptr};
-    if (d == 64)
-      hipLaunchKernelGGL((spmm_long_rows<1, true, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
-                         long_slot0, n_long_rows, partials, d, ep);
-    else
-      hipLaunchKernelGGL((spmm_long_rows<1, false, false>), dim3((unsigned)n_long_rows), dim3(256), 0, s, long_row,
-                         long_slot0, n_long_rows, partials, d, ep);
-    return GCR_LAUNCH_STATUS();
-  }
-  return GCR_OK;
+  return launch_walk(p, d, make_epilogue(val_scale, y, acc_in, acc_out, acc_scale), s,
+                     [&](auto d64, auto hv, dim3 blocks) {
+                       hipLaunchKernelGGL((spmm_rows<decltype(d64)::value, decltype(hv)::value>), blocks, dim3(256), 0, s,
+                                          desc, n_parts, rowptr, col, val, x, d, val_scale, y, acc_in, acc_out, acc_scale,
+                                          partials);
+                     });
 }
 
 extern "C" int32_t gcr_csr_validate(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_cols,

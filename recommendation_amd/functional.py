@@ -26,6 +26,12 @@ def _check_dense(x, n_rows, name):
         raise ValueError("embedding dim must be in [1, 256]")
 
 
+def _plan_head(graph, plan):
+    """The eight arguments every SpMM entry point of gcr.h starts with: a launch plan and the CSR it partitions."""
+    return (_lib.dptr(plan.desc), plan.n_parts, _lib.dptr(plan.long_row), _lib.dptr(plan.long_slot0), plan.n_long,
+            _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val))
+
+
 def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scale=1.0, val_scale=1.0,
               keep_bits=None, l2norm=False, inv_norm_out=None, acc_in2=None, acc_in2_scale=1.0, col_active_bits=None):
     """Raw launch of gcr_spmm_csr_acc2_f32: y = epilogue(val_scale * A[keep] x); optional fused layer
@@ -67,15 +73,12 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
         part = hub.partials(d)
         if d <= HUB_PARTS_MAX_D:          # the companion's own kernel: the same words, the tail of a block gathered in batches
             _lib.check(L.gcr_spmm_hub_parts_f32(
-                _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0),
-                H.plan.n_long, _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(x), d, _lib.dptr(part),
-                _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, stream), "gcr_spmm_hub_parts_f32")
+                *_plan_head(H, H.plan), _lib.dptr(x), d, _lib.dptr(part), _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols,
+                stream), "gcr_spmm_hub_parts_f32")
         else:
             _lib.check(L.gcr_spmm_csr_acc2_f32(
-                _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0),
-                H.plan.n_long, _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d,
-                _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None,
-                stream), "gcr_spmm_csr_acc2_f32")
+                *_plan_head(H, H.plan), None, 1.0, _lib.dptr(x), d, _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None,
+                _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
         _lib.check(L.gcr_spmm_hub_reduce_f32(
             _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
             _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
@@ -83,21 +86,14 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
     if (keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm and inv_norm_out is None
             and d <= ROWS_MAX_D):         # the plain launch's own kernel: the same words on another schedule
         _lib.check(_lib.lib().gcr_spmm_rows_f32(
-            _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
-            _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), float(val_scale), _lib.dptr(x), d,
-            _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), _lib.dptr(ws), graph.n_rows, graph.n_cols,
-            _lib.cur_stream(x.device)), "gcr_spmm_rows_f32")
-        if sink is not None:
-            ev1.record()
-            sink.append((ev0, ev1))
-        return y if y is not None else acc_out
-    rc = _lib.lib().gcr_spmm_csr_acc2_f32(
-        _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
-        _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(keep_bits), float(val_scale),
-        _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_in2), float(acc_in2_scale), _lib.dptr(acc_out),
-        float(acc_scale), SPMM_ROW_L2NORM if l2norm else 0, _lib.dptr(inv_norm_out), _lib.dptr(ws),
-        graph.n_rows, graph.n_cols, _lib.dptr(col_active_bits), _lib.cur_stream(x.device))
-    _lib.check(rc, "gcr_spmm_csr_acc2_f32")
+            *_plan_head(graph, p), float(val_scale), _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out),
+            float(acc_scale), _lib.dptr(ws), graph.n_rows, graph.n_cols, _lib.cur_stream(x.device)), "gcr_spmm_rows_f32")
+    else:
+        _lib.check(_lib.lib().gcr_spmm_csr_acc2_f32(
+            *_plan_head(graph, p), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in),
+            _lib.dptr(acc_in2), float(acc_in2_scale), _lib.dptr(acc_out), float(acc_scale),
+            SPMM_ROW_L2NORM if l2norm else 0, _lib.dptr(inv_norm_out), _lib.dptr(ws), graph.n_rows, graph.n_cols,
+            _lib.dptr(col_active_bits), _lib.cur_stream(x.device)), "gcr_spmm_csr_acc2_f32")
     if sink is not None:
         ev1.record()
         sink.append((ev0, ev1))
@@ -547,12 +543,10 @@ def spmm_dual_into(graph: CsrGraph, x, y_raw, y_norm, inv_norm_out=None, keep_bi
         raise ValueError("keep_bits must be an int32 bitmap with >= nnz bits")
     if inv_norm_out is not None and (inv_norm_out.dtype != torch.float32 or inv_norm_out.numel() != graph.n_rows):
         raise ValueError("inv_norm_out must be float32 [n_rows]")
-    p = graph.plan
     rc = _lib.lib().gcr_spmm_csr_dual_f32(
-        _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
-        _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(keep_bits), float(val_scale),
-        _lib.dptr(x), d, _lib.dptr(y_raw), _lib.dptr(y_norm), _lib.dptr(inv_norm_out), _lib.dptr(graph.workspace(d)),
-        graph.n_rows, graph.n_cols, _lib.cur_stream(x.device))
+        *_plan_head(graph, graph.plan), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y_raw),
+        _lib.dptr(y_norm), _lib.dptr(inv_norm_out), _lib.dptr(graph.workspace(d)), graph.n_rows, graph.n_cols,
+        _lib.cur_stream(x.device))
     _lib.check(rc, "gcr_spmm_csr_dual_f32")
     return y_raw, y_norm
 
@@ -574,12 +568,10 @@ def spmm_dual_acc_into(graph: CsrGraph, x, y_raw, acc_in, acc_out, inv_norm_out,
         raise ValueError("y_raw, y_norm and acc_out must be different buffers")
     if inv_norm_out is None or inv_norm_out.dtype != torch.float32 or inv_norm_out.numel() != graph.n_rows:
         raise ValueError("inv_norm_out must be float32 [n_rows]")
-    p = graph.plan
     rc = _lib.lib().gcr_spmm_csr_dual_acc_f32(
-        _lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
-        _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(keep_bits), float(val_scale),
-        _lib.dptr(x), d, _lib.dptr(y_raw), _lib.dptr(y_norm), _lib.dptr(acc_in), _lib.dptr(acc_out), _lib.dptr(inv_norm_out),
-        _lib.dptr(graph.workspace(d)), graph.n_rows, graph.n_cols, _lib.cur_stream(x.device))
+        *_plan_head(graph, graph.plan), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y_raw),
+        _lib.dptr(y_norm), _lib.dptr(acc_in), _lib.dptr(acc_out), _lib.dptr(inv_norm_out), _lib.dptr(graph.workspace(d)),
+        graph.n_rows, graph.n_cols, _lib.cur_stream(x.device))
     _lib.check(rc, "gcr_spmm_csr_dual_acc_f32")
     return y_raw, acc_out
 

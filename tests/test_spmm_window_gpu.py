@@ -34,7 +34,7 @@ def _near_oracle(got_t, ref, extra=0.0):
 
 
 @pytest.mark.parametrize("has_val", [True, False], ids=["val", "ones"])
-@pytest.mark.parametrize("d", [64, 48, 128])
+@pytest.mark.parametrize("d", [64, 48, 128, 200])
 @pytest.mark.parametrize("kind", ["base", "empty_window", "one_hub", "dup"])
 def test_windowed_order_is_pinned(kind, d, has_val):
     import recommendation_amd as ra
