@@ -133,6 +133,28 @@ int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const int32_t* l
                           int64_t n_long_rows, const int64_t* rowptr, const int32_t* col, const float* val,
                           float val_scale, const float* x, int32_t d, float* y, const float* acc_in, float* acc_out,
                           float acc_scale, float* partials, int64_t n_rows, int64_t n_cols, void* stream);
+/*
+ * A whole windowed launch for d <= 64 in one call: what gcr_spmm_hub_parts_f32 (the hub_* plan head of the companion H, its
+ * split-segment workspace hub_split, row sums into hub_partials [n_windows * n_hub, d]), gcr_spmm_hub_reduce_f32 and
+ * gcr_spmm_rows_f32 (the main plan head with the hub rows skipped, its workspace `partials`) do when called in that order,
+ * in three launches instead of five: one grid walks the partitions of both plans (nothing either reads is written by the
+ * other), one sums the split rows of both, the hub reduction comes last.  The partitions, the fmaf order, the order of
+ * every partial sum and the epilogue are those of the three entries, so every word written -- y, acc_out, hub_partials
+ * and both workspaces -- equals theirs, bit for bit.  main_first = 1: the main plan's blocks lead the grid and the
+ * companion's start at the next multiple of 8 blocks (its descriptors are laid out per XCD); 0: the companion leads;
+ * 2: the two walks as two launches of the same kernel, companion first (what scripts/perf_spmm_ab.py times to tell the
+ * gain of the one grid from that of the merged split-row launch).
+ * The argument checks are those of the three entries; d > 64: GCR_EUNSUPPORTED.
+ */
+int32_t gcr_spmm_windowed_f32(const int64_t* hub_desc, int64_t hub_n_parts, const int32_t* hub_long_row,
+                              const int32_t* hub_long_slot0, int64_t hub_n_long_rows, const int64_t* hub_rowptr,
+                              const int32_t* hub_col, const float* hub_val, float* hub_split,
+                              const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0,
+                              int64_t n_long_rows, const int64_t* rowptr, const int32_t* col, const float* val,
+                              float* partials, const int32_t* hub_row, int64_t n_hub, int32_t n_windows,
+                              float* hub_partials, const float* x, int32_t d, float val_scale, float* y,
+                              const float* acc_in, float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows,
+                              int64_t n_cols, void* stream);
 /* bits[idx[i] >> 5] |= 1 << (idx[i] & 31) for every idx[i] in [0, n_bits) (atomic OR; the caller zeroes `bits`). */
 int32_t gcr_bitmap_set(const int64_t* idx, int64_t n, int64_t n_bits, uint32_t* bits, void* stream);
 

@@ -63,14 +63,14 @@ with torch.no_grad():
     for _ in range(2):
         Fn.lightgcn_propagate(graph, x0, wl["layers"], combine="sum")
 torch.cuda.synchronize()
-# kernels per layer: with the windowed companion of the hub rows (graph.HubPlan) a layer is the companion's spmm_hub_parts
-# (counted as a spmm_parts dispatch, which it was; + spmm_long_rows for its split segments), spmm_hub_rows and the main
-# plan's spmm_parts (+ spmm_long_rows)
+# kernels per layer: with the windowed companion of the hub rows (graph.HubPlan) a layer at d = 64 is spmm_layer (both walks
+# in one grid, counted as one spmm_parts dispatch), spmm_long_rows_pair (both plans' split rows, counted as one
+# spmm_long_rows dispatch) and spmm_hub_rows
 hub = graph.hub if graph.hub is not None and graph.hub.eligible(64) else None
 if hub is None:
     per = {"spmm_parts": 1, "spmm_long_rows": int(graph.plan.n_long > 0), "spmm_hub_rows": 0}
 else:
-    per = {"spmm_parts": 2, "spmm_long_rows": int(hub.H.plan.n_long > 0) + int(hub.main.n_long > 0), "spmm_hub_rows": 1}
+    per = {"spmm_parts": 1, "spmm_long_rows": int(hub.H.plan.n_long + hub.main.n_long > 0), "spmm_hub_rows": 1}
 info = {"workload": name, "nnz": graph.nnz, "n": n, "layers": wl["layers"], "d": 64, "cal_rows": n_cal,
         "cal_parts": cal_parts, "parts": graph.plan.n_parts, "long_rows": graph.plan.n_long,
         "dispatches_per_launch": per,

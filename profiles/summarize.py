@@ -121,9 +121,12 @@ for wl in ("cfg2", "cfg4", "cfg2c_before", "cfg2c_after", "cfg4c_before", "cfg4c
     # the CSV keeps every kernel's own name; `slot` maps the companion's launch (`spmm_hub_parts` at d <= 64, a second
     # `spmm_parts` at wider d and before) to the place it has in the probe's dispatch count and in
     # parts_fetch_kb_by_dispatch (companion first, main second)
-    kname = lambda k: next(n for n in ("spmm_hub_parts", "spmm_parts", "spmm_hub_rows", "spmm_long_rows", "spmm_rows") if n in k)  # noqa: E731
-    # `spmm_rows` is the plain launch's own kernel at d <= 64: the main plan's launch, and the calibration's
-    slot = lambda n: "spmm_parts" if n in ("spmm_hub_parts", "spmm_rows") else n  # noqa: E731
+    kname = lambda k: next(n for n in ("spmm_hub_parts", "spmm_parts", "spmm_hub_rows", "spmm_long_rows_pair", "spmm_long_rows",  # noqa: E731
+                                       "spmm_rows", "spmm_layer") if n in k)
+    # `spmm_rows` is the plain launch's own kernel at d <= 64: the main plan's launch, and the calibration's.  `spmm_layer`
+    # is both walks of a windowed launch in one grid and `spmm_long_rows_pair` both plans' split rows: one dispatch each
+    slot = lambda n: ("spmm_parts" if n in ("spmm_hub_parts", "spmm_rows", "spmm_layer") else  # noqa: E731
+                      "spmm_long_rows" if n == "spmm_long_rows_pair" else n)
     for kind, path in (("fetch", fetch), ("write", write)):
         k = 0
         for r in csv.DictReader(open(path)):

@@ -23,12 +23,15 @@
 //     spmm_long_rows (deterministic; no float atomics).
 //
 // Kernels: `spmm_parts` is the generic walk (every width, mask and epilogue) and the reference the bit-for-bit tests compare
-// the others against.  The other four are shells around two shared pieces:
+// the others against.  The other six are shells around two shared pieces:
 //   * `walk_partition`, one wave's walk over a partition at d <= 64 on a tighter schedule, with a row sink for what happens
 //     at a row end: `spmm_hub_parts` stores the sum (the windowed companion), `spmm_rows` combines it with acc_in through
-//     a two-entry queue (the plain launch);
+//     a two-entry queue (the plain launch), `spmm_layer` is both in one grid, a range of blocks each (the windowed launch);
 //   * `sum_partials`, the fixed-order 4-wave sum of partial rows: `spmm_long_rows` over the chunks of a split row,
-//     `spmm_hub_rows` over the windows of a hub row, either followed by store_row.
+//     `spmm_long_rows_pair` over those of the companion and of the main plan in one grid, `spmm_hub_rows` over the windows
+//     of a hub row, each followed by store_row or a plain store.
+// A windowed launch at d <= 64 (gcr_spmm_windowed_f32) is `spmm_layer`, `spmm_long_rows_pair`, `spmm_hub_rows`: three
+// launches; gcr_spmm_hub_parts_f32 + gcr_spmm_hub_reduce_f32 + gcr_spmm_rows_f32 are the same words in five.
 #include "gcr_common.h"
 
 #include <type_traits>
@@ -366,7 +369,12 @@ __global__ __launch_bounds__(256) void spmm_hub_rows(const int32_t* __restrict__
     store_row<NV, D64, false>(ep, (int64_t)hub_row[h], d, threadIdx.x & 63, acc, false, acc);
 }
 
-// One wave's walk over its partition at d <= 64 (one accumulator register per lane), shared by the two kernels below.  One
+// The partition of this wave in a range of blocks that starts at block `block0`: four waves per block, one partition each.
+__device__ __forceinline__ int64_t wave_partition(unsigned block0) {
+  return (int64_t)__builtin_amdgcn_readfirstlane((int)((blockIdx.x - block0) * 4u + (threadIdx.x >> 6)));
+}
+
+// One wave's walk over partition `part` at d <= 64 (one accumulator register per lane), shared by the kernels below.  One
 // wave per partition in the hardware's dispatch order and one fmaf per non-zero from 0 in stored order, as `spmm_parts`; a
 // whole-row partition hands every row's sum to its row sink (empty rows zeros), a chunk partition stores its slot.  What
 // differs from `spmm_parts` is the schedule:
@@ -380,13 +388,12 @@ __global__ __launch_bounds__(256) void spmm_hub_rows(const int32_t* __restrict__
 // What happens at a row end is the sink's: sink.refill(row, n) runs in front of every batch of gathers (the next n rows to
 // end are row, row + 1, ...; n = 0 in a chunk), sink.flush(row, acc) at every row end.
 template <bool D64, bool HAS_VAL, class Sink>
-__device__ __forceinline__ void walk_partition(const int64_t* __restrict__ desc, int64_t n_parts,
+__device__ __forceinline__ void walk_partition(const int64_t part, const int64_t* __restrict__ desc, int64_t n_parts,
                                                const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                const float* __restrict__ val, const float* __restrict__ x, int d,
                                                float* __restrict__ partials, Sink& sink) {
   constexpr int UNR = 16;
   const int lane = threadIdx.x & 63;
-  const int64_t part = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
   if (part >= n_parts) return;
   const int64_t nnz0 = desc[4 * part + 0];
   const int n = (int)(desc[4 * part + 1] - nnz0);
@@ -550,7 +557,7 @@ __global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict_
                                                       const float* __restrict__ x, int d, float* __restrict__ y,
                                                       float* __restrict__ partials) {
   StoreSink<D64> sink{y, d, (int)(threadIdx.x & 63)};
-  walk_partition<D64, HAS_VAL>(desc, n_parts, rowptr, col, val, x, d, partials, sink);
+  walk_partition<D64, HAS_VAL>(wave_partition(0u), desc, n_parts, rowptr, col, val, x, d, partials, sink);
 }
 
 // The plain launch's own kernel (gcr_spmm_rows_f32), d <= 64: what `spmm_parts<1, D64, HAS_VAL, false, 16, false>` is used
@@ -564,7 +571,72 @@ __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ des
                                                  float val_scale, float* y, const float* acc_in, float* acc_out,
                                                  float acc_scale, float* __restrict__ partials) {
   CombineSink<D64> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
-  walk_partition<D64, HAS_VAL>(desc, n_parts, rowptr, col, val, x, d, partials, sink);
+  walk_partition<D64, HAS_VAL>(wave_partition(0u), desc, n_parts, rowptr, col, val, x, d, partials, sink);
+}
+
+// What one arm of `spmm_layer` walks: a plan's descriptors, the CSR they partition and the split rows' workspace.
+struct WalkSet {
+  const int64_t* desc;
+  int64_t n_parts;
+  const int64_t* rowptr;
+  const int32_t* col;
+  const float* val;
+  float* partials;
+};
+
+// The windowed launch's two walks in one grid (gcr_spmm_windowed_f32), d <= 64: blocks [hub_block0, hub_block0 +
+// hub_blocks) are `spmm_hub_parts` on the companion (row sums into hub_y), every other block is `spmm_rows` on the main plan
+// counted from main_block0.  Nothing either walk reads is written by the other, so the chip never drains between them.  The
+// choice is wave-uniform and made once; each arm is its own call of walk_partition, so each keeps the schedule and the
+// registers of the kernel it replaces, and a partition's words do not depend on where in the grid it runs.  hub_block0 is a
+// multiple of 8: the companion's descriptors are laid out per XCD (reorder.xcd_grouped_order) and blocks go round-robin
+// over the 8 XCDs.  Blocks past a range's partitions (the padding in front of a hub range that comes second) return at once.
+// amdgpu_num_sgpr(96): uncapped, the allocator takes 97 SGPRs at d = 64 with values (the larger arm, `spmm_rows`, takes 81
+// alone; the rest are kernel arguments of both arms loaded in front of the branch).  The hardware allocates in steps of 16,
+// so 97 is 112 and 7 waves per SIMD, although the compiler's report says 8: each arm launched alone through this kernel
+// was slower than its own kernel, the companion's 127.5 against 112.5 us and the main plan's 420.0 against 409.8 per cfg2
+// layer, which ate the whole gain of the one grid.  Capped it is 94 (96 allocated, 8 waves) with two scalars written to
+// VGPR lanes once in the prologue, outside every loop (53 VGPRs, 56 allocated as for 52).
+template <bool D64, bool HAS_VAL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void spmm_layer(WalkSet hub, WalkSet rest, unsigned hub_block0, unsigned hub_blocks,
+                                                  unsigned main_block0, const float* __restrict__ x, int d,
+                                                  float* __restrict__ hub_y, float val_scale, float* y,
+                                                  const float* acc_in, float* acc_out, float acc_scale) {
+  if (blockIdx.x - hub_block0 < hub_blocks) {
+    StoreSink<D64> sink{hub_y, d, (int)(threadIdx.x & 63)};
+    walk_partition<D64, HAS_VAL>(wave_partition(hub_block0), hub.desc, hub.n_parts, hub.rowptr, hub.col, hub.val, x, d,
+                                 hub.partials, sink);
+  } else {
+    CombineSink<D64> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
+    walk_partition<D64, HAS_VAL>(wave_partition(main_block0), rest.desc, rest.n_parts, rest.rowptr, rest.col, rest.val, x,
+                                 d, rest.partials, sink);
+  }
+}
+
+// The split rows of both plans of a windowed launch in one grid, d <= 64: blocks [0, n_long_hub) sum the companion's split
+// segments into hub_y as they stand (`spmm_long_rows` with a val_scale of 1.0 and y only), the others the main plan's
+// split rows with the launch's epilogue.  One call of sum_partials, so one LDS buffer; its order is `spmm_long_rows`'s.
+template <bool D64>
+__global__ __launch_bounds__(256) void spmm_long_rows_pair(const int32_t* __restrict__ hub_long_row,
+                                                           const int32_t* __restrict__ hub_slot0, unsigned n_long_hub,
+                                                           const float* __restrict__ hub_partials,
+                                                           float* __restrict__ hub_y,
+                                                           const int32_t* __restrict__ main_long_row,
+                                                           const int32_t* __restrict__ main_slot0,
+                                                           const float* __restrict__ main_partials, int d, Epilogue ep) {
+  const bool is_hub = blockIdx.x < n_long_hub;
+  const unsigned i = is_hub ? blockIdx.x : blockIdx.x - n_long_hub;
+  const int32_t* slot0 = is_hub ? hub_slot0 : main_slot0;
+  const float* partials = is_hub ? hub_partials : main_partials;
+  const int s0 = slot0[i], s1 = slot0[i + 1];
+  const int lane = threadIdx.x & 63;
+  float acc[1];
+  if (!sum_partials<1, D64>(partials + (int64_t)s0 * d, d, s1 - s0, d, acc)) return;
+  if (is_hub) {
+    if (D64 || lane < d) hub_y[(int64_t)hub_long_row[i] * d + lane] = acc[0];
+  } else {
+    store_row<1, D64, false>(ep, (int64_t)main_long_row[i], d, lane, acc, false, acc);
+  }
 }
 
 __global__ void csr_validate_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -810,6 +882,75 @@ extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const
                                           desc, n_parts, rowptr, col, val, x, d, val_scale, y, acc_in, acc_out, acc_scale,
                                           partials);
                      });
+}
+
+// A whole windowed launch at d <= 64 (graph.py HubPlan) in three launches instead of five: `spmm_layer` walks the companion
+// and the main plan in one grid, `spmm_long_rows_pair` sums the split rows of both, `spmm_hub_rows` reduces the window
+// partials.  Every word written -- outputs, hub partials, both split-row workspaces -- equals what gcr_spmm_hub_parts_f32,
+// gcr_spmm_hub_reduce_f32 and gcr_spmm_rows_f32 write when called in that order.  main_first: the main plan's blocks come
+// first in the grid and the companion's start at the next multiple of 8 blocks; otherwise the companion's come first.
+extern "C" int32_t gcr_spmm_windowed_f32(
+    const int64_t* hub_desc, int64_t hub_n_parts, const int32_t* hub_long_row, const int32_t* hub_long_slot0,
+    int64_t hub_n_long_rows, const int64_t* hub_rowptr, const int32_t* hub_col, const float* hub_val, float* hub_split,
+    const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0, int64_t n_long_rows,
+    const int64_t* rowptr, const int32_t* col, const float* val, float* partials, const int32_t* hub_row, int64_t n_hub,
+    int32_t n_windows, float* hub_partials, const float* x, int32_t d, float val_scale, float* y, const float* acc_in,
+    float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows, int64_t n_cols, void* stream) {
+  GCR_CHECK_ARG(n_hub >= 0 && n_windows >= 1 && n_rows >= 0 && n_rows < (1ll << 31));
+  GCR_CHECK_ARG(n_hub <= n_rows && n_hub * (int64_t)n_windows < (1ll << 31));
+  GCR_CHECK_ARG(main_first >= 0 && main_first <= 2);
+  Plan ph{hub_desc, hub_n_parts, hub_long_row, hub_long_slot0, hub_n_long_rows, hub_rowptr, hub_col, hub_val, hub_split};
+  Plan pm{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  const int32_t sh = check_plan(ph, n_hub * (int64_t)n_windows, n_cols, d, 64);
+  if (sh != GCR_LAUNCH && sh != GCR_OK) return sh;
+  const int32_t sm = check_plan(pm, n_rows, n_cols, d, 64);
+  if (sm != GCR_LAUNCH && sm != GCR_OK) return sm;
+  if (sh == GCR_OK) ph.n_parts = ph.n_long = 0;          // an empty plan: its range of the grid is empty
+  if (sm == GCR_OK) pm.n_parts = pm.n_long = 0;
+  if (n_hub == 0 && pm.n_parts == 0) return GCR_OK;
+  GCR_CHECK_ARG(x != nullptr && (y != nullptr || acc_out != nullptr));
+  GCR_CHECK_ARG(n_hub == 0 || (hub_row != nullptr && hub_partials != nullptr));
+  GCR_CHECK_ARG(ph.n_parts == 0 || (hub_col != nullptr && hub_partials != nullptr));
+  GCR_CHECK_ARG(ph.n_parts == 0 || pm.n_parts == 0 || (hub_val == nullptr) == (val == nullptr));
+  GCR_CHECK_ARG(ph.n_parts + pm.n_parts < (1ll << 31) - 64 && ph.n_long + pm.n_long < (1ll << 31));
+  hipStream_t s = (hipStream_t)stream;
+  const Epilogue ep = make_epilogue(val_scale, y, acc_in, acc_out, acc_scale);
+  const unsigned hub_blocks = (unsigned)((ph.n_parts + 3) / 4), main_blocks = (unsigned)((pm.n_parts + 3) / 4);
+  const unsigned hub_block0 = main_first ? (main_blocks + 7u) / 8u * 8u : 0u;
+  const unsigned main_block0 = main_first ? 0u : hub_blocks;
+  const unsigned blocks = main_first ? hub_block0 + hub_blocks : hub_blocks + main_blocks;
+  const WalkSet wh{ph.desc, ph.n_parts, ph.rowptr, ph.col, ph.val, ph.partials};
+  const WalkSet wm{pm.desc, pm.n_parts, pm.rowptr, pm.col, pm.val, pm.partials};
+  const bool has_val = ph.n_parts > 0 ? hub_val != nullptr : val != nullptr;
+  auto go = [&](auto d64) {
+    constexpr bool D64 = decltype(d64)::value;
+    // one grid, or (main_first == 2, the A/B script's cell for the merged split-row launch alone) one per range
+    auto walk = [&](unsigned n_blocks, unsigned hb0, unsigned hb, unsigned mb0) {
+      if (n_blocks == 0) return (int32_t)GCR_OK;
+      if (has_val)
+        hipLaunchKernelGGL((spmm_layer<D64, true>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
+                           hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
+      else
+        hipLaunchKernelGGL((spmm_layer<D64, false>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
+                           hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
+      return (int32_t)GCR_LAUNCH_STATUS();
+    };
+    int32_t st = main_first == 2 ? walk(hub_blocks, 0u, hub_blocks, 0u) : walk(blocks, hub_block0, hub_blocks, main_block0);
+    if (st == GCR_OK && main_first == 2) st = walk(main_blocks, 0u, 0u, 0u);
+    if (st != GCR_OK) return st;
+    if (ph.n_long + pm.n_long > 0) {
+      hipLaunchKernelGGL((spmm_long_rows_pair<D64>), dim3((unsigned)(ph.n_long + pm.n_long)), dim3(256), 0, s, ph.long_row,
+                         ph.long_slot0, (unsigned)ph.n_long, ph.partials, hub_partials, pm.long_row, pm.long_slot0,
+                         pm.partials, d, ep);
+      const int32_t st = GCR_LAUNCH_STATUS();
+      if (st != GCR_OK) return st;
+    }
+    if (n_hub == 0) return (int32_t)GCR_OK;
+    hipLaunchKernelGGL((spmm_hub_rows<1, D64>), dim3((unsigned)n_hub), dim3(256), 0, s, hub_row, n_hub, n_windows,
+                       hub_partials, d, ep);
+    return (int32_t)GCR_LAUNCH_STATUS();
+  };
+  return d == 64 ? go(std::true_type{}) : go(std::false_type{});
 }
 
 extern "C" int32_t gcr_csr_validate(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_cols,

@@ -11,8 +11,9 @@ from . import _lib
 from .graph import CsrGraph
 
 SPMM_ROW_L2NORM = 1
-ROWS_MAX_D = 64            # gcr_spmm_rows_f32, the plain launch's own kernel, likewise; wider launches keep gcr_spmm_csr_acc2_f32
-HUB_PARTS_MAX_D = 64       # gcr_spmm_hub_parts_f32 holds one register per lane and row; wider launches keep spmm_parts on H
+ROWS_MAX_D = 64            # gcr_spmm_rows_f32, the plain launch's own kernel, holds one register per lane and row; wider
+                           # launches keep gcr_spmm_csr_acc2_f32
+WINDOWED_MAX_D = 64        # gcr_spmm_windowed_f32, a whole windowed launch, likewise; wider ones keep spmm_parts on both plans
 
 # bench.py sets this to a list to receive a (start, end) HIP event pair per gcr_spmm_csr_f32
 # launch, recorded on the stream the kernel is launched on
@@ -64,36 +65,39 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
     if sink is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    # the heaviest rows by column window (graph.HubPlan): plain launches only -- a mask is a predicate per stored non-zero
-    # of the classic order, the second addend and the row normalise have instantiations of their own
-    hub = graph.hub
-    if (hub is not None and keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm
-            and inv_norm_out is None and hub.eligible(d)):
-        L, H, stream = _lib.lib(), hub.H, _lib.cur_stream(x.device)
-        part = hub.partials(d)
-        if d <= HUB_PARTS_MAX_D:          # the companion's own kernel: the same words, the tail of a block gathered in batches
-            _lib.check(L.gcr_spmm_hub_parts_f32(
-                *_plan_head(H, H.plan), _lib.dptr(x), d, _lib.dptr(part), _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols,
-                stream), "gcr_spmm_hub_parts_f32")
-        else:
+    # plain launches: no mask (a predicate per stored non-zero of the classic order), no second addend, no row normalise
+    plain = keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm and inv_norm_out is None
+    L, stream = _lib.lib(), _lib.cur_stream(x.device)
+    # the heaviest rows by column window (graph.HubPlan): plain launches only
+    hub = graph.hub if plain and graph.hub is not None and graph.hub.eligible(d) else None
+    if hub is not None and d <= WINDOWED_MAX_D:
+        # both walks in one grid, both plans' split rows in another, then the hub reduction: the words of the branch below
+        H = hub.H
+        _lib.check(L.gcr_spmm_windowed_f32(
+            *_plan_head(H, H.plan), _lib.dptr(H.workspace(d)), *_plan_head(graph, hub.main), _lib.dptr(ws),
+            _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(hub.partials(d)), _lib.dptr(x), d, float(val_scale),
+            _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), int(hub.main_first), graph.n_rows,
+            graph.n_cols, stream), "gcr_spmm_windowed_f32")
+    else:
+        if hub is not None:               # d > 64: the companion through the generic kernel, the reduction, then `main`
+            H, part = hub.H, hub.partials(d)
             _lib.check(L.gcr_spmm_csr_acc2_f32(
                 *_plan_head(H, H.plan), None, 1.0, _lib.dptr(x), d, _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None,
                 _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
-        _lib.check(L.gcr_spmm_hub_reduce_f32(
-            _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
-            _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
-        p = hub.main                      # every other row: the classic walk with the hub rows skipped
-    if (keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm and inv_norm_out is None
-            and d <= ROWS_MAX_D):         # the plain launch's own kernel: the same words on another schedule
-        _lib.check(_lib.lib().gcr_spmm_rows_f32(
-            *_plan_head(graph, p), float(val_scale), _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out),
-            float(acc_scale), _lib.dptr(ws), graph.n_rows, graph.n_cols, _lib.cur_stream(x.device)), "gcr_spmm_rows_f32")
-    else:
-        _lib.check(_lib.lib().gcr_spmm_csr_acc2_f32(
-            *_plan_head(graph, p), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in),
-            _lib.dptr(acc_in2), float(acc_in2_scale), _lib.dptr(acc_out), float(acc_scale),
-            SPMM_ROW_L2NORM if l2norm else 0, _lib.dptr(inv_norm_out), _lib.dptr(ws), graph.n_rows, graph.n_cols,
-            _lib.dptr(col_active_bits), _lib.cur_stream(x.device)), "gcr_spmm_csr_acc2_f32")
+            _lib.check(L.gcr_spmm_hub_reduce_f32(
+                _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
+                _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
+            p = hub.main                  # every other row: the classic walk with the hub rows skipped
+        if plain and d <= ROWS_MAX_D:     # the plain launch's own kernel: the same words on another schedule
+            _lib.check(L.gcr_spmm_rows_f32(
+                *_plan_head(graph, p), float(val_scale), _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out),
+                float(acc_scale), _lib.dptr(ws), graph.n_rows, graph.n_cols, stream), "gcr_spmm_rows_f32")
+        else:
+            _lib.check(L.gcr_spmm_csr_acc2_f32(
+                *_plan_head(graph, p), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y),
+                _lib.dptr(acc_in), _lib.dptr(acc_in2), float(acc_in2_scale), _lib.dptr(acc_out), float(acc_scale),
+                SPMM_ROW_L2NORM if l2norm else 0, _lib.dptr(inv_norm_out), _lib.dptr(ws), graph.n_rows, graph.n_cols,
+                _lib.dptr(col_active_bits), stream), "gcr_spmm_csr_acc2_f32")
     if sink is not None:
         ev1.record()
         sink.append((ev0, ev1))

@@ -34,6 +34,20 @@ HUB_MIN_TABLE_BYTES = 16 << 20        # the gathered table is at least 4 x one X
 HUB_MAX_WINDOW_BYTES = 4 << 20        # one window of the table is at most one XCD's L2 (d <= 64 at the default window)
 
 
+# The order of the work inside the one grid that walks the companion and the main plan (gcr_spmm_windowed_f32); both are
+# plan decisions and neither changes a word of the result.  Measurements: EXPERIMENTS.md "SpMM: one launch for both walks".
+HUB_MAIN_FIRST = True                 # which range of blocks leads the grid: the main plan's (True) or the companion's
+HUB_MAIN_LONG_ROWS_FIRST = False      # `HubPlan.main`'s descriptors in plan order (False) or by long_rows_first_order
+
+
+def long_rows_first_order(desc):
+    """A permutation of the rows of a plan's descriptors [n_parts, 4]: stable by the number of rows of a partition,
+    ascending, so the chunks of split rows and the partitions of a few long rows are dispatched first and the partitions of
+    many short rows last.  A partition's slot travels with its descriptor, so the split rows' tables stay as they are."""
+    desc = np.asarray(desc, dtype=np.int64).reshape(-1, 4)
+    return np.argsort(desc[:, 2] >> 32, kind="stable")
+
+
 def _np_i64(a):
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
@@ -84,6 +98,18 @@ class SpmmPlan:
         self.long_row = torch.from_numpy(long_row).to(device)
         self.long_slot0 = torch.from_numpy(long_slot0).to(device)
 
+    def permuted(self, order):
+        """This plan with its descriptors in another order (`order`: a permutation of range(n_parts)): the same partitions,
+        one wave each, dispatched in that order.  The split rows' tables and slots are shared and unchanged."""
+        import copy
+        order = np.asarray(order, dtype=np.int64)
+        if not np.array_equal(np.sort(order), np.arange(self.n_parts)):
+            raise ValueError("order must be a permutation of the plan's partitions")
+        q = copy.copy(self)
+        q.desc_host = np.ascontiguousarray(self.desc_host[order])
+        q.desc = torch.from_numpy(q.desc_host if self.n_parts else np.empty((1, 4), dtype=np.int64)).to(self.desc.device)
+        return q
+
 
 class HubPlan:
     """Windowed companion of a graph's heaviest rows: their gathers are made to hit in L2.
@@ -100,7 +126,9 @@ class HubPlan:
                                                gcr_spmm_csr_f32 on H, y only, val_scale 1 at wider d (the same bits)
       2. out[hub rows] = epilogue(sum of a row's window partials in window order)      gcr_spmm_hub_reduce_f32
       3. every other row: the classic walk with the hub rows skipped (`main`)          gcr_spmm_csr_f32
-    on one stream.  The 8 W bound keeps the partial traffic (W x 2 x 4 d bytes per hub row) under a quarter of the row's
+    on one stream.  At d <= 64 gcr_spmm_windowed_f32 does all of it in three launches with the same words: one grid walks
+    the partitions of `main` and of `H` (`main_first`: whose blocks lead; nothing either reads is written by the other),
+    one sums the split rows of both plans, the reduction of step 2 comes last.  The 8 W bound keeps the partial traffic (W x 2 x 4 d bytes per hub row) under a quarter of the row's
     gathers.  `build` returns None when the graph has no hub rows or a hub row's columns are not sorted."""
 
     @classmethod
@@ -149,6 +177,9 @@ class HubPlan:
         skip = np.zeros(graph.n_rows, dtype=np.uint8)
         skip[hub_host] = 1
         self.main = SpmmPlan(graph.rowptr_host, dev, graph.plan.nnz_per_part, skip=skip)
+        if HUB_MAIN_LONG_ROWS_FIRST:
+            self.main = self.main.permuted(long_rows_first_order(self.main.desc_host))
+        self.main_first = HUB_MAIN_FIRST
         self._partials = {}
         return self
 

@@ -19,7 +19,14 @@ relative to the largest output is printed beside it.  --hub-config WINDOW_ROWS:N
 that library once per companion layout instead of the graph's own.  A library that also exports gcr_spmm_hub_parts_f32
 runs the companion (d <= 64) through it, as functional.spmm_into does.  A library that exports gcr_spmm_rows_f32 runs the
 main launch (d <= 64, not --acc2) through it, again as functional.spmm_into does; its words are the generic launch's, so
-`equal_to_base` must hold against a base with the same plan.
+`equal_to_base` must hold against a base with the same plan.  A library that exports gcr_spmm_windowed_f32 runs the whole
+windowed layer (d <= 64, not --acc2) through it, three launches, again as functional.spmm_into does.  --order CELL
+(repeatable; hub_first or main_first, optionally followed by :long_rows_first) times such a library once per cell instead
+of the graph's own order: which range of blocks leads the one grid, and whether the main plan's descriptors keep plan
+order or graph.long_rows_first_order's; two_walks launches the two ranges one after the other (the merged split-row launch
+without the one grid).  --five-launch keeps such a library on the three older entries.  --shared-output makes every
+library write the same output array: with an array of its own per library, a library's place in the list moved its time by
+1-4 % (other addresses), more than most differences this script is asked about; give a library twice to see what is left.
 
 The measurement runs in a child process under a time limit of its own (--timeout seconds); the parent never touches the
 GPU and stops at the first failure."""
@@ -51,8 +58,8 @@ def child(args):
     torch.nn.init.xavier_uniform_(x0, generator=torch.Generator(device=dev).manual_seed(0))
     p, ws = graph.plan, graph.workspace(d)
     res, argt = _lib.SIGNATURES["gcr_spmm_csr_acc2_f32"]
-    from recommendation_amd.graph import HubPlan
-    libs, plans = [], {}
+    from recommendation_amd.graph import HubPlan, long_rows_first_order
+    libs, plans, orders = [], {}, {}
     for path in args.lib:
         h = ctypes.CDLL(os.path.abspath(path))
         fn = h.gcr_spmm_csr_acc2_f32
@@ -62,20 +69,36 @@ def child(args):
             rows.restype, rows.argtypes = _lib.SIGNATURES["gcr_spmm_rows_f32"]
         red = getattr(h, "gcr_spmm_hub_reduce_f32", None)
         if red is None or args.acc2:                       # the second-addend form never takes the windowed plan
-            libs.append((path, fn, None, None, None, rows))
+            libs.append((path, fn, None, None, None, rows, None, None))
             continue
         red.restype, red.argtypes = _lib.SIGNATURES["gcr_spmm_hub_reduce_f32"]
         own = getattr(h, "gcr_spmm_hub_parts_f32", None) if d <= 64 else None
         if own is not None:
             own.restype, own.argtypes = _lib.SIGNATURES["gcr_spmm_hub_parts_f32"]
+        fused = getattr(h, "gcr_spmm_windowed_f32", None) if d <= 64 and not args.five_launch else None
+        if fused is not None:
+            fused.restype, fused.argtypes = _lib.SIGNATURES["gcr_spmm_windowed_f32"]
+
+        def add(name, hub):
+            if fused is None or hub is None or not args.order:
+                cell = None if fused is None or hub is None else (int(hub.main_first), hub.main)
+                libs.append((name, fn, red, hub, own, rows, fused, cell))
+                return
+            for c in args.order:                           # one entry per order of the work, the same plans
+                first, _, desc_order = c.partition(":")
+                if (first, desc_order) not in orders:
+                    orders[first, desc_order] = (["hub_first", "main_first", "two_walks"].index(first), hub.main if not desc_order else
+                                                 hub.main.permuted(long_rows_first_order(hub.main.desc_host)))
+                libs.append((f"{name} [{c}]", fn, red, hub, own, rows, fused, orders[first, desc_order]))
+
         if not args.hub_config:
-            hub = graph.hub if graph.hub is not None and graph.hub.eligible(d) else None
-            libs.append((path, fn, red, hub, own, rows))
+            add(path, graph.hub if graph.hub is not None and graph.hub.eligible(d) else None)
         for cfg in args.hub_config or []:
             wr, npp, *mind = (int(v) for v in cfg.split(":"))
             if cfg not in plans:                           # one companion per layout, shared by the libraries
                 plans[cfg] = HubPlan.build(graph, wr, min_degree=mind[0] if mind else None, nnz_per_part=npp, forced=True)
-            libs.append((f"{path} [hub {cfg}]", fn, red, plans[cfg], own, rows))
+            orders = {}
+            add(f"{path} [hub {cfg}]", plans[cfg])
     stream = _lib.cur_stream(torch.device(dev))
 
     # --acc2: the Horner backward's form, a second addend with its own scale (the ACC2 instantiation of the kernel)
@@ -83,8 +106,19 @@ def child(args):
     in2_scale = 0.25 if args.acc2 else 0.0
 
     def launch(lib, x, out):
-        _, fn, red, hub, own, rows = lib
+        _, fn, red, hub, own, rows, fused, cell = lib
         q = p
+        if cell is not None:
+            main_first, q = cell
+            H, hp = hub.H, hub.H.plan
+            _lib.check(fused(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
+                             _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(H.workspace(d)),
+                             _lib.dptr(q.desc), q.n_parts, _lib.dptr(q.long_row), _lib.dptr(q.long_slot0), q.n_long,
+                             _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(ws),
+                             _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(hub.partials(d)), _lib.dptr(x), d,
+                             1.0, None, _lib.dptr(x0), _lib.dptr(out), 1.0, main_first, graph.n_rows, graph.n_cols, stream),
+                       "gcr_spmm_windowed_f32")
+            return
         if hub is not None:
             H, hp, part = hub.H, hub.H.plan, hub.partials(d)
             if own is not None:
@@ -112,10 +146,17 @@ def child(args):
 
     z = torch.empty_like(x0)
     launch(libs[0], x0, z)                         # layer 1 of the base: the input of the timed (second) layer
-    outs = [torch.empty_like(x0) for _ in libs]
+    # --shared-output: every library writes the same array, so no cell is timed on other addresses than the base (an output
+    # array of its own per library moved a cell by 1-4 % with its position in the list); the words are compared on copies
+    shared = torch.empty_like(x0) if args.shared_output else None
+    outs = [shared if args.shared_output else torch.empty_like(x0) for _ in libs]
+    snaps = []
     for lib, out in zip(libs, outs):
         for _ in range(args.warmup):
             launch(lib, z, out)
+        if args.shared_output:
+            torch.cuda.synchronize()
+            snaps.append(out.clone())
     torch.cuda.synchronize()
     ms = [[] for _ in libs]
     for _ in range(args.alternations):
@@ -127,14 +168,17 @@ def child(args):
             e1.record()
             torch.cuda.synchronize()
             ms[k].append(e0.elapsed_time(e1) / args.launches)
+    if args.shared_output:
+        outs = snaps
     report = {"workload": args.workload, "acc2": bool(args.acc2), "d": d, "nnz": graph.nnz, "n_parts": p.n_parts, "n_long": p.n_long,
               "alternations": args.alternations, "launches": args.launches, "libs": []}
-    for k, (path, _, _, hub, _, rows) in enumerate(libs):
+    for k, (path, _, _, hub, _, rows, _, cell) in enumerate(libs):
         m = sum(ms[k]) / len(ms[k])
         ent = {"lib": path, "ms_per_layer": [round(v, 5) for v in ms[k]], "mean": round(m, 5),
                "spread": round(max(ms[k]) - min(ms[k]), 5), "equal_to_base": bool(torch.equal(outs[k], outs[0])),
                "max_diff_over_max": float((outs[k] - outs[0]).abs().max() / outs[0].abs().max()),
-               "main_entry": "gcr_spmm_csr_acc2_f32" if rows is None else "gcr_spmm_rows_f32",
+               "main_entry": "gcr_spmm_windowed_f32" if cell is not None else
+                             "gcr_spmm_csr_acc2_f32" if rows is None else "gcr_spmm_rows_f32",
                "windowed": None if hub is None else {"window_rows": hub.window_rows, "windows": hub.n_windows,
                                                       "n_hub": hub.n_hub, "hub_nnz": hub.hub_nnz,
                                                       "nnz_per_part": hub.H.plan.nnz_per_part}}
@@ -166,6 +210,11 @@ def main():
     ap.add_argument("--acc2", action="store_true", help="time the second-addend form (acc_in2 given) instead")
     ap.add_argument("--hub-config", action="append", metavar="WINDOW_ROWS:NNZ_PER_PART[:MIN_DEGREE]",
                     help="time a library with the windowed plan once per companion layout (default: the graph's own)")
+    ap.add_argument("--order", action="append", metavar="CELL",
+                    choices=["hub_first", "main_first", "hub_first:long_rows_first", "main_first:long_rows_first", "two_walks"],
+                    help="time a library with gcr_spmm_windowed_f32 once per order of the work (default: the graph's own)")
+    ap.add_argument("--shared-output", action="store_true", help="every library writes the same output array")
+    ap.add_argument("--five-launch", action="store_true", help="keep every library on the three older windowed entries")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per workload (child process)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -188,6 +237,12 @@ def main():
             cmd.append("--acc2")
         for cfg in args.hub_config or []:
             cmd += ["--hub-config", cfg]
+        for c in args.order or []:
+            cmd += ["--order", c]
+        if args.five_launch:
+            cmd.append("--five-launch")
+        if args.shared_output:
+            cmd.append("--shared-output")
         try:
             rc = subprocess.run(cmd, timeout=args.timeout).returncode
         except subprocess.TimeoutExpired:
