@@ -804,6 +804,41 @@ int32_t gcr_directau_bwd_f32(const float* user_tab, const float* item_tab, int32
                              int64_t n_items, float t, const float* inv_norm, const float* r, const float* o,
                              const float* g_sums, float* g_user_tab, float* g_item_tab, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SEPT: tri-training pseudo-labels + neighbour discrimination for three views (csrc/gcr_tri.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * replaces  label_prediction x3, generate_pesudo_labels x3 (torch.topk), neighbor_discrimination x3
+ *           univariate/sept_social.py:394-420, 447-457  (about 60 launches and three M x M matrices per batch).
+ * x_f, x_s, x_r, aug: [n_rows, d] row-major float32 (friend, sharing, rec view and the augmented table); uniq: int64 [m],
+ * strictly ascending (torch.unique of the batch's users); an id outside [0, n_rows) reads as a zero row and receives no
+ * gradient (gcr_gather_rows_f32's contract).  With e_v[i] = x_v[uniq[i]] / max(|.|, 1e-12), a[j] likewise from aug and
+ * S_v[i, j] = <e_v[i], a[j]>:
+ *   P_v = softmax_j S_v (temperature 1);   pos_f[i] = top-k_j (P_s + P_r)[i, :], pos_s = top-k (P_f + P_r),
+ *   pos_r = top-k (P_f + P_s), descending, ties to the smaller column (gcr_topk_masked_f32's rule);
+ *   loss[v] = -sum_i ( log sum_{j in pos_v[i]} exp(S_v[i, j] inv_t) - log sum_j exp(S_v[i, j] inv_t) ).
+ * Outputs: loss [3]; positive int64 [3, m, k] (replay != 0: READ instead of selected — rows of distinct columns in
+ * [0, m)); rsum [2, 3, m] = 1 / sum_j e and 1 / sum_{pos} e with e = exp((S - 1) inv_t) (reciprocals, not log-sums: f32
+ * keeps their relative precision); inv_norm [4, m]; member: gcr_tri_member_words(m)
+ * 32-bit words, bit j of row (v, i) = j in pos_v[i] (zeroed by the call).  The M x M matrices are never written; scores
+ * come from the f32-input MFMA and are f32-accurate.  Six launches (replay: five).
+ * Backward, for upstream g [3] on the device: w_v[i, j] = g_v inv_t (softmax_j(S_v inv_t) - [j in pos_v[i]] softmax over
+ * pos_v[i]); d e_v[i] = sum_j w a[j], d a[j] = sum_v sum_i w e_v[i], through the normalisation, WRITTEN to rows uniq of
+ * d_f / d_s / d_r / d_aug (the other rows are the caller's: zero them).  One writer per row, fixed-order sums, no float
+ * atomics: bitwise reproducible.  Five launches.
+ * Supported (gcr_tri_supported): d in {32, 64, 128}, 1 <= k <= 32; GCR_EUNSUPPORTED otherwise.  m = 0 launches nothing;
+ * 0 < m < k is GCR_EINVAL, and so is inv_t outside (0, 40] (the reference hard-codes 10).  Both calls take gcr_tri_workspace_bytes(m, d, k) bytes.
+ */
+int32_t gcr_tri_supported(int32_t d, int32_t k);
+int64_t gcr_tri_workspace_bytes(int64_t m, int32_t d, int32_t k);
+int64_t gcr_tri_member_words(int64_t m);
+int32_t gcr_tri_fwd_f32(const float* x_f, const float* x_s, const float* x_r, const float* aug, int64_t n_rows, int32_t d,
+                        const int64_t* uniq, int64_t m, int32_t k, float inv_t, int32_t replay, float* loss,
+                        int64_t* positive, float* rsum, float* inv_norm, uint32_t* member, void* workspace, void* stream);
+int32_t gcr_tri_bwd_f32(const float* x_f, const float* x_s, const float* x_r, const float* aug, int64_t n_rows, int32_t d,
+                        const int64_t* uniq, int64_t m, int32_t k, float inv_t, const float* rsum, const uint32_t* member,
+                        const float* g, float* d_f, float* d_s, float* d_r, float* d_aug, void* workspace, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

@@ -128,7 +128,14 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P]),
     "gcr_directau_bwd_f32": (c_int32, [_P, _P, c_int32, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, c_float,
                                        _P, _P, _P, _P, _P, _P, _P]),
-    "gcr_mask_columns_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
+    "gcr_tri_supported": (c_int32, [c_int32, c_int32]),
+    "gcr_tri_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "gcr_tri_member_words": (c_int64, [c_int64]),
+    "gcr_tri_fwd_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, c_int32, c_float, c_int32, _P, _P, _P, _P, _P,
+                                  _P, _P]),
+    "gcr_tri_bwd_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P,
+                                  _P, _P]),
+    "gcr_mask_columns_f32":(c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "gcr_spgemm_expand_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_csr_lookup_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P]),
     "gcr_gather_rows_f32": (c_int32, [_P, _P, c_int64, c_int32, c_int64, _P, _P]),

@@ -1612,3 +1612,106 @@ def gather_dropout_views(table, idx, p, seed, n_views=2, keep_bits=None):
             raise ValueError(f"keep_bits must be int32 [{n_views}, {n_words}] (and p < 1)")
         keep_bits = keep_bits.contiguous()
     return _GatherDropoutViews.apply(table, idx, p, int(seed) & (2 ** 64 - 1), n_views, keep_bits)
+
+
+# ---------------------------------------------------------------------------------------------
+# SEPT's tri-training block (univariate/sept_social.py:394-420, 447-457)
+# ---------------------------------------------------------------------------------------------
+class _TriTraining(torch.autograd.Function):
+    """gcr_tri_fwd_f32 / gcr_tri_bwd_f32: saves the four tables, uniq, the [2, 3, M] reciprocal sums and the membership bitmap
+    (3 M^2 bits), never an M x M matrix."""
+
+    @staticmethod
+    def forward(ctx, x_f, x_s, x_r, aug, uniq, k, inv_t, positives):
+        L = _lib.lib()
+        tabs = [t.contiguous() for t in (x_f, x_s, x_r, aug)]
+        n_rows, d = tabs[0].shape
+        m, dev = uniq.numel(), tabs[0].device
+        loss = torch.empty(3, dtype=torch.float32, device=dev)
+        replay = positives is not None
+        pos = positives if replay else torch.empty(3, m, k, dtype=torch.int64, device=dev)
+        rsum = torch.empty(2, 3, m, dtype=torch.float32, device=dev)
+        inv_norm = torch.empty(4, m, dtype=torch.float32, device=dev)
+        member = torch.empty(int(L.gcr_tri_member_words(m)), dtype=torch.int32, device=dev)
+        ws = torch.empty(max(int(L.gcr_tri_workspace_bytes(m, d, k)), 4) // 4, dtype=torch.float32, device=dev)
+        _lib.check(L.gcr_tri_fwd_f32(*(_lib.dptr(t) for t in tabs), n_rows, d, _lib.dptr(uniq), m, k, inv_t, int(replay),
+                                     _lib.dptr(loss), _lib.dptr(pos), _lib.dptr(rsum), _lib.dptr(inv_norm), _lib.dptr(member),
+                                     _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_tri_fwd_f32")
+        ctx.save_for_backward(*tabs, uniq, rsum, member)
+        ctx.args = (k, inv_t)
+        ctx.mark_non_differentiable(pos)
+        return loss, pos
+
+    @staticmethod
+    def backward(ctx, g, _g_pos):
+        *tabs, uniq, rsum, member = ctx.saved_tensors
+        k, inv_t = ctx.args
+        L = _lib.lib()
+        n_rows, d = tabs[0].shape
+        m, dev = uniq.numel(), tabs[0].device
+        g = g.to(torch.float32).contiguous()
+        grads = [torch.zeros_like(t) for t in tabs]
+        ws = torch.empty(max(int(L.gcr_tri_workspace_bytes(m, d, k)), 4) // 4, dtype=torch.float32, device=dev)
+        _lib.check(L.gcr_tri_bwd_f32(*(_lib.dptr(t) for t in tabs), n_rows, d, _lib.dptr(uniq), m, k, inv_t, _lib.dptr(rsum),
+                                     _lib.dptr(member), _lib.dptr(g), *(_lib.dptr(t) for t in grads), _lib.dptr(ws),
+                                     _lib.cur_stream(dev)), "gcr_tri_bwd_f32")
+        return (*grads, None, None, None, None)
+
+
+def tri_training_supported(d, k):
+    """True when the fused kernels (gcr_tri_*) serve rows of width d with k pseudo-labels: d in {32, 64, 128}, 1 <= k <= 32."""
+    return bool(_lib.lib().gcr_tri_supported(int(d), int(k)))
+
+
+def tri_training_loss_composed(x_f, x_s, x_r, aug, uniq, k, temperature=0.1, positives=None):
+    """`tri_training_loss` as the reference writes it, from the ops that were there before the fused kernel: torch's
+    label_prediction (sept_social.py:394-399), `torch.topk` (:401-406) and `losses.neighbor_discrimination` (:408-420)."""
+    import torch.nn.functional as F
+    from . import losses as Ls
+    a = aug[uniq]
+    views = [x[uniq] for x in (x_f, x_s, x_r)]
+    if positives is None:
+        with torch.no_grad():                        # nothing flows through the probabilities or the indices
+            an = F.normalize(a)
+            p_f, p_s, p_r = (F.softmax(torch.matmul(F.normalize(e), an.T), dim=1) for e in views)
+            positives = torch.stack([torch.topk((p1 + p2) / 2, k, dim=1).indices
+                                     for p1, p2 in ((p_s, p_r), (p_f, p_r), (p_f, p_s))])
+    loss = torch.stack([Ls.neighbor_discrimination(positives[v], views[v], a, temperature) for v in range(3)])
+    return loss, positives
+
+
+def tri_training_loss(x_f, x_s, x_r, aug, uniq, k, temperature=0.1, positives=None):
+    """The tri-training block of univariate/sept_social.py:447-457 for the friend, sharing and rec view tables and the
+    augmented table (all float32 [U, d]) over the distinct batch users `uniq` = torch.unique(user_idx) (int64 [M], strictly
+    ascending — computed once here where the reference computes it six times):
+        P_v = label_prediction(x_v)                                     :394-399
+        pos_f = topk(P_s + P_r), pos_s = topk(P_f + P_r), pos_r = topk(P_f + P_s)      :401-406, 451-453
+        loss[v] = neighbor_discrimination(pos_v, x_v)  at temperature `temperature` (the reference hard-codes 0.1)  :408-420
+    Returns (loss [3] in the order friend, sharing, rec; positives int64 [3, M, k], every row in descending order of the
+    combined probability, ties to the smaller column).  One autograd node, differentiable in the four tables; nothing flows
+    through the probabilities or the indices.  positives=: replays given label sets (rows of distinct columns in [0, M))
+    instead of selecting.  Shapes outside `tri_training_supported(d, k)`, and temperatures below 1 / 40, run
+    `tri_training_loss_composed`.  M < k raises
+    (the reference's topk does); M = 0 gives zeros."""
+    _lib.require_cuda(x_f, x_s, x_r, aug)
+    tabs = (x_f, x_s, x_r, aug)
+    if any(t.dim() != 2 or t.dtype != torch.float32 or t.shape != x_f.shape for t in tabs):
+        raise ValueError("the four tables must be float32 [U, d] of one shape")
+    k = int(k)
+    uniq = _as_index(uniq, x_f.device).reshape(-1)
+    m = uniq.numel()
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    if m == 0:
+        return sum(t.sum() for t in tabs) * torch.zeros(3, device=x_f.device), torch.zeros(3, 0, k, dtype=torch.int64, device=x_f.device)
+    if m < k:
+        raise ValueError(f"tri_training_loss: {m} distinct users cannot give {k} pseudo-labels each")
+    if positives is not None:
+        positives = torch.as_tensor(positives).to(device=x_f.device, dtype=torch.int64).contiguous()
+        if tuple(positives.shape) != (3, m, k):
+            raise ValueError(f"positives must be int64 [3, {m}, {k}]")
+    if not tri_training_supported(x_f.shape[1], k) or not (0.025 <= float(temperature)):
+        return tri_training_loss_composed(x_f, x_s, x_r, aug, uniq, k, temperature, positives)
+    if positives is not None:
+        positives = positives.clone()                # the node returns the tensor it was given: keep the caller's apart
+    return _TriTraining.apply(x_f, x_s, x_r, aug, uniq, k, 1.0 / float(temperature), positives)

@@ -164,3 +164,27 @@ def build_hyper_graphs(s_row, s_col, y_row, y_col, n_users, n_items, device):
     matrix (mhcn.py:340-368,401) as CsrGraph handles for mhcn.MHCNEncoder."""
     hs, hj, hp, Y = motif_adjacency(s_row, s_col, y_row, y_col, n_users, n_items, device)
     return hs.row_normalised_graph(), hj.row_normalised_graph(), hp.row_normalised_graph(), Y.row_normalised_graph()
+
+
+def social_related_views(s_row, s_col, y_row, y_col, n_users, n_items, device):
+    """(friend view, sharing view) of univariate/sept_social.py as CsrGraph [U, U] operators:
+    `Relation.get_birectional_social_mat` (:141-144: `S.multiply(S)`, the element-wise SQUARE of the directed social
+    matrix, not S * S^T) followed by `get_social_related_views` (:361-368):
+        friend  = normalize((S2 @ S2) * S2 + I),   sharing = normalize((Y @ Y^T) * S2 + I),
+    normalize = `Graph.normalize_graph_mat`'s square branch, D^-1/2 A D^-1/2 with the ROW sums on both sides.  S and Y
+    hold unit entries, a repeated pair sums (scipy's csr_matrix constructor).  Neither result is symmetric; their
+    transposes (built on first use) serve the backward."""
+    from .graph import sym_norm_device
+    ones = lambda n: torch.ones(n, device=device)      # noqa: E731
+    s_row, s_col = torch.as_tensor(s_row, device=device), torch.as_tensor(s_col, device=device)
+    y_row, y_col = torch.as_tensor(y_row, device=device), torch.as_tensor(y_col, device=device)
+    S = Sp.from_coo(s_row, s_col, ones(s_row.numel()), n_users, n_users, device)
+    Y = Sp.from_coo(y_row, y_col, ones(y_row.numel()), n_users, n_items, device)
+    S2 = Sp(S.rowptr, S.col, S.val * S.val, n_users, n_users)
+    diag = torch.arange(n_users, device=device)
+    eye = Sp.from_coo(diag, diag, ones(n_users), n_users, n_users, device)
+    out = []
+    for m in ((S2 @ S2) * S2 + eye, (Y @ Y.T) * S2 + eye):
+        val = sym_norm_device(m.rowptr, m.col, m.val, n_users)
+        out.append(CsrGraph(m.rowptr, m.col, val, n_users, n_users, device, symmetric=False, validate=False))
+    return out[0], out[1]

@@ -1,0 +1,231 @@
+#!/usr/bin/env python3
+"""TEST INFRASTRUCTURE ONLY — write tests/golden/sept_steps.npz: eight training steps of univariate/sept_social.py run by
+the reference itself.
+
+Runs ONLY where the reference sources are (like scripts/gen_golden_mhcn_steps.py, whose data and helpers it shares); the
+fixture is plain data.  sept_social.py does not import (tensorflow), so its pieces are taken out of its AST and executed
+unchanged:
+  * `TFGraphInterface`, `GraphAugmentor`, `Graph`, `Relation`, `Interaction`, `bpr_loss`, `next_batch_pairwise` (top level);
+  * SEPT's `build`, `get_social_related_views`, `encoder`, `social_encoder`, `label_prediction`, `sampling`,
+    `generate_pesudo_labels`, `neighbor_discrimination`;
+  * the statements sept_social.py:432-465 of `SEPT.train` (the four encoders, bpr_loss + reg, the tri-training block,
+    zero_grad, backward, Adam step), once per batch.
+sept_social.py:427 cannot run (`Interaction` has no `convert_to_laplacian_mat`): `aug_mat` is injected.  Steps
+0-1 run with epoch = 0 (`aug_mat = norm_adj`, the plain branch), steps 2-7 with epoch = 3 > maxEpoch // 3 (maxEpoch = 6) and
+`aug_mat` = the raw bipartite operator [[0, D], [D^T, 0]] of ONE seeded `GraphAugmentor.edge_dropout(interaction_mat, 0.3)`.
+One Adam across the eight steps.
+
+Per configuration, from the same float32 initial tables: a float64 run (per-step terms, final tables as
+float32(final - init), the label sets sorted per row, the minimum relative gap between the k-th and (k+1)-th combined
+probability per step), a float32 run (terms, per-table slack = max |f32 - f64|), float64 runs with ss_rate = 0 and with
+reg_lambda = 0 (what a dropped term moves).  The batch-sampler seed is scanned per configuration from 0 upward and the first
+one whose minimum gap is >= 1e-5 is kept and recorded.
+
+The seed of the initial tables is scanned too, from 3 + c upward, for the first at which no element of the float64 run's
+FIRST-step gradient is smaller than 10 x Adam's eps (1e-7).  Adam's first update is lr g / (|g| + eps): at |g| ~ eps it moves
+by lr eps / (|g| + eps)^2 = 3.5e4 per unit of gradient error, so ONE element with |g| = 7e-9 (seed 3 of the first
+configuration) turned 1.8e-11 of float32 rounding in the reference's own gradient into its whole slack on the user table,
+6.2e-7, where the same run at a seed without such an element has 4e-8 (measured on the reference alone; later steps divide
+by a sqrt(v) that carries the history and show nothing of the kind).  The HIP path's gradient error at that element, 9.7e-11,
+is below the median error of its whole user gradient (1.3e-10) and still moved the element by 3.3e-6.  A slack that is one draw of that lottery is no
+yardstick for another float32 implementation, in either direction; with the element excluded it measures the precision of a
+step, and the tolerance that follows from it is the tighter one.
+Asserted when the file is written: f32 and f64 terms within 1e-5 relative; the f32 run selects the f64 run's label sets; the
+gap and the first-step gradient condition; each table moves by more than 50 x max(4 x slack, 1e-7) when either term is dropped.
+
+Usage:  python scripts/gen_golden_sept_steps.py [--out DIR]
+"""
+import copy
+import math
+import os
+import random
+import sys
+from collections import defaultdict
+
+import numpy as np
+import scipy.sparse as sp
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, ".."))
+sys.path.insert(0, HERE)
+from oracle.gen_golden import REF, _lift_class_methods, load_stmts  # noqa: E402
+import gen_golden_mhcn_steps as mh  # noqa: E402
+
+OUT = os.path.join(HERE, "..", "tests", "golden")
+PATH = os.path.join(REF, "univariate", "sept_social.py")
+
+BATCH, STEPS, PLAIN_STEPS, MAX_EPOCH, TRI_EPOCH, DROP_SEED, MIN_GAP = 128, 8, 2, 6, 3, 11, 1e-5
+MIN_FIRST_GRAD = 1e-7       # 10 x Adam's eps
+BASE = {"lr": 1e-3, "reg_lambda": 1e-4, "ss_rate": 0.005, "drop_rate": 0.3}
+CONFIGS = [dict(n_layer=2, d=64, ins_cnt=10), dict(n_layer=3, d=32, ins_cnt=5)]
+TERMS = ("rec_loss", "neighbor_dis_loss", "total_loss")
+TABLES = ("user_embeddings", "item_embeddings")
+METHODS = {"build", "get_social_related_views", "encoder", "social_encoder", "label_prediction", "sampling",
+           "generate_pesudo_labels", "neighbor_discrimination"}
+
+
+class Reference:
+    def __init__(self):
+        self.cls, self.ns = _lift_class_methods(
+            PATH, "SEPT", METHODS, extra_ns={"defaultdict": defaultdict, "math": math, "random": random, "eye": sp.eye},
+            top_level=("TFGraphInterface", "GraphAugmentor", "Graph", "Relation", "Interaction", "bpr_loss",
+                       "next_batch_pairwise"))
+        self.body = load_stmts(PATH, "SEPT.train", 432, 465)
+
+    def model(self, train, social, cfg, hp, dtype, seed):
+        m = self.cls()
+        m.data = self.ns["Interaction"]({}, train, train[:10])
+        m.social_data = self.ns["Relation"]({}, copy.deepcopy(social), m.data.user)      # __initialize deletes in place
+        m.n_layers, m.emb_size, m.instance_cnt = cfg["n_layer"], cfg["d"], cfg["ins_cnt"]
+        m.ss_rate, m.reg, m.drop_rate, m.lRate = hp["ss_rate"], hp["reg_lambda"], hp["drop_rate"], hp["lr"]
+        m.batch_size, m.maxEpoch, m.device = BATCH, MAX_EPOCH, torch.device("cpu")
+        torch.manual_seed(seed)
+        m.user_embeddings = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(m.data.user_num, m.emb_size)))
+        m.item_embeddings = torch.nn.Parameter(torch.nn.init.xavier_uniform_(torch.empty(m.data.item_num, m.emb_size)))
+        m.build()
+        if dtype == torch.float64:
+            m.user_embeddings = torch.nn.Parameter(m.user_embeddings.detach().double())
+            m.item_embeddings = torch.nn.Parameter(m.item_embeddings.detach().double())
+            for k in ("social_mat", "sharing_mat", "norm_adj"):
+                setattr(m, k, getattr(m, k).double())
+        m.opt = torch.optim.Adam([m.user_embeddings, m.item_embeddings], lr=m.lRate)
+        return m
+
+    def aug_mat(self, m, dropped, dtype):
+        """[[0, D], [D^T, 0]]: the un-normalised bipartite operator of the dropped interaction matrix."""
+        full = sp.bmat([[None, dropped], [dropped.T, None]], format="csr")
+        return self.ns["TFGraphInterface"].convert_sparse_mat_to_tensor(full).to(dtype)
+
+    def run(self, train, social, cfg, hp, dtype, seed, batches, dropped):
+        """The reference's loop body over the batches -> (terms [steps, 3], final tables in float64, label sets per
+        tri-training step [3, M, k] sorted per row, minimum relative gap per tri-training step, the smallest |gradient| of
+        the first step over both tables)."""
+        m = self.model(train, social, cfg, hp, dtype, seed)
+        aug = self.aug_mat(m, dropped, dtype)
+        terms, labels, gaps = [], [], []
+        for n, batch in enumerate(batches):
+            tri = n >= PLAIN_STEPS
+            env = dict(self.ns, self=m, batch=batch, epoch=TRI_EPOCH if tri else 0, aug_mat=aug if tri else m.norm_adj)
+            exec(self.body, env)
+            if n == 0:
+                first_grad = min(float(getattr(m, k).grad.abs().min()) for k in TABLES)
+            terms.append([float(env["rec_loss"]), float(env["neighbor_dis_loss"]) if tri else 0.0, float(env["total_loss"])])
+            if tri:
+                labels.append(np.stack([np.sort(env[k].numpy(), axis=1) for k in ("f_pos", "sh_pos", "r_pos")]))
+                pf, ps, pr = (env[k].detach().double() for k in ("social_prediction", "sharing_prediction", "rec_prediction"))
+                gap = np.inf
+                for v in ((ps + pr) / 2, (pf + pr) / 2, (pf + ps) / 2):
+                    top = torch.topk(v, m.instance_cnt + 1, dim=1).values
+                    gap = min(gap, float(((top[:, -2] - top[:, -1]) / top[:, -2]).min()))
+                gaps.append(gap)
+        final = {k: getattr(m, k).detach().double().numpy().copy() for k in TABLES}
+        return np.array(terms), final, labels, np.array(gaps), first_grad
+
+    def batches(self, data, seed):
+        random.seed(seed)
+        out = []
+        for u, p, q in self.ns["next_batch_pairwise"](data, BATCH):
+            if len(out) == STEPS:
+                break
+            assert len(u) == BATCH
+            out.append((u, p, q))
+        return out
+
+
+def main(out_dir):
+    ref = Reference()
+    rng = np.random.default_rng(20261018)
+    train, social = mh.synthetic_lists(rng)
+    probe = ref.model(train, social, CONFIGS[0], BASE, torch.float32, 0)
+    data = probe.data
+    assert (data.user_num, data.item_num) == (mh.N_USERS, mh.N_ITEMS)
+    kept = probe.social_data.relation
+    assert len(kept) == len(social) - 2, "the two pairs naming unknown users must be dropped"
+    assert probe.social_data.get_social_mat().max() == 2.0 and data.interaction_mat.max() == 2.0
+    np.random.seed(DROP_SEED)
+    dropped = ref.ns["GraphAugmentor"].edge_dropout(data.interaction_mat, BASE["drop_rate"])
+    kept_u, kept_i = dropped.nonzero()
+    n_pairs = len(data.interaction_mat.nonzero()[0])
+    assert len(kept_u) == int(n_pairs * (1 - BASE["drop_rate"])) and dropped.max() == 1.0
+
+    out = dict(train_user=np.array([t[0] for t in train]), train_item=np.array([t[1] for t in train]),
+               social_follower=np.array([t[0] for t in social]), social_followee=np.array([t[1] for t in social]),
+               user_ids=np.array([data.id2user[k] for k in range(mh.N_USERS)]),
+               item_ids=np.array([data.id2item[k] for k in range(mh.N_ITEMS)]),
+               S_row=np.array([data.user[p[0]] for p in kept], dtype=np.int16),
+               S_col=np.array([data.user[p[1]] for p in kept], dtype=np.int16),
+               Y_row=np.array([data.user[t[0]] for t in train], dtype=np.int16),
+               Y_col=np.array([data.item[t[1]] for t in train], dtype=np.int16),
+               kept_user=kept_u.astype(np.int16), kept_item=kept_i.astype(np.int16), drop_seed=DROP_SEED,
+               steps=STEPS, plain_steps=PLAIN_STEPS, max_epoch=MAX_EPOCH, tri_epoch=TRI_EPOCH, batch_size=BATCH,
+               configs=len(CONFIGS), min_gap=MIN_GAP, **{f"hp/{k}": v for k, v in BASE.items()})
+    for name in ("social", "sharing"):
+        t = getattr(probe, f"{name}_mat").coalesce()
+        mat = sp.csr_matrix((t.values().numpy(), tuple(t.indices().numpy())), shape=tuple(t.shape))
+        out.update(mh.csr_dict(name, mat))
+        assert (mat != mat.T).nnz > 0, f"{name}: expected a non-symmetric operator"
+
+    for c, cfg in enumerate(CONFIGS):
+        pre = f"c{c}/"
+        out.update({pre + k: v for k, v in cfg.items()})
+        for seed in range(3 + c, 3 + c + 32):         # the first table seed without a first-step gradient of Adam's eps' size
+            for bseed in range(64):                   # the first sampler seed whose label sets are all decided by >= MIN_GAP
+                batches = ref.batches(data, bseed)
+                l64, p64, lab64, gaps, first_grad = ref.run(train, social, cfg, BASE, torch.float64, seed, batches, dropped)
+                print(f"config {c}: table seed {seed}, sampler seed {bseed}: min gap per step {gaps}, smallest first-step "
+                      f"|gradient| {first_grad:.3g}")
+                if gaps.min() >= MIN_GAP:
+                    break
+            else:
+                raise AssertionError("no sampler seed below 64 satisfies the gap condition")
+            if first_grad >= MIN_FIRST_GRAD:
+                break
+        else:
+            raise AssertionError("no table seed satisfies the first-step gradient condition")
+        out[pre + "table_seed"], out[pre + "first_grad"] = seed, first_grad
+        out[pre + "batch_seed"], out[pre + "gaps"] = bseed, gaps
+        for n, (u, p, q) in enumerate(batches):
+            out[f"{pre}batch{n}_users"], out[f"{pre}batch{n}_pos"], out[f"{pre}batch{n}_neg"] = \
+                (t.numpy().astype(np.int16) for t in (u, p, q))
+        l32, p32, lab32, _, _ = ref.run(train, social, cfg, BASE, torch.float32, seed, batches, dropped)
+        same = all(np.array_equal(a, b) for a, b in zip(lab64, lab32))
+        assert same, "the float32 run selected other label sets than the float64 run"
+        out[pre + "f32_labels_equal"] = same
+        for n, lab in enumerate(lab64):
+            assert lab.shape == (3, len(np.unique(batches[PLAIN_STEPS + n][0].numpy())), cfg["ins_cnt"])
+            out[f"{pre}labels{n}"] = lab.astype(np.int16)
+        out[pre + "f64/losses"], out[pre + "f32/losses"] = l64, l32
+        assert np.isfinite(l64).all() and (np.abs(l32 - l64) <= 1e-5 * np.abs(l64)).all()
+        assert (l64[:PLAIN_STEPS, 1] == 0).all() and (l64[PLAIN_STEPS:, 1] > 0).all()
+        print(f"config {c} {cfg}: f64 terms\n{l64}\n  max rel |f32 - f64| per term "
+              f"{(np.abs(l32 - l64) / np.maximum(np.abs(l64), 1e-300)).max(0)}")
+        finals = {"ss": ref.run(train, social, cfg, dict(BASE, ss_rate=0.0), torch.float64, seed, batches, dropped)[1],
+                  "reg": ref.run(train, social, cfg, dict(BASE, reg_lambda=0.0), torch.float64, seed, batches, dropped)[1]}
+        m0 = ref.model(train, social, cfg, BASE, torch.float32, seed)
+        for k in TABLES:
+            init = getattr(m0, k).detach().numpy().copy()
+            assert init.dtype == np.float32
+            delta = (p64[k] - init.astype(np.float64)).astype(np.float32)
+            assert np.abs(delta).max() < 2e-2
+            assert np.abs(init.astype(np.float64) + delta.astype(np.float64) - p64[k]).max() < 2e-9
+            out[f"{pre}init/{k}"], out[f"{pre}f64/delta/{k}"] = init, delta
+            slack = out[f"{pre}slack/{k}"] = float(np.abs(p32[k] - p64[k]).max())
+            atol = max(4 * slack, 1e-7)
+            row = [f"{k:16s} slack {slack:.3g}"]
+            for term, final in finals.items():
+                d = out[f"{pre}delta_{term}/{k}"] = float(np.abs(final[k] - p64[k]).max())
+                row.append(f"d_{term} {d:.3g} ({d / atol:.0f}x)")
+                assert d > 50 * atol, (k, term, d, atol)
+            print("  " + "  ".join(row))
+
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "sept_steps.npz")
+    np.savez_compressed(path, **out)
+    size = os.path.getsize(path)
+    print("wrote", os.path.abspath(path), size, "bytes")
+    assert size < 1_000_000
+
+
+if __name__ == "__main__":
+    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)

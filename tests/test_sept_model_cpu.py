@@ -1,0 +1,81 @@
+"""tests/golden/sept_steps.npz (scripts/gen_golden_sept_steps.py) and the host-side rules of recommendation_amd.sept, without
+a device: the fixture's size and keys, the generator's conditions re-checked from the stored numbers, SEPTModel's config
+parsing and the epoch rule of univariate/sept_social.py:425,446."""
+import os
+
+import numpy as np
+import pytest
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sept_steps.npz")
+TABLES = ("user_embeddings", "item_embeddings")
+
+
+@pytest.fixture(scope="module")
+def g():
+    return np.load(GOLDEN)
+
+
+def test_fixture_is_small_plain_data_with_the_expected_keys(g):
+    assert os.path.getsize(GOLDEN) < 1_000_000
+    for k in g.files:
+        assert g[k].dtype.kind in "iufbU", (k, g[k].dtype)           # numbers and names only: nothing pickled
+    top = {"train_user", "train_item", "social_follower", "social_followee", "user_ids", "item_ids", "S_row", "S_col", "Y_row",
+           "Y_col", "kept_user", "kept_item", "steps", "plain_steps", "max_epoch", "tri_epoch", "batch_size", "configs", "min_gap",
+           "hp/lr", "hp/reg_lambda", "hp/ss_rate", "hp/drop_rate"}
+    top |= {f"{n}_{p}" for n in ("social", "sharing") for p in ("indptr", "indices", "data", "shape")}
+    assert top <= set(g.files)
+    assert (int(g["steps"]), int(g["plain_steps"]), int(g["configs"]), int(g["batch_size"])) == (8, 2, 2, 128)
+    assert [(int(g[f"c{c}/n_layer"]), int(g[f"c{c}/d"]), int(g[f"c{c}/ins_cnt"])) for c in (0, 1)] == [(2, 64, 10), (3, 32, 5)]
+    n_u, n_i = g["user_ids"].size, g["item_ids"].size
+    pairs = set(zip(g["Y_row"].tolist(), g["Y_col"].tolist()))
+    kept = set(zip(g["kept_user"].tolist(), g["kept_item"].tolist()))
+    assert len(kept) == g["kept_user"].size == int(len(pairs) * (1 - float(g["hp/drop_rate"]))) and kept < pairs
+    for c in (0, 1):
+        d = int(g[f"c{c}/d"])
+        assert g[f"c{c}/init/user_embeddings"].shape == (n_u, d) and g[f"c{c}/init/item_embeddings"].shape == (n_i, d)
+        assert g[f"c{c}/f64/losses"].shape == g[f"c{c}/f32/losses"].shape == (8, 3) and g[f"c{c}/gaps"].shape == (6,)
+        for n in range(8):
+            for s in ("users", "pos", "neg"):
+                assert g[f"c{c}/batch{n}_{s}"].shape == (128,)
+        for n in range(6):
+            m = np.unique(g[f"c{c}/batch{n + 2}_users"]).size
+            lab = g[f"c{c}/labels{n}"]
+            assert lab.shape == (3, m, int(g[f"c{c}/ins_cnt"])) and lab.min() >= 0 and lab.max() < m
+            assert (np.diff(lab.astype(np.int64), axis=2) > 0).all()       # sorted per row, no column twice
+
+
+def test_the_generators_conditions_hold_in_the_stored_numbers(g):
+    assert float(g["min_gap"]) == 1e-5
+    assert int(g["tri_epoch"]) > int(g["max_epoch"]) // 3 >= 1
+    for c in (0, 1):
+        l64, l32 = g[f"c{c}/f64/losses"], g[f"c{c}/f32/losses"]
+        assert np.isfinite(l64).all() and (np.abs(l32 - l64) <= 1e-5 * np.abs(l64)).all()
+        assert (l64[:2, 1] == 0).all() and (l64[2:, 1] > 0).all()            # two plain steps, six tri-training steps
+        ss = float(g["hp/ss_rate"])
+        assert np.allclose(l64[:, 2], l64[:, 0] + ss * l64[:, 1], rtol=1e-12)
+        assert float(g[f"c{c}/gaps"].min()) >= 1e-5 and int(g[f"c{c}/batch_seed"]) >= 0
+        assert bool(g[f"c{c}/f32_labels_equal"])
+        # no first-step gradient of the size of Adam's eps: the slack measures a step's precision, not one element's lottery
+        assert float(g[f"c{c}/first_grad"]) >= 1e-7 and int(g[f"c{c}/table_seed"]) >= 3 + c
+        for k in TABLES:
+            atol = max(4 * float(g[f"c{c}/slack/{k}"]), 1e-7)
+            for term in ("ss", "reg"):
+                assert float(g[f"c{c}/delta_{term}/{k}"]) > 50 * atol, (c, k, term)
+            assert np.abs(g[f"c{c}/f64/delta/{k}"]).max() > 1e-3
+
+
+def test_config_parsing_and_the_epoch_rule():
+    from recommendation_amd.sept import is_tri_training_epoch, parse_config
+    conf = {"max.epoch": "7", "SEPT": {"n_layer": "2", "ss_rate": "0.005", "drop_rate": "0.3", "ins_cnt": "10"}}
+    p = parse_config(conf)
+    assert (p.n_layers, p.ss_rate, p.drop_rate, p.instance_cnt) == (2, 0.005, 0.3, 10)
+    assert (p.emb_size, p.batch_size, p.lRate, p.reg, p.maxEpoch, p.topN) == (64, 2048, 0.001, 0.0001, 7, [10, 20, 30, 50])
+    p = parse_config(dict(conf, emb_size=32, batch_size=128, lr=0.01, reg_lambda=0.1, **{"item.ranking.topN": ["5", 40]}))
+    assert (p.emb_size, p.batch_size, p.lRate, p.reg, p.topN) == (32, 128, 0.01, 0.1, [5, 40])
+    with pytest.raises(KeyError):
+        parse_config({"max.epoch": 3})
+    # epoch > maxEpoch // 3 (sept_social.py:425): the tuner's max.epoch = 1 never reaches the branch
+    assert [e for e in range(6) if is_tri_training_epoch(e, 6)] == [3, 4, 5]
+    assert [e for e in range(7) if is_tri_training_epoch(e, 7)] == [3, 4, 5, 6]
+    assert [e for e in range(2) if is_tri_training_epoch(e, 2)] == [1]
+    assert not is_tri_training_epoch(0, 1)
