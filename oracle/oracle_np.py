@@ -125,18 +125,20 @@ def norm_adj_csr(uid, iid, num_users, num_items):
     return rowptr, c, sym_norm_values(rowptr, c, v)
 
 
-def gcn_norm_weights(edge_index, num_nodes):
+def gcn_norm_weights(edge_index, num_nodes, dtype=np.float32):
     """lightgcn.py:17,25 -> torch_geometric LGConv -> gcn_norm(add_self_loops=False)
     (documented semantics; PARITY UNPINNED, see module docstring): deg[v] = number of
     edges whose target is v (duplicates counted); w_e = deg^-1/2[src] * deg^-1/2[dst], inf -> 0;
-    out[dst] += w_e * x[src]."""
+    out[dst] += w_e * x[src].  In `dtype`: float32 as the reference's float32 model computes them, float64 for
+    its float64 run (tests/golden/lightgcn_steps.npz)."""
+    dtype = np.dtype(dtype).type
     src, dst = np.asarray(edge_index[0]), np.asarray(edge_index[1])
-    deg = np.zeros(num_nodes, dtype=np.float32)
-    np.add.at(deg, dst, np.float32(1.0))
+    deg = np.zeros(num_nodes, dtype=dtype)
+    np.add.at(deg, dst, dtype(1.0))
     with np.errstate(divide="ignore"):
-        dis = np.power(deg, np.float32(-0.5), dtype=np.float32)
+        dis = np.power(deg, dtype(-0.5), dtype=dtype)
     dis[np.isinf(dis)] = 0.0
-    return (dis[src] * dis[dst]).astype(np.float32)
+    return (dis[src] * dis[dst]).astype(dtype)
 
 
 def coo_sums_f64(index, val, n):
@@ -225,14 +227,16 @@ def lgcn_encoder_forward(rowptr, col, val, x0, n_layers, combine="mean", layer_n
     return acc, all_emb
 
 
-def lightgcn_forward(edge_index, user_w, item_w, n_layers):
+def lightgcn_forward(edge_index, user_w, item_w, n_layers, weight_dtype=np.float32):
     """lightgcn.py:21-27: x = cat(U, I); out = x; for conv: out = LGConv(out); x += out.
-    Returns (x[:U], x[U:]) = sum over layers 0..K (no division, Q3)."""
+    Returns (x[:U], x[U:]) = sum over layers 0..K (no division, Q3).  The sums are float64; the edge weights are
+    computed in `weight_dtype` (`gcn_norm_weights`)."""
     x0 = np.concatenate([user_w, item_w]).astype(F64)
     n = x0.shape[0]
-    w = gcn_norm_weights(edge_index, n)
+    w = gcn_norm_weights(edge_index, n, weight_dtype)
     # out[dst] += w * x[src]  <=> CSR over rows = dst, cols = src
-    rowptr, col, val, _ = coo_to_csr_stable(edge_index[1], edge_index[0], w, n)
+    rowptr, col, _, order = coo_to_csr_stable(edge_index[1], edge_index[0], w, n)
+    val = w[order]
     acc, _ = lgcn_encoder_forward(rowptr, col, val, x0, n_layers, combine="sum")
     return acc[: user_w.shape[0]], acc[user_w.shape[0]:]
 
