@@ -818,8 +818,9 @@ int32_t gcr_directau_bwd_f32(const float* user_tab, const float* item_tab, int32
  *   pos_r = top-k (P_f + P_s), descending, ties to the smaller column (gcr_topk_masked_f32's rule);
  *   loss[v] = -sum_i ( log sum_{j in pos_v[i]} exp(S_v[i, j] inv_t) - log sum_j exp(S_v[i, j] inv_t) ).
  * Outputs: loss [3]; positive int64 [3, m, k] (replay != 0: READ instead of selected — rows of distinct columns in
- * [0, m)); rsum [2, 3, m] = 1 / sum_j e and 1 / sum_{pos} e with e = exp((S - 1) inv_t) (reciprocals, not log-sums: f32
- * keeps their relative precision); inv_norm [4, m]; member: gcr_tri_member_words(m)
+ * [0, m)); rsum [2, 3, m] = 1 / sum_j e and 1 / sum_j e - 1 / sum_{pos} e with e = exp((S - 1) inv_t) (reciprocals, not
+ * log-sums: f32 keeps their relative precision; the difference, which nearly cancels when m - k is small, is formed from
+ * double sums and rounded once); inv_norm [4, m]; member: gcr_tri_member_words(m)
  * 32-bit words, bit j of row (v, i) = j in pos_v[i] (zeroed by the call).  The M x M matrices are never written; scores
  * come from the f32-input MFMA and are f32-accurate.  Six launches (replay: five).
  * Backward, for upstream g [3] on the device: w_v[i, j] = g_v inv_t (softmax_j(S_v inv_t) - [j in pos_v[i]] softmax over

@@ -12,14 +12,18 @@
 //             sweep 0: row sums of exp(S_v).  sweep 1: P_v = exp(S_v) / Z_v goes through the LDS so that wave v reads the
 //             two OTHER views' tiles, c_v = P_a + P_b, and keeps a sorted k-candidate list per lane in the LDS (a later
 //             candidate of a lane always has the larger column, so `>` alone gives ties to the smaller column); the same
-//             sweep sums exp((S_v - 1) / t).  |S| <= 1: no running maximum anywhere.
+//             sweep sums exp((S_v - 1) / t), in double: the backward subtracts the reciprocals of this sum and of the sum
+//             over the positives, two numbers that agree to 1 / (M - k) when nearly every column is a positive.
+//             |S| <= 1: no running maximum anywhere.
 //   finish    one wave per (view, row): merges the 2 x splits candidate lists by rank (value descending, then column
 //             ascending: gcr_topk_masked_f32's rule), writes `positive`, sets the row's membership bits, recomputes the k
-//             positive scores on the MFMA in the sweep's operand order (bitwise the sweep's S) and writes the two sums' reciprocals.
+//             positive scores on the MFMA in the sweep's operand order (bitwise the sweep's S), sums their exponentials in
+//             double like the sweep, and writes 1 / sum_j e and 1 / sum_j e - 1 / sum_{pos} e, the cancelling difference of
+//             the two sums formed in double.
 //   reduce    the three losses from the per-row terms, summed in double in a fixed order.
 //
 // Backward: prepare again, then two sweeps that recompute the score tiles, form
-//   w_v[i, j] = (g_v / t) exp((S - 1) / t) (1 / sum_j e - [j in pos_v[i]] / sum_{pos} e)
+//   w_v[i, j] = (g_v / t) exp((S - 1) / t) (1 / sum_j e - [j in pos_v[i]] / sum_{pos} e)      (the forward's two numbers)
 // (membership read from the forward's bitmap: no scatter) and feed w straight back into the MFMA as the B operand of
 // w^T a (rows) or w e_v (columns) — the accumulator layout of the first product IS the B layout of the second, as in
 // gcr_directau.hip.  Per-split partials are added in split (and view) order by the last kernel, which applies the
@@ -96,14 +100,24 @@ __device__ __forceinline__ void load_half_row(const float* __restrict__ tab, int
   }
 }
 
-// MODE 0: part_z[split, v, i] = sum_j exp(S_v[i, j]) over the split's columns
-// MODE 1: the same sums of exp((S_v - 1) inv_t)                                         (replay: no selection)
+// MODE 0: part_z[split, v, i] = sum_j exp(S_v[i, j]) over the split's columns (float: a softmax denominator)
+// MODE 1: the same sums of exp((S_v - 1) inv_t), float terms added in double (double)    (replay: no selection)
 // MODE 2: MODE 1 + the candidate lists, from z1 = the MODE 0 partials
+template <int MODE>
+struct TriSum {                      // the type of a MODE's partial sums
+  typedef double type;
+};
+template <>
+struct TriSum<0> {
+  typedef float type;
+};
+
 template <int D, int MODE>
 __global__ __launch_bounds__(192) void tri_sweep_kernel(const float* __restrict__ xhat, int64_t m, int n_tiles, int n_splits,
                                                         int k, float inv_t, const float* __restrict__ z1,
-                                                        float* __restrict__ part_z, float* __restrict__ cand_val,
-                                                        int* __restrict__ cand_col) {
+                                                        typename TriSum<MODE>::type* __restrict__ part_z,
+                                                        float* __restrict__ cand_val, int* __restrict__ cand_col) {
+  typedef typename TriSum<MODE>::type sum_t;
   extern __shared__ float tri_lds[];
   float* ptile = tri_lds;                                        // [3][16][64]
   float* lval = tri_lds + kViews * 16 * 64;                      // [3][k][64]
@@ -131,7 +145,7 @@ __global__ __launch_bounds__(192) void tri_sweep_kernel(const float* __restrict_
       my_col[q * 64] = kNoCol;
     }
   }
-  float run = 0.f;
+  sum_t run = 0;
   for (int jt = split; jt < n_tiles; jt += n_splits) {
     const int64_t b0 = (int64_t)jt * kTile;
     float xc[D / 2];
@@ -142,14 +156,14 @@ __global__ __launch_bounds__(192) void tri_sweep_kernel(const float* __restrict_
 #pragma unroll
     for (int q = 0; q < D / 2; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[q], xr[q], acc, 0, 0, 0);
     // acc[r] = S_v[i][b0 + acc_row(r, h)]
-    float part = 0.f;
+    sum_t part = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const bool live = row_ok && b0 + acc_row(r, h) < m;
       if (MODE == 0) {
         part += live ? expf(acc[r]) : 0.f;
       } else {
-        part += live ? expf((acc[r] - 1.0f) * inv_t) : 0.f;
+        part += (sum_t)(live ? expf((acc[r] - 1.0f) * inv_t) : 0.f);
         if (MODE == 2) ptile[(v * 16 + r) * 64 + lane] = live ? expf(acc[r]) * inv_z : 0.f;
       }
     }
@@ -192,12 +206,15 @@ __global__ __launch_bounds__(192) void tri_sweep_kernel(const float* __restrict_
   }
 }
 
-// one wave per (view, row).  rsum [2, 3, m] = 1 / (sum_j e, sum_{pos} e) with e = exp((S - 1) / t); row_loss [3, m].
-// The reciprocals keep f32's RELATIVE precision; a log-sum of size ~1/t stored in f32 carries an absolute error of
-// ulp(1/t) ~ 1e-6 into every softmax the backward rebuilds from it
+// one wave per (view, row).  rsum [2, 3, m] = (1 / sum_j e, 1 / sum_j e - 1 / sum_{pos} e) with e = exp((S - 1) / t);
+// row_loss [3, m].  The reciprocals keep f32's RELATIVE precision; a log-sum of size ~1/t stored in f32 carries an absolute
+// error of ulp(1/t) ~ 1e-6 into every softmax the backward rebuilds from it.  The second number is what a positive's weight
+// multiplies: with M - k columns outside the label set the two reciprocals agree to 1 / (M - k), and one ulp of either
+// (of a float sum, of a reciprocal rounded to float) is M - k ulps of their difference.  Both sums add the same float terms
+// in double and the difference is (sum_{pos} e - sum_j e) / sum_j e / sum_{pos} e, the numerator formed in double.
 template <int D>
 __global__ __launch_bounds__(256) void tri_finish_kernel(const float* __restrict__ xhat, int64_t m, int n_tiles, int n_splits,
-                                                         int k, float inv_t, int replay, const float* __restrict__ part_zt,
+                                                         int k, float inv_t, int replay, const double* __restrict__ part_zt,
                                                          const float* __restrict__ cand_val, const int* __restrict__ cand_col,
                                                          int64_t* __restrict__ positive, float* __restrict__ rsum,
                                                          float* __restrict__ row_loss, uint32_t* __restrict__ member) {
@@ -263,15 +280,18 @@ __global__ __launch_bounds__(256) void tri_finish_kernel(const float* __restrict
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float ps = 0.f;
+    double ps = 0.0;
     for (int q = 0; q < k; ++q)
-      if (sel[wave][q] >= 0) ps += expf((sc[wave][q] - 1.0f) * inv_t);
-    float zt = 0.f;
+      if (sel[wave][q] >= 0) ps += (double)expf((sc[wave][q] - 1.0f) * inv_t);
+    double zt = 0.0;
     for (int s = 0; s < n_splits; ++s) zt += part_zt[((int64_t)s * kViews + v) * m + i];
     if (lane == 0) {
-      rsum[(int64_t)v * m + i] = 1.0f / zt;
-      rsum[((int64_t)kViews + v) * m + i] = 1.0f / ps;
-      row_loss[(int64_t)v * m + i] = -logf(ps / zt);                 // :419 forms the ratio first, too
+      const float zf = (float)zt, pf = (float)ps;
+      rsum[(int64_t)v * m + i] = 1.0f / zf;
+      // 1 / zt - 1 / ps, the cancellation in double.  Two quotients, not one by zf * pf: e >= exp(-2 kMaxInvT) = 1.8e-35 keeps
+      // either sum a normal float, their product it does not; the first quotient lies in [-1, 0], the second within 1 / pf
+      rsum[((int64_t)kViews + v) * m + i] = (float)(ps - zt) / zf / pf;
+      row_loss[(int64_t)v * m + i] = -logf(pf / zf);                 // :419 forms the ratio first, too
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -302,13 +322,13 @@ __global__ __launch_bounds__(192) void tri_bwd_sweep_kernel(const float* __restr
   const float* F = xhat + (int64_t)(COLSIDE ? 3 : v) * m * D;
   const float* S = xhat + (int64_t)(COLSIDE ? v : 3) * m * D;
   const float* iz_v = rsum + (int64_t)v * m;
-  const float* ip_v = rsum + ((int64_t)kViews + v) * m;
+  const float* id_v = rsum + ((int64_t)kViews + v) * m;          // 1 / sum_j e - 1 / sum_{pos} e
   const uint32_t* mem_v = member + (int64_t)v * m * n_tiles;
   float xr[D / 2];
   load_half_row<D>(F, f, f_ok, h, xr);
   const float gt = g[v] * inv_t;
   const float iz_f = (!COLSIDE && f_ok) ? iz_v[f] : 0.f;
-  const float ip_f = (!COLSIDE && f_ok) ? ip_v[f] : 0.f;
+  const float id_f = (!COLSIDE && f_ok) ? id_v[f] : 0.f;
   f32x16 oacc[D / 32];
 #pragma unroll
   for (int ch = 0; ch < D / 32; ++ch)
@@ -336,14 +356,14 @@ __global__ __launch_bounds__(192) void tri_bwd_sweep_kernel(const float* __restr
       const int ar = acc_row(r, h);
       const int64_t sw = s0 + ar;
       const bool live = f_ok && sw < m;
-      float iz = iz_f, ip = ip_f;
+      float iz = iz_f, id = id_f;
       bool bit = (word_f >> ar) & 1u;
       if (COLSIDE) {
         iz = live ? iz_v[sw] : 0.f;
-        ip = live ? ip_v[sw] : 0.f;
+        id = live ? id_v[sw] : 0.f;
         bit = live ? ((mem_v[sw * n_tiles + blockIdx.x] >> l32) & 1u) : false;
       }
-      const float w = gt * expf((acc[r] - 1.0f) * inv_t) * (iz - (bit ? ip : 0.f));
+      const float w = gt * expf((acc[r] - 1.0f) * inv_t) * (bit ? id : iz);
       acc[r] = live ? w : 0.f;
     }
 #pragma unroll
@@ -425,7 +445,7 @@ TriWorkspace tri_layout(int64_t m, int d, int k) {
   w.inv_norm = w.xhat + align64f(4 * m * d);
   w.z1 = w.inv_norm + align64f(4 * m);
   w.zt = w.z1 + align64f((int64_t)ns * kViews * m);
-  w.row_loss = w.zt + align64f((int64_t)ns * kViews * m);
+  w.row_loss = w.zt + align64f(2 * (int64_t)ns * kViews * m);                                // doubles
   w.cand_val = w.row_loss + align64f(kViews * m);
   w.cand_col = w.cand_val + align64f((int64_t)kViews * m * 2 * ns * k);
   w.part_e = w.cand_col + align64f((int64_t)kViews * m * 2 * ns * k);
@@ -490,20 +510,21 @@ extern "C" int32_t gcr_tri_fwd_f32(const float* x_f, const float* x_s, const flo
   const dim3 grid((unsigned)n_tiles, (unsigned)ns);
   const size_t lds_sel = (size_t)(kViews * 16 * 64 + 2 * kViews * k * 64) * sizeof(float);
   int* cand_col = reinterpret_cast<int*>(ws + w.cand_col);
+  double* zt = reinterpret_cast<double*>(ws + w.zt);             // every offset is a multiple of 64 words
 #define GCR_TRI_FWD(D)                                                                                                     \
   hipLaunchKernelGGL((tri_prepare_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, T, uniq, m, n_rows, ws + w.xhat,   \
                      inv_norm);                                                                                            \
   if (replay) {                                                                                                            \
     hipLaunchKernelGGL((tri_sweep_kernel<D, 1>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,        \
-                       (const float*)nullptr, ws + w.zt, (float*)nullptr, (int*)nullptr);                                  \
+                       (const float*)nullptr, zt, (float*)nullptr, (int*)nullptr);                                         \
   } else {                                                                                                                 \
     hipLaunchKernelGGL((tri_sweep_kernel<D, 0>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,        \
                        (const float*)nullptr, ws + w.z1, (float*)nullptr, (int*)nullptr);                                  \
     hipLaunchKernelGGL((tri_sweep_kernel<D, 2>), grid, dim3(192), lds_sel, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,  \
-                       ws + w.z1, ws + w.zt, ws + w.cand_val, cand_col);                                                   \
+                       ws + w.z1, zt, ws + w.cand_val, cand_col);                                                          \
   }                                                                                                                        \
   hipLaunchKernelGGL((tri_finish_kernel<D>), dim3(row_blocks(kViews * m)), dim3(256), 0, s, ws + w.xhat, m, n_tiles, ns,   \
-                     (int)k, inv_t, (int)replay, ws + w.zt, ws + w.cand_val, cand_col, positive, rsum, ws + w.row_loss,     \
+                     (int)k, inv_t, (int)replay, zt, ws + w.cand_val, cand_col, positive, rsum, ws + w.row_loss,           \
                      member)
   GCR_TRI_BY_D(GCR_TRI_FWD);
 #undef GCR_TRI_FWD

@@ -1618,8 +1618,8 @@ def gather_dropout_views(table, idx, p, seed, n_views=2, keep_bits=None):
 # SEPT's tri-training block (univariate/sept_social.py:394-420, 447-457)
 # ---------------------------------------------------------------------------------------------
 class _TriTraining(torch.autograd.Function):
-    """gcr_tri_fwd_f32 / gcr_tri_bwd_f32: saves the four tables, uniq, the [2, 3, M] reciprocal sums and the membership bitmap
-    (3 M^2 bits), never an M x M matrix."""
+    """gcr_tri_fwd_f32 / gcr_tri_bwd_f32: saves the four tables, uniq, the [2, 3, M] reciprocal sums (1 / all and
+    1 / all - 1 / positives) and the membership bitmap (3 M^2 bits), never an M x M matrix."""
 
     @staticmethod
     def forward(ctx, x_f, x_s, x_r, aug, uniq, k, inv_t, positives):

@@ -8,7 +8,12 @@ Bound rule (tests/f64_pins.py) with the torch fp32 composition on the GPU as the
 (the loss is a sum of positive terms, so S = the loss itself).  Where the composition is not finite (its
 log(sigmoid(x)) is -inf at x = -100) it sets no drift and the floor 2^-20 holds alone.  Where a float64 gradient cancels
 to nothing (n = 2 with identity permutations: neg1 = neg2 = pos, d_em = -edge / 2 + edge / 2), max|f64| is no normaliser
-and S is the magnitude of the un-cancelled terms instead: sum_k |dL / d score_k| |d score_k / d x| over the five scores."""
+and S is the magnitude of the un-cancelled terms instead: sum_k |dL / d score_k| |d score_k / d x| over the five scores.
+
+Measured on an MI355X, worst err / bound (every bound is the floor 2^-20 there) of the 28 cases of ROWS x WIDTHS: loss 0.48
+(n = 1, d = 256: 4.6e-7), d_em 0.16, d_edge 0.17; of the 6 cases of FOLD_CASES (18 to 1024 workgroups: the folds' second
+batch of loads, every chain count, both grid caps): loss 0.045 (n = 33025, d = 32: 4.3e-8), d_em 0.16 (n = 4353, d = 256:
+1.5e-7), d_edge 0.19 (n = 131080, d = 256: 1.8e-7)."""
 import math
 
 import numpy as np
@@ -94,6 +99,33 @@ def test_mim_loss_and_gradients_match_the_float64_restatement(n, d):
         got = kernel(em, edge, perms, up)
         for name, g, r, c, mag in zip(("loss", "d_em", "d_edge"), got, ref, comp, ref[4]):
             check(f"n={n} d={d} up={up} {name}", g, r, c, mag)
+
+
+# (n, d, workgroups nb = min(1024, ceil(n / 256)), rows per workgroup = ceil(n / nb)).  ROWS stops at nb = 4; the last workgroup
+# folds the nb partials per column in 256 / d interleaved chains, 16 loads in flight at a time, and the loss over 64 lanes:
+FOLD_CASES = (
+    (4353, 256, 18, 242),       # one chain of 18: its second batch of 16 loads
+    (4353, 128, 18, 242),       # two chains of 9
+    (16641, 64, 66, 253),       # four chains of 16-17: the second batch; the loss fold loads twice in lanes 0-1
+    (33025, 32, 130, 255),      # eight chains of 16-17: the second batch; the loss fold three deep
+    (263000, 32, 1024, 257),    # the cap of 1024 workgroups: more than 256 rows each
+    (131080, 256, 513, 256),    # 16385 > 16384 workgroups wanted by mim_bwd_kernel: its second grid-stride trip
+)
+
+
+@pytest.mark.parametrize("up", (1.0, -2.5))
+@pytest.mark.parametrize("n,d,nb,per", FOLD_CASES)
+def test_mim_matches_the_float64_restatement_beyond_one_fold_batch(n, d, nb, per, up):
+    """FOLD_CASES, loss and both gradients by the bound rule; tests/test_launch_geometry_cpu.py asserts that each shape reaches
+    the nb and the rows per workgroup named there.  Left out on purpose: the 16384-workgroup cap of mim_inverse_kernel needs
+    n > 1.39 M rows; that kernel is a plain grid-stride scatter, and a float64 restatement at that n takes far longer than a
+    test may."""
+    em, edge, perms = rows(n, d, 1000 * d + n)
+    ref = restate(em, edge, perms, up)
+    comp = restate(em, edge, perms, up, torch.float32, DEV)
+    got = kernel(em, edge, perms, up)
+    for name, g, r, c, mag in zip(("loss", "d_em", "d_edge"), got, ref, comp, ref[4]):
+        check(f"n={n} d={d} up={up} {name}", g, r, c, mag)
 
 
 @pytest.mark.parametrize("d", WIDTHS)

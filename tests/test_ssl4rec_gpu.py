@@ -3,6 +3,9 @@
   * kernel forward: bit-equal to gather_rows x the unpacked gcr_edge_mask_bits draw x 1 / (1 - p), replay of recorded
     bits, distinct masks per view and seed;
   * kernel backward: float64 autograd of that composition, per-element bound from the number of addends;
+  * both again where the entry points take their other kernel (one column per lane instead of 16 bytes per lane): widths
+    that are no multiple of four, a table and a gradient that start 4 bytes past a 16-byte boundary (equal to the 16-byte
+    kernels' results: keep1 against keep4), and more batch rows than the grid cap holds waves;
   * trajectory: six train_steps per fixture config (tests/golden/ssl4rec_steps.npz: ssl4rec.py's own loop body run in
     float64 by the reference, the dropout masks recorded) — loss terms and final parameters;
   * evaluation: embeddings() and the metric definitions of ssl4rec.py:104-123 restated in numpy;
@@ -19,6 +22,8 @@ pytestmark = pytest.mark.gpu
 
 NS = (1, 127, 2048, 4096)
 PS = (0.0, 0.1, 0.3, 1.0)
+ODD_WIDTHS = (1, 3, 50, 101, 130)                 # d % 4 != 0: the one-column-per-lane kernels, forward and backward
+N_CAPPED = 32768 + 37                             # more rows than 8192 workgroups x 4 waves: the second grid-stride trip
 
 
 def _unpack(bits, n):
@@ -52,6 +57,92 @@ def _composition(table, idx, p, seed, n_views):
         keeps.append(keep)
         blocks.append(torch.where(keep, rows * scale, torch.zeros_like(rows)))
     return torch.cat(blocks), keeps
+
+
+def _composition_indexed(table, idx, p, seed, n_views):
+    """`_composition` with the clean rows from plain torch indexing instead of gather_rows (whose own choice of kernel by
+    width and alignment must not decide what the reference is); the keep masks are the same independent statement of
+    "bit i * d + c of the flat stream of seed + v"."""
+    from recommendation_amd import functional as Fn
+    n, d = idx.numel(), table.shape[1]
+    ok = ((idx >= 0) & (idx < table.shape[0])).unsqueeze(1)
+    rows = torch.where(ok, table[idx.clamp(0, table.shape[0] - 1)], torch.zeros((), device=table.device))
+    blocks = [rows]
+    scale = torch.tensor(_scale(p) if p < 1 else np.float32(np.inf), device="cuda")
+    for v in range(n_views):
+        keep = _unpack(Fn.edge_mask_bits(n * d, p, seed + v, "cuda"), n * d).view(n, d)
+        blocks.append(torch.where(keep, rows * scale, torch.zeros_like(rows)))
+    return torch.cat(blocks)
+
+
+def _misaligned(shape, rng):
+    """A contiguous float32 tensor of this shape, 4 bytes past a 16-byte boundary, and an aligned copy of it."""
+    numel = int(np.prod(shape))
+    buf = torch.from_numpy(rng.standard_normal(numel + 8).astype(np.float32)).cuda()
+    t = buf[1:1 + numel].view(*shape)
+    assert t.data_ptr() % 16 == 4 and t.is_contiguous()                # otherwise the vec4 kernel runs and nothing is tested
+    aligned = t.clone()
+    assert aligned.data_ptr() % 16 == 0
+    return t, aligned
+
+
+@pytest.mark.parametrize("d", ODD_WIDTHS)
+def test_gather_dropout_forward_at_widths_that_are_no_multiple_of_four(d):
+    """gather_dropout_kernel (one column per lane, keep1): bit-equal to the composition over indexed rows, replay of the
+    recorded bits included, zero rows for ids outside the table in every block."""
+    from recommendation_amd import functional as Fn
+    rng = np.random.default_rng(1000 + d)
+    n_rows = 300
+    table = torch.from_numpy(rng.standard_normal((n_rows, d)).astype(np.float32)).cuda()
+    for n in NS:
+        idx = _ids(rng, n, n_rows)
+        assert torch.equal(_composition_indexed(table, idx, 0.0, 0, 1)[:n], Fn.gather_rows(table, idx))
+        for p in PS:
+            seed = 1000 * n + int(100 * p) + 7
+            got = Fn.gather_dropout_views(table, idx, p, seed, 2)
+            assert got.shape == (3 * n, d)
+            assert torch.equal(got, _composition_indexed(table, idx, p, seed, 2)), (d, n, p)
+            if n >= 4:
+                bad = torch.tensor([0, n // 2, n - 1], device="cuda")
+                assert not got.view(3, n, d)[:, bad].any()
+            if 0 < p < 1:
+                bits = torch.stack([Fn.edge_mask_bits(n * d, p, seed + v, "cuda") for v in range(2)])
+                assert torch.equal(Fn.gather_dropout_views(table, idx, p, seed + 12345, 2, keep_bits=bits), got)
+    if d == 50:
+        idx = _ids(rng, 127, n_rows)
+        for n_views in (1, 3, 4):
+            got = Fn.gather_dropout_views(table, idx, 0.3, 5, n_views)
+            assert torch.equal(got, _composition_indexed(table, idx, 0.3, 5, n_views)), n_views
+
+
+def test_gather_dropout_forward_from_a_misaligned_table():
+    """d = 64 from a table that starts 4 bytes past a 16-byte boundary takes the one-column-per-lane kernel; its aligned copy
+    takes the vec4 kernel.  Equal outputs: keep1 is component e & 3 of keep4, for drawn and for recorded bits."""
+    from recommendation_amd import functional as Fn
+    rng = np.random.default_rng(64)
+    table, aligned = _misaligned((300, 64), rng)
+    for n in (127, 2048):
+        idx = _ids(rng, n, 300)
+        got = Fn.gather_dropout_views(table, idx, 0.3, 11, 2)
+        assert torch.equal(got, Fn.gather_dropout_views(aligned, idx, 0.3, 11, 2))
+        assert torch.equal(got, _composition_indexed(aligned, idx, 0.3, 11, 2))
+        bits = torch.stack([Fn.edge_mask_bits(n * 64, 0.3, 500 + v, "cuda") for v in range(2)])
+        rec = Fn.gather_dropout_views(table, idx, 0.3, 0, 2, keep_bits=bits)
+        assert torch.equal(rec, Fn.gather_dropout_views(aligned, idx, 0.3, 0, 2, keep_bits=bits))
+        assert torch.equal(rec, _composition_indexed(aligned, idx, 0.3, 500, 2)) and not torch.equal(rec, got)
+
+
+@pytest.mark.parametrize("d", [32, 50])
+def test_gather_dropout_beyond_the_grid_cap(d):
+    """N_CAPPED rows over a 300-row table: the waves of both forward and both backward kernels (d = 32: vec4, d = 50: one
+    column per lane) take a second trip, and a table row collects about a hundred duplicates."""
+    from recommendation_amd import functional as Fn
+    rng = np.random.default_rng(d)
+    table = torch.from_numpy(rng.standard_normal((300, d)).astype(np.float32)).cuda()
+    idx = _ids(rng, N_CAPPED, 300)
+    got = Fn.gather_dropout_views(table, idx, 0.3, 21, 2)
+    assert torch.equal(got, _composition_indexed(table, idx, 0.3, 21, 2))
+    _check_backward(d, N_CAPPED, 0.3, 2)
 
 
 @pytest.mark.parametrize("d", [32, 64, 100, 1024])
@@ -109,22 +200,45 @@ def test_gather_dropout_view_counts(n_views):
                                            (100, 2048, 0.1, 3), (1024, 127, 0.3, 2), (1024, 2048, 0.1, 1), (64, 1, 0.3, 2),
                                            (64, 2048, 0.0, 2), (64, 2048, 1.0, 2), (32, 4096, 0.3, 4)])
 def test_gather_dropout_backward_against_float64_autograd(d, n, p, n_views):
-    """grad_table against float64 autograd of the composition (index gather, mask, scale, stack).  Per element the
-    kernel and the atomics add m = duplicates x (1 + V) float32 terms: the error is at most (m - 1) roundings of 2^-24
-    relative to a partial sum, each partial sum at most sum |terms|, and forming a term (one multiply by the scale) is
-    one more rounding each — together under (m - 1) x 2^-23 x sum |terms| (m >= 2).  Replay of the bits gives the
-    same gradient to that bound as well."""
-    from recommendation_amd import functional as Fn
-    rng = np.random.default_rng(d * 7 + n)
-    n_rows = 300
-    table = torch.from_numpy(rng.standard_normal((n_rows, d)).astype(np.float32)).cuda().requires_grad_(True)
-    idx = _ids(rng, n, n_rows)
-    seed = 99
-    g_out = torch.from_numpy(rng.standard_normal(((1 + n_views) * n, d)).astype(np.float32)).cuda()
-    out = Fn.gather_dropout_views(table, idx, p, seed, n_views)
-    out.backward(g_out)
-    got = table.grad.double()
+    _check_backward(d, n, p, n_views)
 
+
+@pytest.mark.parametrize("d,n,p,n_views", [(50, 127, 0.3, 2), (50, 2048, 0.1, 3), (101, 2048, 0.3, 2), (3, 4096, 0.3, 4),
+                                           (1, 127, 0.3, 2), (50, 2048, 1.0, 2)])
+def test_gather_dropout_backward_at_widths_that_are_no_multiple_of_four(d, n, p, n_views):
+    """gather_dropout_bwd_kernel (one column per lane, keep1) by the rule of `_check_backward`."""
+    _check_backward(d, n, p, n_views)
+
+
+def test_gather_dropout_backward_from_a_misaligned_gradient():
+    """d = 64 with a grad_out that starts 4 bytes past a 16-byte boundary takes the one-column-per-lane kernel.  The entry point
+    is called directly, as tests/test_tri_gpu.py calls its own: autograd is free to hand the node a copy of the gradient."""
+    from recommendation_amd import _lib
+    rng = np.random.default_rng(640)
+    d, n, n_rows, p, seed, n_views = 64, 2048, 300, 0.3, 99, 2
+    idx = _ids(rng, n, n_rows)
+    g_mis, g_al = _misaligned(((1 + n_views) * n, d), rng)
+    table = torch.from_numpy(rng.standard_normal((n_rows, d)).astype(np.float32)).cuda()
+    ref, bound, count = _float64_gradient(table, idx, p, seed, n_views, g_al)
+    L = _lib.lib()
+    got = []
+    for g in (g_mis, g_al):
+        gt = torch.zeros(n_rows, d, device="cuda")
+        _lib.check(L.gcr_gather_dropout_bwd_f32(_lib.dptr(g), _lib.dptr(idx), n, d, n_rows, p, seed, n_views, None,
+                                                _lib.dptr(gt), _lib.cur_stream(gt.device)), "gcr_gather_dropout_bwd_f32")
+        assert bool(((gt.double() - ref).abs() <= bound).all())
+        got.append(gt.double())
+    worst = float(((got[0] - got[1]).abs() / bound.clamp(min=1e-300)).max())
+    print(f"misaligned grad_out d={d} n={n}: max |misaligned - aligned| / bound = {worst:.3f}")
+    assert bool(((got[0] - got[1]).abs() <= bound).all()), worst
+    assert bool((got[0][count.squeeze(1) == 0] == 0).all())
+
+
+def _float64_gradient(table, idx, p, seed, n_views, g_out):
+    """(grad_table of the composition by float64 autograd, the bound of `_check_backward` per table element, duplicates per
+    table row)."""
+    from recommendation_amd import functional as Fn
+    n, (n_rows, d) = idx.numel(), table.shape
     ok = ((idx >= 0) & (idx < n_rows))
     safe = idx.clamp(0, n_rows - 1)
     scale = float(_scale(p)) if p < 1 else 0.0
@@ -145,6 +259,27 @@ def test_gather_dropout_backward_against_float64_autograd(d, n, p, n_views):
     count = torch.bincount(safe[ok], minlength=n_rows).double().unsqueeze(1)
     m = count * (1 + n_views)
     bound = (m - 1).clamp(min=0) * 2.0 ** -23 * sum_abs
+    return ref, bound, count
+
+
+def _check_backward(d, n, p, n_views):
+    """grad_table against float64 autograd of the composition (index gather, mask, scale, stack).  Per element the
+    kernel and the atomics add m = duplicates x (1 + V) float32 terms: the error is at most (m - 1) roundings of 2^-24
+    relative to a partial sum, each partial sum at most sum |terms|, and forming a term (one multiply by the scale) is
+    one more rounding each — together under (m - 1) x 2^-23 x sum |terms| (m >= 2).  Replay of the bits gives the
+    same gradient to that bound as well."""
+    from recommendation_amd import functional as Fn
+    rng = np.random.default_rng(d * 7 + n)
+    n_rows = 300
+    table = torch.from_numpy(rng.standard_normal((n_rows, d)).astype(np.float32)).cuda().requires_grad_(True)
+    idx = _ids(rng, n, n_rows)
+    seed = 99
+    g_out = torch.from_numpy(rng.standard_normal(((1 + n_views) * n, d)).astype(np.float32)).cuda()
+    out = Fn.gather_dropout_views(table, idx, p, seed, n_views)
+    out.backward(g_out)
+    got = table.grad.double()
+    ref, bound, count = _float64_gradient(table, idx, p, seed, n_views, g_out)
+    m = count * (1 + n_views)
     err = (got - ref).abs()
     worst = float((err / bound.clamp(min=1e-300)).max())
     print(f"d={d} n={n} p={p} V={n_views}: max err / bound = {worst:.3f}, max m = {int(m.max())}")
