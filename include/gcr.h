@@ -840,6 +840,54 @@ int32_t gcr_tri_bwd_f32(const float* x_f, const float* x_s, const float* x_r, co
                         const int64_t* uniq, int64_t m, int32_t k, float inv_t, const float* rsum, const uint32_t* member,
                         const float* g, float* d_f, float* d_s, float* d_r, float* d_aug, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BUIR: predictor + bootstrap cosine loss, and the row-wise target update (csrc/gcr_buir.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * replaces  BUIR_NB.forward's predictor calls and the encoders' batch gathers  univariate/buir.py:260-262, 323-325,
+ *           get_loss  buir.py:269-277  (four gathers, nn.Linear twice, four F.normalize, products, sums, mean).
+ * on_user / tg_user [n_users, d], on_item / tg_item [n_items, d]: the propagated tables, row-major float32 (they may be
+ * the halves of one [N, d] array); u_idx, i_idx int64 [batch]; w [d, d] row-major as nn.Linear.weight (p = W x + bias),
+ * bias [d].  An id outside its table reads as a zero row and receives no gradient (gcr_gather_rows_f32's contract).
+ * With n(v) = v / max(|v|, 1e-12), p_u = W on_user[u_b] + bias, p_i = W on_item[i_b] + bias:
+ *   c_ui = <n(p_u), n(tg_item[i_b])>,  c_iu = <n(p_i), n(tg_user[u_b])>,  loss[0] = (1 / batch) sum_b (4 - 2 c_ui - 2 c_iu)
+ * written to the device, no host read-back.  The products run on the f32-input MFMA (exact f32 products, f32 sums).
+ * SAVED for the backward: stats [2, 3, batch] = per side (0: p_u with tg_item, 1: p_i with tg_user) the rows |p|, |t|, c.
+ * Nothing of width d is saved: the backward RECOMPUTES p (the same product, bit for bit).  Two launches.
+ * Backward, for an upstream scalar g[0] on the device:
+ *   dp_u = -(2 g / batch) (n(t_i) - c_ui n(p_u)) / max(|p_u|, 1e-12)   (|p_u| < 1e-12: torch's clamp branch, the norm is a
+ *   constant there: -(2 g / batch) n(t_i) / 1e-12), dp_i likewise;  g_w = sum_b dp_u x_u^T + dp_i x_i^T,
+ *   g_bias = sum_b dp_u + dp_i;  W^T dp_u summed over the positions holding one user is WRITTEN to that row of g_on_user,
+ *   items likewise (the other rows are the caller's: zero them — gcr_tri_bwd_f32's contract).  No gradient to the targets.
+ * (keys_u, perm_u) = gcr_sort_index(u_idx, batch, n_users) and (keys_i, perm_i) likewise give the runs of equal ids.
+ * Its intermediates dp and dx = W^T dp ([2, batch, d] each) and the split partials of g_w / g_bias live in `workspace`
+ * (gcr_buir_workspace_bytes(batch, d) bytes, 16-B aligned).  One writer per word, sums in a fixed order (positions in
+ * ascending order inside a run; the at most 32 splits of g_w / g_bias in split order), no float atomics: every output is
+ * bitwise reproducible.  Three launches (plus the caller's two sorts).
+ * Supported (gcr_buir_supported): d % 16 == 0, 16 <= d <= 512; GCR_EUNSUPPORTED otherwise.  batch = 0 launches nothing;
+ * batch < 2^24, tables < 2^31 rows; the table, w and bias pointers 16-B aligned.
+ */
+int32_t gcr_buir_supported(int32_t d);
+int64_t gcr_buir_workspace_bytes(int64_t batch, int32_t d);
+int32_t gcr_buir_fwd_f32(const float* on_user, const float* on_item, const float* tg_user, const float* tg_item,
+                         int64_t n_users, int64_t n_items, int32_t d, const int64_t* u_idx, const int64_t* i_idx,
+                         int64_t batch, const float* w, const float* bias, float* loss, float* stats, void* stream);
+int32_t gcr_buir_bwd_f32(const float* on_user, const float* on_item, const float* tg_user, const float* tg_item,
+                         int64_t n_users, int64_t n_items, int32_t d, const int64_t* u_idx, const int64_t* i_idx,
+                         int64_t batch, const float* w, const float* bias, const float* stats, const float* g,
+                         const uint32_t* keys_u, const int32_t* perm_u, const uint32_t* keys_i, const int32_t* perm_i,
+                         float* g_on_user, float* g_on_item, float* g_w, float* g_bias, void* workspace, void* stream);
+/*
+ * replaces  BUIR_NB.update_target  buir.py:254-257  (t[idx] = t[idx] * m + o[idx] * (1 - m): eight index kernels).
+ * target[r] = fl(fl(target[r] m) + fl(online[r] (1 - m))) with m and 1 - m rounded to float32 from the double, EXACTLY ONCE
+ * per distinct r of idx [n] however often r recurs (what the reference's indexed assignment does); ids outside
+ * [0, n_rows) are skipped, rows not named are not touched.  A wave owns a row when its atomic OR sets the row's bit in
+ * claim_bits (uint32 [ceil(n_rows / 32)], zeroed by the call): an integer claim, so the result does not depend on which
+ * position wins and is bitwise the same from run to run.  One memset and one launch, no host read-back.
+ */
+int32_t gcr_ema_rows_f32(float* target, const float* online, const int64_t* idx, int64_t n, int32_t d, int64_t n_rows,
+                         double momentum, uint32_t* claim_bits, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 import torch
 
@@ -135,6 +135,12 @@ SIGNATURES = {
                                   _P, _P]),
     "gcr_tri_bwd_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, _P, c_int64, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P,
                                   _P, _P]),
+    "gcr_buir_supported": (c_int32, [c_int32]),
+    "gcr_buir_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "gcr_buir_fwd_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P]),
+    "gcr_buir_bwd_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P, _P, _P, _P, _P]),
+    "gcr_ema_rows_f32": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int64, c_double, _P, _P]),
     "gcr_mask_columns_f32":(c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "gcr_spgemm_expand_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_csr_lookup_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P]),

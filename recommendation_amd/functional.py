@@ -175,8 +175,10 @@ class _Propagate(torch.autograd.Function):
         h_K = g_K + c g_final ; h_k = g_k + c g_final + A^T h_{k+1} ; dx0 = h_0."""
 
     @staticmethod
-    def forward(ctx, x0, graph, n_layers, scale, want_layers):
+    def forward(ctx, x0, graph, n_layers, scale, want_layers, keep_bits=None, keep_bits_t=None, val_scale=1.0):
         ctx.graph, ctx.n_layers, ctx.scale, ctx.want_layers = graph, n_layers, scale, want_layers
+        ctx.mask_t = mk_t = dict(keep_bits=keep_bits_t, val_scale=val_scale)      # the backward's launches: A^T's order
+        mk = dict(keep_bits=keep_bits, val_scale=val_scale)
         x0 = x0.contiguous()
         if not want_layers and n_layers > 0:
             # Horner form  sum_k A^k x0 = x0 + A (x0 + A (x0 + ...)): every layer reads x0 and writes ONE
@@ -184,7 +186,7 @@ class _Propagate(torch.autograd.Function):
             z = x0
             for k in range(n_layers):
                 nxt = torch.empty_like(x0)
-                spmm_into(graph, z, acc_in=x0, acc_out=nxt, acc_scale=scale if k == n_layers - 1 else 1.0)
+                spmm_into(graph, z, acc_in=x0, acc_out=nxt, acc_scale=scale if k == n_layers - 1 else 1.0, **mk)
                 z = nxt
             return z
         cur, acc = x0, x0
@@ -194,7 +196,7 @@ class _Propagate(torch.autograd.Function):
             need_y = want_layers or not last
             y = torch.empty_like(x0) if need_y else None
             acc_out = torch.empty_like(x0) if k == 0 else acc  # in place after the first layer
-            spmm_into(graph, cur, y=y, acc_in=acc, acc_out=acc_out, acc_scale=scale if last else 1.0)
+            spmm_into(graph, cur, y=y, acc_in=acc, acc_out=acc_out, acc_scale=scale if last else 1.0, **mk)
             acc = acc_out
             if need_y:
                 cur = y
@@ -205,10 +207,10 @@ class _Propagate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_final, *g_layers):
-        gt, K, c = ctx.graph.t, ctx.n_layers, ctx.scale
+        gt, K, c, mk_t = ctx.graph.t, ctx.n_layers, ctx.scale, ctx.mask_t
         g = g_final.contiguous()
         if K == 0:
-            return g * c, None, None, None, None
+            return g * c, None, None, None, None, None, None, None
         # the recurrence on h' = h / c: h'_K = g + g_K / c, h'_k = g + g_k / c + A^T h'_{k+1}, dx0 = c h'_0 — the scale
         # rides on the last launch's epilogue instead of a pass over g_final
         gl = [x.contiguous() if x is not None else None for x in g_layers] if ctx.want_layers else [None] * K
@@ -218,18 +220,22 @@ class _Propagate(torch.autograd.Function):
         h = g if gl[K - 1] is None else torch.add(g, gl[K - 1], alpha=inv_c)
         for k in range(K - 1, 0, -1):
             out = torch.empty_like(g)
-            spmm_into(gt, h, acc_in=g, acc_in2=gl[k - 1], acc_in2_scale=inv_c, acc_out=out)
+            spmm_into(gt, h, acc_in=g, acc_in2=gl[k - 1], acc_in2_scale=inv_c, acc_out=out, **mk_t)
             h = out
         dx0 = torch.empty_like(g)
-        spmm_into(gt, h, acc_in=g, acc_out=dx0, acc_scale=c)
-        return dx0, None, None, None, None
+        spmm_into(gt, h, acc_in=g, acc_out=dx0, acc_scale=c, **mk_t)
+        return dx0, None, None, None, None, None, None, None
 
 
-def lightgcn_propagate(graph: CsrGraph, x0, n_layers: int, combine: str = "mean", return_layers: bool = False):
+def lightgcn_propagate(graph: CsrGraph, x0, n_layers: int, combine: str = "mean", return_layers: bool = False,
+                       keep_bits=None, keep_bits_t=None, val_scale=1.0):
     """K-layer LightGCN message pass with the layer combine fused into the SpMM epilogue.
     combine='mean' -> ncl.py:415-422 / selfcf.py:475-485 (mean of the K+1 layer outputs);
     combine='sum'  -> lightgcn.py:21-27 (x += out, no division, Q3).
-    Returns final [N, d] (and the list [x0, A x0, ..., A^K x0] when return_layers)."""
+    Returns final [N, d] (and the list [x0, A x0, ..., A^K x0] when return_layers).
+    keep_bits / keep_bits_t / val_scale: every layer runs on the dropped, rescaled operator val_scale * A[keep]
+    (buir.py:300-320), the mask in A's non-zero order and, for the backward, in A^T's — `functional.spmm`'s arguments and
+    its rule: a gradient through a masked graph without keep_bits_t raises.  Without them nothing changes."""
     if combine not in ("mean", "sum"):
         raise ValueError("combine must be 'mean' or 'sum'")
     _lib.require_cuda(x0)
@@ -237,7 +243,13 @@ def lightgcn_propagate(graph: CsrGraph, x0, n_layers: int, combine: str = "mean"
     if graph.n_rows != graph.n_cols:
         raise ValueError("propagation needs a square operator")
     scale = 1.0 / (n_layers + 1) if combine == "mean" else 1.0
-    out = _Propagate.apply(x0, graph, int(n_layers), scale, bool(return_layers))
+    if keep_bits is None:
+        if keep_bits_t is not None:
+            raise ValueError("keep_bits_t without keep_bits")
+    elif keep_bits_t is None and x0.requires_grad and torch.is_grad_enabled():
+        raise ValueError("backward through a masked graph needs keep_bits_t (the mask in A^T's non-zero order); "
+                         "for a symmetric graph build it with graph.mirror_perm()")
+    out = _Propagate.apply(x0, graph, int(n_layers), scale, bool(return_layers), keep_bits, keep_bits_t, float(val_scale))
     if return_layers:
         return out[0], [x0, *out[1:]]
     return out
@@ -1715,3 +1727,120 @@ def tri_training_loss(x_f, x_s, x_r, aug, uniq, k, temperature=0.1, positives=No
     if positives is not None:
         positives = positives.clone()                # the node returns the tensor it was given: keep the caller's apart
     return _TriTraining.apply(x_f, x_s, x_r, aug, uniq, k, 1.0 / float(temperature), positives)
+
+
+# ---------------------------------------------------------------------------------------------
+# BUIR's bootstrap loss and target update (univariate/buir.py:251-277)
+# ---------------------------------------------------------------------------------------------
+class _BuirLoss(torch.autograd.Function):
+    """gcr_buir_fwd_f32 / gcr_buir_bwd_f32: saves the inputs and stats [2, 3, B] = (|p|, |t|, cosine) per side; the
+    backward recomputes the predictions.  No gradient to the target tables."""
+
+    @staticmethod
+    def forward(ctx, on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias):
+        L = _lib.lib()
+        tabs = [t.contiguous() for t in (on_user, on_item, tg_user, tg_item)]
+        weight, bias = weight.contiguous(), bias.contiguous()
+        d, batch, dev = weight.shape[0], u_idx.numel(), weight.device
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        stats = torch.empty(2, 3, batch, dtype=torch.float32, device=dev)
+        _lib.check(L.gcr_buir_fwd_f32(*(_lib.dptr(t) for t in tabs), tabs[0].shape[0], tabs[1].shape[0], d, _lib.dptr(u_idx),
+                                      _lib.dptr(i_idx), batch, _lib.dptr(weight), _lib.dptr(bias), _lib.dptr(loss),
+                                      _lib.dptr(stats), _lib.cur_stream(dev)), "gcr_buir_fwd_f32")
+        ctx.save_for_backward(*tabs, u_idx, i_idx, weight, bias, stats)
+        ctx.stacked = _halves_of_one_table(tabs[0], tabs[1])
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias, stats = ctx.saved_tensors
+        L = _lib.lib()
+        d, batch, dev = weight.shape[0], u_idx.numel(), weight.device
+        n_users, n_items = on_user.shape[0], on_item.shape[0]
+        if ctx.stacked:                                     # one buffer for both halves: _SplitRows.backward hands it on
+            gfull = torch.zeros(n_users + n_items, d, dtype=torch.float32, device=dev)
+            gu, gi = gfull[:n_users], gfull[n_users:]
+        else:
+            gu, gi = torch.zeros_like(on_user), torch.zeros_like(on_item)
+        gw, gb = torch.zeros_like(weight), torch.zeros_like(bias)
+        if batch:
+            ku, pu, _ = _sorted_order(u_idx, n_users)
+            ki, pi, _ = _sorted_order(i_idx, n_items)
+            ws = torch.empty(int(L.gcr_buir_workspace_bytes(batch, d)) // 4, dtype=torch.float32, device=dev)
+            g = g.to(torch.float32).reshape(1).contiguous()
+            _lib.check(L.gcr_buir_bwd_f32(
+                _lib.dptr(on_user), _lib.dptr(on_item), _lib.dptr(tg_user), _lib.dptr(tg_item), n_users, n_items, d,
+                _lib.dptr(u_idx), _lib.dptr(i_idx), batch, _lib.dptr(weight), _lib.dptr(bias), _lib.dptr(stats), _lib.dptr(g),
+                _lib.dptr(ku), _lib.dptr(pu), _lib.dptr(ki), _lib.dptr(pi), _lib.dptr(gu), _lib.dptr(gi), _lib.dptr(gw),
+                _lib.dptr(gb), _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_buir_bwd_f32")
+        return gu, gi, None, None, None, None, gw, gb
+
+
+def buir_supported(d):
+    """True when the fused kernels (gcr_buir_*) serve rows of width d: a multiple of 16 in [16, 512]."""
+    return bool(_lib.lib().gcr_buir_supported(int(d)))
+
+
+def _buir_args(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias):
+    _lib.require_cuda(on_user, on_item, tg_user, tg_item, weight, bias)
+    d = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != d or tuple(bias.shape) != (d,) or weight.dtype != torch.float32 \
+            or bias.dtype != torch.float32:
+        raise ValueError("weight must be float32 [d, d] and bias float32 [d]")
+    for t, o in ((on_user, tg_user), (on_item, tg_item)):
+        if t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != d or o.shape != t.shape or o.dtype != torch.float32:
+            raise ValueError("the online and target tables must be float32 [n, d] of one shape per side")
+    u_idx, i_idx = _as_index(u_idx, weight.device).reshape(-1), _as_index(i_idx, weight.device).reshape(-1)
+    if u_idx.numel() != i_idx.numel():
+        raise ValueError("u_idx and i_idx must have one length")
+    return u_idx, i_idx
+
+
+def buir_loss_composed(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias):
+    """`buir_loss` as the reference writes it, from the ops that were there before the fused kernels: `gather_rows`
+    (buir.py:323-325), torch's linear (:262) and F.normalize, the products, the sums and the mean (:269-277)."""
+    import torch.nn.functional as F
+    u_idx, i_idx = _buir_args(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias)
+    p_u = F.normalize(F.linear(gather_rows(on_user, u_idx), weight, bias), dim=-1)
+    p_i = F.normalize(F.linear(gather_rows(on_item, i_idx), weight, bias), dim=-1)
+    with torch.no_grad():
+        t_u, t_i = F.normalize(gather_rows(tg_user, u_idx), dim=-1), F.normalize(gather_rows(tg_item, i_idx), dim=-1)
+    loss_ui = 2 - 2 * (p_u * t_i).sum(dim=-1)
+    loss_iu = 2 - 2 * (p_i * t_u).sum(dim=-1)
+    return (loss_ui + loss_iu).mean()
+
+
+def buir_loss(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias):
+    """BUIR's batch loss, univariate/buir.py:260-262, 269-277, 323-325, for the propagated online and target tables
+    (float32 [U, d] / [I, d]), the batch ids and the predictor `nn.Linear(d, d)`'s weight and bias:
+        p_u = W on_user[u] + b,  p_i = W on_item[i] + b
+        loss = mean_b (2 - 2 <n(p_u), n(tg_item[i])>) + (2 - 2 <n(p_i), n(tg_user[u])>),   n = F.normalize
+    One autograd node (two launches forward, three backward and the two id sorts), differentiable in on_user, on_item,
+    weight and bias; the targets get no gradient.  An id outside its table reads as a zero row (`gather_rows`' contract).
+    Every output is bitwise reproducible.  Widths outside `buir_supported(d)` run `buir_loss_composed`.  An empty batch
+    launches nothing and gives 0 with zero gradients."""
+    u_idx, i_idx = _buir_args(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias)
+    if not buir_supported(weight.shape[0]):
+        return buir_loss_composed(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias)
+    if u_idx.numel() == 0:
+        return (on_user.sum() + on_item.sum() + weight.sum() + bias.sum()) * 0.0
+    return _BuirLoss.apply(on_user, on_item, tg_user.detach(), tg_item.detach(), u_idx, i_idx, weight, bias)
+
+
+def ema_rows_(target, online, idx, momentum):
+    """In place `target[idx] = target[idx] * momentum + online[idx] * (1 - momentum)` (buir.py:254-257) for float32
+    [N, d] tables: every distinct row of idx is updated exactly once however often it recurs, ids outside [0, N) are
+    skipped, the other rows are not touched (gcr_ema_rows_f32; no host read-back, bitwise reproducible).  Returns target."""
+    _lib.require_cuda(target, online)
+    if target.dim() != 2 or target.dtype != torch.float32 or online.shape != target.shape or online.dtype != torch.float32 \
+            or not target.is_contiguous():
+        raise ValueError("target (contiguous) and online must be float32 [N, d] of one shape")
+    if target.requires_grad and torch.is_grad_enabled():
+        raise ValueError("ema_rows_ writes in place: call it on a tensor outside autograd (or under no_grad)")
+    idx = _as_index(idx, target.device).reshape(-1)
+    n_rows, d = target.shape
+    claim = torch.empty((n_rows + 31) // 32, dtype=torch.int32, device=target.device)
+    _lib.check(_lib.lib().gcr_ema_rows_f32(_lib.dptr(target), _lib.dptr(online.detach().contiguous()), _lib.dptr(idx),
+                                           idx.numel(), d, n_rows, float(momentum), _lib.dptr(claim),
+                                           _lib.cur_stream(target.device)), "gcr_ema_rows_f32")
+    return target

@@ -356,19 +356,27 @@ class CsrGraph:
         """Stable sort by row (COO order kept inside a row, duplicates kept — torch.sparse.mm on the
         uncoalesced COO of ncl.py:203-209 sums them), or (row, col)-sorted with duplicates summed
         when `coalesce` (scipy `tmp + tmp.T`, selfcf.py:297; `.coalesce()`, sept.py:50).
+        want_perm=True (not with coalesce) keeps `coo_perm`, int64 [nnz]: non-zero e of the CSR is COO entry coo_perm[e] —
+        the map that brings a per-entry mask recorded in COO order (buir.py:300-309) into non-zero order.
         On a GPU device the sort / merge runs in gcr_coo_to_csr; the numpy path only serves
         CPU-resident graphs (host logic, gloo tests)."""
+        want_perm = bool(kw.pop("want_perm", False)) and not coalesce
         if torch.device(device).type == "cuda":
-            rp, c, v, _ = coo_to_csr_device(row, col, val, n_rows, n_cols, device, coalesce=coalesce)
-            return cls(rp, c, v, n_rows, n_cols, device, symmetric=symmetric, **kw)
+            rp, c, v, perm = coo_to_csr_device(row, col, val, n_rows, n_cols, device, coalesce=coalesce, want_perm=want_perm)
+            g = cls(rp, c, v, n_rows, n_cols, device, symmetric=symmetric, **kw)
+            g.coo_perm = perm
+            return g
         row, col = _np_i64(row), _np_i64(col)
         if val is not None and isinstance(val, torch.Tensor):
             val = val.detach().cpu().numpy()
+        perm = None
         if coalesce:
             rp, c, v = _coalesce_host(row, col, val, n_rows, n_cols)
         else:
-            rp, c, v, _ = _coo_to_csr_host(row, col, val, n_rows)
-        return cls(rp, c, v, n_rows, n_cols, device, symmetric=symmetric, **kw)
+            rp, c, v, perm = _coo_to_csr_host(row, col, val, n_rows)
+        g = cls(rp, c, v, n_rows, n_cols, device, symmetric=symmetric, **kw)
+        g.coo_perm = torch.from_numpy(perm) if want_perm else None
+        return g
 
     @classmethod
     def bipartite_raw(cls, uid, iid, num_users, num_items, device, **kw):

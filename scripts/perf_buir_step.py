@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""Times BUIR's loss + target-update side and BUIRModel.train_step on the HIP path:
+
+    side_fused      functional.buir_loss (gcr_buir_fwd_f32 / gcr_buir_bwd_f32), forward + backward, then functional.ema_rows_
+                    on the user and the item rows (gcr_ema_rows_f32), on given propagated tables at B = 2048, d = 64
+    side_composed   the same through functional.buir_loss_composed (gather_rows, torch's linear / normalize) and the
+                    reference's indexed assignment t[idx] = t[idx] * m + o[idx] * (1 - m): what the library could run before
+                    the kernels — there is no earlier BUIR step to compare with
+    step_fused      a whole train_step on the cfg2-size synthetic graph (1M users x 100K items, 10M interactions), d = 64,
+                    2 layers, B = 2048, Adam: six masked SpMM launches (two forward passes, one backward), the draws, the side
+    step_composed   the same step of a second model held on the composition
+
+One child process under its own time limit (the parent never touches the GPU); inside it the variants alternate round by
+round, every call between its own pair of device events after warm-up.  Prints ONE JSON line: per variant the median, min,
+max and the 10 % / 90 % quantiles of the per-call times — `spread` = p90 - p10 — over rounds x steps >= 20 calls, the share
+of the step that the side is, and the device kernels one call of each side launches (torch.profiler).  Needs a GPU.
+
+    python scripts/perf_buir_step.py [--steps 5] [--warmup 3] [--rounds 4]
+    python scripts/perf_buir_step.py --only side_fused --steps 30      (one variant in this process, for a kernel trace)
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+EMB, BATCH, LAYERS, TAU = 64, 2048, 2, 0.995
+USERS, ITEMS, EDGES, SEED = 1_000_000, 100_000, 10_000_000, 20261019
+VARIANTS = ("side_fused", "side_composed", "step_fused", "step_composed")
+LEG_TIMEOUT_S = 540
+
+
+def ema_indexed(target, online, idx, momentum):
+    """buir.py:254-257 as written."""
+    target[idx] = target[idx] * momentum + online[idx] * (1 - momentum)
+    return target
+
+
+def leg(args):
+    import numpy as np
+    import torch
+    import recommendation_amd as ra
+    from recommendation_amd import functional as Fn
+    from recommendation_amd.buir import BUIRModel
+
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(SEED)
+    u = torch.randint(0, USERS, (EDGES,), device=dev, generator=gen)
+    i = torch.randint(0, ITEMS, (EDGES,), device=dev, generator=gen)
+    keys = torch.unique(u * ITEMS + i)
+    pu, pi = keys // ITEMS, keys % ITEMS
+    rowptr = torch.zeros(USERS + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(pu, minlength=USERS), 0)
+    norm_adj = ra.CsrGraph.bipartite_raw(u, i, USERS, ITEMS, dev)
+    conf = {"emb_size": EMB, "batch_size": BATCH, "lr": 1e-3, "BUIR": {"n_layer": LAYERS, "tau": TAU, "drop_rate": 0.2}}
+    models = {k: BUIRModel.from_graphs(conf, norm_adj, USERS, u, i, rowptr, pi.to(torch.int32).contiguous(), seed=0)
+              for k in ("step_fused", "step_composed")}
+    models["step_composed"].loss_fn, models["step_composed"].ema_fn = Fn.buir_loss_composed, ema_indexed
+    assert Fn.buir_supported(EMB)
+    m0 = models["step_fused"]
+    with torch.no_grad():
+        on = [t.clone().requires_grad_(True) for t in m0.encode(m0.online_user, m0.online_item)]
+        tg = [t.clone() for t in m0.encode(m0.online_user * 0.9, m0.online_item * 0.9)]
+    w, b = m0.weight.detach().clone().requires_grad_(True), m0.bias.detach().clone().requires_grad_(True)
+    tg_raw = {k: (m0.target_user.clone(), m0.target_item.clone()) for k in ("side_fused", "side_composed")}
+
+    def batches(count):
+        sel = [torch.randint(0, EDGES, (BATCH,), device=dev, generator=gen) for _ in range(count)]
+        return [(u[s].contiguous(), i[s].contiguous()) for s in sel]
+
+    def side(name, loss_fn, ema_fn):
+        def run(batch):
+            for t in (*on, w, b):
+                t.grad = None
+            loss_fn(on[0], on[1], tg[0], tg[1], batch[0], batch[1], w, b).backward()
+            ema_fn(tg_raw[name][0], m0.online_user.detach(), batch[0], TAU)
+            ema_fn(tg_raw[name][1], m0.online_item.detach(), batch[1], TAU)
+        return run
+
+    fns = {"side_fused": side("side_fused", Fn.buir_loss, Fn.ema_rows_),
+           "side_composed": side("side_composed", Fn.buir_loss_composed, ema_indexed),
+           "step_fused": lambda bt: models["step_fused"].train_step(bt),
+           "step_composed": lambda bt: models["step_composed"].train_step(bt)}
+
+    def timed(fn, data):
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in data]
+        for (e0, e1), bt in zip(evs, data):
+            e0.record()
+            fn(bt)
+            e1.record()
+        torch.cuda.synchronize()
+        return [e0.elapsed_time(e1) for e0, e1 in evs]
+
+    if args.only:
+        timed(fns[args.only], batches(args.steps))
+        print(json.dumps({"only": args.only, "steps": args.steps}))
+        return
+    for k in VARIANTS:
+        timed(fns[k], batches(args.warmup))
+    ms = {k: [] for k in VARIANTS}
+    for _ in range(args.rounds):                          # alternate: drift of the clocks hits all variants alike
+        data = batches(args.steps)
+        for k in VARIANTS:
+            ms[k] += timed(fns[k], data)
+    case = {"users": USERS, "items": ITEMS, "edges": EDGES, "emb": EMB, "batch": BATCH, "layers": LAYERS,
+            "calls_per_variant": args.rounds * args.steps, "device": torch.cuda.get_device_name(0)}
+    for k in VARIANTS:
+        q = np.quantile(ms[k], [0.1, 0.5, 0.9])
+        case[k + "_ms"] = {"median": round(float(q[1]), 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
+                           "p10": round(float(q[0]), 4), "p90": round(float(q[2]), 4), "spread": round(float(q[2] - q[0]), 4)}
+    for a, c in (("side_fused", "side_composed"), ("step_fused", "step_composed")):
+        f, s = case[a + "_ms"], case[c + "_ms"]
+        case[f"{c}_minus_{a}_ms"] = round(s["median"] - f["median"], 4)
+        case[f"{a}_faster_by_more_than_spread"] = bool(s["median"] - f["median"] > max(f["spread"], s["spread"]))
+    case["side_share_of_step_fused"] = round(case["side_fused_ms"]["median"] / case["step_fused_ms"]["median"], 4)
+    case["side_share_of_step_composed"] = round(case["side_composed_ms"]["median"] / case["step_composed_ms"]["median"], 4)
+    one = batches(1)[0]
+    for k in ("side_fused", "side_composed"):             # device kernels (and memsets / copies) of one call
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                fns[k](one)
+                torch.cuda.synchronize()
+            case[k + "_launches"] = int(sum(e.count for e in prof.key_averages() if getattr(e, "device_time_total", 0) > 0
+                                            or getattr(e, "cuda_time_total", 0) > 0))
+        except Exception as exc:                          # a profiler that cannot attach is not a failed measurement
+            case[k + "_launches"] = None
+            case[k + "_launches_error"] = repr(exc)[:200]
+    print(json.dumps(case))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--only", choices=VARIANTS)
+    ap.add_argument("--leg", action="store_true", help="(internal) measure in this process")
+    args = ap.parse_args()
+    if args.rounds * args.steps < 20 and not args.only:
+        raise SystemExit("at least 20 measured calls per variant (rounds x steps)")
+    if args.leg or args.only:
+        return leg(args)
+    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--steps", str(args.steps), "--warmup", str(args.warmup),
+           "--rounds", str(args.rounds)]
+    try:
+        res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=LEG_TIMEOUT_S)
+    except subprocess.TimeoutExpired:
+        raise SystemExit(f"no result within {LEG_TIMEOUT_S} s; stopping")
+    if res.returncode != 0:
+        raise SystemExit(f"the measurement failed with status {res.returncode}; stopping")
+    print(res.stdout.strip().splitlines()[-1])
+
+
+if __name__ == "__main__":
+    main()
