@@ -36,18 +36,27 @@ __device__ __forceinline__ float group16_sum(float v) {
   return v;
 }
 
-// d(loss)/dx and loss for x = pos - neg
+// d(loss)/dx and loss for x = pos - neg.  s = sigmoid(x) = 1 / (1 + e), e = exp(-x).  The subtraction 1 - s is exact, so
+// it carries s's rounding: 2^-25 absolute whatever x is.  That is within 2^-20 of 1 - s (the floor of the float64 pins'
+// bound rule) while 1 - s >= 2^-5, i.e. up to x ~ 3.4; for a converged pair it is 0.1 % off at x = 12 and exactly 0 from
+// x ~ 17 on, where torch's logsigmoid backward keeps its relative accuracy.  Below 2^-5 the value is e * s = e / (1 + e)
+// instead: no subtraction, relative error of a few ulp at any x.
 __device__ __forceinline__ void bpr_point(int variant, float x, float& loss, float& dl) {
-  const float s = 1.0f / (1.0f + __expf(-x));
+  const float e = __expf(-x);
+  const float s = 1.0f / (1.0f + e);
+  float t = 1.0f - s;                       // 1 - sigmoid(x)
+  if (t < 0x1p-5f) t = e * s;
+  // dl is assigned once, ahead of the branches: with the same `dl = -t` closing each of the last two, hipcc 7.2
+  // (clang 22.0.0git) -O3 left dl unwritten on the -log(sigmoid) path of one form of this function (read off the ISA;
+  // tests/test_bpr_paths_gpu.py and the LightGCN goldens saw that gradient 100 % off)
+  dl = -t;
   if (variant == GCR_BPR_NCL) {            // -log(1e-5 + sigmoid(x))   ncl.py:119 (literal 10e-6)
     loss = -__logf(10e-6f + s);
-    dl = -(s * (1.0f - s)) / (10e-6f + s);
+    dl = -(s * t) / (10e-6f + s);
   } else if (variant == GCR_BPR_LOGSIGMOID) {  // -logsigmoid(x)          gcl.py:221, sept.py:37
-    loss = (x > 0.f) ? log1pf(__expf(-x)) : (-x + log1pf(__expf(x)));
-    dl = -(1.0f - s);
+    loss = (x > 0.f) ? log1pf(e) : (-x + log1pf(__expf(x)));
   } else {                                  // -log(sigmoid(x))          lightgcn.py:108
     loss = -__logf(s);
-    dl = -(1.0f - s);
   }
 }
 

@@ -8,13 +8,19 @@ tests/test_tri_gpu.py (`rows_for(MAX_K)`, `SPLIT_CASES`) and tests/test_mim_gpu.
   (c) the waves and workgroups wanted lie on the intended side of each grid cap.
 
 A constant retuned in a kernel file fails this test at the GPU case that no longer reaches its branch.  The workspace
-functions are host-only: no device is touched here."""
+functions are host-only: no device is touched here.
+
+csrc/gcr_bpr.hip's geometry for tests/test_bpr_paths_gpu.py (`WIDTHS`, `BATCH_EDGES`, `TRIPS`): `fwd_blocks` is pinned to the
+library through gcr_bpr_workspace_floats (five partials per block); the atomic backward's grid cap and the sorted kernels'
+chunk and gather-group sizes are restated only — no workspace function exposes them, so these restatements are NOT pinned to
+the library and a retuned constant there has to be carried over here by hand."""
 import os
 
 import pytest
 
 # the case tables are read from the GPU test modules themselves, so the shapes asserted here are the shapes run there.  Those
 # modules must stay importable without a device: nothing at their module level may touch one (their tests are marked gpu)
+import test_bpr_paths_gpu as bpr
 import test_mim_gpu as mim
 import test_ssl4rec_gpu as drop
 import test_tri_gpu as tri
@@ -23,6 +29,13 @@ TILE, MAX_SPLITS, ROW_BLOCKS = 32, 8, 8192                 # gcr_tri.hip: kTile,
 MIM_MAX_BLOCKS, MIM_BWD_BLOCKS = 1024, 16384               # gcr_mim.hip: kMaxBlocks, the grid cap of mim_bwd_kernel
 FOLD_LOADS, WAVE = 16, 64                                  # gcr_mim.hip: kFoldLoads, the lanes of the loss fold
 DROPOUT_BLOCKS = 8192                                      # gcr_dropout.hip: dropout_grid()'s cap (4 rows each)
+BPR_FWD_GROUPS, BPR_FWD_BLOCKS = 16, 4096                  # gcr_bpr.hip: kGroups (samples per block), fwd_blocks()'s cap
+# gcr_bpr.hip, NOT pinned to the library (no workspace function depends on them): a retuned constant must be restated here
+BPR_BWD_BLOCKS, BPR_BWD_WAVES = 8192, 4                    # gcr_bpr_bwd_f32's grid cap, one sample per wave
+BPR_CHUNK = 64                                             # entries a wave of the sorted kernels walks
+BPR_GATHER_SORTED = {1: 8, 2: 4, 3: 4, 4: 4}               # kGather of bpr_bwd_sorted_kernel by NV
+BPR_GATHER_NEG_ITEMS = {1: 16, 2: 8, 3: 8, 4: 8}           # kGather of bpr_neg_items_sorted_kernel by NV
+BPR_SORTED_BLOCKS = 65536                                  # grid cap of the sorted, neg-block and edge-values kernels
 
 
 @pytest.fixture(scope="module")
@@ -136,3 +149,76 @@ def test_dropout_grid_cap():
     """dropout_grid(): one wave per batch row, four per workgroup, at most 8192 workgroups."""
     assert ceil_div(max(drop.NS), 4) <= DROPOUT_BLOCKS < ceil_div(drop.N_CAPPED, 4)
     assert drop.N_CAPPED == 4 * DROPOUT_BLOCKS + 37
+
+
+def bpr_fwd_blocks(batch):
+    return max(1, min(BPR_FWD_BLOCKS, ceil_div(batch, BPR_FWD_GROUPS)))
+
+
+def bpr_nv(d):
+    return ceil_div(d, 64)
+
+
+def bpr_batches():
+    return sorted({bpr.WIDTH_BATCH, bpr.PATTERN_BATCH} | {c[1] for c in bpr.BATCH_EDGES} | {t[0] for t in bpr.TRIPS})
+
+
+def test_bpr_forward_blocks_are_the_librarys(lib):
+    """gcr_bpr_workspace_floats is five partial sums per forward block: equality pins `bpr_fwd_blocks` to fwd_blocks()."""
+    for batch in bpr_batches() + [0, 16 * 4096, 16 * 4096 + 1, 2_000_000]:
+        assert lib.gcr_bpr_workspace_floats(batch) == 5 * bpr_fwd_blocks(batch), batch
+    assert bpr_fwd_blocks(16 * 4096) == 4096 == bpr_fwd_blocks(16 * 4096 + 1)
+
+
+def test_bpr_trips_lie_past_the_cap_they_name():
+    fwd_cap, bwd_cap = BPR_FWD_GROUPS * BPR_FWD_BLOCKS, BPR_BWD_WAVES * BPR_BWD_BLOCKS
+    assert (fwd_cap, bwd_cap) == (65536, 32768)
+    for batch, path, variant, trip in bpr.TRIPS:
+        assert path in bpr.SUMS_PATHS and trip in ("fwd", "bwd")
+        if trip == "bwd":                                      # the atomic backward alone: the forward still takes one trip
+            assert path == "atomic" and bwd_cap < batch <= fwd_cap
+        else:
+            assert batch > fwd_cap and ceil_div(batch, BPR_FWD_GROUPS) > BPR_FWD_BLOCKS
+        assert 0 < batch % bwd_cap < 16                        # the last trip has few samples: most waves and groups idle
+        # the sorted kernels' cap is out of reach of a quick test: one trip covers 16 M entries
+        assert ceil_div(ceil_div(batch, BPR_CHUNK), 4) <= BPR_SORTED_BLOCKS and ceil_div(batch, 256) <= BPR_SORTED_BLOCKS
+    assert {t[3] for t in bpr.TRIPS} == {"fwd", "bwd"}
+    assert {t[1] for t in bpr.TRIPS if t[3] == "fwd"} == {"atomic", "sorted_payload"}
+    assert BPR_SORTED_BLOCKS * 4 * BPR_CHUNK == 1 << 24
+    # every other table stays within one trip of every kernel
+    assert max(b for b in bpr_batches() if b not in {t[0] for t in bpr.TRIPS}) <= min(fwd_cap, bwd_cap)
+
+
+def test_bpr_batch_edges_lie_where_the_table_says():
+    """Each row names a unit (a gather group of one of the two sorted kernels at the row's NV, or the 64-entry chunk), a
+    multiple k and an offset: batch = k * unit + off, off in -1, 0, +1 (the single-sample batch: +1 past zero)."""
+    seen = {}
+    for d, batch, n_neg, unit, k, off in bpr.BATCH_EDGES:
+        nv = bpr_nv(d)
+        assert unit in (BPR_GATHER_SORTED[nv], BPR_GATHER_NEG_ITEMS[nv], BPR_CHUNK), (d, unit)
+        assert batch == k * unit + off and off in (-1, 0, 1) and batch >= 1
+        seen.setdefault((nv, unit), set()).add(off)
+    assert seen[(1, 8)] == seen[(1, 16)] == seen[(1, 64)] == seen[(2, 4)] == {-1, 0, 1}
+    assert 1 in seen[(2, 64)]
+    # NV = 2's group of 8 in bpr_neg_items_sorted_kernel is met by the negatives' batch * n_neg entries
+    slots = {batch * n_neg for d, batch, n_neg, *_ in bpr.BATCH_EDGES if d == 100}
+    assert {BPR_GATHER_NEG_ITEMS[2] - 2, BPR_GATHER_NEG_ITEMS[2], BPR_GATHER_NEG_ITEMS[2] + 2} <= slots
+    # both ONE_NEG branches at d = 64; a last chunk that is full, one entry long and one short of full
+    assert {n for d, _, n, *_ in bpr.BATCH_EDGES if d == 64} == {1, 3}
+    assert {batch % BPR_CHUNK for _, batch, *_ in bpr.BATCH_EDGES} >= {0, 1, BPR_CHUNK - 1}
+    # the straddling run of PATTERNS: entries 60 .. 69 of the sorted order cross the first chunk boundary
+    assert 60 < BPR_CHUNK < 70 and bpr.PATTERN_BATCH == 4 * BPR_CHUNK + 1
+
+
+def test_bpr_widths_reach_every_template():
+    cases = bpr.width_cases()
+    assert [c[0] for c in cases] == list(bpr.WIDTHS) and all(1 <= d <= 256 for d in bpr.WIDTHS)
+    pairs = {(d % 4 == 0, bpr_nv(d)) for d in bpr.WIDTHS}
+    assert pairs == {(vec4, nv) for vec4 in (True, False) for nv in (1, 2, 3, 4)}
+    for nv in (1, 2, 3, 4):
+        n_negs = {n_neg for d, _, n_neg in cases if bpr_nv(d) == nv}
+        assert 1 in n_negs and max(n_negs) > 1, nv                 # ONE_NEG true and false
+        assert 64 * nv in bpr.WIDTHS                               # every lane of the last column group live
+    assert {bpr_nv(d) for d in bpr.WIDTHS if d % 64} == {1, 2, 3, 4}   # a last column group that is partly masked
+    assert {v for _, v, _ in cases} == {0, 1, 2}
+    assert set(bpr.EDGE_WIDTHS) <= set(bpr.WIDTHS) and {bpr_nv(d) for d in bpr.EDGE_WIDTHS} == {1, 3}
