@@ -951,6 +951,15 @@ int32_t gcr_probe_read_f32(const float* src, int64_t n_floats, float* sink, void
  * to [0, n_rows). out: [n_idx / 64, 64]. */
 int32_t gcr_probe_gather_rows_f32(const float* table, int64_t n_rows, const int32_t* idx, int64_t n_idx,
                                   float* out, void* stream);
+/* The gather probe over two tables of 256-B rows in one launch, with the one-touch streams of a plain SpMM launch beside
+ * it.  idx holds n_idx ids (a multiple of 64): those at even positions name rows of `hot` (always plain loads), those at
+ * odd positions rows of `cold`, so every batch of 16 gathers in flight mixes them 1 : 1; ids are clamped to their table.
+ * Every batch of 16 also reads 1 KiB of stream_in in order (64 B per gather; n_idx * 16 floats, 16-B aligned) and stores
+ * one 256-B row of out (n_idx * 4 floats).  nt_flags: bit 0 puts `nt` on the cold gathers, bit 1 on the stream loads,
+ * bit 2 on the row stores. */
+int32_t gcr_probe_policy_rows_f32(const float* hot, int64_t n_hot, const float* cold, int64_t n_cold,
+                                  const int32_t* idx, int64_t n_idx, const float* stream_in, float* out,
+                                  uint32_t nt_flags, void* stream);
 
 #ifdef __cplusplus
 }

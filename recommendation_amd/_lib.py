@@ -153,6 +153,7 @@ SIGNATURES = {
     "gcr_probe_copy_f32": (c_int32, [_P, _P, c_int64, _P]),
     "gcr_probe_read_f32": (c_int32, [_P, c_int64, _P, _P]),
     "gcr_probe_gather_rows_f32": (c_int32, [_P, c_int64, _P, c_int64, _P, _P]),
+    "gcr_probe_policy_rows_f32": (c_int32, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_uint32, _P]),
 }
 
 _lib = None

@@ -52,6 +52,21 @@ constexpr int unroll_for() { return NV == 1 ? 16 : 8; }
 template <int NV, bool ACC2>
 constexpr int acc_queue_for() { return (NV == 1 && !ACC2) ? 2 : 0; }
 
+// One-touch traffic of the kernels below the generic one: the CSR words, acc_in, the output rows and the partial rows are
+// each touched once per launch, and every line of them an L2 allocates pushes out a gathered row that would have been hit
+// again.  `nt` on such a load or store lowers what its line displaces (measured with gcr_probe_policy_rows_f32:
+// EXPERIMENTS.md "SpMM: cache-policy hints, the gate"); the gathers themselves stay plain.  Same words, same order.
+template <bool NT = true, class T>
+__device__ __forceinline__ T stream_load(const T* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT = true, class T>
+__device__ __forceinline__ void stream_store(T* p, T v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
 struct Epilogue {
   float val_scale;
   float* y;
@@ -71,7 +86,9 @@ struct Epilogue {
 // have_pre: `pre` already holds acc_in[row] (loaded a gather batch ago by the caller's queue), so the combine below issues
 // no load and waits for none.  The two arms are kept apart on purpose: a load in one arm of a diamond makes the wait at
 // the join a vmcnt(0) for both.
-template <int NV, bool D64, bool ACC2>
+// STREAM: the reducers' form, acc_in and the output rows as one-touch traffic (stream_load / stream_store); the generic
+// kernel keeps plain accesses.
+template <int NV, bool D64, bool ACC2, bool STREAM = false>
 __device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d, int lane, float (&acc)[NV],
                                           bool have_pre, const float (&pre)[NV]) {
   // No contraction anywhere in the epilogue: `acc * val_scale` and the add of acc_in stay two roundings in both arms.  The
@@ -87,7 +104,7 @@ __device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         const int c = lane + 64 * v;
-        if (D64 || c < d) ep.y_raw[rb + c] = yv[v];
+        if (D64 || c < d) stream_store<STREAM>(ep.y_raw + rb + c, yv[v]);
       }
     }
     float ss = 0.f;
@@ -104,7 +121,7 @@ __device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int c = lane + 64 * v;
-      if (D64 || c < d) ep.y[base + c] = yv[v];
+      if (D64 || c < d) stream_store<STREAM>(ep.y + base + c, yv[v]);
     }
   }
   if (ep.acc_out == nullptr) return;
@@ -112,16 +129,16 @@ __device__ __forceinline__ void store_row(const Epilogue& ep, int64_t row, int d
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int c = lane + 64 * v;
-      if (D64 || c < d) ep.acc_out[base + c] = (pre[v] + yv[v]) * ep.acc_scale;
+      if (D64 || c < d) stream_store<STREAM>(ep.acc_out + base + c, (pre[v] + yv[v]) * ep.acc_scale);
     }
   } else {
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       const int c = lane + 64 * v;
       if (D64 || c < d) {
-        float prev = ep.acc_in != nullptr ? ep.acc_in[base + c] : 0.f;
-        if (ACC2) prev = fmaf(ep.acc_in2[base + c], ep.acc_in2_scale, prev);
-        ep.acc_out[base + c] = (prev + yv[v]) * ep.acc_scale;
+        float prev = ep.acc_in != nullptr ? stream_load<STREAM>(ep.acc_in + base + c) : 0.f;
+        if (ACC2) prev = fmaf(stream_load<STREAM>(ep.acc_in2 + base + c), ep.acc_in2_scale, prev);
+        stream_store<STREAM>(ep.acc_out + base + c, (prev + yv[v]) * ep.acc_scale);
       }
     }
   }
@@ -323,7 +340,7 @@ __device__ __forceinline__ bool sum_partials(const float* __restrict__ p0, int64
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int v = 0; v < NV; ++v)
-        t[u][v] = (D64 || lane + 64 * v < d) ? p0[(int64_t)(k + 4 * u) * stride + lane + 64 * v] : 0.f;
+        t[u][v] = (D64 || lane + 64 * v < d) ? stream_load(p0 + (int64_t)(k + 4 * u) * stride + lane + 64 * v) : 0.f;
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -332,7 +349,7 @@ __device__ __forceinline__ bool sum_partials(const float* __restrict__ p0, int64
   for (; k < count; k += 4)
 #pragma unroll
     for (int v = 0; v < NV; ++v)
-      if (D64 || lane + 64 * v < d) acc[v] += p0[(int64_t)k * stride + lane + 64 * v];
+      if (D64 || lane + 64 * v < d) acc[v] += stream_load(p0 + (int64_t)k * stride + lane + 64 * v);
   if (wave > 0) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) red[wave - 1][v * 64 + lane] = acc[v];
@@ -355,7 +372,7 @@ __global__ __launch_bounds__(256) void spmm_long_rows(const int32_t* __restrict_
   const int s0 = long_slot0[i], s1 = long_slot0[i + 1];
   float acc[NV];
   if (sum_partials<NV, D64>(partials + (int64_t)s0 * d, d, s1 - s0, d, acc))
-    store_row<NV, D64, ACC2>(ep, (int64_t)long_row[i], d, threadIdx.x & 63, acc, false, acc);
+    store_row<NV, D64, ACC2, true>(ep, (int64_t)long_row[i], d, threadIdx.x & 63, acc, false, acc);
 }
 
 // The windowed companion's reduction (graph.py HubPlan), one block per hub row: hub row h was multiplied window by window
@@ -366,7 +383,7 @@ __global__ __launch_bounds__(256) void spmm_hub_rows(const int32_t* __restrict__
   const int64_t h = blockIdx.x;
   float acc[NV];
   if (sum_partials<NV, D64>(partials + h * d, n_hub * d, n_win, d, acc))
-    store_row<NV, D64, false>(ep, (int64_t)hub_row[h], d, threadIdx.x & 63, acc, false, acc);
+    store_row<NV, D64, false, true>(ep, (int64_t)hub_row[h], d, threadIdx.x & 63, acc, false, acc);
 }
 
 // The partition of this wave in a range of blocks that starts at block `block0`: four waves per block, one partition each.
@@ -406,7 +423,7 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
 
   // local end offsets of the (<= 64) rows of a whole-row partition, one per lane
   int ends_v = 0x7fffffff;
-  if (whole_rows && lane < nrows) ends_v = (int)(rowptr[row0 + lane + 1] - nnz0);
+  if (whole_rows && lane < nrows) ends_v = (int)(stream_load(rowptr + row0 + lane + 1) - nnz0);
   int cur = 0;
   int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
 
@@ -424,8 +441,8 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
     vv_o = 0.f;
     if (lane < n - b) {
       const int64_t e = nnz0 + b + lane;
-      cv_o = col[e];
-      vv_o = HAS_VAL ? val[e] : 1.0f;
+      cv_o = stream_load(col + e);
+      vv_o = HAS_VAL ? stream_load(val + e) : 1.0f;
     }
   };
 
@@ -483,7 +500,7 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
       flush();
     }
   } else {
-    if (on) partials[slot * (int64_t)d + lane] = acc;
+    if (on) stream_store(partials + slot * (int64_t)d + lane, acc);
   }
 }
 
@@ -496,7 +513,7 @@ struct StoreSink {
   int d, lane;
   __device__ __forceinline__ void refill(int64_t, int) {}
   __device__ __forceinline__ void flush(int64_t row, float acc) {
-    if (D64 || lane < d) y[row * d + lane] = acc;
+    if (D64 || lane < d) stream_store(y + row * d + lane, acc);
   }
 };
 
@@ -519,8 +536,8 @@ struct CombineSink {
   __device__ __forceinline__ void refill(int64_t row, int n) {
     const bool on = D64 || lane < d;
     if (!queues) n = 0;
-    if (nq < 1 && 0 < n) q0 = on ? acc_in[row * d + lane] : 0.f;
-    if (nq < 2 && 1 < n) q1 = on ? acc_in[(row + 1) * d + lane] : 0.f;
+    if (nq < 1 && 0 < n) q0 = on ? stream_load(acc_in + row * d + lane) : 0.f;
+    if (nq < 2 && 1 < n) q1 = on ? stream_load(acc_in + (row + 1) * d + lane) : 0.f;
     nq = max(nq, min(2, n));
   }
   __device__ __forceinline__ void flush(int64_t row, float acc) {
@@ -530,18 +547,18 @@ struct CombineSink {
     const float yv = acc * val_scale;
     const int64_t base = row * d + lane;
     if (y != nullptr) {
-      if (on) y[base] = yv;
+      if (on) stream_store(y + base, yv);
     }
     if (acc_out != nullptr) {
       if (nq > 0) {
-        if (on) acc_out[base] = (q0 + yv) * acc_scale;
+        if (on) stream_store(acc_out + base, (q0 + yv) * acc_scale);
         q0 = q1;
         --nq;
       } else {
         // fewer queued rows than row ends in one batch (degree-1 runs), or nothing to prefetch: load at the flush
         if (on) {
-          const float prev = acc_in != nullptr ? acc_in[base] : 0.f;
-          acc_out[base] = (prev + yv) * acc_scale;
+          const float prev = acc_in != nullptr ? stream_load(acc_in + base) : 0.f;
+          stream_store(acc_out + base, (prev + yv) * acc_scale);
         }
       }
     }
@@ -633,9 +650,9 @@ __global__ __launch_bounds__(256) void spmm_long_rows_pair(const int32_t* __rest
   float acc[1];
   if (!sum_partials<1, D64>(partials + (int64_t)s0 * d, d, s1 - s0, d, acc)) return;
   if (is_hub) {
-    if (D64 || lane < d) hub_y[(int64_t)hub_long_row[i] * d + lane] = acc[0];
+    if (D64 || lane < d) stream_store(hub_y + (int64_t)hub_long_row[i] * d + lane, acc[0]);
   } else {
-    store_row<1, D64, false>(ep, (int64_t)main_long_row[i], d, lane, acc, false, acc);
+    store_row<1, D64, false, true>(ep, (int64_t)main_long_row[i], d, lane, acc, false, acc);
   }
 }
 
