@@ -314,7 +314,8 @@ int32_t gcr_edge_mask_bits(int64_t nnz, float pe, uint64_t seed, const int64_t* 
  * logsumexp; the M x N score matrix is never materialised.  d must be 32, 64, 128 or 256
  * (GCR_EUNSUPPORTED otherwise; the host wrapper zero-pads other widths).  f32 in, f32 out, f32
  * accuracy on both engines: the f32 MFMA (v_mfma_f32_32x32x2_f32), or for d <= 128 the bf16 MFMA on
- * three error-free bf16 planes per operand (csrc/gcr_infonce.hip, "split-operand engine").
+ * three error-free bf16 planes per operand (the f32 engine is csrc/gcr_tile.h, the "split-operand engine"
+ * csrc/gcr_b3.h; the kernels built on them are in csrc/gcr_infonce.hip).
  * --------------------------------------------------------------------------------------------- */
 /* engine the InfoNCE / k-means kernels use for width d by default: 0 = f32 MFMA, 1 = split-operand bf16
  * (d <= 128); GCR_INFONCE_ENGINE_F32 in the flags of the _ex entry points selects 0 for one call */
@@ -550,7 +551,8 @@ int32_t gcr_bce_bwd_f32(const float* x, int64_t mx, const float* y, int64_t ny, 
  * index.search(x, 1); faiss itself is an un-vendored dependency, not installed: what is restated is its published
  * Clustering::train loop — Lloyd iterations + split_clusters for empty clusters; PARITY WITH FAISS UNPINNED).
  * --------------------------------------------------------------------------------------------- */
-/* assign[i] = argmin_c ||x_i - centroids_c||^2 (ties -> smaller c) on the MFMA tile engine;
+/* assign[i] = argmin_c ||x_i - centroids_c||^2 (ties -> smaller c) on the MFMA tile engine (csrc/gcr_tile.h; this
+ * and every other k-means kernel is in csrc/gcr_kmeans.hip);
  * half_sqnorm[c] = 0.5 ||centroids_c||^2 (kept up to date by gcr_kmeans_update_f32);
  * best_score (optional) = <x_i, c> - 0.5 ||c||^2 of the winner.  d in {32, 64, 128, 256}. */
 int32_t gcr_kmeans_assign_f32(const float* x, int64_t n, const float* centroids, const float* half_sqnorm,

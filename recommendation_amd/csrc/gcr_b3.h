@@ -1,7 +1,11 @@
-// Split-operand ("b3") MFMA helpers shared by the InfoNCE / k-means kernels (gcr_infonce.hip) and the fused
-// ranking kernel (gcr_rank.hip).  Included INSIDE each translation unit's anonymous namespace, after
-// f32x16 / kTileJ / acc_row are defined there.
+// Split-operand ("b3") MFMA helpers shared by the InfoNCE / BCE kernels (gcr_infonce.hip), the nearest-centroid search
+// (gcr_kmeans.hip) and the fused ranking kernel (gcr_rank.hip).  Self-contained: included at file scope like any other
+// header, it brings the f32 engine's names (gcr_tile.h) with it and keeps its own in an anonymous namespace.
 #pragma once
+#include "gcr_tile.h"
+
+namespace {
+
 // ------------------------------------------------------------------------------------------
 // Split-operand engine ("b3").  gfx950's bf16 MFMA (v_mfma_f32_32x32x16_bf16) runs at 16x the rate
 // of the f32 MFMA and accumulates in f32.  Every f32 operand x is split ERROR-FREE into three
@@ -126,3 +130,4 @@ __device__ __forceinline__ void score_tile_b3(const unsigned char* __restrict__ 
   }
 }
 
+}  // namespace

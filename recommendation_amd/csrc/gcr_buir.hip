@@ -20,18 +20,13 @@
 //             finish   waves of the first range: one per sorted position; the head of a run of equal ids adds the run's dx
 //                      rows in sorted (= position) order and WRITES the row.  The others add the S partials in split order.
 // One writer per word, fixed orders, no float atomics: every output is bitwise reproducible.
-#include "gcr_common.h"
+#include "gcr_tile.h"   // f32x16, acc_row, kTileJ = 32 rows of a tile
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;
 constexpr int kMaxD = 512;
 constexpr int kMaxSplits = 32;
 constexpr float kNormEps = 1e-12f;   // F.normalize's eps
-
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ float4 ld4(const float* p) {
   return p ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -76,10 +71,10 @@ __device__ __forceinline__ const float* row_of(const float* tab, const int64_t* 
 }
 
 __global__ __launch_bounds__(256) void buir_fwd_rows_kernel(BuirArgs A, float* __restrict__ stats) {
-  __shared__ float red[3][4][kTile];
+  __shared__ float red[3][4][kTileJ];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l32 = lane & 31, h = lane >> 5;
   const int side = blockIdx.y, d = A.d;
-  const int64_t b = (int64_t)blockIdx.x * kTile + l32;
+  const int64_t b = (int64_t)blockIdx.x * kTileJ + l32;
   const float* x_row = row_of(A.on[side], A.idx[side], A.n[side], b, A.batch, d);
   const float* t_row = row_of(A.tg[1 - side], A.idx[1 - side], A.n[1 - side], b, A.batch, d);
   const int n_chunks = (d + 31) >> 5;
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(256) void buir_fwd_rows_kernel(BuirArgs A, float* _
     red[2][wave][l32] = tt;
   }
   __syncthreads();
-  if (threadIdx.x < kTile && b < A.batch) {
+  if (threadIdx.x < kTileJ && b < A.batch) {
     float s[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] = ((red[k][0][l32] + red[k][1][l32]) + red[k][2][l32]) + red[k][3][l32];
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(64) void buir_dp_kernel(BuirArgs A, const float* __
                                                      float* __restrict__ dp) {
   const int lane = threadIdx.x, l32 = lane & 31, h = lane >> 5;
   const int side = blockIdx.y, d = A.d, o0 = blockIdx.z * 32, o = o0 + l32;
-  const int64_t b = (int64_t)blockIdx.x * kTile + l32;
+  const int64_t b = (int64_t)blockIdx.x * kTileJ + l32;
   const bool live = b < A.batch;
   const float* x_row = row_of(A.on[side], A.idx[side], A.n[side], b, A.batch, d);
   const float* t_row = row_of(A.tg[1 - side], A.idx[1 - side], A.n[1 - side], b, A.batch, d);
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(64) void buir_grad_kernel(BuirArgs A, const float* 
     blk /= n_chunks;
     const int side = blk & 1, tile = blk >> 1;
     const int k = kc * 32 + l32;
-    const int64_t b = (int64_t)tile * kTile + l32;
+    const int64_t b = (int64_t)tile * kTileJ + l32;
     const bool live = b < A.batch;
     const float* drow = live ? dp + ((int64_t)side * A.batch + b) * d : nullptr;
     const float* wcol = k < d ? A.w + k : nullptr;
@@ -378,7 +373,7 @@ extern "C" int32_t gcr_buir_fwd_f32(const float* on_user, const float* on_item, 
   A.on[0] = on_user; A.on[1] = on_item; A.tg[0] = tg_user; A.tg[1] = tg_item;
   A.idx[0] = u_idx; A.idx[1] = i_idx; A.n[0] = n_users; A.n[1] = n_items;
   A.batch = batch; A.d = d; A.w = w; A.bias = bias;
-  const unsigned n_tiles = (unsigned)((batch + kTile - 1) / kTile);
+  const unsigned n_tiles = (unsigned)((batch + kTileJ - 1) / kTileJ);
   hipLaunchKernelGGL(buir_fwd_rows_kernel, dim3(n_tiles, 2), dim3(256), 0, s, A, stats);
   hipLaunchKernelGGL(buir_loss_kernel, dim3(1), dim3(256), 0, s, stats, batch, loss);
   return GCR_LAUNCH_STATUS();
@@ -407,7 +402,7 @@ extern "C" int32_t gcr_buir_bwd_f32(const float* on_user, const float* on_item, 
   O.grad[0] = g_on_user; O.grad[1] = g_on_item;
   const BuirWorkspace L = buir_layout(batch, d);
   float* ws = reinterpret_cast<float*>(workspace);
-  const int n_tiles = (int)((batch + kTile - 1) / kTile), n_chunks = (d + 31) / 32;
+  const int n_tiles = (int)((batch + kTileJ - 1) / kTileJ), n_chunks = (d + 31) / 32;
   hipLaunchKernelGGL(buir_dp_kernel, dim3((unsigned)n_tiles, 2, (unsigned)n_chunks), dim3(64), 0, s, A, stats, g, ws + L.dp);
   const int n_dx = n_tiles * 2 * n_chunks, n_dw = n_chunks * n_chunks * L.n_splits;
   hipLaunchKernelGGL(buir_grad_kernel, dim3((unsigned)(n_dx + n_dw)), dim3(64), 0, s, A, ws + L.dp, n_tiles, n_chunks, n_dx,

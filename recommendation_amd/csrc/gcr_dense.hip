@@ -19,11 +19,9 @@
 //                     mixed = sum_k score_k e_k (+ scale * extra: the `+ simple / 2` of mhcn.py:443) in one pass; the
 //                     backward gives d e_k = score_k g + dlogit_k v, d extra and the partial sums of d v in one pass
 //                     (torch: ~30 launches per call, three calls per step).
-#include "gcr_common.h"
+#include "gcr_tile.h"   // f32x16
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // 16 lanes per row, float4 per lane and 64 columns (d % 4 == 0); out may alias g_n or g_raw.
 // FROM_RAW: `nrm` holds the RAW rows z = A x (the forward did not keep the normalised copy): n = z * inv on the fly.

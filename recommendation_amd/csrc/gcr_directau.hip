@@ -27,21 +27,16 @@
 // Backward: one launch, one wave per batch position.  From r, o, inv_norm and the table rows it forms the gradient with
 // respect to x^ of every set, applies the normalize backward and the 2 g_Q x term, and adds the row into the table
 // gradient with one float atomic per element (duplicate ids collide, as in gcr_scatter_add_rows_f32).
-#include "gcr_common.h"
+#include "gcr_tile.h"   // f32x16, acc_row, kTileJ = 32: rows of a tile (the MFMA's M and N)
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;            // rows of a tile (the MFMA's M and N)
-constexpr int kKC = 64;              // feature columns staged per chunk = width of an o slice
+constexpr int kKC = 64;             // feature columns staged per chunk = width of an o slice
 constexpr int kStride = kKC + 1;     // LDS row stride: odd, so 32 rows of one column fall into 32 banks
 constexpr int kWaves = 4;
 constexpr int kMaxPrepBlocks = 256;
 constexpr int kPrepVals = 5;         // A_pos, A_neg, Q_u, Q_p, Q_n
 constexpr float kNormEps = 1e-12f;   // F.normalize's eps
-
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -137,16 +132,16 @@ __global__ __launch_bounds__(256) void au_tile_kernel(const float* __restrict__ 
                                                       float* __restrict__ r_part,
                                                       const float* __restrict__ prep_part, int prep_blocks,
                                                       unsigned* __restrict__ ticket, float* __restrict__ sums) {
-  __shared__ float rowt[kTile * kStride];
-  __shared__ float colt[kWaves][kTile * kStride];
-  __shared__ float red_r[kWaves][kTile];      // sum_b e over the pairs that carry a gradient
-  __shared__ float red_g[kWaves][kTile];      // sum_b e over all pairs (G)
+  __shared__ float rowt[kTileJ * kStride];
+  __shared__ float colt[kWaves][kTileJ * kStride];
+  __shared__ float red_r[kWaves][kTileJ];      // sum_b e over the pairs that carry a gradient
+  __shared__ float red_g[kWaves][kTileJ];      // sum_b e over all pairs (G)
   __shared__ int is_last;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l32 = lane & 31, h = lane >> 5;
   const int s = blockIdx.y, z = blockIdx.z;
-  const int64_t a0 = (int64_t)blockIdx.x * kTile;
-  const int64_t n_tiles = (batch + kTile - 1) / kTile;
+  const int64_t a0 = (int64_t)blockIdx.x * kTileJ;
+  const int64_t n_tiles = (batch + kTileJ - 1) / kTileJ;
   const int n_chunks = (d + kKC - 1) / kKC;
   const float* X = xhat + (int64_t)s * batch * d;
   const float* N2 = sqn + (int64_t)s * batch;
@@ -158,7 +153,7 @@ __global__ __launch_bounds__(256) void au_tile_kernel(const float* __restrict__ 
 
   auto load_row_chunk = [&](int kc) {                        // all 256 threads: rows a0.. of chunk kc
     const int kw = min(kKC, d - kc * kKC);
-    for (int i = tid; i < kTile * kw; i += 256) {
+    for (int i = tid; i < kTileJ * kw; i += 256) {
       const int row = i / kw, c = i - row * kw;
       const int64_t ar = a0 + row;
       rowt[row * kStride + c] = ar < batch ? X[ar * d + kc * kKC + c] : 0.f;
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(256) void au_tile_kernel(const float* __restrict__ 
   for (int64_t it = 0; it < n_iter; ++it) {
     const int64_t jt = it * kWaves + wave;
     const bool active = jt < n_tiles;
-    const int64_t b0 = jt * kTile;
+    const int64_t b0 = jt * kTileJ;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -186,7 +181,7 @@ __global__ __launch_bounds__(256) void au_tile_kernel(const float* __restrict__ 
       const int kw = min(kKC, d - kc * kKC);
       __syncthreads();                                       // everyone is done with the previous chunk
       if (n_chunks > 1) load_row_chunk(kc);
-      for (int i = lane; i < kTile * kw; i += 64) {
+      for (int i = lane; i < kTileJ * kw; i += 64) {
         const int row = i / kw, c = i - row * kw;
         const int64_t br = b0 + row;
         colt[wave][row * kStride + c] = (active && br < batch) ? X[br * d + kc * kKC + c] : 0.f;
@@ -259,7 +254,7 @@ __global__ __launch_bounds__(256) void au_tile_kernel(const float* __restrict__ 
       }
     }
     __syncthreads();
-    for (int i = tid; i < kTile * kw_z; i += 256) {
+    for (int i = tid; i < kTileJ * kw_z; i += 256) {
       const int row = i / kw_z, c = i - row * kw_z;
       const int o = row * kStride + c;
       const float v = ((colt[0][o] + colt[1][o]) + colt[2][o]) + colt[3][o];
@@ -361,7 +356,7 @@ struct AuWorkspace {
 
 AuWorkspace au_layout(int64_t batch, int d) {
   AuWorkspace w;
-  const int64_t n_tiles = (batch + kTile - 1) / kTile;
+  const int64_t n_tiles = (batch + kTileJ - 1) / kTileJ;
   w.xhat = 0;
   w.sqn = w.xhat + align64f(3 * batch * d);
   w.row_id = w.sqn + align64f(3 * batch);
@@ -415,7 +410,7 @@ extern "C" int32_t gcr_directau_fwd_f32(const float* user_tab, const float* item
 #undef GCR_AU_PREP
   int32_t st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
-  const unsigned n_tiles = (unsigned)((batch + kTile - 1) / kTile);
+  const unsigned n_tiles = (unsigned)((batch + kTileJ - 1) / kTileJ);
   if (o != nullptr) {
     const unsigned n_slices = (unsigned)((d + kKC - 1) / kKC);
     hipLaunchKernelGGL((au_tile_kernel<true>), dim3(n_tiles, (unsigned)n_sets, n_slices), dim3(256), 0, s, ws + w.xhat,

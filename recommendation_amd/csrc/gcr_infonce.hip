@@ -19,102 +19,22 @@
 // a column range of the table; table tiles of 32 rows are staged global -> registers -> LDS
 // (normalised on the way) one tile ahead of the MFMAs (double buffer, one barrier per tile).
 // Grid = anchor blocks x column splits; split partials (max, sum) are merged by a second kernel.
+//
+// This file holds the InfoNCE forward and backward kernels and the BCE-with-logits launches, which instantiate the same
+// kernel templates with another epilogue.  The f32 engine they are built on (Shape<D>, stage_load / stage_store,
+// load_stationary, score_tile) is gcr_tile.h, the split-operand engine gcr_b3.h; the nearest-centroid search of the
+// k-means E-step, a third user of both, is in gcr_kmeans.hip.
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "gcr_common.h"
+#include "gcr_b3.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTileJ = 32;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 constexpr float kNegBig = -1.0e30f;
-
-template <int D>
-struct Shape {
-  static constexpr int KH = D / 2;                       // k-steps per 32x32 tile (2 k per MFMA)
-  static constexpr int STRIDE = D + 4;                   // floats; +16 B pad -> conflict-free b128
-  static constexpr int NT = D <= 128 ? 2 : 1;            // anchor tiles of 32 per wave
-  static constexpr int NLD = (kTileJ * D / 4) / 256;     // float4 staged per thread and tile
-  static constexpr int ANCHORS_PER_BLOCK = 4 * 32 * NT;
-};
-
-// C/D layout of the 32x32 accumulator: register r of lane (col = lane&31, h = lane>>5) is row
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// Branch-free staging load (keeps the tile loop one scheduling region): rows past the table are
-// clamped to the last row and multiplied by 0.
-template <int D>
-__device__ __forceinline__ void stage_load(const float* __restrict__ b, const float* __restrict__ b_scale,
-                                           int64_t n_rows, int64_t j0, int tid, float4 (&regs)[Shape<D>::NLD],
-                                           float mult = 1.0f) {
-#pragma unroll
-  for (int u = 0; u < Shape<D>::NLD; ++u) {
-    const int idx = tid + 256 * u;
-    const int row = idx / (D / 4), c4 = idx % (D / 4);
-    const int64_t j = j0 + row;
-    const int64_t jj = j < n_rows ? j : n_rows - 1;
-    float4 v = *reinterpret_cast<const float4*>(b + jj * D + 4 * c4);
-    float s = b_scale != nullptr ? b_scale[jj] * mult : mult;
-    s = j < n_rows ? s : 0.f;
-    v.x *= s; v.y *= s; v.z *= s; v.w *= s;
-    regs[u] = v;
-  }
-}
-
-template <int D>
-__device__ __forceinline__ void stage_store(float* __restrict__ tile, int tid, const float4 (&regs)[Shape<D>::NLD]) {
-#pragma unroll
-  for (int u = 0; u < Shape<D>::NLD; ++u) {
-    const int idx = tid + 256 * u;
-    const int row = idx / (D / 4), c4 = idx % (D / 4);
-    *reinterpret_cast<float4*>(tile + row * Shape<D>::STRIDE + 4 * c4) = regs[u];
-  }
-}
-
-// stationary operand: lane (i = lane&31, h) holds features [h*KH, (h+1)*KH) of its row, pre-scaled
-template <int D>
-__device__ __forceinline__ void load_stationary(const float* __restrict__ a, const float* __restrict__ a_scale,
-                                                int64_t m_rows, int64_t row, int h, float mult,
-                                                float (&frag)[Shape<D>::KH]) {
-  const bool valid = row < m_rows;
-  const float s = valid ? (a_scale != nullptr ? a_scale[row] : 1.0f) * mult : 0.f;
-  const float* p = a + (valid ? row : 0) * D + h * Shape<D>::KH;
-#pragma unroll
-  for (int q = 0; q < Shape<D>::KH / 4; ++q) {
-    float4 v = valid ? *reinterpret_cast<const float4*>(p + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-    frag[4 * q + 0] = v.x * s;
-    frag[4 * q + 1] = v.y * s;
-    frag[4 * q + 2] = v.z * s;
-    frag[4 * q + 3] = v.w * s;
-  }
-}
-
-// S^T tile: acc[t][r] = log2-domain logit of (table row acc_row(r,h), anchor tile t / lane&31)
-template <int D>
-__device__ __forceinline__ void score_tile(const float* __restrict__ tile, int i32, int h,
-                                           const float (&bfrag)[Shape<D>::NT][Shape<D>::KH],
-                                           f32x16 (&acc)[Shape<D>::NT]) {
-#pragma unroll
-  for (int t = 0; t < Shape<D>::NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  const float* base = tile + i32 * Shape<D>::STRIDE + h * Shape<D>::KH;
-#pragma unroll
-  for (int q = 0; q < Shape<D>::KH / 4; ++q) {
-    const float4 av = *reinterpret_cast<const float4*>(base + 4 * q);
-    const float ae[4] = {av.x, av.y, av.z, av.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int t = 0; t < Shape<D>::NT; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae[e], bfrag[t][4 * q + e], acc[t], 0, 0, 0);
-  }
-}
 
 // online-softmax update with one finished score tile; `rem` = table rows left from this lane's
 // first accumulator row (n_rows - j0 - 4h): rows at or past it are masked out (ragged last tile).
@@ -299,8 +219,6 @@ __global__ __launch_bounds__(256, (D <= 64 ? 3 : 2)) void infonce_fwd_kernel(con
     if (h == 0 && row < m_rows) part[(int64_t)split * m_rows + row] = BCE ? make_float2(0.f, l_run[t] + l_o) : make_float2(m, l);
   }
 }
-
-#include "gcr_b3.h"  // (included inside the anonymous namespace: split-operand helpers shared with gcr_rank.hip)
 
 // deferred rescale of the flash forwards: the reference point of a row's running sums only moves when a tile's
 // maximum exceeds it by more than 2^kDefer
@@ -731,14 +649,14 @@ __global__ __launch_bounds__(64 * NW, 2) void infonce_fwd_e_kernel(const float* 
   }
 }
 
-// Engine selection.  Default: the split-operand bf16 engine for d <= 128, where forward AND backward have
-// it; d = 256 stays on the f32 MFMA (its three operand planes would not fit the registers).  The flag
+// Engine selection (use_b3, gcr_tile.h).  Default: the split-operand bf16 engine for d <= 128, where forward AND
+// backward have it; d = 256 stays on the f32 MFMA (its three operand planes would not fit the registers).  The flag
 // GCR_INFONCE_ENGINE_F32 of the _ex entry points forces the f32 MFMA.  The choice is an ARGUMENT, never
 // read from the environment: the host wrapper resolves it once per forward and hands the same flag to
 // the backward (which must recompute the forward's logits with the forward's engine, or sum_j P_ij = 1
 // only holds to ~1e-6 and near-cancelling gradients lose digits).
-bool use_b3(int d, bool force_f32 = false) { return d <= 128 && !force_f32; }
-// the two-plane f16 format of the pipelined two-product loop (EngH2 below): rows of at most unit norm (the caller's
+//
+// The two-plane f16 format of the pipelined two-product loop (EngH2 below): rows of at most unit norm (the caller's
 // promise), d <= 64, 1/tau within the pre-scale's head-room
 // (1/tau <= 20 covers every call site of the reference — tau in 0.07 .. 0.5 — and keeps the format's logit error,
 // 3 * 2^-22 * inv_tau * log2 e in the worst case, an order below the 1e-5 of the parity tests; at 1/tau = 40 .. 60 the
@@ -2231,8 +2149,6 @@ int32_t launch_fwd_o(const float* a, const float* a_scale, int64_t m, const floa
   return GCR_LAUNCH_STATUS();
 }
 
-bool dim_supported(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
-
 // ------------------------------------------------------------------------------------------
 // BCE-with-logits over the all-pairs score matrix (lightgcn.py:109-113, loss_type == "bce"):
 //   scores = user_vecs @ item_emb.T;  labels one-hot at pos_i;  F.binary_cross_entropy_with_logits(scores, labels)
@@ -2401,651 +2317,7 @@ int32_t launch_bce_bwd(const float* x, int64_t mx, const float* y, int64_t ny, c
   return reduce_splits(p, gpart, mx, D, g, s);
 }
 
-// ------------------------------------------------------------------------------------------
-// Nearest-centroid assignment for the NCL prototype step (ncl.py:340-356: faiss.Kmeans.train +
-// index.search(x, 1)): argmin_k ||x_i - c_k||^2 = argmax_k (<x_i, c_k> - 0.5 ||c_k||^2).  Same MFMA
-// tile engine as the InfoNCE forward (points stationary on the lanes, centroids streamed through
-// LDS); the epilogue is an in-lane running arg-max instead of an exp2-sum.  Ties go to the
-// smaller centroid id.
-// ------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256, (D <= 64 ? 3 : 2)) void kmeans_assign_kernel(
-    const float* __restrict__ x, int64_t n, const float* __restrict__ cent, const float* __restrict__ half_sq,
-    int64_t k, int64_t* __restrict__ assign, float* __restrict__ best_out) {
-  using S = Shape<D>;
-  __shared__ __align__(16) float lds[2][kTileJ * S::STRIDE];
-  __shared__ __align__(16) float st_bias[2][kTileJ];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i32 = lane & 31, h = lane >> 5;
-  const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * (32 * S::NT);
-  float bfrag[S::NT][S::KH];
-#pragma unroll
-  for (int t = 0; t < S::NT; ++t) load_stationary<D>(x, nullptr, n, i0 + 32 * t + i32, h, 1.0f, bfrag[t]);
-  float best[S::NT];
-  int bidx[S::NT];
-#pragma unroll
-  for (int t = 0; t < S::NT; ++t) {
-    best[t] = -INFINITY;
-    bidx[t] = 0x7fffffff;
-  }
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  float4 regs[S::NLD];
-  float bias = 0.f;
-  auto load_bias = [&](int64_t j0) {
-    if (tid < kTileJ) bias = (j0 + tid < k) ? -half_sq[j0 + tid] : -INFINITY;  // rows past k never win
-  };
-  stage_load<D>(cent, nullptr, k, 0, tid, regs);
-  load_bias(0);
-  stage_store<D>(lds[0], tid, regs);
-  if (tid < kTileJ) st_bias[0][tid] = bias;
-  __syncthreads();
-  for (int64_t tt = 0; tt < tiles; ++tt) {
-    const int cur = (int)(tt & 1);
-    const int64_t nxt = tt + 1 < tiles ? tt + 1 : tt;
-    stage_load<D>(cent, nullptr, k, nxt * kTileJ, tid, regs);
-    load_bias(nxt * kTileJ);
-    f32x16 acc[S::NT];
-    score_tile<D>(lds[cur], i32, h, bfrag, acc);
-    const int j0 = (int)(tt * kTileJ);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 bb = *reinterpret_cast<const float4*>(&st_bias[cur][8 * g + 4 * h]);
-      const float be[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int r = 4 * g + e;
-        const int j = j0 + acc_row(r, h);
-#pragma unroll
-        for (int t = 0; t < S::NT; ++t) {
-          const float v = acc[t][r] + be[e];
-          const bool better = v > best[t] || (v == best[t] && j < bidx[t]);
-          best[t] = better ? v : best[t];
-          bidx[t] = better ? j : bidx[t];
-        }
-      }
-    }
-    stage_store<D>(lds[cur ^ 1], tid, regs);
-    if (tid < kTileJ) st_bias[cur ^ 1][tid] = bias;
-    __syncthreads();
-  }
-#pragma unroll
-  for (int t = 0; t < S::NT; ++t) {
-    const float v_o = __shfl_xor(best[t], 32, 64);
-    const int j_o = __shfl_xor(bidx[t], 32, 64);
-    const bool other = v_o > best[t] || (v_o == best[t] && j_o < bidx[t]);
-    const float v = other ? v_o : best[t];
-    const int j = other ? j_o : bidx[t];
-    const int64_t row = i0 + 32 * t + i32;
-    if (h == 0 && row < n) {
-      assign[row] = j;
-      if (best_out != nullptr) best_out[row] = v;
-    }
-  }
-}
-
-// The same on the split-operand engine (d <= 128), software-pipelined by hand like the InfoNCE forward.
-// -0.5 ||c||^2 rides in as the MFMA C operand of the tile's first product; the running arg-max costs
-// three VALU instructions per score (compare, select the register number, max) plus one tile-number
-// select per tile: a lane walks its rows in increasing centroid id, so a strict `>` keeps the smallest
-// id among equal scores; the two lane halves are merged with an explicit id comparison at the end.
-template <int D>
-__global__ __launch_bounds__(256, 2) void kmeans_assign_b3_kernel(
-    const float* __restrict__ x, int64_t n, const float* __restrict__ cent, const float* __restrict__ half_sq,
-    int64_t k, int64_t* __restrict__ assign, float* __restrict__ best_out, float* __restrict__ acc_sums = nullptr,
-    float* __restrict__ acc_counts = nullptr, int n_copies = 1) {
-  using S = ShapeB3<D>;
-  constexpr int NS = 6 * S::KC * S::NT, NU = 16 * S::NT + S::NLD;
-  constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};
-  __shared__ __align__(16) unsigned char lds[2][3 * S::PLANE];
-  __shared__ __align__(16) float st_bias[2][kTileJ];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i32 = lane & 31, h = lane >> 5;
-  const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * (32 * S::NT);
-  u32x4 bq[S::NT][3][S::KC];
-#pragma unroll
-  for (int t = 0; t < S::NT; ++t) load_stationary_b3<D>(x, nullptr, n, i0 + 32 * t + i32, h, 1.0f, bq[t]);
-  float best[S::NT];
-  int btile[S::NT], breg[S::NT];
-#pragma unroll
-  for (int t = 0; t < S::NT; ++t) {
-    best[t] = -INFINITY;
-    btile[t] = 0;
-    breg[t] = 0;
-  }
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  const int64_t last = tiles - 1;
-  // One centroid tile's share of a lane between its global loads and its LDS stores.  The loads are LOADS ONLY — the rows
-  // as they are (rows past k repeat the last centroid: their bias is -inf, they never win), ½|c|² as it is, from every
-  // lane without a branch — and a tile is loaded a whole step before it is staged.  (The bias used to be negated and
-  // selected on the spot inside `if (tid < 32)`, the rows multiplied by their 0/1 scale on the spot: every tile opened with
-  // `global_load ...; s_waitcnt vmcnt(0)` in wave 0, a memory round trip that the other three waves sat out at the
-  // barrier — half of the 1.9 us a tile took.)
-  struct Staged {
-    float4 v[S::NLD];
-    float hb;
-    bool live;
-  };
-  Staged ga, gb;
-  auto load_tile = [&](int64_t t, Staged& g) {
-    const int64_t j0 = min(t, last) * kTileJ;
-#pragma unroll
-    for (int u = 0; u < S::NLD; ++u) {
-      const int idx = tid + 256 * u;
-      const int row = idx / (D / 4), c4 = idx % (D / 4);
-      const int64_t jj = min(j0 + row, k - 1);
-      g.v[u] = *reinterpret_cast<const float4*>(cent + jj * D + 4 * c4);
-    }
-    const int64_t jb = j0 + (tid & (kTileJ - 1));
-    g.hb = half_sq[min(jb, k - 1)];
-    g.live = jb < k;
-  };
-  auto store_tile = [&](unsigned char* out, int sbuf, const Staged& g) {
-#pragma unroll
-    for (int u = 0; u < S::NLD; ++u) stage_store_b3_one<D>(out, tid, g.v[u], u);
-    if (tid < kTileJ) st_bias[sbuf][tid] = g.live ? -g.hb : -INFINITY;          // rows past k never win
-  };
-  // one tile: scores of the tile in lds[buf] into `nxt` (C = bias), optionally interleaved with the
-  // arg-max over `cur` (the previous tile, number tt) and the staging of the tile held in `st`
-  auto tile = [&](auto with_cur, const f32x16 (&cur)[S::NT], f32x16 (&nxt)[S::NT], int64_t tt, int buf, const Staged& st) {
-    constexpr bool CUR = decltype(with_cur)::value;
-    const unsigned char* base = lds[buf] + i32 * S::ROWB + h * (S::KH * 2);
-    unsigned char* out = lds[buf ^ 1];
-    float binit[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 bb = *reinterpret_cast<const float4*>(&st_bias[buf][8 * g + 4 * h]);
-      binit[4 * g + 0] = bb.x; binit[4 * g + 1] = bb.y; binit[4 * g + 2] = bb.z; binit[4 * g + 3] = bb.w;
-    }
-    float bprev[S::NT];
-#pragma unroll
-    for (int t = 0; t < S::NT; ++t) bprev[t] = best[t];
-    auto micro = [&](int m) {
-      if (m < 16 * S::NT) {
-        const int r = m / S::NT, t = m % S::NT;
-        const float v = cur[t][r];
-        breg[t] = v > best[t] ? r : breg[t];
-        best[t] = fmaxf(best[t], v);
-      } else {
-        const int u = m - 16 * S::NT;
-        stage_store_b3_one<D>(out, tid, st.v[u], u);
-        if (u == 0 && tid < kTileJ) st_bias[buf ^ 1][tid] = st.live ? -st.hb : -INFINITY;
-      }
-    };
-    u32x4 ap[2][3];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) ap[0][pl] = *reinterpret_cast<const u32x4*>(base + pl * S::PLANE);
-#pragma unroll
-    for (int c = 0; c < S::KC; ++c) {
-      if (c + 1 < S::KC) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          ap[(c + 1) & 1][pl] = *reinterpret_cast<const u32x4*>(base + pl * S::PLANE + 16 * (c + 1));
-      }
-#pragma unroll
-      for (int term = 0; term < 6; ++term) {
-#pragma unroll
-        for (int t = 0; t < S::NT; ++t) {
-          const int slot = (c * 6 + term) * S::NT + t;
-          f32x16 cin = nxt[t];
-          if (c == 0 && term == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) cin[r] = binit[r];
-          }
-          nxt[t] = mfma_bf16(ap[c & 1][TA[term]], bq[t][TB[term]][c], cin);
-          if (CUR) {
-#pragma unroll
-            for (int u = slot * NU / NS; u < (slot + 1) * NU / NS; ++u) micro(u);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    if (CUR) {
-#pragma unroll
-      for (int t = 0; t < S::NT; ++t) {
-        btile[t] = best[t] > bprev[t] ? (int)tt : btile[t];
-        asm volatile("" : "+v"(best[t]), "+v"(breg[t]), "+v"(btile[t]));
-      }
-    }
-  };
-  auto argmax_only = [&](const f32x16 (&cur)[S::NT], int64_t tt) {
-#pragma unroll
-    for (int t = 0; t < S::NT; ++t) {
-      const float bp = best[t];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        breg[t] = cur[t][r] > best[t] ? r : breg[t];
-        best[t] = fmaxf(best[t], cur[t][r]);
-      }
-      btile[t] = best[t] > bp ? (int)tt : btile[t];
-    }
-  };
-  f32x16 acc_a[S::NT], acc_b[S::NT];
-  load_tile(0, ga);
-  load_tile(1, gb);
-  store_tile(lds[0], 0, ga);
-  load_tile(2, ga);
-  __syncthreads();
-  tile(std::false_type{}, acc_b, acc_a, 0, 0, gb);      // scores of tile 0; nothing to reduce yet
-  store_tile(lds[1], 1, gb);
-  __syncthreads();
-  int64_t tt = 0;
-  for (; tt + 2 <= last; tt += 2) {                     // step tt stages tile tt + 2 (loaded a step ago), loads tile tt + 3
-    load_tile(tt + 3, gb);
-    tile(std::true_type{}, acc_a, acc_b, tt, 1, ga);
-    __syncthreads();
-    load_tile(tt + 4, ga);
-    tile(std::true_type{}, acc_b, acc_a, tt + 1, 0, gb);
-    __syncthreads();
-  }
-  if (tt < last) {
-    tile(std::true_type{}, acc_a, acc_b, tt, 1, ga);
-    __syncthreads();
-    argmax_only(acc_b, last);
-  } else {
-    argmax_only(acc_a, last);
-  }
-#pragma unroll
-  for (int t = 0; t < S::NT; ++t) {
-    const int jl = best[t] > -INFINITY ? btile[t] * kTileJ + (breg[t] & 3) + 8 * (breg[t] >> 2) + 4 * h : 0x7fffffff;
-    const float v_o = __shfl_xor(best[t], 32, 64);
-    const int j_o = __shfl_xor(jl, 32, 64);
-    const bool other = v_o > best[t] || (v_o == best[t] && j_o < jl);
-    const float v = other ? v_o : best[t];
-    const int j = other ? j_o : jl;
-    const int64_t row = i0 + 32 * t + i32;
-    if (h == 0 && row < n) {
-      if (assign != nullptr) assign[row] = j;
-      if (best_out != nullptr) best_out[row] = v;
-    }
-    btile[t] = j;                                         // kept for the fused centroid update below
-  }
-  // Lloyd update fused into the search (gcr_kmeans_assign_accumulate_f32): every point's row is added to its cluster's
-  // sum straight away — 256-B float-atomic rows into private copy blockIdx % n_copies — instead of a second kernel that
-  // re-reads the assignment.  The rows are re-read from L2 (the registers hold them as bf16 planes); 8 loads in flight.
-  if (acc_sums != nullptr) {
-    float* __restrict__ sb = acc_sums + (int64_t)(blockIdx.x % n_copies) * k * D;
-    float* __restrict__ cb = acc_counts + (int64_t)(blockIdx.x % n_copies) * k;
-    constexpr int NVX = (D + 63) / 64;
-#pragma unroll
-    for (int t = 0; t < S::NT; ++t) {
-      // all rows of the tile in flight at once (d <= 64: 32 loads; a batch of 8 per round trip left the wave waiting on
-      // eight dependent L2 round trips per tile: ~20 of the iteration's 53 us), then the row atomics
-      constexpr int PB = NVX == 1 ? 32 : 8;
-      for (int p0 = 0; p0 < 32; p0 += PB) {
-        float xv[PB][NVX];
-        int cj[PB];
-#pragma unroll
-        for (int q = 0; q < PB; ++q) {
-          const int64_t row = i0 + 32 * t + p0 + q;
-          cj[q] = __builtin_amdgcn_readlane(btile[t], p0 + q);
-          if (row >= n || cj[q] < 0 || cj[q] >= k) cj[q] = -1;
-          const float* xp = x + (row < n ? row : 0) * D;
-#pragma unroll
-          for (int c = 0; c < NVX; ++c) xv[q][c] = (lane + 64 * c < D) ? xp[lane + 64 * c] : 0.f;
-        }
-#pragma unroll
-        for (int q = 0; q < PB; ++q) {
-          if (cj[q] < 0) continue;                        // wave-uniform
-#pragma unroll
-          for (int c = 0; c < NVX; ++c)
-            if (lane + 64 * c < D) atomicAdd(sb + (int64_t)cj[q] * D + lane + 64 * c, xv[q][c]);
-          if (lane == 0) atomicAdd(cb + cj[q], 1.0f);
-        }
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// The e_step's search at NCL's sizes (76.8 K sampled points x 300 centroids, 25 times per table and step) is a LATENCY
-// problem: the launch above puts ~1 wave on every SIMD, and each of its ten centroid tiles costs a wave the tile's
-// staging (split + LDS stores), a workgroup barrier and the first operand reads, none of it hidden — 19 us of search
-// for 7 us of matrix work.  Here the centroids are split into their three bf16 planes ONCE per Lloyd iteration, by
-// kmeans_image_kernel, into an image in MFMA-fragment order: for tile T, k-chunk c, plane p the 64 lanes' operand
-// registers are 1 KB of consecutive memory — one coalesced global_load_dwordx4 per fragment, served by L2 (120 KB for
-// k = 300).  A wave then needs no LDS, no barrier and no partner: 32 points stationary in registers (NT = 1: twice the
-// waves of the tiled kernel, so that the 1024 SIMDs hold 2-3 each), the next tile's twelve fragments in flight while
-// this tile's 24 MFMAs run, the running arg-max of the previous tile in their shadow.
-// ------------------------------------------------------------------------------------------
-// image[((T * KC + c) * 3 + p) * 64 + lane] = the 8 bf16 of plane p, features [h * KH + 8 c, + 8) of centroid 32 T + i32
-// (lane = 32 h + i32); bias[32 T + r] = -0.5 |c|^2, -inf past k (such a row never wins).
-template <int D>
-__global__ __launch_bounds__(256) void kmeans_image_kernel(const float* __restrict__ cent, const float* __restrict__ half_sq,
-                                                           int64_t k, u32x4* __restrict__ image, float* __restrict__ bias) {
-  using S = ShapeB3<D>;
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one thread per (tile, chunk, lane)
-  if (idx < tiles * kTileJ) bias[idx] = idx < k ? -half_sq[idx] : -INFINITY;
-  if (idx >= tiles * S::KC * 64) return;
-  const int lane = (int)(idx & 63);
-  const int c = (int)((idx >> 6) % S::KC);
-  const int64_t T = (idx >> 6) / S::KC;
-  const int i32 = lane & 31, h = lane >> 5;
-  const int64_t row = T * kTileJ + i32;
-  float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-  if (row < k) {
-    const float* p = cent + row * D + h * S::KH + 8 * c;
-    v0 = *reinterpret_cast<const float4*>(p);
-    v1 = *reinterpret_cast<const float4*>(p + 4);
-  }
-  unsigned q[3][4];
-  split3(v0.x, v0.y, q[0][0], q[1][0], q[2][0]);
-  split3(v0.z, v0.w, q[0][1], q[1][1], q[2][1]);
-  split3(v1.x, v1.y, q[0][2], q[1][2], q[2][2]);
-  split3(v1.z, v1.w, q[0][3], q[1][3], q[2][3]);
-#pragma unroll
-  for (int pl = 0; pl < 3; ++pl)
-    image[((T * S::KC + c) * 3 + pl) * 64 + lane] = (u32x4){q[pl][0], q[pl][1], q[pl][2], q[pl][3]};
-}
-
-// LOWREG: the same search at <= 128 registers per lane (four waves per SIMD): fragments are fetched one k-chunk ahead
-// (three 16-B loads in flight per lane instead of two tiles' worth), one accumulator, the arg-max right behind its tile —
-// each wave now stalls on L2 latency, and the other three waves of the SIMD cover it.  What it buys is CO-RESIDENCE: a
-// wave of this kernel fits into the registers the InfoNCE loops of the same training step leave free on a SIMD (2 x 176-192
-// of 512), so the e_step's chain of small launches no longer waits for those grids to drain.
-// INCR (gcr_kmeans_search_image_incr_f32): the cluster sums are kept in 64-bit FIXED POINT across the Lloyd iterations and
-// only the points whose assignment CHANGED touch them — the row leaves its old cluster's sum and joins the new one's.
-// Integer adds are exact and commute, so the incremental sums equal a fresh accumulation bit for bit, in any order: no
-// drift over the 25 iterations, and the e_step becomes run-to-run reproducible (float row atomics are not).  After the first
-// iterations a few per cent of the points move, and the accumulation — 15-19 of an iteration's ~46 us as float row atomics
-// at the memory-side unit's rate — all but disappears (3-4 full passes' worth over 25 iterations instead of 25).
-// q = round(x * qscale[0]), qscale[0] a power of two with |q| < 2^30 (set from max |x| by the caller).
-template <int D, bool LOWREG = false, bool INCR = false>
-__global__ __launch_bounds__(256, LOWREG ? 4 : 2) void kmeans_search_img_kernel(
-    const float* __restrict__ x, int64_t n, const u32x4* __restrict__ image, const float* __restrict__ bias, int64_t k,
-    int64_t* __restrict__ assign, float* __restrict__ acc_sums, float* __restrict__ acc_counts, int n_copies,
-    int32_t* __restrict__ prev_assign = nullptr, const float* __restrict__ qscale = nullptr,
-    long long* __restrict__ sums_q = nullptr, int32_t* __restrict__ counts_i = nullptr) {
-  using S = ShapeB3<D>;
-  constexpr int KC = S::KC, NF = 3 * KC;                   // fragments per centroid tile
-  constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};     // (streamed plane, stationary plane), smallest terms first
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i32 = lane & 31, h = lane >> 5;
-  const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * 32;
-  if (i0 >= n) return;                                      // (whole waves only: nothing below synchronises across waves)
-  u32x4 bq[3][KC];
-  load_stationary_b3<D>(x, nullptr, n, i0 + i32, h, 1.0f, bq);
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  float best = -INFINITY;
-  int btile = 0, breg = 0;
-  u32x4 fa[NF], fb[NF];
-  float4 ba[4], bb[4];
-  auto load_tile = [&](int64_t t, u32x4 (&f)[NF], float4 (&b4)[4]) {
-    const int64_t tt = min(t, tiles - 1);
-    const u32x4* base = image + tt * (NF * 64) + lane;
-#pragma unroll
-    for (int q = 0; q < NF; ++q) f[q] = base[q * 64];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) b4[g] = *reinterpret_cast<const float4*>(bias + tt * kTileJ + 8 * g + 4 * h);
-  };
-  auto scores = [&](const u32x4 (&f)[NF], const float4 (&b4)[4], f32x16& acc) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      acc[4 * g + 0] = b4[g].x; acc[4 * g + 1] = b4[g].y; acc[4 * g + 2] = b4[g].z; acc[4 * g + 3] = b4[g].w;
-    }
-#pragma unroll
-    for (int c = 0; c < KC; ++c)
-#pragma unroll
-      for (int term = 0; term < 6; ++term) acc = mfma_bf16(f[c * 3 + TA[term]], bq[TB[term]][c], acc);
-  };
-  auto argmax = [&](const f32x16& acc, int64_t t) {
-    const float bp = best;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      breg = acc[r] > best ? r : breg;
-      best = fmaxf(best, acc[r]);
-    }
-    btile = best > bp ? (int)t : btile;                     // a lane walks its rows in increasing centroid id: strict > keeps the smallest
-  };
-  if constexpr (LOWREG) {
-    const u32x4* fp = image + lane;
-    u32x4 cur[3], nxt[3];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) cur[pl] = fp[pl * 64];
-    for (int64_t t = 0; t < tiles; ++t) {
-      f32x16 acc;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const float4 b4 = *reinterpret_cast<const float4*>(bias + t * kTileJ + 8 * g + 4 * h);
-        acc[4 * g + 0] = b4.x; acc[4 * g + 1] = b4.y; acc[4 * g + 2] = b4.z; acc[4 * g + 3] = b4.w;
-      }
-#pragma unroll
-      for (int c = 0; c < KC; ++c) {
-        // the next chunk's three fragments (the next tile's first ones behind the last chunk; the image is read once past
-        // its end by the last tile: clamped)
-        const int64_t nq = min((t * KC + c + 1) * 3, (tiles * KC - 1) * 3);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) nxt[pl] = fp[(nq + pl) * 64];
-#pragma unroll
-        for (int term = 0; term < 6; ++term) acc = mfma_bf16(cur[TA[term]], bq[TB[term]][c], acc);
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) cur[pl] = nxt[pl];
-      }
-      argmax(acc, t);
-    }
-  } else {
-  f32x16 acc_a, acc_b;
-  load_tile(0, fa, ba);
-  load_tile(1, fb, bb);
-  scores(fa, ba, acc_a);
-  int64_t t = 0;
-  for (; t + 2 < tiles; t += 2) {                           // tile t's scores are in acc_a, tile t + 1's fragments in fb
-    load_tile(t + 2, fa, ba);
-    scores(fb, bb, acc_b);
-    argmax(acc_a, t);
-    load_tile(t + 3, fb, bb);
-    scores(fa, ba, acc_a);
-    argmax(acc_b, t + 1);
-  }
-  argmax(acc_a, t);
-  if (t + 1 < tiles) {
-    scores(fb, bb, acc_b);
-    argmax(acc_b, t + 1);
-  }
-  }
-  const int jl = best > -INFINITY ? btile * kTileJ + (breg & 3) + 8 * (breg >> 2) + 4 * h : 0x7fffffff;
-  const float v_o = __shfl_xor(best, 32, 64);
-  const int j_o = __shfl_xor(jl, 32, 64);
-  const bool other = v_o > best || (v_o == best && j_o < jl);
-  const int j = other ? j_o : jl;
-  const int64_t row = i0 + i32;
-  if (h == 0 && row < n && assign != nullptr) assign[row] = j;
-  if constexpr (INCR) {
-    const float qs = qscale[0];
-    // private copy = workgroup % n_copies (the first iterations move every point: 76.8 K 512-B rows onto a few hundred
-    // rows of ONE copy serialise in the memory-side atomic unit: 144 us for the first launch); integer sums of the copies
-    // add up exactly, whichever copy a row joined and whichever it leaves
-    sums_q += (int64_t)(blockIdx.x % n_copies) * k * D;
-    counts_i += (int64_t)(blockIdx.x % n_copies) * k;
-    const int old_l = (h == 0 && row < n) ? prev_assign[row] : -1;
-    const bool moved_l = h == 0 && row < n && old_l != j;
-    if (moved_l) prev_assign[row] = j;
-    unsigned long long moved = __ballot(moved_l);           // bit q: point q of the wave changed cluster
-    while (moved != 0ull) {                                 // wave-uniform walk over the moved points only
-      const int q = __builtin_ctzll(moved);
-      moved &= moved - 1ull;
-      const int cn = __builtin_amdgcn_readlane(j, q), co = __builtin_amdgcn_readlane(old_l, q);
-      const float* xp = x + (i0 + q) * D;
-#pragma unroll
-      for (int c = 0; c < (D + 63) / 64; ++c) {
-        if (lane + 64 * c < D) {
-          const long long v = __float2ll_rn(xp[lane + 64 * c] * qs);
-          if (cn >= 0 && cn < k) atomicAdd(reinterpret_cast<unsigned long long*>(sums_q + (int64_t)cn * D + lane + 64 * c), (unsigned long long)v);
-          if (co >= 0 && co < k) atomicAdd(reinterpret_cast<unsigned long long*>(sums_q + (int64_t)co * D + lane + 64 * c), (unsigned long long)(-v));
-        }
-      }
-      if (lane == 0) {
-        if (cn >= 0 && cn < k) atomicAdd(counts_i + cn, 1);
-        if (co >= 0 && co < k) atomicAdd(counts_i + co, -1);
-      }
-    }
-    return;
-  }
-  if (acc_sums == nullptr) return;
-  // Lloyd update fused in, as in kmeans_assign_b3_kernel: every point's row goes to its cluster's sum as one 256-B
-  // float-atomic row (private copy = workgroup % n_copies), all 32 rows of the wave loaded before the first atomic
-  float* __restrict__ sb = acc_sums + (int64_t)(blockIdx.x % n_copies) * k * D;
-  float* __restrict__ cb = acc_counts + (int64_t)(blockIdx.x % n_copies) * k;
-  constexpr int NVX = (D + 63) / 64;
-  constexpr int PB = 32;                                    // rows in flight (the point planes are dead by now)
-#pragma unroll
-  for (int p0 = 0; p0 < 32; p0 += PB) {
-    float xv[PB][NVX];
-    int cj[PB];
-#pragma unroll
-    for (int q = 0; q < PB; ++q) {
-      const int64_t r = i0 + p0 + q;
-      cj[q] = __builtin_amdgcn_readlane(j, p0 + q);
-      if (r >= n || cj[q] < 0 || cj[q] >= k) cj[q] = -1;
-      const float* xp = x + (r < n ? r : 0) * D;
-#pragma unroll
-      for (int c = 0; c < NVX; ++c) xv[q][c] = (lane + 64 * c < D) ? xp[lane + 64 * c] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < PB; ++q) {
-      if (cj[q] < 0) continue;                              // wave-uniform
-#pragma unroll
-      for (int c = 0; c < NVX; ++c)
-        if (lane + 64 * c < D) atomicAdd(sb + (int64_t)cj[q] * D + lane + 64 * c, xv[q][c]);
-      if (lane == 0) atomicAdd(cb + cj[q], 1.0f);
-    }
-  }
-}
-
-// (Tried and removed in round 4: the image shared by a workgroup's four waves through a four-slot LDS ring filled by LDS-DMA
-// three tiles ahead — global_load_lds issued from inline assembly so that hipcc does not drain it with vmcnt(0), counted
-// vmcnt + one raw s_barrier per tile, 64 points per wave: an eighth of the L2 traffic, same assignments, 29.4 us against
-// 27.4 us for the search alone and 8.74 against 8.42 ms for the NCL iteration.  The three designs — LDS staging with a
-// barrier per tile 32 us, per-wave L2 streaming 27 us, LDS-DMA ring 29 us — all sit at ~2 us per centroid tile for 0.75 us
-// of matrix work at 2.4 GHz: what they share is 2400 wave-tiles on 1024 SIMDs (2.3 per SIMD: a makespan of 3) and the
-// clock the chip holds under 1024 SIMDs of back-to-back bf16 MFMAs, not their operand path.)
 }  // namespace
-
-extern "C" int64_t gcr_kmeans_image_bytes(int64_t k, int32_t d) {
-  if (k < 1 || !(d == 32 || d == 64 || d == 128)) return 0;
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  return tiles * (3 * (d / 16) * 64 * 16 + kTileJ * (int64_t)sizeof(float));      // fragments, then the bias rows
-}
-
-extern "C" int32_t gcr_kmeans_centroid_image_f32(const float* centroids, const float* half_sqnorm, int64_t k, int32_t d,
-                                                 void* image, void* stream) {
-  GCR_CHECK_ARG(k >= 1 && k < (1ll << 31));
-  if (!(d == 32 || d == 64 || d == 128)) return GCR_EUNSUPPORTED;
-  GCR_CHECK_ARG(centroids && half_sqnorm && image);
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  u32x4* img = reinterpret_cast<u32x4*>(image);
-  float* bias = reinterpret_cast<float*>(img + tiles * 3 * (d / 16) * 64);
-  const int64_t threads = tiles * (d / 16) * 64;           // >= tiles * 32: covers the bias rows too
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((threads + 255) / 256));
-  switch (d) {
-    case 32: hipLaunchKernelGGL((kmeans_image_kernel<32>), grid, dim3(256), 0, s, centroids, half_sqnorm, k, img, bias); break;
-    case 64: hipLaunchKernelGGL((kmeans_image_kernel<64>), grid, dim3(256), 0, s, centroids, half_sqnorm, k, img, bias); break;
-    default: hipLaunchKernelGGL((kmeans_image_kernel<128>), grid, dim3(256), 0, s, centroids, half_sqnorm, k, img, bias); break;
-  }
-  return GCR_LAUNCH_STATUS();
-}
-
-extern "C" int32_t gcr_kmeans_search_image_f32(const float* x, int64_t n, const void* image, int64_t k, int32_t d,
-                                               int64_t* assign, float* sums, float* counts, int32_t n_copies, uint32_t flags,
-                                               void* stream) {
-  GCR_CHECK_ARG(n >= 0 && k >= 1 && k < (1ll << 31) && (flags & ~(uint32_t)GCR_KMEANS_SEARCH_LOW_REGISTERS) == 0);
-  if (!(d == 32 || d == 64)) return GCR_EUNSUPPORTED;      // (d = 128: the point planes + two tiles of fragments exceed 256 registers)
-  if (n == 0) return GCR_OK;
-  GCR_CHECK_ARG(x && image && (assign || sums));
-  GCR_CHECK_ARG((sums == nullptr) == (counts == nullptr) && (sums == nullptr || (n_copies >= 1 && n_copies <= 64)));
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  const u32x4* img = reinterpret_cast<const u32x4*>(image);
-  const float* bias = reinterpret_cast<const float*>(img + tiles * 3 * (d / 16) * 64);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((n + 127) / 128));
-  const bool low = (flags & GCR_KMEANS_SEARCH_LOW_REGISTERS) != 0;
-  if (d == 32) {
-    if (low) hipLaunchKernelGGL((kmeans_search_img_kernel<32, true>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-    else hipLaunchKernelGGL((kmeans_search_img_kernel<32, false>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-  } else {
-    if (low) hipLaunchKernelGGL((kmeans_search_img_kernel<64, true>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-    else hipLaunchKernelGGL((kmeans_search_img_kernel<64, false>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-  }
-  return GCR_LAUNCH_STATUS();
-}
-
-extern "C" int32_t gcr_kmeans_search_image_incr_f32(const float* x, int64_t n, const void* image, int64_t k, int32_t d,
-                                                    int32_t* prev_assign, const float* qscale, int64_t* sums_q,
-                                                    int32_t* counts, int32_t n_copies, uint32_t flags, void* stream) {
-  GCR_CHECK_ARG(n >= 0 && k >= 1 && k < (1ll << 31) && (flags & ~(uint32_t)GCR_KMEANS_SEARCH_LOW_REGISTERS) == 0);
-  GCR_CHECK_ARG(n_copies >= 1 && n_copies <= 64);
-  if (!(d == 32 || d == 64)) return GCR_EUNSUPPORTED;
-  if (n == 0) return GCR_OK;
-  GCR_CHECK_ARG(x && image && prev_assign && qscale && sums_q && counts);
-  const int64_t tiles = (k + kTileJ - 1) / kTileJ;
-  const u32x4* img = reinterpret_cast<const u32x4*>(image);
-  const float* bias = reinterpret_cast<const float*>(img + tiles * 3 * (d / 16) * 64);
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)((n + 127) / 128));
-  const bool low = (flags & GCR_KMEANS_SEARCH_LOW_REGISTERS) != 0;
-  long long* sq = reinterpret_cast<long long*>(sums_q);
-
-#define GCR_KMI(DD, LOW)                                                                                                \
-  hipLaunchKernelGGL((kmeans_search_img_kernel<DD, LOW, true>), grid, dim3(256), 0, s, x, n, img, bias, k, (int64_t*)nullptr, \
-                     (float*)nullptr, (float*)nullptr, (int)n_copies, prev_assign, qscale, sq, counts)
-  if (d == 32) {
-    if (low) GCR_KMI(32, true); else GCR_KMI(32, false);
-  } else {
-    if (low) GCR_KMI(64, true); else GCR_KMI(64, false);
-  }
-#undef GCR_KMI
-  return GCR_LAUNCH_STATUS();
-}
-
-extern "C" int32_t gcr_kmeans_assign_f32(const float* x, int64_t n, const float* centroids, const float* half_sqnorm,
-                                         int64_t k, int32_t d, int64_t* assign, float* best_score, void* stream) {
-  GCR_CHECK_ARG(n >= 0 && k >= 1 && k < (1ll << 31));
-  if (!dim_supported(d)) return GCR_EUNSUPPORTED;
-  if (n == 0) return GCR_OK;
-  GCR_CHECK_ARG(x && centroids && half_sqnorm && assign);
-  hipStream_t s = (hipStream_t)stream;
-#define GCR_KM(DD)                                                                                             \
-  hipLaunchKernelGGL((kmeans_assign_kernel<DD>), dim3((unsigned)((n + Shape<DD>::ANCHORS_PER_BLOCK - 1) /      \
-                                                                 Shape<DD>::ANCHORS_PER_BLOCK)),               \
-                     dim3(256), 0, s, x, n, centroids, half_sqnorm, k, assign, best_score)
-#define GCR_KM3(DD)                                                                                            \
-  hipLaunchKernelGGL((kmeans_assign_b3_kernel<DD>), dim3((unsigned)((n + ShapeB3<DD>::ANCHORS_PER_BLOCK - 1) / \
-                                                                    ShapeB3<DD>::ANCHORS_PER_BLOCK)),          \
-                     dim3(256), 0, s, x, n, centroids, half_sqnorm, k, assign, best_score)
-  const bool b3 = use_b3(d);
-  switch (d) {
-    case 32: if (b3) GCR_KM3(32); else GCR_KM(32); break;
-    case 64: if (b3) GCR_KM3(64); else GCR_KM(64); break;
-    case 128: if (b3) GCR_KM3(128); else GCR_KM(128); break;
-    default: GCR_KM(256); break;
-  }
-#undef GCR_KM
-#undef GCR_KM3
-  return GCR_LAUNCH_STATUS();
-}
-
-extern "C" int32_t gcr_kmeans_assign_accumulate_f32(const float* x, int64_t n, const float* centroids,
-                                                    const float* half_sqnorm, int64_t k, int32_t d, int64_t* assign,
-                                                    float* sums, float* counts, int32_t n_copies, void* stream) {
-  GCR_CHECK_ARG(n >= 0 && k >= 1 && k < (1ll << 31) && n_copies >= 1 && n_copies <= 64);
-  if (!dim_supported(d) || !use_b3(d)) return GCR_EUNSUPPORTED;      // split-operand engine only (d <= 128)
-  if (n == 0) return GCR_OK;
-  GCR_CHECK_ARG(x && centroids && half_sqnorm && sums && counts);
-  hipStream_t s = (hipStream_t)stream;
-#define GCR_KMA(DD)                                                                                            \
-  hipLaunchKernelGGL((kmeans_assign_b3_kernel<DD>), dim3((unsigned)((n + ShapeB3<DD>::ANCHORS_PER_BLOCK - 1) / \
-                                                                    ShapeB3<DD>::ANCHORS_PER_BLOCK)),          \
-                     dim3(256), 0, s, x, n, centroids, half_sqnorm, k, assign, (float*)nullptr, sums, counts, (int)n_copies)
-  switch (d) {
-    case 32: GCR_KMA(32); break;
-    case 64: GCR_KMA(64); break;
-    default: GCR_KMA(128); break;
-  }
-#undef GCR_KMA
-  return GCR_LAUNCH_STATUS();
-}
 
 extern "C" int32_t gcr_infonce_engine(int32_t d) { return dim_supported(d) && use_b3(d) ? 1 : 0; }
 

@@ -12,36 +12,19 @@
 //   3-pass radix select (11 + 11 + 10 bits) of the k-th largest key over the L2-resident row, gather
 //   the winners, bitonic sort by (score desc, item id asc).  Ties at the threshold are resolved
 //   towards the smaller item id (deterministic).
-#include "gcr_common.h"
+#include "gcr_b3.h"   // the f32 tile engine (gcr_tile.h) and the split-operand bf16 MFMA helpers
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;
-
-template <int D>
-struct RShape {
-  static constexpr int KH = D / 2;
-  static constexpr int STRIDE = D + 4;
-  static constexpr int NT = D <= 128 ? 2 : 1;
-  static constexpr int NLD = (kTile * D / 4) / 256;
-  static constexpr int ITEMS_PER_BLOCK = 4 * 32 * NT;
-};
-
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-constexpr int kTileJ = 32;
-#include "gcr_b3.h"   // split-operand bf16 MFMA helpers (inside this anonymous namespace)
-
+// (Shape<D>'s "anchors" are the stationary ITEMS here: ANCHORS_PER_BLOCK items per block)
 template <int D>
 __global__ __launch_bounds__(256, 2) void score_rows_kernel(const float* __restrict__ user_emb,
                                                             const int64_t* __restrict__ user_ids, int64_t n_query,
                                                             int64_t n_users, const float* __restrict__ item_emb,
                                                             int64_t n_items, int64_t q_tiles_per_split, int nsplit,
                                                             float* __restrict__ scores) {
-  using S = RShape<D>;
-  __shared__ __align__(16) float lds[2][kTile * S::STRIDE];
+  using S = Shape<D>;
+  __shared__ __align__(16) float lds[2][kTileJ * S::STRIDE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i32 = lane & 31, h = lane >> 5;
   const int64_t iblk = blockIdx.x / nsplit;
@@ -63,11 +46,11 @@ __global__ __launch_bounds__(256, 2) void score_rows_kernel(const float* __restr
       bfrag[t][4 * q + 3] = v.w;
     }
   }
-  const int64_t total_tiles = (n_query + kTile - 1) / kTile;
+  const int64_t total_tiles = (n_query + kTileJ - 1) / kTileJ;
   const int64_t tile0 = (int64_t)split * q_tiles_per_split;
   const int64_t tile1 = min(total_tiles, tile0 + q_tiles_per_split);
   float4 regs[S::NLD];
-  auto stage_load = [&](int64_t q0) {
+  auto stage_load_users = [&](int64_t q0) {                // (gathered by id: not the engine's stage_load)
 #pragma unroll
     for (int u = 0; u < S::NLD; ++u) {
       const int idx = tid + 256 * u;
@@ -81,41 +64,19 @@ __global__ __launch_bounds__(256, 2) void score_rows_kernel(const float* __restr
       regs[u] = v;
     }
   };
-  auto stage_store = [&](float* tile) {
-#pragma unroll
-    for (int u = 0; u < S::NLD; ++u) {
-      const int idx = tid + 256 * u;
-      const int row = idx / (D / 4), c4 = idx % (D / 4);
-      *reinterpret_cast<float4*>(tile + row * S::STRIDE + 4 * c4) = regs[u];
-    }
-  };
   if (tile0 < tile1) {
-    stage_load(tile0 * kTile);
-    stage_store(lds[0]);
+    stage_load_users(tile0 * kTileJ);
+    stage_store<D>(lds[0], tid, regs);
   }
   __syncthreads();
   for (int64_t tt = tile0; tt < tile1; ++tt) {
     const int cur = (int)((tt - tile0) & 1);
     const int64_t nxt = tt + 1 < tile1 ? tt + 1 : tt;
-    stage_load(nxt * kTile);
+    stage_load_users(nxt * kTileJ);
     f32x16 acc[S::NT];
-#pragma unroll
-    for (int t = 0; t < S::NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const float* base = lds[cur] + i32 * S::STRIDE + h * S::KH;
-#pragma unroll
-    for (int q = 0; q < S::KH / 4; ++q) {
-      const float4 av = *reinterpret_cast<const float4*>(base + 4 * q);
-      const float ae[4] = {av.x, av.y, av.z, av.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int t = 0; t < S::NT; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ae[e], bfrag[t][4 * q + e], acc[t], 0, 0, 0);
-    }
+    score_tile<D>(lds[cur], i32, h, bfrag, acc);
     // register r = query row acc_row(r, h) of this tile, lane = item: 128-B coalesced row segments
-    const int64_t q0 = tt * kTile;
+    const int64_t q0 = tt * kTileJ;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int64_t q = q0 + acc_row(r, h);
@@ -127,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void score_rows_kernel(const float* __restr
         }
       }
     }
-    stage_store(lds[cur ^ 1]);
+    stage_store<D>(lds[cur ^ 1], tid, regs);
     __syncthreads();
   }
 }
@@ -771,8 +732,8 @@ bool rank_dim_supported(int d) { return d == 32 || d == 64 || d == 128 || d == 2
 template <int D>
 int32_t launch_score(const float* user_emb, const int64_t* user_ids, int64_t n_query, int64_t n_users,
                      const float* item_emb, int64_t n_items, float* scores, hipStream_t s) {
-  const int64_t iblocks = (n_items + RShape<D>::ITEMS_PER_BLOCK - 1) / RShape<D>::ITEMS_PER_BLOCK;
-  const int64_t total_tiles = (n_query + kTile - 1) / kTile;
+  const int64_t iblocks = (n_items + Shape<D>::ANCHORS_PER_BLOCK - 1) / Shape<D>::ANCHORS_PER_BLOCK;
+  const int64_t total_tiles = (n_query + kTileJ - 1) / kTileJ;
   int64_t nsplit = iblocks * 2 <= 512 ? 512 / iblocks : (total_tiles + 63) / 64;
   if (nsplit > total_tiles) nsplit = total_tiles;
   if (nsplit < 1) nsplit = 1;

@@ -29,21 +29,16 @@
 // gcr_directau.hip.  Per-split partials are added in split (and view) order by the last kernel, which applies the
 // normalisation backward and writes row uniq[i] of each gradient table: one writer per row, no float atomics, bitwise
 // reproducible.
-#include "gcr_common.h"
+#include "gcr_tile.h"   // f32x16, acc_row, kTileJ = 32 rows of a tile
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTile = 32;
 constexpr int kViews = 3;
 constexpr int kMaxSplits = 8;
 constexpr int kMaxK = 32;
 constexpr float kNormEps = 1e-12f;   // F.normalize's eps
 constexpr int kNoCol = 0x7fffffff;
 constexpr float kMaxInvT = 40.f;    // e = exp((S - 1) / t) >= exp(-2 / t) stays a normal f32
-
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(192) void tri_sweep_kernel(const float* __restrict_
   const int tid = threadIdx.x, lane = tid & 63, v = tid >> 6;
   const int l32 = lane & 31, h = lane >> 5;
   const int split = blockIdx.y;
-  const int64_t i = (int64_t)blockIdx.x * kTile + l32;
+  const int64_t i = (int64_t)blockIdx.x * kTileJ + l32;
   const bool row_ok = i < m;
   const float* E = xhat + (int64_t)v * m * D;
   const float* A = xhat + (int64_t)3 * m * D;
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(192) void tri_sweep_kernel(const float* __restrict_
   }
   sum_t run = 0;
   for (int jt = split; jt < n_tiles; jt += n_splits) {
-    const int64_t b0 = (int64_t)jt * kTile;
+    const int64_t b0 = (int64_t)jt * kTileJ;
     float xc[D / 2];
     load_half_row<D>(A, b0 + l32, b0 + l32 < m, h, xc);
     f32x16 acc;
@@ -221,7 +216,7 @@ __global__ __launch_bounds__(256) void tri_finish_kernel(const float* __restrict
   __shared__ float cv[4][2 * kMaxSplits * kMaxK];
   __shared__ int cc[4][2 * kMaxSplits * kMaxK];
   __shared__ int sel[4][kMaxK];
-  __shared__ float sc[4][kTile];
+  __shared__ float sc[4][kTileJ];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* A = xhat + (int64_t)3 * m * D;
   for (int64_t w = (int64_t)blockIdx.x * 4 + wave; w < kViews * m; w += (int64_t)gridDim.x * 4) {
@@ -313,11 +308,11 @@ __global__ __launch_bounds__(192) void tri_bwd_sweep_kernel(const float* __restr
                                                             const uint32_t* __restrict__ member, const float* __restrict__ g,
                                                             float* __restrict__ part) {
   constexpr int kStride = D + 1;
-  __shared__ float swt[kViews][kTile * kStride];
+  __shared__ float swt[kViews][kTileJ * kStride];
   const int tid = threadIdx.x, lane = tid & 63, v = tid >> 6;
   const int l32 = lane & 31, h = lane >> 5;
   const int split = blockIdx.y;
-  const int64_t f = (int64_t)blockIdx.x * kTile + l32;
+  const int64_t f = (int64_t)blockIdx.x * kTileJ + l32;
   const bool f_ok = f < m;
   const float* F = xhat + (int64_t)(COLSIDE ? 3 : v) * m * D;
   const float* S = xhat + (int64_t)(COLSIDE ? v : 3) * m * D;
@@ -336,9 +331,9 @@ __global__ __launch_bounds__(192) void tri_bwd_sweep_kernel(const float* __restr
     for (int r = 0; r < 16; ++r) oacc[ch][r] = 0.f;
   float* mine = swt[v];
   for (int st = split; st < n_tiles; st += n_splits) {
-    const int64_t s0 = (int64_t)st * kTile;
+    const int64_t s0 = (int64_t)st * kTileJ;
     __syncthreads();
-    for (int idx = lane; idx < kTile * D; idx += 64) {
+    for (int idx = lane; idx < kTileJ * D; idx += 64) {
       const int row = idx / D, c = idx - row * D;
       mine[row * kStride + c] = s0 + row < m ? S[(s0 + row) * D + c] : 0.f;
     }
@@ -439,7 +434,7 @@ struct TriWorkspace {
 
 TriWorkspace tri_layout(int64_t m, int d, int k) {
   TriWorkspace w;
-  const int64_t n_tiles = (m + kTile - 1) / kTile;
+  const int64_t n_tiles = (m + kTileJ - 1) / kTileJ;
   const int ns = splits_for(n_tiles < 1 ? 1 : n_tiles);
   w.xhat = 0;
   w.inv_norm = w.xhat + align64f(4 * m * d);
@@ -475,7 +470,7 @@ extern "C" int64_t gcr_tri_workspace_bytes(int64_t m, int32_t d, int32_t k) {
 }
 
 extern "C" int64_t gcr_tri_member_words(int64_t m) {
-  return m < 1 ? 0 : kViews * m * ((m + kTile - 1) / kTile);
+  return m < 1 ? 0 : kViews * m * ((m + kTileJ - 1) / kTileJ);
 }
 
 #define GCR_TRI_BY_D(CALL) \
@@ -501,7 +496,7 @@ extern "C" int32_t gcr_tri_fwd_f32(const float* x_f, const float* x_s, const flo
   GCR_CHECK_ARG(x_f && x_s && x_r && aug && uniq && positive && rsum && inv_norm && member && workspace);
   const TriWorkspace w = tri_layout(m, d, k);
   float* ws = reinterpret_cast<float*>(workspace);
-  const int n_tiles = (int)((m + kTile - 1) / kTile);
+  const int n_tiles = (int)((m + kTileJ - 1) / kTileJ);
   const int ns = splits_for(n_tiles);
   TriTabs T;
   T.tab[0] = x_f; T.tab[1] = x_s; T.tab[2] = x_r; T.tab[3] = aug;
@@ -543,7 +538,7 @@ extern "C" int32_t gcr_tri_bwd_f32(const float* x_f, const float* x_s, const flo
   GCR_CHECK_ARG(x_f && x_s && x_r && aug && uniq && rsum && member && g && d_f && d_s && d_r && d_aug && workspace);
   const TriWorkspace w = tri_layout(m, d, k);
   float* ws = reinterpret_cast<float*>(workspace);
-  const int n_tiles = (int)((m + kTile - 1) / kTile);
+  const int n_tiles = (int)((m + kTileJ - 1) / kTileJ);
   const int ns = splits_for(n_tiles);
   TriTabs T;
   T.tab[0] = x_f; T.tab[1] = x_s; T.tab[2] = x_r; T.tab[3] = aug;
