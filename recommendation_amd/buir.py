@@ -10,7 +10,8 @@ BUIR_NB) on the HIP ops.
     update_target                                             :251-257           functional.ema_rows_ (gcr_ema_rows_f32)
     the loop body: forward, loss, zero_grad, backward, Adam, update_target   :194-203   BUIRModel.train_step
     get_embedding (no dropout, online encoder)                :264-267, 328-340  BUIRModel.get_embedding
-    train, save, predict, test, fast_evaluation, evaluate     :149-173, 189-232  the methods of the same names
+    train, save, predict                                      :149-166, 189-225  the methods of the same names
+    test, fast_evaluation, evaluate                           :167-173, 227-232  model_base.RankingModel over `_final`
 
 The reference's quirks, kept:
   * `tau` IS the momentum of the target update (:181); `lambda`, `factors` and `max.epoch` are never read, and training is
@@ -33,11 +34,10 @@ import torch
 
 from . import functional as Fn
 from .encoders import Interaction
-from .evaluate import ranking_evaluation, test as rank_test
+from .model_base import MASK64, RankingModel, default_device, index_batch, is_prepared, prepared_data, seeded
 from .optim import FusedAdam
 from .sampler import next_batch_pairwise
 
-_MASK64 = 2 ** 64 - 1
 STATE_NAMES = {"online_encoder.embedding_dict.user_emb": "online_user", "online_encoder.embedding_dict.item_emb": "online_item",
                "target_encoder.embedding_dict.user_emb": "target_user", "target_encoder.embedding_dict.item_emb": "target_item",
                "predictor.weight": "weight", "predictor.bias": "bias"}
@@ -52,7 +52,7 @@ def parse_config(conf):
         topN=[int(n) for n in conf.get("item.ranking.topN", [10, 20, 30, 50])])
 
 
-class BUIRModel:
+class BUIRModel(RankingModel):
     def __init__(self, conf, train_set, test_set, device=None, seed=0):
         """conf: conf['BUIR']['n_layer' | 'tau' | 'drop_rate'], `emb_size` (64), `lr` (1e-3), `batch_size` (2048),
         `item.ranking.topN` ([10, 20, 30, 50]).  seed: initial tables, predictor, batch order and the dropout draws are
@@ -61,12 +61,11 @@ class BUIRModel:
         for k, v in vars(parse_config(conf)).items():
             setattr(self, k, v)
         self.max_N = max(self.topN)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.data = train_set if hasattr(train_set, "norm_adj") else Interaction(conf, train_set, test_set, device=self.device)
+        self.device = default_device(device)
+        self.data = train_set if is_prepared(train_set, "norm_adj") else Interaction(conf, train_set, test_set, device=self.device)
         n_u, n_i, d = self.data.user_num, self.data.item_num, self.emb_size
         self.norm_adj = self.data.norm_adj              # the raw adjacency, duplicates kept (Q1)
-        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
-            torch.manual_seed(self.seed)
+        with seeded(self.seed, self.device):
             xav = torch.nn.init.xavier_uniform_
             self.online_user = torch.nn.Parameter(xav(torch.empty(n_u, d, device=self.device)))
             self.online_item = torch.nn.Parameter(xav(torch.empty(n_i, d, device=self.device)))
@@ -85,9 +84,8 @@ class BUIRModel:
         """BUIRModel over an operator that already lives on the device: the raw bipartite adjacency [U + I, U + I], the
         training pairs' dense ids and the CSR of the distinct pairs (int64 [U + 1], int32 [nnz]) — what the training step
         reads from the data object without the Python id maps (scripts/perf_buir_step.py)."""
-        data = types.SimpleNamespace(user_num=int(n_users), item_num=norm_adj.n_rows - int(n_users), device=norm_adj.device,
-                                     norm_adj=norm_adj, uid_dev=uid_dev, iid_dev=iid_dev, user_rowptr=user_rowptr,
-                                     user_items_sorted=user_items_sorted, test_set={}, training_set_u={}, user={}, item={})
+        data = prepared_data(n_users, norm_adj.n_rows - int(n_users), norm_adj.device, norm_adj=norm_adj, uid_dev=uid_dev,
+                             iid_dev=iid_dev, user_rowptr=user_rowptr, user_items_sorted=user_items_sorted)
         return cls(conf, data, None, device=norm_adj.device, **kw)
 
     def parameters(self):
@@ -114,7 +112,7 @@ class BUIRModel:
         nnz, out = self.norm_adj.nnz, []
         for enc in (0, 1):
             rate = float(np.random.default_rng([self.seed, int(step), enc]).random()) * self.drop_rate
-            mseed = ((self.seed * 1_000_003 + int(step)) * 2 + enc) & _MASK64
+            mseed = ((self.seed * 1_000_003 + int(step)) * 2 + enc) & MASK64
             bits = Fn.edge_mask_bits(nnz, rate, mseed, self.device)
             if enc == 0:
                 out.append((rate, bits, Fn.edge_mask_bits(nnz, rate, mseed, self.device, edge_id=self.norm_adj.mirror_perm())))
@@ -145,7 +143,7 @@ class BUIRModel:
         """One body of :194-203 for batch = (user_idx, item_idx[, unused negatives]): the two masked propagations, the
         loss, zero_grad, backward, Adam, then the target update on the batch's rows.  views: recorded draws to replay
         (`draw_views`' layout).  Returns the detached loss."""
-        u, i = (torch.as_tensor(t, device=self.device, dtype=torch.int64).contiguous() for t in batch[:2])
+        u, i = index_batch(batch[:2], self.device)
         if views is None:
             views = self.draw_views(self.step_count)
         self.step_count += 1
@@ -177,31 +175,18 @@ class BUIRModel:
     def save(self):
         self.best_p_u, self.best_u, self.best_p_i, self.best_i = self.get_embedding()
 
-    def _final(self):
+    def _tables(self):
         if not hasattr(self, "p_u_online"):                 # never trained: the current parameters
             self.p_u_online, self.u_online, self.p_i_online, self.i_online = self.get_embedding()
         return self.p_u_online, self.u_online, self.p_i_online, self.i_online
 
     def predict(self, u):
         """:220-225: p_u[u] . i_online^T + u_online[u] . p_i^T for raw user id u."""
-        p_u, u_on, p_i, i_on = self._final()
+        p_u, u_on, p_i, i_on = self._tables()
         u = self.data.get_user_id(u)
         return (torch.matmul(p_u[u], i_on.T) + torch.matmul(u_on[u], p_i.T)).cpu().numpy()
 
-    def test(self):
+    def _final(self):
         """The same score as one product of the concatenated 2 d-wide tables [p_u | u_on] . [i_on | p_i]^T."""
-        p_u, u_on, p_i, i_on = self._final()
-        return rank_test(self.data, torch.cat([p_u, u_on], 1).contiguous(), torch.cat([i_on, p_i], 1).contiguous(), self.max_N)
-
-    def fast_evaluation(self, epoch):
-        """:167-173: the four metrics at max_N; bestPerformance follows Recall."""
-        lines = ranking_evaluation(self.data.test_set, self.test(), [self.max_N], device=self.device)
-        performance = {k: float(v) for m in lines[1:] for k, v in [m.strip().split(":")]}
-        if not self.bestPerformance or performance.get("Recall", 0) > self.bestPerformance[1].get("Recall", 0):
-            self.bestPerformance = [epoch + 1, performance]
-        return performance
-
-    def evaluate(self):
-        """:227-232: every cut-off's metrics flattened into one dict, so the last cut-off's four remain."""
-        metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN, device=self.device)
-        return {k: float(v) for m in metrics[1:] if ":" in m for k, v in [m.strip().split(":", 1)]}
+        p_u, u_on, p_i, i_on = self._tables()
+        return torch.cat([p_u, u_on], 1).contiguous(), torch.cat([i_on, p_i], 1).contiguous()

@@ -17,27 +17,24 @@ Stage by stage (reference line -> here):
     torch.optim.Adam(lr) | SGD(lr, 0.9)       directau.py:211-216   optim.FusedAdam | optim.FusedSGD (gcr_adam_step_f32 |
                                                                     gcr_sgd_momentum_step_f32)
     next_batch_pairwise                       directau.py:14-32     sampler.next_batch_pairwise (gcr_neg_sample)
-    test / evaluate                           directau.py:167-178, 261-266   evaluate.test / ranking_evaluation (gcr_rank_*)
+    test / evaluate / predict                 directau.py:167-178, 253-266   model_base.RankingModel over `_final`
+                                                                    (evaluate.test / ranking_evaluation: gcr_rank_*)
 The tuner (directau.py:296-358), the print every 100 batches (directau.py:230-233) and the result files are out of
 scope.
 """
 from __future__ import annotations
-
-import types
 
 import torch
 
 from . import functional as Fn
 from . import losses as Ls
 from .encoders import Interaction, LGCNEncoder
-from .evaluate import ranking_evaluation, test as rank_test
+from .model_base import RankingModel, default_device, index_batch, is_prepared, prepared_data, seeded
 from .optim import FusedAdam, FusedSGD
-from .sampler import next_batch_pairwise
-
-MAX_TRIALS = 1 << 20          # directau.py:27-31 retries until a negative is found
+from .sampler import MAX_TRIALS, next_batch_pairwise          # directau.py:27-31 retries until a negative is found
 
 
-class DirectAUModel:
+class DirectAUModel(RankingModel):
     def __init__(self, conf, train_set, test_set, device=None, seed=0):
         """conf: the reference's keys (directau.py:197-207) — conf['DirectAU']['gamma' | 'n_layers'], `reg.lambda` (1e-4),
         `batch.size` (512), `embedding.size` (64), `learning.rate` (1e-3), `optimizer` ('adam' | 'sgd'),
@@ -53,13 +50,11 @@ class DirectAUModel:
         self.optimizer_type = str(conf.get("optimizer", "adam")).lower()
         if self.optimizer_type not in ("adam", "sgd"):
             raise ValueError(f"Unsupported optimizer: {self.optimizer_type}")          # directau.py:216
-        self.topN = [int(n) for n in conf.get("item.ranking.topN", [10, 20, 30, 50])]
-        self.max_N = max(self.topN)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self._read_topn(conf)
+        self.device = default_device(device)
         # `train_set` may be a prepared data object (`from_graph`): graphs too large for Python id maps
-        self.data = train_set if hasattr(train_set, "norm_adj") else Interaction(conf, train_set, test_set, device=self.device)
-        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
-            torch.manual_seed(self.seed)              # initial weights: a function of `seed`, the caller's RNG untouched
+        self.data = train_set if is_prepared(train_set, "norm_adj") else Interaction(conf, train_set, test_set, device=self.device)
+        with seeded(self.seed, self.device):
             self.model = LGCNEncoder(self.data, self.emb_size, self.n_layers)
         params = list(self.model.parameters())
         self.optimizer = FusedAdam(params, lr=self.lRate) if self.optimizer_type == "adam" else \
@@ -70,8 +65,7 @@ class DirectAUModel:
     def from_graph(cls, conf, norm_adj, user_num, item_num, **kw):
         """DirectAUModel over an operator that already lives on the device: what the training step reads from
         `Interaction` — sizes, the operator, the device — without the Python id maps (scripts/perf_directau_step.py)."""
-        data = types.SimpleNamespace(user_num=int(user_num), item_num=int(item_num), norm_adj=norm_adj, device=norm_adj.device,
-                                     test_set={}, training_set_u={}, user={}, item={})
+        data = prepared_data(user_num, item_num, norm_adj.device, norm_adj=norm_adj)
         return cls(conf, data, None, device=norm_adj.device, **kw)
 
     def encode(self):
@@ -82,8 +76,7 @@ class DirectAUModel:
 
     def losses(self, u, i, j):
         """directau.py:220-226 on the HIP path: (pos_loss, neg_loss, l2, loss), differentiable, no host sync."""
-        dev = self.device
-        u, i, j = (torch.as_tensor(t, device=dev, dtype=torch.int64).contiguous() for t in (u, i, j))
+        u, i, j = index_batch((u, i, j), self.device)
         user_emb, item_emb = self.encode()
         return Ls.directau_loss(user_emb, item_emb, u, i, j, self.gamma, self.reg, self.batch_size)
 
@@ -91,11 +84,7 @@ class DirectAUModel:
         """One body of directau.py:219-229 for batch = (user_idx, pos_idx, neg_idx): zero_grad, losses, backward, optimizer
         step.  Returns the detached terms (pos_loss, neg_loss, l2, loss); l2 is l2_reg_loss before the division by the
         configured batch size that `loss` applies."""
-        self.optimizer.zero_grad(set_to_none=True)
-        out = self.losses(*batch)
-        out[3].backward()
-        self.optimizer.step()
-        return tuple(t.detach() for t in out)
+        return self._optimise(*batch)
 
     def embeddings(self):
         with torch.no_grad():
@@ -128,16 +117,3 @@ class DirectAUModel:
         if not hasattr(self, "user_emb"):                                               # directau.py:255-258
             self.user_emb, self.item_emb = self.embeddings()
         return self.user_emb, self.item_emb
-
-    def predict(self, u):
-        user_emb, item_emb = self._final()
-        return torch.matmul(user_emb[self.data.get_user_id(u)], item_emb.T).cpu().numpy()
-
-    def test(self):
-        user_emb, item_emb = self._final()
-        return rank_test(self.data, user_emb, item_emb, self.max_N)
-
-    def evaluate(self):
-        """directau.py:261-266: every cut-off's metrics flattened into one dict, so the last cut-off's four remain."""
-        metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN, device=self.device)
-        return {k: float(v) for m in metrics[1:] if ":" in m for k, v in [m.strip().split(":", 1)]}

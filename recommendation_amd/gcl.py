@@ -31,13 +31,12 @@ from . import losses as Ls
 from .encoders import load_data
 from .evaluate import rank_metric_terms, rank_topk
 from .graph import CsrGraph
+from .model_base import MASK64, default_device, index_batch, optimise, seeded
 from .optim import FusedAdam
-from .sampler import EdgeRemoving, next_batch_pairwise
+from .sampler import MAX_TRIALS, EdgeRemoving, next_batch_pairwise      # gcl.py:120-124 retries forever: a large max_trials
 
 ENCODERS = ("linear", "lightgcn")
 KS = (10, 20, 30, 50)                       # gcl.py:232
-MAX_TRIALS = 1 << 20                        # gcl.py:120-124 retries forever; the sampler's docstring: a large max_trials
-_MASK64 = 2 ** 64 - 1
 
 
 class GraphView:
@@ -147,7 +146,7 @@ class GCLModel:
         self.ssl_temp, self.drop_edge, self.reg_weight = float(c["ssl_temp"]), float(c["drop_edge"]), float(c["reg_weight"])
         self.ssl_weight = float(c.get("ssl_weight", 1.0))
         self.batch_size, self.max_epoch = int(c["batch_size"]), int(c["max_epoch"])
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = default_device(device)
         tu, ti = (np.asarray(a, dtype=np.int64) for a in train)
         su, si = (np.asarray(a, dtype=np.int64) for a in test)
         if num_users is None:
@@ -164,8 +163,7 @@ class GCLModel:
         if encoder == "lightgcn":
             graph = CsrGraph.bipartite_sym_norm(self.data.uid_dev, self.data.iid_dev, self.num_users, self.num_items,
                                                 self.device)
-        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
-            torch.manual_seed(self.seed)              # initial weights: a function of `seed`, the caller's RNG untouched
+        with seeded(self.seed, self.device):
             self.model = GRACEModel(self.num_users, self.num_items, self.emb_size, self.num_layers, encoder=encoder,
                                     graph=graph, device=self.device)
         self.aug = EdgeRemoving(pe=self.drop_edge, seed=self.seed)
@@ -184,14 +182,13 @@ class GCLModel:
         out = []
         for _ in range(2):
             self.aug.calls += 1              # EdgeRemoving's counter: every view its own draws
-            seed = (self.aug.seed * 0x9E3779B97F4A7C15 + self.aug.calls) & _MASK64
+            seed = (self.aug.seed * 0x9E3779B97F4A7C15 + self.aug.calls) & MASK64
             out.append(GraphView(self.model.graph, self.drop_edge, seed))
         return tuple(out)
 
     def losses(self, users, pos, neg, views=None):
         """gcl.py:211-224 on the HIP path: (ssl_loss, bpr_loss, reg_loss, total_loss), differentiable, no host sync."""
-        dev = self.device
-        users, pos, neg = (torch.as_tensor(t, device=dev, dtype=torch.int64).contiguous() for t in (users, pos, neg))
+        users, pos, neg = index_batch((users, pos, neg), self.device)
         v1, v2 = self.views() if views is None else views
         z1, z2 = self.model(v1, v2)
         n_u = self.num_users
@@ -209,11 +206,7 @@ class GCLModel:
     def train_step(self, users, pos, neg, views=None):
         """One body of gcl.py:208-225 (zero_grad, two views, losses, backward, Adam step).  Returns the four loss terms
         as device tensors.  views: the step's two views when the caller drew them (default: `views()`)."""
-        self.optimizer.zero_grad(set_to_none=True)
-        out = self.losses(users, pos, neg, views)
-        out[3].backward()
-        self.optimizer.step()
-        return tuple(t.detach() for t in out)
+        return optimise(self, users, pos, neg, views)
 
     def train(self):
         self.model.train()
@@ -333,7 +326,7 @@ class ShardedGCLStep(nn.Module):
         self.steps += 1
         v1 = v2 = None
         if self.encoder == "lightgcn" and self.drop_edge > 0:
-            base = (self.seed * 0x9E3779B97F4A7C15 + 2 * self.steps) & _MASK64
+            base = (self.seed * 0x9E3779B97F4A7C15 + 2 * self.steps) & MASK64
             v1, v2 = ops.edge_drop(g, self.drop_edge, base + 1), ops.edge_drop(g, self.drop_edge, base + 2)
         hu1, hi1 = self._encode(v1)
         zu1, zi1 = self.proj_head(hu1), self.proj_head(hi1)

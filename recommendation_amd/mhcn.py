@@ -22,12 +22,11 @@ MHCNModel is the reference's model class (mhcn.py:316-555) on these pieces:
     forward, bpr_loss, the 20 norms, Adam      mhcn.py:528-539   MHCNModel.train_step: propagate, self_supervision,
                                                                  losses.bpr_gather_loss (BPR_NCL), optim.FusedAdam
     next_batch_pairwise                        mhcn.py:13-31     sampler.next_batch_pairwise (gcr_neg_sample)
-    train_model, save, predict, evaluate       mhcn.py:508-555   MHCNModel.train / save / predict / test / evaluate
+    train_model, save                          mhcn.py:508-518   MHCNModel.train / save
+    fast_evaluation, predict, evaluate         mhcn.py:306-312,546-555  model_base.RankingModel over `_final`
 The tuner (mhcn.py:558-), the prints and a sharded model are out of scope.
 """
 from __future__ import annotations
-
-import types
 
 import torch
 import torch.nn as nn
@@ -36,13 +35,11 @@ from . import functional as Fn
 from . import losses as Ls
 from .distributed import _hip_dual, _hip_spmm_t
 from .encoders import Interaction, multi_stream_spmm
-from .evaluate import ranking_evaluation, test as rank_test
 from .graph import CsrGraph
 from .graph_ops import build_hyper_graphs
+from .model_base import RankingModel, default_device, index_batch, is_prepared, prepared_data, seeded
 from .optim import FusedAdam
-from .sampler import next_batch_pairwise
-
-MAX_TRIALS = 1 << 20          # mhcn.py:26-30 retries until a negative is found (as directau.py's sampler)
+from .sampler import MAX_TRIALS, next_batch_pairwise          # mhcn.py:26-30 retries until a negative is found
 
 
 class MHCNEncoder(nn.Module):
@@ -252,7 +249,7 @@ def social_pairs(social_data, user):
     return torch.tensor(rows, dtype=torch.int64), torch.tensor(cols, dtype=torch.int64)
 
 
-class MHCNModel:
+class MHCNModel(RankingModel):
     def __init__(self, conf, train_set, test_set, social_data=None, device=None, seed=0):
         """conf: the reference's keys (mhcn.py:316-327) — conf['MHCN']['n_layer' | 'ss_rate'], `emb_size` (64),
         `batch_size` (2048), `lr` (1e-3), `reg_lambda` (1e-4), `max.epoch`, `item.ranking.topN` ([10, 20, 30, 50]).
@@ -266,10 +263,9 @@ class MHCNModel:
         self.lRate = conf.get("lr", 0.001)
         self.reg = conf.get("reg_lambda", 0.0001)
         self.maxEpoch = int(conf["max.epoch"])
-        self.topN = [int(n) for n in conf.get("item.ranking.topN", [10, 20, 30, 50])]
-        self.max_N = max(self.topN)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if hasattr(train_set, "graphs"):                    # prepared operators (`from_graphs`)
+        self._read_topn(conf)
+        self.device = default_device(device)
+        if is_prepared(train_set, "graphs"):                    # prepared operators (`from_graphs`)
             self.data = train_set
             graphs = train_set.graphs
         else:
@@ -278,8 +274,7 @@ class MHCNModel:
             self.social_pairs = (s_row, s_col)
             graphs = build_hyper_graphs(s_row, s_col, self.data.uid_dev, self.data.iid_dev, self.data.user_num,
                                         self.data.item_num, self.device)
-        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
-            torch.manual_seed(self.seed)              # initial weights: a function of `seed`, the caller's RNG untouched
+        with seeded(self.seed, self.device):
             self.model = MHCNEncoder(*graphs, emb_size=self.emb_size, n_layers=self.n_layers, ss_rate=self.ss_rate)
         self.optimizer = FusedAdam(list(self.model.parameters()), lr=self.lRate)
         self.bestPerformance = []
@@ -288,8 +283,7 @@ class MHCNModel:
     def from_graphs(cls, conf, h_s, h_j, h_p, r, **kw):
         """MHCNModel over operators that already live on the device (row-normalised H_s, H_j, H_p [U, U] and R [U, I]):
         what the training step reads from the data object without the Python id maps (scripts/perf_mhcn_step.py)."""
-        data = types.SimpleNamespace(user_num=r.n_rows, item_num=r.n_cols, device=r.device, graphs=(h_s, h_j, h_p, r),
-                                     test_set={}, training_set_u={}, user={}, item={})
+        data = prepared_data(r.n_rows, r.n_cols, r.device, graphs=(h_s, h_j, h_p, r))
         return cls(conf, data, None, None, device=r.device, **kw)
 
     def losses(self, u, i, j, perms=None):
@@ -309,15 +303,9 @@ class MHCNModel:
         """One body of mhcn.py:528-539 for batch = (user_idx, pos_idx, neg_idx): losses, zero_grad, backward, Adam step.
         perms: optional 9 row permutations replaying the self-supervision's randperm draws.  Returns the detached terms
         (rec_loss, reg_loss, ss_loss, total_loss)."""
-        dev = self.device
-        u, i, j = (torch.as_tensor(t, device=dev, dtype=torch.int64).contiguous() for t in batch)
         if perms is not None:
-            perms = [torch.as_tensor(p, device=dev, dtype=torch.int64) for p in perms]
-        self.optimizer.zero_grad(set_to_none=True)
-        out = self.losses(u, i, j, perms)
-        out[3].backward()
-        self.optimizer.step()
-        return tuple(t.detach() for t in out)
+            perms = [torch.as_tensor(p, device=self.device, dtype=torch.int64) for p in perms]
+        return self._optimise(*index_batch(batch, self.device), perms)
 
     def train_epoch(self, epoch):
         self.model.train()
@@ -347,24 +335,4 @@ class MHCNModel:
             self.U, self.V = fu.contiguous(), fi.contiguous()
         return self.U, self.V
 
-    def predict(self, u):
-        """mhcn.py:546-548: V @ U[u], the scores of every item for raw user id u."""
-        U, V = self._final()
-        return torch.matmul(V, U[self.data.get_user_id(u)]).cpu().numpy()
-
-    def test(self):
-        U, V = self._final()
-        return rank_test(self.data, U, V, self.max_N)
-
-    def fast_evaluation(self, epoch):
-        """mhcn.py:306-312: the four metrics at max_N; bestPerformance follows Recall."""
-        lines = ranking_evaluation(self.data.test_set, self.test(), [self.max_N], device=self.device)
-        performance = {k: float(v) for m in lines[1:] for k, v in [m.strip().split(":")]}
-        if not self.bestPerformance or performance.get("Recall", 0) > self.bestPerformance[1].get("Recall", 0):
-            self.bestPerformance = [epoch + 1, performance]
-        return performance
-
-    def evaluate(self):
-        """mhcn.py:550-555: every cut-off's metrics flattened into one dict, so the last cut-off's four remain."""
-        metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN, device=self.device)
-        return {k: float(v) for m in metrics[1:] if ":" in m for k, v in [m.strip().split(":", 1)]}
+    predict = RankingModel.predict_item_major             # mhcn.py:546-548: V @ U[u]

@@ -8,7 +8,8 @@ Stage by stage (reference line -> here):
     e_step / run_kmeans (faiss)          ncl.py:340-356           kmeans.py   (gcr_kmeans_*; parity with faiss unpinned)
     bpr_loss, l2_reg_loss                ncl.py:116-123           losses.py   (gcr_bpr_*)
     ssl_layer_loss, ProtoNCE_loss        ncl.py:358-375           losses.py   (gcr_infonce_*)
-    test / evaluate                      ncl.py:253-264, 377-384  evaluate.py (gcr_score_rows_f32, gcr_topk_masked_f32)
+    test / evaluate                      ncl.py:253-264, 377-384  evaluate.py (gcr_score_rows_f32, gcr_topk_masked_f32);
+                                                                  test and predict: model_base.RankingModel over `_final`
 The tuner, logging and result files around it are out of scope.
 """
 from __future__ import annotations
@@ -18,8 +19,9 @@ import torch
 from . import functional as Fn
 from . import losses as Ls
 from .encoders import Interaction, LGCNEncoder
-from .evaluate import ranking_evaluation, test as rank_test
+from .evaluate import ranking_evaluation
 from .kmeans import FAISS_MIN_POINTS_PER_CENTROID, FAISS_NITER, FAISS_SEED, assign_to_centroids, run_kmeans
+from .model_base import RankingModel, index_batch, is_prepared, metric_lines_to_dict, prepared_data
 from .ncl_step import FusedNCLStep
 from .optim import FusedAdam
 from .sampler import next_batch_pairwise
@@ -34,7 +36,7 @@ _CONF_DEFAULTS = {"batch_size": ("batch.size", 2048), "emb_size": ("embedding.si
                   "ranking": ("item.ranking.topN", [10, 20, 30, 50])}
 
 
-class NCLModel:
+class NCLModel(RankingModel):
     def __init__(self, conf, train_set, test_set, device=None, seed=0, kmeans_niter=FAISS_NITER, kmeans_seed=FAISS_SEED,
                  fused_step=True, graph_capture=False, reorder=None, reorder_guard=True):
         """kmeans_niter / kmeans_seed: the two parameters of `faiss.Kmeans(d, k, gpu=False)` that ncl.py:352 leaves at
@@ -53,11 +55,10 @@ class NCLModel:
             setattr(self, attr, conf.get(key, default))
         for attr, key in _NCL_ARGS.items():
             setattr(self, attr, conf["NCL"][key])
-        self.topN = list(map(int, self.ranking))
-        self.max_N = max(self.topN)
+        self._read_topn(conf)
         # `train_set` may be a prepared data object (user_num, item_num, norm_adj, device, ...) instead of the triple list:
         # NCLModel.from_graph builds one around a device-resident operator (graphs too large for Python id maps)
-        self.data = train_set if hasattr(train_set, "norm_adj") else Interaction(conf, train_set, test_set, device=device,
+        self.data = train_set if is_prepared(train_set, "norm_adj") else Interaction(conf, train_set, test_set, device=device,
                                                                                   reorder=reorder, reorder_guard=reorder_guard)
         self.model = LGCNEncoder(self.data, self.emb_size, self.n_layers)
         self.user_centroids = self.item_centroids = None
@@ -69,9 +70,7 @@ class NCLModel:
     def from_graph(cls, conf, norm_adj, user_num, item_num, **kw):
         """NCLModel over an operator that already lives on the device (bench.py's 1M x 100K graph): everything the
         training step reads from `Interaction` — sizes, the operator, the device — without the Python id maps."""
-        import types
-        data = types.SimpleNamespace(user_num=int(user_num), item_num=int(item_num), norm_adj=norm_adj, device=norm_adj.device,
-                                     test_set={}, training_set_u={}, user={}, item={})
+        data = prepared_data(user_num, item_num, norm_adj.device, norm_adj=norm_adj)
         return cls(conf, data, None, device=norm_adj.device, **kw)
 
     # ncl.py:340-356
@@ -180,7 +179,7 @@ class NCLModel:
                 if self.graph_capture:
                     self._fused.capture(len(user_idx))
             dev = self.model.table.device
-            idx = [torch.as_tensor(t, device=dev, dtype=torch.int64).contiguous() for t in (user_idx, pos_idx, neg_idx)]
+            idx = index_batch(batch, dev)
             if self.graph_capture and self._fused.capturable_for(len(user_idx)):
                 return self._fused.replay(*idx)
             return self._fused(*idx)
@@ -221,20 +220,11 @@ class NCLModel:
             self.user_emb, self.item_emb, _ = self.model()
         return self.evaluate()
 
-    def test(self):
-        return rank_test(self.data, self.user_emb.contiguous(), self.item_emb.contiguous(), self.max_N)
+    def _final(self):
+        return self.user_emb.contiguous(), self.item_emb.contiguous()
 
     def evaluate(self):
         metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN)
         print("Detailed TopN Evaluation :")
         print("".join(metrics))
-        result = {}
-        for line in metrics[1:]:          # "Hit Ratio:0.1234\n" ... of the last cut-off, as the reference returns
-            name, sep, value = line.partition(":")
-            if sep:
-                result[name] = float(value)
-        return result
-
-    def predict(self, u):
-        uid = self.data.get_user_id(u)
-        return torch.matmul(self.user_emb[uid], self.item_emb.T).cpu().numpy()
+        return metric_lines_to_dict(metrics)      # "Hit Ratio:0.1234\n" ... of the last cut-off, as the reference returns

@@ -10,8 +10,9 @@ from __future__ import annotations
 import torch
 
 from . import functional as Fn
+from .model_base import MASK64
 
-_MASK64 = 2 ** 64 - 1
+MAX_TRIALS = 1 << 20          # a reference sampler that retries until a negative is found (mhcn, sept, directau, gcl)
 
 
 def next_batch_pairwise(data, batch_size, n_negs=1, *, seed=0, epoch=0, max_trials=101, drop_incomplete=True, prefetch=32):
@@ -25,7 +26,7 @@ def next_batch_pairwise(data, batch_size, n_negs=1, *, seed=0, epoch=0, max_tria
     n = data.uid_dev.numel()
     g = torch.Generator(device=dev).manual_seed((int(seed) * 1_000_003 + int(epoch)) & (2 ** 63 - 1))
     perm = torch.randperm(n, device=dev, generator=g)
-    base = (int(epoch) << 40) & _MASK64
+    base = (int(epoch) << 40) & MASK64
     # negatives are drawn for `chunk` batches per launch (slot s of the epoch uses the same counter whatever the launch
     # boundaries, so the draws equal the per-batch ones) and the incomplete-batch test is ONE read-back per chunk
     # instead of one per batch — a per-batch read-back would drain the stream in front of every training step
@@ -56,7 +57,7 @@ def randint_negatives(num_samples, num_items, n_neg=1, *, seed=0, step=0, device
     dev = torch.device(device)
     dummy_rowptr = torch.zeros(2, dtype=torch.int64, device=dev)
     u = torch.zeros(num_samples, dtype=torch.int64, device=dev)
-    out = Fn.neg_sample(dummy_rowptr, None, u, n_neg, num_items, seed, (int(step) << 40) & _MASK64, 0)
+    out = Fn.neg_sample(dummy_rowptr, None, u, n_neg, num_items, seed, (int(step) << 40) & MASK64, 0)
     return out if n_neg == 1 else out.view(num_samples, n_neg)
 
 
@@ -92,6 +93,6 @@ class EdgeRemoving:
 
     def __call__(self, edge_index):
         self.calls += 1
-        bits = Fn.edge_mask_bits(edge_index.size(1), self.pe, (self.seed * 0x9E3779B97F4A7C15 + self.calls) & _MASK64,
+        bits = Fn.edge_mask_bits(edge_index.size(1), self.pe, (self.seed * 0x9E3779B97F4A7C15 + self.calls) & MASK64,
                                  edge_index.device)
         return EdgeView(edge_index, bits, self.pe)

@@ -10,7 +10,8 @@
     the loop body: four encoders, bpr_loss + reg, the tri-training terms, Adam   :432-465   SEPTModel.losses / train_step
     GraphAugmentor.edge_dropout                       sept_social.py:72-78     SEPTModel.augmented_graph (gcr_edge_mask_exact_bits)
     next_batch_pairwise                               sept_social.py:15-33     sampler.next_batch_pairwise (gcr_neg_sample)
-    train, save, predict, evaluate                    sept_social.py:422-488   SEPTModel.train / save / predict / test / evaluate
+    train, save                                       sept_social.py:422-473   SEPTModel.train / save
+    fast_evaluation, predict, evaluate                :323-329, 479-488        model_base.RankingModel over `_final`
 
 sept_social.py:427 calls `self.data.convert_to_laplacian_mat`, which `Interaction` does not have: the reference
 cannot run an epoch of its tri-training branch.  The choice made here: the augmented operator is the
@@ -27,10 +28,10 @@ import torch
 from . import functional as Fn
 from . import losses as Ls
 from .encoders import Interaction, sept_encoder
-from .evaluate import ranking_evaluation, test as rank_test
 from .graph import CsrGraph
 from .graph_ops import social_related_views
 from .mhcn import MAX_TRIALS, social_pairs
+from .model_base import RankingModel, default_device, index_batch, is_prepared, prepared_data, seeded
 from .optim import FusedAdam
 from .sampler import next_batch_pairwise
 
@@ -50,7 +51,7 @@ def is_tri_training_epoch(epoch, max_epoch):
     return epoch > max_epoch // 3
 
 
-class SEPTModel:
+class SEPTModel(RankingModel):
     def __init__(self, conf, train_set, test_set, social_data=None, device=None, seed=0):
         """conf: conf['SEPT']['n_layer' | 'ss_rate' | 'drop_rate' | 'ins_cnt'], `emb_size` (64), `batch_size` (2048), `lr`
         (1e-3), `reg_lambda` (1e-4), `max.epoch`, `item.ranking.topN` ([10, 20, 30, 50]).  social_data: [follower, followee,
@@ -59,8 +60,8 @@ class SEPTModel:
         for k, v in vars(parse_config(conf)).items():
             setattr(self, k, v)
         self.max_N = max(self.topN)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if hasattr(train_set, "graphs"):                    # prepared operators (`from_graphs`)
+        self.device = default_device(device)
+        if is_prepared(train_set, "graphs"):                   # prepared operators (`from_graphs`)
             self.data = train_set
             self.social_mat, self.sharing_mat = train_set.graphs
         else:
@@ -76,8 +77,7 @@ class SEPTModel:
         self.pair_user = torch.repeat_interleave(torch.arange(n_u, device=self.device), rp[1:] - rp[:-1])
         self.pair_item = self.data.user_items_sorted.to(torch.int64)
         self.tri_loss = Fn.tri_training_loss            # the fused kernels where they serve (d, k), the composition elsewhere
-        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
-            torch.manual_seed(self.seed)
+        with seeded(self.seed, self.device):
             xav = torch.nn.init.xavier_uniform_
             self.user_embeddings = torch.nn.Parameter(xav(torch.empty(n_u, self.emb_size, device=self.device)))
             self.item_embeddings = torch.nn.Parameter(xav(torch.empty(n_i, self.emb_size, device=self.device)))
@@ -91,9 +91,8 @@ class SEPTModel:
         normalised social views [U, U] and the CSR of the distinct training pairs (int64 [U + 1], int32 [nnz]) — what the
         training step reads from the data object without the Python id maps (scripts/perf_sept_step.py)."""
         n_u = social_mat.n_rows
-        data = types.SimpleNamespace(user_num=n_u, item_num=norm_adj.n_rows - n_u, device=norm_adj.device, norm_adj=norm_adj,
-                                     graphs=(social_mat, sharing_mat), user_rowptr=user_rowptr,
-                                     user_items_sorted=user_items_sorted, test_set={}, training_set_u={}, user={}, item={})
+        data = prepared_data(n_u, norm_adj.n_rows - n_u, norm_adj.device, norm_adj=norm_adj, graphs=(social_mat, sharing_mat),
+                             user_rowptr=user_rowptr, user_items_sorted=user_items_sorted)
         return cls(conf, data, None, None, device=norm_adj.device, **kw)
 
     def parameters(self):
@@ -147,12 +146,7 @@ class SEPTModel:
     def train_step(self, batch, tri_training, aug_graph=None, positives=None):
         """One body of :432-465 for batch = (user_idx, pos_idx, neg_idx): losses, zero_grad, backward, Adam step.  Returns
         the detached (rec_loss, neighbor_dis_loss, total_loss)."""
-        u, i, j = (torch.as_tensor(t, device=self.device, dtype=torch.int64).contiguous() for t in batch)
-        self.optimizer.zero_grad(set_to_none=True)
-        out = self.losses(u, i, j, tri_training, aug_graph, positives)
-        out[2].backward()
-        self.optimizer.step()
-        return tuple(t.detach() for t in out)
+        return self._optimise(*index_batch(batch, self.device), tri_training, aug_graph, positives)
 
     def train_epoch(self, epoch):
         tri = is_tri_training_epoch(epoch, self.maxEpoch)
@@ -182,24 +176,4 @@ class SEPTModel:
             self.U, self.V = fu.contiguous(), fi.contiguous()
         return self.U, self.V
 
-    def predict(self, u):
-        """:479-481: V @ U[u], the scores of every item for raw user id u."""
-        U, V = self._final()
-        return torch.matmul(V, U[self.data.get_user_id(u)]).cpu().numpy()
-
-    def test(self):
-        U, V = self._final()
-        return rank_test(self.data, U, V, self.max_N)
-
-    def fast_evaluation(self, epoch):
-        """:323-329: the four metrics at max_N; bestPerformance follows Recall."""
-        lines = ranking_evaluation(self.data.test_set, self.test(), [self.max_N], device=self.device)
-        performance = {k: float(v) for m in lines[1:] for k, v in [m.strip().split(":")]}
-        if not self.bestPerformance or performance.get("Recall", 0) > self.bestPerformance[1].get("Recall", 0):
-            self.bestPerformance = [epoch + 1, performance]
-        return performance
-
-    def evaluate(self):
-        """:483-488: every cut-off's metrics flattened into one dict, so the last cut-off's four remain."""
-        metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN, device=self.device)
-        return {k: float(v) for m in metrics[1:] if ":" in m for k, v in [m.strip().split(":", 1)]}
+    predict = RankingModel.predict_item_major             # :479-481: V @ U[u]

@@ -13,7 +13,11 @@ Stage by stage (reference line -> here):
     torch.optim.Adam(lr)                 ssl4rec.py:212       optim.FusedAdam (gcr_adam_step_f32)
     next_batch_pairwise                  ssl4rec.py:33-50     sampler.next_batch_pairwise(max_trials=0): the loop drops the
                                                               negatives (ssl4rec.py:218), so none is rejection-sampled
-    test / evaluate                      ssl4rec.py:143-153, 248-252   evaluate.test / ranking_evaluation (gcr_rank_*)
+    test / evaluate / predict            ssl4rec.py:143-153, 248-252   model_base.RankingModel over `_final` (evaluate.test /
+                                                              ranking_evaluation: gcr_rank_*).  `self.topN` is passed as it
+                                                              is: ssl4rec.py:250 wraps the list in a list, which fails inside
+                                                              ranking_evaluation (univariate/ssl4rec_univariate.py has the
+                                                              fix); the result is the metrics of the last cut-off
 The tuner, the progress prints and the summary around it are out of scope.
 """
 from __future__ import annotations
@@ -24,12 +28,11 @@ import torch.nn as nn
 from . import functional as Fn
 from . import losses as Ls
 from .encoders import Interaction
-from .evaluate import ranking_evaluation, test as rank_test
+from .model_base import MASK64, RankingModel, default_device, index_batch, is_prepared, seeded
 from .optim import FusedAdam
 from .sampler import next_batch_pairwise
 
 HIDDEN_DIM, OUT_DIM = 1024, 128             # ssl4rec.py:178-180
-_MASK64 = 2 ** 64 - 1
 _TOWER_ROWS = 1 << 18                       # rows per tower call of the epoch-end pass (bounds the 1024-wide activations)
 
 
@@ -74,7 +77,7 @@ class DNNEncoder(nn.Module):
             return tower(self.user_net, self.initial_user), tower(self.item_net, self.initial_item)
 
 
-class SSL4RecModel:
+class SSL4RecModel(RankingModel):
     def __init__(self, conf, train_set, test_set, device=None, seed=0):
         """conf: the reference's keys — `embedding.size`, `batch.size`, `learning.rate`, `max.epoch` (default 1),
         `item.ranking.topN` (default [10]), conf['SSL4Rec']['alpha' | 'tau' | 'drop'], top-level `n.layers` (default 1) and
@@ -84,19 +87,17 @@ class SSL4RecModel:
         self.emb_size, self.batch_size, self.lRate = conf["embedding.size"], conf["batch.size"], conf["learning.rate"]
         self.reg = conf.get("reg.lambda")
         self.maxEpoch = conf.get("max.epoch", 1)
-        self.topN = list(map(int, conf.get("item.ranking.topN", [10])))
-        self.max_N = max(self.topN)
+        self._read_topn(conf, [10])
         args = conf["SSL4Rec"]
         self.cl_rate, self.tau, self.drop = float(args["alpha"]), float(args["tau"]), float(args["drop"])
         self.n_layers = conf.get("n.layers", 1)
         self.reg_weight = conf.get("reg.weight", 0.0001)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = default_device(device)
         # `train_set` may be a prepared data object (user_num, item_num, device, ...) instead of the triple list, as for
         # NCLModel: tables too large for Python id maps (scripts/perf_ssl4rec_step.py)
-        self.data = train_set if hasattr(train_set, "user_num") else \
+        self.data = train_set if is_prepared(train_set, "user_num") else \
             Interaction(conf, train_set, test_set, device=self.device, id_order="first_seen")
-        with torch.random.fork_rng(devices=[self.device] if self.device.type == "cuda" else []):
-            torch.manual_seed(self.seed)              # initial weights: a function of `seed`, the caller's RNG untouched
+        with seeded(self.seed, self.device):
             self.model = DNNEncoder(self.data, self.emb_size, self.drop, self.tau, self.n_layers, device=self.device)
         self.optimizer = FusedAdam(self.model.parameters(), lr=self.lRate)        # ssl4rec.py:212: no weight decay
         self.steps = 0
@@ -106,10 +107,9 @@ class SSL4RecModel:
         """ssl4rec.py:221-224 on the HIP path: (rec_loss, cl_loss, batch_loss), differentiable, no host sync.  Every call
         draws the step's two dropout masks from a seed of its own; keep_bits (int32 [2, ceil(B * emb / 32)]) replays
         recorded ones."""
-        dev = self.device
-        u, i = (torch.as_tensor(t, device=dev, dtype=torch.int64).contiguous() for t in (u, i))
+        u, i = index_batch((u, i), self.device)
         self.steps += 1
-        step_seed = (self.seed * 0x9E3779B97F4A7C15 + 2 * self.steps) & _MASK64      # view v draws with step_seed + v
+        step_seed = (self.seed * 0x9E3779B97F4A7C15 + 2 * self.steps) & MASK64      # view v draws with step_seed + v
         u_emb = self.model.user_net(Fn.gather_rows(self.model.initial_user, u))
         i_emb, v1, v2 = self.model.item_views(i, step_seed, keep_bits)
         rec_loss = Ls.batch_softmax_loss(u_emb, i_emb, self.tau)
@@ -120,11 +120,7 @@ class SSL4RecModel:
     def train_step(self, u, i, keep_bits=None):
         """One body of ssl4rec.py:218-225 (zero_grad, losses, backward, Adam step).  Returns (rec_loss, cl_loss,
         batch_loss) as detached device tensors."""
-        self.optimizer.zero_grad(set_to_none=True)
-        out = self.losses(u, i, keep_bits)
-        out[2].backward()
-        self.optimizer.step()
-        return tuple(t.detach() for t in out)
+        return self._optimise(u, i, keep_bits)
 
     def embeddings(self):
         """(query_emb [U, 128], item_emb [I, 128]): the towers over all rows under no_grad (ssl4rec.py:231-235)."""
@@ -152,14 +148,8 @@ class SSL4RecModel:
         self.best_epoch, self.best_performance = best_epoch, best_metric
         return best_metric
 
-    def test(self):
-        return rank_test(self.data, self.query_emb.contiguous(), self.item_emb.contiguous(), self.max_N)
-
-    def evaluate(self):
-        """ssl4rec.py:248-252 with `self.topN` passed as it is (ssl4rec.py:250 wraps the list in a list, which fails
-        inside ranking_evaluation; univariate/ssl4rec_univariate.py has the fix): the metrics of the last cut-off."""
-        metrics = ranking_evaluation(self.data.test_set, self.test(), self.topN, device=self.device)
-        return {k: float(v) for m in metrics[1:] if ":" in m for k, v in [m.strip().split(":")]}
+    def _final(self):
+        return self.query_emb.contiguous(), self.item_emb.contiguous()
 
     def is_better(self, current, best):
         return current.get("Recall", 0) > best.get("Recall", 0)
@@ -167,7 +157,3 @@ class SSL4RecModel:
     def save(self):
         """ssl4rec.py:257-262 runs the towers again on unchanged parameters; the epoch's own outputs are those values."""
         self.best_query_emb, self.best_item_emb = self.query_emb, self.item_emb
-
-    def predict(self, u):
-        uid = self.data.get_user_id(u)
-        return torch.matmul(self.query_emb[uid], self.item_emb.T).cpu().numpy()

@@ -14,11 +14,11 @@ quantiles of the per-step times — `spread` = p90 - p10 — over rounds x steps
         kernel trace: rocprofv3 --kernel-trace --stats -- python scripts/perf_directau_step.py --only ...; two step
         counts give the launches per step by difference)
 """
-import argparse
 import json
 import os
-import subprocess
 import sys
+
+import perf_step_common as pc
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -59,7 +59,6 @@ def composed_loss(user_emb, item_emb, u, i, j, gamma, reg, batch_size, once=Fals
 
 def leg(args):
     """One batch size (or one `--only` variant) in this process."""
-    import numpy as np
     import torch
     import bench
     import recommendation_amd as ra
@@ -101,63 +100,25 @@ def leg(args):
            "composed_loss": loss_side(lambda b: composed_loss(tabs[0], tabs[1], *b, GAMMA, REG, args.batch)),
            "composed_once_loss": loss_side(lambda b: composed_loss(tabs[0], tabs[1], *b, GAMMA, REG, args.batch, once=True))}
 
-    def timed(fn, data):
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in data]
-        for (e0, e1), b in zip(evs, data):
-            e0.record()
-            fn(b)
-            e1.record()
-        torch.cuda.synchronize()
-        return [e0.elapsed_time(e1) for e0, e1 in evs]
-
-    if args.only:
-        timed(fns[args.only], batches(args.steps))
-        print(json.dumps({"only": args.only, "batch": args.batch, "steps": args.steps}))
+    ms = pc.measure(fns, VARIANTS, batches, args, batch=args.batch)
+    if ms is None:
         return
-    for k in VARIANTS:
-        timed(fns[k], batches(args.warmup))
-    ms = {k: [] for k in VARIANTS}
-    for _ in range(args.rounds):                          # alternate: drift of the clocks hits all variants alike
-        data = batches(args.steps)
-        for k in VARIANTS:
-            ms[k] += timed(fns[k], data)
     case = {"batch": args.batch, "steps_per_variant": args.rounds * args.steps, "device": torch.cuda.get_device_name(0)}
-    for k in VARIANTS:
-        q = np.quantile(ms[k], [0.1, 0.5, 0.9])
-        case[k + "_ms"] = {"median": round(float(q[1]), 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
-                           "p10": round(float(q[0]), 4), "p90": round(float(q[2]), 4), "spread": round(float(q[2] - q[0]), 4)}
+    pc.add_records(case, ms, VARIANTS)
     for side in ("loss", "step", "once_loss"):
-        f, c = case["fused_loss_ms" if side == "once_loss" else f"fused_{side}_ms"], case[f"composed_{side}_ms"]
-        case[f"{side}_composed_minus_fused_ms"] = round(c["median"] - f["median"], 4)
-        case[f"{side}_faster_by_more_than_spread"] = bool(c["median"] - f["median"] > max(f["spread"], c["spread"]))
+        pc.add_verdict(case, "fused_loss" if side == "once_loss" else f"fused_{side}", f"composed_{side}",
+                       f"{side}_composed_minus_fused_ms", f"{side}_faster_by_more_than_spread")
     print(json.dumps(case))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=4)
-    ap.add_argument("--batch", type=int, default=None)
-    ap.add_argument("--only", choices=VARIANTS)
-    ap.add_argument("--leg", action="store_true", help="(internal) measure --batch in this process")
-    args = ap.parse_args()
-    if args.rounds * args.steps < 20 and not args.only:
-        raise SystemExit("at least 20 measured steps per variant (rounds x steps)")
+    args = pc.parse_args(VARIANTS, steps=10, warmup=5, rounds=4, what="steps", batch=True)
     if args.leg or args.only:
         args.batch = args.batch or 2048
         return leg(args)
     out = {"graph": "cfg2 (1M x 100K, 10M interactions, raw adjacency)", "emb": EMB, "n_layers": LAYERS, "cases": []}
     for batch in ((args.batch,) if args.batch else (512, 2048)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--batch", str(batch), "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--rounds", str(args.rounds)]
-        try:
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=LEG_TIMEOUT_S)
-        except subprocess.TimeoutExpired:
-            raise SystemExit(f"B = {batch}: no result within {LEG_TIMEOUT_S} s; stopping")
-        if res.returncode != 0:
-            raise SystemExit(f"B = {batch}: the measurement failed with status {res.returncode}; stopping")
-        out["cases"].append(json.loads(res.stdout.strip().splitlines()[-1]))
+        out["cases"].append(json.loads(pc.run_child(__file__, args, LEG_TIMEOUT_S, ("--batch", str(batch)), f"B = {batch}: ")))
     print(json.dumps(out))
 
 

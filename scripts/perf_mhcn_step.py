@@ -20,11 +20,11 @@ Needs a GPU.
     python scripts/perf_mhcn_step.py --only mim_only --steps 30      (one variant in this process, for a kernel trace:
         rocprofv3 --kernel-trace --stats -- python scripts/perf_mhcn_step.py --only ...)
 """
-import argparse
 import json
 import os
-import subprocess
 import sys
+
+import perf_step_common as pc
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -43,7 +43,6 @@ def mim_bytes(n, d):
 
 
 def leg(args):
-    import numpy as np
     import torch
     import bench
     import recommendation_amd as ra
@@ -104,36 +103,14 @@ def leg(args):
            "step_composed": lambda b: models["step_composed"].train_step(b),
            "mim_only": mim_only, "composed_only": composed_only}
 
-    def timed(fn, data):
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in data]
-        for (e0, e1), b in zip(evs, data):
-            e0.record()
-            fn(b)
-            e1.record()
-        torch.cuda.synchronize()
-        return [e0.elapsed_time(e1) for e0, e1 in evs]
-
-    if args.only:
-        timed(fns[args.only], batches(args.steps))
-        print(json.dumps({"only": args.only, "steps": args.steps}))
+    ms = pc.measure(fns, VARIANTS, batches, args)
+    if ms is None:
         return
-    for k in VARIANTS:
-        timed(fns[k], batches(args.warmup))
-    ms = {k: [] for k in VARIANTS}
-    for _ in range(args.rounds):                          # alternate: drift of the clocks hits all variants alike
-        data = batches(args.steps)
-        for k in VARIANTS:
-            ms[k] += timed(fns[k], data)
     case = {"users": n_u, "items": n_i, "emb": EMB, "batch": BATCH, "calls_per_variant": args.rounds * args.steps,
             "device": torch.cuda.get_device_name(0)}
-    for k in VARIANTS:
-        q = np.quantile(ms[k], [0.1, 0.5, 0.9])
-        case[k + "_ms"] = {"median": round(float(q[1]), 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
-                           "p10": round(float(q[0]), 4), "p90": round(float(q[2]), 4), "spread": round(float(q[2] - q[0]), 4)}
+    pc.add_records(case, ms, VARIANTS)
     for a, b in (("ss_kernel", "ss_composed"), ("step_kernel", "step_composed"), ("mim_only", "composed_only")):
-        f, c = case[a + "_ms"], case[b + "_ms"]
-        case[f"{b}_minus_{a}_ms"] = round(c["median"] - f["median"], 4)
-        case[f"{a}_faster_by_more_than_spread"] = bool(c["median"] - f["median"] > max(f["spread"], c["spread"]))
+        pc.add_verdict(case, a, b)
     case["ss_share_of_step"] = round(case["ss_kernel_ms"]["median"] / case["step_kernel_ms"]["median"], 4)
     case["ss_composed_share_of_step"] = round(case["ss_composed_ms"]["median"] / case["step_composed_ms"]["median"], 4)
     tbs = mim_bytes(n_u, EMB) / (case["mim_only_ms"]["median"] * 1e-3) / 1e12       # includes the three randperm draws
@@ -145,26 +122,10 @@ def leg(args):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=4)
-    ap.add_argument("--only", choices=VARIANTS)
-    ap.add_argument("--leg", action="store_true", help="(internal) measure in this process")
-    args = ap.parse_args()
-    if args.rounds * args.steps < 20 and not args.only:
-        raise SystemExit("at least 20 measured calls per variant (rounds x steps)")
+    args = pc.parse_args(VARIANTS, steps=5, warmup=3, rounds=4)
     if args.leg or args.only:
         return leg(args)
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--rounds", str(args.rounds)]
-    try:
-        res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=LEG_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        raise SystemExit(f"no result within {LEG_TIMEOUT_S} s; stopping")
-    if res.returncode != 0:
-        raise SystemExit(f"the measurement failed with status {res.returncode}; stopping")
-    print(res.stdout.strip().splitlines()[-1])
+    print(pc.run_child(__file__, args, LEG_TIMEOUT_S))
 
 
 if __name__ == "__main__":

@@ -16,11 +16,11 @@ max and the 10 % / 90 % quantiles of the per-call times — `spread` = p90 - p10
     python scripts/perf_sept_step.py [--steps 5] [--warmup 3] [--rounds 4]
     python scripts/perf_sept_step.py --only tri_fused --steps 30      (one variant in this process, for a kernel trace)
 """
-import argparse
 import json
 import os
-import subprocess
 import sys
+
+import perf_step_common as pc
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
@@ -32,7 +32,6 @@ LEG_TIMEOUT_S = 420
 
 
 def leg(args):
-    import numpy as np
     import torch
     import recommendation_amd as ra
     from recommendation_amd import functional as Fn
@@ -79,60 +78,22 @@ def leg(args):
            "step_fused": lambda b: models["step_fused"].train_step(b, True, aug),
            "step_composed": lambda b: models["step_composed"].train_step(b, True, aug)}
 
-    def timed(fn, data):
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in data]
-        for (e0, e1), b in zip(evs, data):
-            e0.record()
-            fn(b)
-            e1.record()
-        torch.cuda.synchronize()
-        return [e0.elapsed_time(e1) for e0, e1 in evs]
-
-    if args.only:
-        timed(fns[args.only], batches(args.steps))
-        print(json.dumps({"only": args.only, "steps": args.steps}))
+    ms = pc.measure(fns, VARIANTS, batches, args)
+    if ms is None:
         return
-    for k in VARIANTS:
-        timed(fns[k], batches(args.warmup))
-    ms = {k: [] for k in VARIANTS}
-    for _ in range(args.rounds):                          # alternate: drift of the clocks hits all variants alike
-        data = batches(args.steps)
-        for k in VARIANTS:
-            ms[k] += timed(fns[k], data)
     case = {"users": USERS, "items": ITEMS, "emb": EMB, "batch": BATCH, "k": K, "m_tri": M_TRI,
             "calls_per_variant": args.rounds * args.steps, "device": torch.cuda.get_device_name(0)}
-    for k in VARIANTS:
-        q = np.quantile(ms[k], [0.1, 0.5, 0.9])
-        case[k + "_ms"] = {"median": round(float(q[1]), 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
-                           "p10": round(float(q[0]), 4), "p90": round(float(q[2]), 4), "spread": round(float(q[2] - q[0]), 4)}
+    pc.add_records(case, ms, VARIANTS)
     for a, b in (("tri_fused", "tri_composed"), ("step_fused", "step_composed")):
-        f, c = case[a + "_ms"], case[b + "_ms"]
-        case[f"{b}_minus_{a}_ms"] = round(c["median"] - f["median"], 4)
-        case[f"{a}_faster_by_more_than_spread"] = bool(c["median"] - f["median"] > max(f["spread"], c["spread"]))
+        pc.add_verdict(case, a, b)
     print(json.dumps(case))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=4)
-    ap.add_argument("--only", choices=VARIANTS)
-    ap.add_argument("--leg", action="store_true", help="(internal) measure in this process")
-    args = ap.parse_args()
-    if args.rounds * args.steps < 20 and not args.only:
-        raise SystemExit("at least 20 measured calls per variant (rounds x steps)")
+    args = pc.parse_args(VARIANTS, steps=5, warmup=3, rounds=4)
     if args.leg or args.only:
         return leg(args)
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--rounds", str(args.rounds)]
-    try:
-        res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=LEG_TIMEOUT_S)
-    except subprocess.TimeoutExpired:
-        raise SystemExit(f"no result within {LEG_TIMEOUT_S} s; stopping")
-    if res.returncode != 0:
-        raise SystemExit(f"the measurement failed with status {res.returncode}; stopping")
-    print(res.stdout.strip().splitlines()[-1])
+    print(pc.run_child(__file__, args, LEG_TIMEOUT_S))
 
 
 if __name__ == "__main__":
