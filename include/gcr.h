@@ -315,7 +315,8 @@ int32_t gcr_edge_mask_bits(int64_t nnz, float pe, uint64_t seed, const int64_t* 
  * (GCR_EUNSUPPORTED otherwise; the host wrapper zero-pads other widths).  f32 in, f32 out, f32
  * accuracy on both engines: the f32 MFMA (v_mfma_f32_32x32x2_f32), or for d <= 128 the bf16 MFMA on
  * three error-free bf16 planes per operand (the f32 engine is csrc/gcr_tile.h, the "split-operand engine"
- * csrc/gcr_b3.h; the kernels built on them are in csrc/gcr_infonce.hip).
+ * csrc/gcr_b3.h; the kernels built on them are in csrc/gcr_pairs.h and csrc/gcr_pairs_loop.h, launched from
+ * csrc/gcr_infonce.hip, csrc/gcr_infonce_flash.hip and csrc/gcr_bce.hip).
  * --------------------------------------------------------------------------------------------- */
 /* engine the InfoNCE / k-means kernels use for width d by default: 0 = f32 MFMA, 1 = split-operand bf16
  * (d <= 128); GCR_INFONCE_ENGINE_F32 in the flags of the _ex entry points selects 0 for one call */
@@ -363,7 +364,7 @@ int32_t gcr_infonce_fwd_f32(const float* a, const float* a_scale, int64_t m,
  * operand range known, the split-operand launches (gcr_infonce_fwd_ex_f32, gcr_infonce_fwd_o_f32,
  * gcr_infonce_bwd_ex_f32) of d <= 64 — the two-product launches gcr_infonce_fwd_o_f32 / gcr_infonce_bwd_ex_f32 also of
  * d = 128 — and inv_tau <= 20 run on TWO f16 planes per operand and three product terms instead of three bf16 planes and
- * six (csrc/gcr_infonce.hip, EngH2): half the matrix-core work, operands rounded at 2^-22 instead of 2^-27 — a few f32
+ * six (csrc/gcr_b3.h, EngH2): half the matrix-core work, operands rounded at 2^-22 instead of 2^-27 — a few f32
  * roundings per product, inside the 1e-5 of every parity test.  Without the promise nothing changes. */
 #define GCR_INFONCE_UNIT_ROWS 2u
 int32_t gcr_infonce_fwd_ex_f32(const float* a, const float* a_scale, int64_t m,

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_b3_kernel(
   const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * (32 * S::NT);
   u32x4 bq[S::NT][3][S::KC];
 #pragma unroll
-  for (int t = 0; t < S::NT; ++t) load_stationary_b3<D>(x, nullptr, n, i0 + 32 * t + i32, h, 1.0f, bq[t]);
+  for (int t = 0; t < S::NT; ++t) load_stationary_e<EngB3, D>(x, nullptr, n, i0 + 32 * t + i32, h, 1.0f, bq[t]);
   float best[S::NT];
   int btile[S::NT], breg[S::NT];
 #pragma unroll
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_b3_kernel(
   };
   auto store_tile = [&](unsigned char* out, int sbuf, const Staged& g) {
 #pragma unroll
-    for (int u = 0; u < S::NLD; ++u) stage_store_b3_one<D>(out, tid, g.v[u], u);
+    for (int u = 0; u < S::NLD; ++u) stage_store_e_one<EngB3, D>(out, tid, g.v[u], u);
     if (tid < kTileJ) st_bias[sbuf][tid] = g.live ? -g.hb : -INFINITY;          // rows past k never win
   };
   // one tile: scores of the tile in lds[buf] into `nxt` (C = bias), optionally interleaved with the
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_b3_kernel(
         best[t] = fmaxf(best[t], v);
       } else {
         const int u = m - 16 * S::NT;
-        stage_store_b3_one<D>(out, tid, st.v[u], u);
+        stage_store_e_one<EngB3, D>(out, tid, st.v[u], u);
         if (u == 0 && tid < kTileJ) st_bias[buf ^ 1][tid] = st.live ? -st.hb : -INFINITY;
       }
     };
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256, LOWREG ? 4 : 2) void kmeans_search_img_kernel(
   const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * 32;
   if (i0 >= n) return;                                      // (whole waves only: nothing below synchronises across waves)
   u32x4 bq[3][KC];
-  load_stationary_b3<D>(x, nullptr, n, i0 + i32, h, 1.0f, bq);
+  load_stationary_e<EngB3, D>(x, nullptr, n, i0 + i32, h, 1.0f, bq);
   const int64_t tiles = (k + kTileJ - 1) / kTileJ;
   float best = -INFINITY;
   int btile = 0, breg = 0;

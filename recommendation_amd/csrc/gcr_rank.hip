@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void rank_fused_b3_kernel(
     int64_t u = q < n_query ? (user_ids != nullptr ? user_ids[q] : q) : -1;
     const bool ok = u >= 0 && u < n_users;
     uid[t] = ok ? u : -1;
-    load_stationary_b3<D>(user_emb, nullptr, ok ? u + 1 : 0, ok ? u : 0, h, 1.0f, bq[t]);
+    load_stationary_e<EngB3, D>(user_emb, nullptr, ok ? u + 1 : 0, ok ? u : 0, h, 1.0f, bq[t]);
     thr_l[t] = (MODE == 1 && ok) ? thr[q] : INFINITY;       // an invalid query never produces a candidate
     cnt[t] = 0;
   }
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void rank_fused_b3_kernel(
   };
   if (tile0 < tile1) {
     stage_load_items(tile0 * kTileJ);
-    stage_store_b3<D>(lds[0], tid, regs);
+    stage_store_e<EngB3, D>(lds[0], tid, regs);
   }
   __syncthreads();
   for (int64_t tt = tile0; tt < tile1; ++tt) {
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void rank_fused_b3_kernel(
     const int64_t nxt = tt + 1 < tile1 ? tt + 1 : tt;
     stage_load_items(nxt * kTileJ);
     f32x16 acc[S::NT];
-    score_tile_b3<D, S::NT>(lds[cur], i32, h, bq, acc);
+    score_tile_e<EngB3, D, S::NT>(lds[cur], i32, h, bq, acc);
     const int64_t j0 = tt * kTileJ;
     if (MODE == 0) {
       // dense sample: registers 4g .. 4g+3 are items j0 + 8g + 4h .. +3 of the lane's user: one 16-B store
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256, 2) void rank_fused_b3_kernel(
         }
       }
     }
-    stage_store_b3<D>(lds[cur ^ 1], tid, regs);
+    stage_store_e<EngB3, D>(lds[cur ^ 1], tid, regs);
     __syncthreads();
   }
   if (MODE == 1) {

@@ -1,6 +1,6 @@
-// The f32 MFMA tile engine (v_mfma_f32_32x32x2_f32) under the InfoNCE / BCE kernels (gcr_infonce.hip), the
+// The f32 MFMA tile engine (v_mfma_f32_32x32x2_f32) under the InfoNCE / BCE kernels (gcr_pairs.h and its three units), the
 // nearest-centroid search (gcr_kmeans.hip) and the ranking kernels (gcr_rank.hip), with the names its split-operand
-// sibling (gcr_b3.h) is written in.  Included at file scope; everything lives in an anonymous namespace.  The other
+// sibling (gcr_b3.h, the header of the split-operand engines EngB3 / EngH2) is written in.  Included at file scope; everything lives in an anonymous namespace.  The other
 // MFMA sources (gcr_directau, gcr_buir, gcr_tri, gcr_dense) have loops of their own and take only the accumulator's
 // type, its row layout and the tile height from here.
 //
@@ -101,7 +101,7 @@ __device__ __forceinline__ void score_tile(const float* __restrict__ tile, int i
 }
 
 // Which engine and which widths: shared by the InfoNCE / BCE launches and the k-means search.  The split-operand bf16
-// engine (gcr_b3.h) serves d <= 128 unless the caller forces the f32 MFMA; gcr_infonce.hip says why it is an argument.
+// engine (gcr_b3.h) serves d <= 128 unless the caller forces the f32 MFMA; gcr_pairs.h says why it is an argument.
 bool use_b3(int d, bool force_f32 = false) { return d <= 128 && !force_f32; }
 bool dim_supported(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
 

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""ISA check behind DESIGN 4.2b's ring analysis: in every instantiation of infonce_pipe_kernel, no LDS instruction may
+"""ISA check behind DESIGN 4.2b's ring analysis: in every instantiation of infonce_pipe_kernel (csrc/gcr_pairs_loop.h; instantiated by
+csrc/gcr_infonce_flash.hip and csrc/gcr_bce.hip — scan both), no LDS instruction may
 stand between the last `s_waitcnt ... lgkmcnt(0)` and an `s_barrier` (every read has returned and every write has landed
 when a barrier separates it from its counterpart).  Textual scan of the gfx950 assembly:
-    hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I recommendation_amd/csrc -c recommendation_amd/csrc/gcr_infonce.hip \\
+    hipcc -O3 -std=c++17 --offload-arch=gfx950 -I include -I recommendation_amd/csrc -c recommendation_amd/csrc/gcr_infonce_flash.hip \\
           -o /tmp/isa/infonce.o -save-temps=obj
-    python scripts/exp/check_barrier_waits.py /tmp/isa/gcr_infonce-hip-amdgcn-amd-amdhsa-gfx950.s"""
+    python scripts/exp/check_barrier_waits.py /tmp/isa/gcr_infonce_flash-hip-amdgcn-amd-amdhsa-gfx950.s"""
 import collections
 import re
 import sys

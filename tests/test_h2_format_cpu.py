@@ -1,4 +1,4 @@
-"""The two-f16-plane operand format of the InfoNCE kernels (csrc/gcr_infonce.hip, EngH2), emulated in numpy: the bounds
+"""The two-f16-plane operand format of the InfoNCE kernels (csrc/gcr_b3.h, EngH2), emulated in numpy: the bounds
 DESIGN §4.2b states for it.  x = hi + lo with hi = f16(x), lo = f16(x - hi) (round-to-nearest-even, gradual underflow —
 numpy's float16 conversion does both, as v_cvt_pk_f16_f32 does); a product keeps hi*hi + hi*lo + lo*hi."""
 import numpy as np
@@ -58,7 +58,7 @@ def test_probability_plane_range():
 
 def test_unit_product_prescales_cost_no_accuracy():
     """Round 4: stationary x 2^-2, streamed x 2^2 — product 1, so the accumulator is the log2-domain score itself (EngH2::kSX /
-    kSY / kSInv in csrc/gcr_infonce.hip).  Elements under 2^-3 after scaling have a sub-normal residual plane (absolute error
+    kSY / kSInv in csrc/gcr_b3.h).  Elements under 2^-3 after scaling have a sub-normal residual plane (absolute error
     <= 2^-25), which a dot product of unit rows tolerates: the worst score error over dense rows, near-duplicate pairs and
     rows with a few large and many tiny elements stays within 10 % of the old pre-scales' and under 3e-6 at 1/tau = 20."""
     rng = np.random.default_rng(2)

@@ -20,7 +20,7 @@ def Fn():
 
 @pytest.fixture(autouse=True, params=["auto", "b3", "f32"])
 def engine(request, monkeypatch, Fn):
-    """Every test of this module runs three ways (csrc/gcr_infonce.hip), with the same tolerances: "auto", the
+    """Every test of this module runs three ways (csrc/gcr_infonce.hip, csrc/gcr_infonce_flash.hip), with the same tolerances: "auto", the
     library default (split-operand engine for d <= 128; its two-product launches on two f16 planes when the op
     normalises the rows itself and d <= 64 — the GCR_INFONCE_UNIT_ROWS promise); "b3", the promise withheld (three
     bf16 planes everywhere); "f32", the f32 MFMA engine (GCR_INFONCE_ENGINE_F32).  The host resolves the flags once
