@@ -9,7 +9,10 @@
 //     gcr_spmm_plan_*): a partition is either up to 64 whole rows or one chunk of a long row, so
 //     every wave moves the same number of bytes whatever the degree skew;
 //   * lane l owns feature columns l, l+64, ...: with d = 64 one neighbour row is exactly one
-//     coalesced 256-B wave load whose base address is wave-uniform (SGPR base + lane*4);
+//     coalesced 256-B wave load.  Its base is wave-uniform, but what is compiled is a 64-bit VGPR address per gather in
+//     flight: v_readlane of the column, s_mul_hi / s_mul by d, v_lshl_add_u64 onto x + lane*4, global_load_dword
+//     v, v[a:a+1], off.  The SGPR-base form (a 32-bit offset per gather) was built and measured: 0.3-0.8 % of a cfg2
+//     layer, below the bar, so it is not here (EXPERIMENTS.md "SpMM: the walk's scalar work");
 //   * column ids / values of 64 non-zeros are fetched with one coalesced vector load each and
 //     handed out with v_readlane (scalar), so all control flow (row boundaries, edge mask,
 //     tails) is scalar and divergence-free;
@@ -402,8 +405,10 @@ __device__ __forceinline__ int64_t wave_partition(unsigned block0) {
 //     time: the companion's partitions average 96 non-zeros, so 7-8 of a partition's gathers were such single round trips
 //     beside the six batches that carried the rest, and that is where its waves waited (EXPERIMENTS.md "SpMM:
 //     spmm_hub_parts, the companion's own kernel").
-// What happens at a row end is the sink's: sink.refill(row, n) runs in front of every batch of gathers (the next n rows to
-// end are row, row + 1, ...; n = 0 in a chunk), sink.flush(row, acc) at every row end.
+// What happens at a row end is the sink's: sink.begin(row0) names the partition's first row, once; sink.refill(n) runs in
+// front of every batch of gathers (n rows of the partition have not ended yet; n = 0 in a chunk), sink.flush(acc) at every
+// row end, in row order.  The rows of a partition are consecutive, so a sink steps its row addresses from one flush to the
+// next and multiplies a row by d once per partition, in begin().
 template <bool D64, bool HAS_VAL, class Sink>
 __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t* __restrict__ desc, int64_t n_parts,
                                                const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -428,9 +433,10 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
   int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
 
   float acc = 0.f;
-  auto refill = [&]() { sink.refill((int64_t)row0 + cur, whole_rows ? nrows - cur : 0); };
+  sink.begin((int64_t)row0);
+  auto refill = [&]() { sink.refill(whole_rows ? nrows - cur : 0); };
   auto flush = [&]() {
-    sink.flush((int64_t)row0 + cur, acc);
+    sink.flush(acc);
     acc = 0.f;
     ++cur;
     cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
@@ -469,10 +475,14 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
         const float* xp = x + (int64_t)gcr_readlane_i(cv, jb + u) * d;
         xr[u] = on ? xp[lane] : 0.f;
       }
+      // The row end relative to this batch, so that position u compares a constant with one scalar; a chunk needs no test
+      // of its own, its cur_end is the sentinel 0x7fffffff and stays above every position.
+      int end = cur_end - (b + jb);
 #pragma unroll
       for (int u = 0; u < B; ++u) {
-        if (whole_rows) {
-          while (b + jb + u >= cur_end) flush();
+        while (u >= end) {
+          flush();
+          end = cur_end - (b + jb);
         }
         const float w = HAS_VAL ? gcr_readlane_f(vv, jb + u) : 1.0f;
         acc = fmaf(w, xr[u], acc);
@@ -505,15 +515,18 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
 }
 
 // Row sink of the windowed companion: no epilogue and no acc_in, a row's sum is stored as it stands (`spmm_parts` multiplied
-// it by a val_scale of 1.0).
+// it by a val_scale of 1.0).  `y` is the row of the next flush: a wave-uniform pointer, so a store is that SGPR pair plus the
+// lane's byte offset, and a row end moves it on by d floats with one 64-bit scalar add (the output may exceed 4 GiB).
 template <bool D64>
 struct StoreSink {
   static constexpr bool queued = false;
   float* __restrict__ y;
   int d, lane;
-  __device__ __forceinline__ void refill(int64_t, int) {}
-  __device__ __forceinline__ void flush(int64_t row, float acc) {
-    if (D64 || lane < d) stream_store(y + row * d + lane, acc);
+  __device__ __forceinline__ void begin(int64_t row0) { y += row0 * d; }
+  __device__ __forceinline__ void refill(int) {}
+  __device__ __forceinline__ void flush(float acc) {
+    if (D64 || lane < d) stream_store(y + lane, acc);
+    y += d;
   }
 };
 
@@ -522,7 +535,13 @@ struct StoreSink {
 // batch's gathers, so the combine at a row end waits for nothing younger than a gather it has already waited for.  Nothing
 // is queued for chunks (n = 0), y-only launches and acc_in == NULL.  In place (acc_in == acc_out) stays correct: a row is
 // read before this wave, its only writer, stores it.
-template <bool D64>
+// HORNER: acc_in and acc_out are given (they may be the same array) and y is not, known at compile time.  It is what a
+// LightGCN layer launches forward and backward; none of the tests of launch-uniform pointers below is left in that
+// instantiation, refill and flush branch on the queue's fill and nothing else.  The other forms read the pointers at run time.
+// `y`, `acc_in` and `acc_out` are wave-uniform row pointers once begin() has run: y and acc_out the row of the next flush,
+// acc_in the row of the next load, which is the row of the next flush + nq whichever arm loads it (acc_in is read only
+// when rows are queued).  Each moves on by d floats with one 64-bit scalar add; a NULL pointer is never moved.
+template <bool D64, bool HORNER>
 struct CombineSink {
   static constexpr bool queued = true;
   float val_scale, acc_scale;
@@ -532,38 +551,67 @@ struct CombineSink {
   int d, lane;
   float q0 = 0.f, q1 = 0.f;
   int nq = 0;
-  const bool queues = acc_in != nullptr && acc_out != nullptr;
-  __device__ __forceinline__ void refill(int64_t row, int n) {
-    const bool on = D64 || lane < d;
+  const bool has_y = !HORNER && y != nullptr;
+  const bool has_out = HORNER || acc_out != nullptr;
+  const bool queues = HORNER || (acc_in != nullptr && acc_out != nullptr);
+  __device__ __forceinline__ void begin(int64_t row0) {
+    if (has_y) y += row0 * d;
+    if (has_out) acc_out += row0 * d;
+    if (queues) acc_in += row0 * d;
+  }
+  __device__ __forceinline__ float load_next() {
+    const float v = (D64 || lane < d) ? stream_load(acc_in + lane) : 0.f;
+    acc_in += d;
+    return v;
+  }
+  __device__ __forceinline__ void refill(int n) {
     if (!queues) n = 0;
-    if (nq < 1 && 0 < n) q0 = on ? stream_load(acc_in + row * d + lane) : 0.f;
-    if (nq < 2 && 1 < n) q1 = on ? stream_load(acc_in + (row + 1) * d + lane) : 0.f;
+    if (nq < 1 && 0 < n) q0 = load_next();
+    if (nq < 2 && 1 < n) q1 = load_next();
     nq = max(nq, min(2, n));
   }
-  __device__ __forceinline__ void flush(int64_t row, float acc) {
+  __device__ __forceinline__ void flush(float acc) {
     // two roundings, as store_row: `acc * val_scale`, then the add of acc_in, never contracted
 #pragma clang fp contract(off)
     const bool on = D64 || lane < d;
     const float yv = acc * val_scale;
-    const int64_t base = row * d + lane;
-    if (y != nullptr) {
-      if (on) stream_store(y + base, yv);
+    if (has_y) {
+      if (on) stream_store(y + lane, yv);
+      y += d;
     }
-    if (acc_out != nullptr) {
+    if (has_out) {
       if (nq > 0) {
-        if (on) stream_store(acc_out + base, (q0 + yv) * acc_scale);
+        if (on) stream_store(acc_out + lane, (q0 + yv) * acc_scale);
         q0 = q1;
         --nq;
       } else {
         // fewer queued rows than row ends in one batch (degree-1 runs), or nothing to prefetch: load at the flush
-        if (on) {
-          const float prev = acc_in != nullptr ? stream_load(acc_in + base) : 0.f;
-          stream_store(acc_out + base, (prev + yv) * acc_scale);
-        }
+        const float prev = queues ? load_next() : 0.f;
+        if (on) stream_store(acc_out + lane, (prev + yv) * acc_scale);
       }
+      acc_out += d;
     }
   }
 };
+
+// What one arm of `spmm_layer` walks: a plan's descriptors, the CSR they partition and the split rows' workspace.
+struct WalkSet {
+  const int64_t* desc;
+  int64_t n_parts;
+  const int64_t* rowptr;
+  const int32_t* col;
+  const float* val;
+  float* partials;
+};
+
+// The plain launch's walk of partition `part`, for `spmm_rows` and the main arm of `spmm_layer`.
+template <bool D64, bool HAS_VAL, bool HORNER>
+__device__ __forceinline__ void walk_combine(int64_t part, const WalkSet& w, const float* __restrict__ x, int d,
+                                             float val_scale, float* y, const float* acc_in, float* acc_out,
+                                             float acc_scale) {
+  CombineSink<D64, HORNER> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
+  walk_partition<D64, HAS_VAL>(part, w.desc, w.n_parts, w.rowptr, w.col, w.val, x, d, w.partials, sink);
+}
 
 // The windowed companion's own kernel (graph.py HubPlan, step 1 of a windowed launch: partials = H x, nothing else), d <= 64:
 // the words it writes are those of `spmm_parts` on H with y only.  No mask, no epilogue, no acc_in queue.
@@ -579,27 +627,19 @@ __global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict_
 
 // The plain launch's own kernel (gcr_spmm_rows_f32), d <= 64: what `spmm_parts<1, D64, HAS_VAL, false, 16, false>` is used
 // for and nothing else.  No edge or column mask, no second addend, no row normalise, no second output; every word written
-// equals `spmm_parts`'s.  52 VGPRs / 81 SGPRs at d = 64 with values, 8 waves per SIMD without an SGPR cap and without lane
-// spills (`spmm_parts`: 63 / 94 capped, 18 scalars in VGPR lanes).  Measurements: EXPERIMENTS.md "SpMM: spmm_rows".
-template <bool D64, bool HAS_VAL>
+// equals `spmm_parts`'s.  50 VGPRs / 62 SGPRs at d = 64 with values in the Horner form, 46 / 81 in the others, 8 waves per
+// SIMD without an SGPR cap and without lane spills (`spmm_parts`: 63 / 94 capped, 18 scalars in VGPR lanes).
+// Measurements: EXPERIMENTS.md "SpMM: spmm_rows" and "SpMM: the walk's scalar work".
+// HORNER: the host entry saw acc_in and acc_out and no y (is_horner), the compile-time form of CombineSink.
+template <bool D64, bool HAS_VAL, bool HORNER>
 __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ desc, int64_t n_parts,
                                                  const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                  const float* __restrict__ val, const float* __restrict__ x, int d,
                                                  float val_scale, float* y, const float* acc_in, float* acc_out,
                                                  float acc_scale, float* __restrict__ partials) {
-  CombineSink<D64> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
-  walk_partition<D64, HAS_VAL>(wave_partition(0u), desc, n_parts, rowptr, col, val, x, d, partials, sink);
+  walk_combine<D64, HAS_VAL, HORNER>(wave_partition(0u), WalkSet{desc, n_parts, rowptr, col, val, partials}, x, d,
+                                     val_scale, y, acc_in, acc_out, acc_scale);
 }
-
-// What one arm of `spmm_layer` walks: a plan's descriptors, the CSR they partition and the split rows' workspace.
-struct WalkSet {
-  const int64_t* desc;
-  int64_t n_parts;
-  const int64_t* rowptr;
-  const int32_t* col;
-  const float* val;
-  float* partials;
-};
 
 // The windowed launch's two walks in one grid (gcr_spmm_windowed_f32), d <= 64: blocks [hub_block0, hub_block0 +
 // hub_blocks) are `spmm_hub_parts` on the companion (row sums into hub_y), every other block is `spmm_rows` on the main plan
@@ -612,9 +652,10 @@ struct WalkSet {
 // alone; the rest are kernel arguments of both arms loaded in front of the branch).  The hardware allocates in steps of 16,
 // so 97 is 112 and 7 waves per SIMD, although the compiler's report says 8: each arm launched alone through this kernel
 // was slower than its own kernel, the companion's 127.5 against 112.5 us and the main plan's 420.0 against 409.8 per cfg2
-// layer, which ate the whole gain of the one grid.  Capped it is 94 (96 allocated, 8 waves) with two scalars written to
-// VGPR lanes once in the prologue, outside every loop (53 VGPRs, 56 allocated as for 52).
-template <bool D64, bool HAS_VAL>
+// layer, which ate the whole gain of the one grid.  Capped it was 94 (96 allocated, 8 waves) with two scalars written to
+// VGPR lanes once in the prologue.  With the stepped row addresses the Horner form takes 79 SGPRs and 46 VGPRs and the
+// other forms 94 and 46, neither with a scalar in a VGPR lane; the cap stays for the other forms.
+template <bool D64, bool HAS_VAL, bool HORNER>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void spmm_layer(WalkSet hub, WalkSet rest, unsigned hub_block0, unsigned hub_blocks,
                                                   unsigned main_block0, const float* __restrict__ x, int d,
                                                   float* __restrict__ hub_y, float val_scale, float* y,
@@ -624,9 +665,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void spmm
     walk_partition<D64, HAS_VAL>(wave_partition(hub_block0), hub.desc, hub.n_parts, hub.rowptr, hub.col, hub.val, x, d,
                                  hub.partials, sink);
   } else {
-    CombineSink<D64> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
-    walk_partition<D64, HAS_VAL>(wave_partition(main_block0), rest.desc, rest.n_parts, rest.rowptr, rest.col, rest.val, x,
-                                 d, rest.partials, sink);
+    walk_combine<D64, HAS_VAL, HORNER>(wave_partition(main_block0), rest, x, d, val_scale, y, acc_in, acc_out, acc_scale);
   }
 }
 
@@ -770,6 +809,18 @@ int32_t launch_walk(const Plan& p, int d, const Epilogue& ep, hipStream_t stream
   return d == 64 ? go(std::true_type{}) : go(std::false_type{});
 }
 
+// The form CombineSink's HORNER instantiation is for: acc_in and acc_out given (in place included), no y.
+bool is_horner(const float* y, const float* acc_in, const float* acc_out) {
+  return y == nullptr && acc_in != nullptr && acc_out != nullptr;
+}
+
+// f(bool_constant<b>): a launch-time fact becomes a template argument
+template <class F>
+void dispatch_bool(bool b, F f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 }  // namespace
 
 extern "C" int32_t gcr_spmm_csr_acc2_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
@@ -895,9 +946,11 @@ extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const
   hipStream_t s = (hipStream_t)stream;
   return launch_walk(p, d, make_epilogue(val_scale, y, acc_in, acc_out, acc_scale), s,
                      [&](auto d64, auto hv, dim3 blocks) {
-                       hipLaunchKernelGGL((spmm_rows<decltype(d64)::value, decltype(hv)::value>), blocks, dim3(256), 0, s,
-                                          desc, n_parts, rowptr, col, val, x, d, val_scale, y, acc_in, acc_out, acc_scale,
-                                          partials);
+                       dispatch_bool(is_horner(y, acc_in, acc_out), [&](auto horner) {
+                         hipLaunchKernelGGL((spmm_rows<decltype(d64)::value, decltype(hv)::value, decltype(horner)::value>),
+                                            blocks, dim3(256), 0, s, desc, n_parts, rowptr, col, val, x, d, val_scale, y,
+                                            acc_in, acc_out, acc_scale, partials);
+                       });
                      });
 }
 
@@ -944,12 +997,15 @@ extern "C" int32_t gcr_spmm_windowed_f32(
     // one grid, or (main_first == 2, the A/B script's cell for the merged split-row launch alone) one per range
     auto walk = [&](unsigned n_blocks, unsigned hb0, unsigned hb, unsigned mb0) {
       if (n_blocks == 0) return (int32_t)GCR_OK;
-      if (has_val)
-        hipLaunchKernelGGL((spmm_layer<D64, true>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
-                           hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
-      else
-        hipLaunchKernelGGL((spmm_layer<D64, false>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
-                           hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
+      dispatch_bool(is_horner(y, acc_in, acc_out), [&](auto horner) {
+        constexpr bool HORNER = decltype(horner)::value;
+        if (has_val)
+          hipLaunchKernelGGL((spmm_layer<D64, true, HORNER>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
+                             hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
+        else
+          hipLaunchKernelGGL((spmm_layer<D64, false, HORNER>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
+                             hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
+      });
       return (int32_t)GCR_LAUNCH_STATUS();
     };
     int32_t st = main_first == 2 ? walk(hub_blocks, 0u, hub_blocks, 0u) : walk(blocks, hub_block0, hub_blocks, main_block0);

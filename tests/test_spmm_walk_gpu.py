@@ -1,0 +1,196 @@
+"""The partition walk's row-end test and its row sinks change no word.
+
+`walk_partition` (behind gcr_spmm_rows_f32 and gcr_spmm_windowed_f32) tests a row end relative to the batch, in chunks as
+in whole-row partitions, and its row sinks step their row addresses from one row end to the next: StoreSink (the
+companion), HornerSink (acc_in and acc_out given, no y: a compile-time form) and CombineSink (every other form).
+`spmm_parts` (behind gcr_spmm_csr_acc2_f32) has none of that and is the reference: on the same plans every word of y,
+acc_out, both split-row workspaces and the hub partials, all NaN-filled beforehand, must be `torch.equal` to what the
+generic route writes -- `spmm_parts` on the companion (y only, val_scale 1), `spmm_parts` on the main plan and the hub rows'
+reduction (gcr_spmm_hub_reduce_f32, which this walk does not touch).  A second launch must equal the first.
+
+Graphs: the 300 users x 40 items and the 5 x 3 bipartite sym-norm operators of tests/test_spmm_policy_gpu.py; a hand-built
+CSR (34 rows x 700 columns) whose first partition holds exactly 512 non-zeros in whole rows -- empty rows first, in the
+middle and last, a row ending exactly at non-zero 64 and one at 65, five degree-1 rows inside one batch of 16 (more row
+ends than the two-entry acc_in queue holds: the load-at-flush arm) -- followed by a row of 1 300 non-zeros (chunks and
+`spmm_long_rows`; the hub row when the hub plan is on) and one of 600 (a split row of the main plan either way); and a
+one-non-zero matrix.  d = 64, 48, 4; with values and all-ones; hub plan forced with a 64-row window, and off."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+HAND_COLS = 700
+# (y, acc_in: None | 'given' | 'inplace', acc_out, val_scale, acc_scale)
+FORMS = {"horner": (False, "given", True, 1.0, 1.0), "horner_scaled": (False, "given", True, 0.75, 0.25),
+         "horner_in_place": (False, "inplace", True, 1.0, 0.5), "y_only": (True, None, False, 1.0 / 0.65, 1.0),
+         "y_and_acc": (True, "given", True, 1.0 / 0.65, 1.0 / 3.0), "acc_without_acc_in": (False, None, True, -1.5, 0.5)}
+# graph, hub plan on; a graph without a row above its hub degree has no hub plan to force
+CASES = [("300x40", False), ("300x40", True), ("5x3", False), ("5x3", True), ("hand", False), ("hand", True), ("one_nnz", False)]
+BIPARTITE = {"300x40": (300, 40, 3000, 100), "5x3": (5, 3, None, 3)}         # users, items, interactions, hub_min_degree
+
+
+def _bipartite(shape, has_val):
+    """rowptr, col, val, n_rows, n_cols, hub_min_degree, nnz_per_part: users first, sym-norm values, sorted columns."""
+    n_u, n_i, e, min_deg = BIPARTITE[shape]
+    if e is None:
+        u, i = np.array([0, 1, 2, 4, 1, 4, 2]), np.array([0, 0, 0, 0, 1, 2, 2])           # user 3 has no interaction
+    else:
+        rng = np.random.default_rng(20251)
+        p = 1.0 / np.arange(1, n_i + 1) ** 0.8                                            # a few items most users name
+        u = rng.integers(0, n_u - 7, e)                                                   # the last users: empty rows
+        i = rng.choice(n_i, e, p=p / p.sum())
+        keep = np.unique(u * n_i + i)
+        u, i = keep // n_i, keep % n_i
+    n = n_u + n_i
+    rows, cols = np.concatenate([u, i + n_u]), np.concatenate([i + n_u, u])
+    order = np.lexsort((cols, rows))
+    rows, cols = rows[order], cols[order]
+    deg = np.bincount(rows, minlength=n)
+    rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    val = (1.0 / np.sqrt(deg[rows] * deg[cols])).astype(F32) if has_val else None
+    return rowptr, cols.astype(np.int32), val, n, n, min_deg, 64
+
+
+HAND_HEAD = [0, 0, 0, 30, 34, 1, 1, 1, 1, 1, 1, 0, 0, 10, 9, 11, 12, 8, 13, 16, 17, 2]      # 168 non-zeros
+HAND_DEG = HAND_HEAD + [512 - sum(HAND_HEAD)] + [1300, 3, 0, 5, 600, 1, 7, 0, 0]
+
+
+def _hand(has_val):
+    deg = np.asarray(HAND_DEG, dtype=np.int64)
+    rng = np.random.default_rng(97 + int(has_val))
+    rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    col = np.concatenate([np.sort(rng.integers(0, HAND_COLS, k)) for k in deg]).astype(np.int32)   # sorted inside a row
+    val = rng.standard_normal(col.size).astype(F32) if has_val else None
+    return rowptr, col, val, deg.size, HAND_COLS, 1000, 512
+
+
+@functools.lru_cache(maxsize=None)
+def _graph(name, has_val, hub):
+    import recommendation_amd as ra
+    if name in BIPARTITE:
+        rowptr, col, val, n_rows, n_cols, min_deg, npp = _bipartite(name, has_val)
+    elif name == "hand":
+        rowptr, col, val, n_rows, n_cols, min_deg, npp = _hand(has_val)
+    else:
+        rowptr, col, val = np.array([0, 1], dtype=np.int64), np.array([5], dtype=np.int32), (np.array([0.5], F32) if has_val else None)
+        n_rows, n_cols, min_deg, npp = 1, 9, None, 512
+    kw = dict(hub_window_rows=64, hub_min_degree=min_deg) if hub else dict(hub_window_rows=0)
+    g = ra.CsrGraph(rowptr, col, val, n_rows, n_cols, "cuda", symmetric=n_rows == n_cols, nnz_per_part=npp, **kw)
+    assert (g.hub is not None) == hub
+    if name == "hand":
+        desc = g.plan.desc_host
+        ends = (rowptr[1:23] - rowptr[0]).tolist()
+        assert int(desc[0, 1] - desc[0, 0]) == 512 and desc[0, 3] < 0 and int(desc[0, 2] >> 32) == 23, "first partition: 23 whole rows, 512 non-zeros"
+        assert ends[3:11] == [30, 64, 65, 66, 67, 68, 69, 70], "row ends at 64 and 65, then five more inside the batch [64, 80)"
+        assert g.plan.n_long == 2
+        if hub:
+            assert g.hub.n_hub == 1 and g.hub.main.n_long == 1 and g.hub.n_windows == 11
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(name, d):
+    g = _graph(name, True, False)
+    rng = np.random.default_rng(31 * d + g.n_rows)
+    return (torch.from_numpy(rng.standard_normal((g.n_cols, d)).astype(F32)).cuda(),
+            torch.from_numpy(rng.standard_normal((g.n_rows, d)).astype(F32)).cuda())
+
+
+def _head(plan, csr):
+    from recommendation_amd import _lib
+    return (_lib.dptr(plan.desc), plan.n_parts, _lib.dptr(plan.long_row), _lib.dptr(plan.long_slot0), plan.n_long,
+            _lib.dptr(csr.rowptr), _lib.dptr(csr.col), _lib.dptr(csr.val))
+
+
+def _nan(rows, d):
+    return torch.full((max(int(rows), 1), d), float("nan"), device="cuda")
+
+
+class _Out:
+    def __init__(self, g, d, form, acc_in):
+        want_y, a_in, want_acc, self.val_scale, self.acc_scale = FORMS[form]
+        self.y = _nan(g.n_rows, d) if want_y else None
+        self.acc_out = _nan(g.n_rows, d) if want_acc else None
+        self.acc_in = acc_in.clone() if a_in else None
+        if a_in == "inplace":
+            self.acc_out = self.acc_in
+
+
+def _generic(plan, csr, xt, d, y, acc_in, acc_out, val_scale, acc_scale, ws):
+    """`spmm_parts` over `plan`.  Rows the plan skips stay as they were."""
+    from recommendation_amd import _lib
+    _lib.check(_lib.lib().gcr_spmm_csr_acc2_f32(
+        *_head(plan, csr), None, val_scale, _lib.dptr(xt), d, _lib.dptr(y), _lib.dptr(acc_in), None, 0.0, _lib.dptr(acc_out),
+        acc_scale, 0, None, _lib.dptr(ws), csr.n_rows, csr.n_cols, None, _lib.cur_stream(xt.device)), "gcr_spmm_csr_acc2_f32")
+
+
+def _reference(g, xt, d, form, a_in):
+    """[y, acc_out, main workspace, hub partials, companion workspace] by the generic route; None where there is none."""
+    from recommendation_amd import _lib
+    o = _Out(g, d, form, a_in)
+    if g.hub is None:
+        ws = _nan(g.plan.n_slots, d)
+        _generic(g.plan, g, xt, d, o.y, o.acc_in, o.acc_out, o.val_scale, o.acc_scale, ws)
+        torch.cuda.synchronize()
+        return [o.y, o.acc_out, ws, None, None]
+    hub, H, main = g.hub, g.hub.H, g.hub.main
+    part, hws, mws = _nan(H.n_rows, d), _nan(H.plan.n_slots, d), _nan(main.n_slots, d)
+    _generic(H.plan, H, xt, d, part, None, None, 1.0, 1.0, hws)
+    _generic(main, g, xt, d, o.y, o.acc_in, o.acc_out, o.val_scale, o.acc_scale, mws)
+    _lib.check(_lib.lib().gcr_spmm_hub_reduce_f32(_lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, o.val_scale,
+                                                  _lib.dptr(o.y), _lib.dptr(o.acc_in), _lib.dptr(o.acc_out), o.acc_scale, g.n_rows,
+                                                  _lib.cur_stream(xt.device)), "gcr_spmm_hub_reduce_f32")
+    torch.cuda.synchronize()
+    return [o.y, o.acc_out, mws, part, hws]
+
+
+def _walk(g, xt, d, form, a_in):
+    """The same five arrays by the entry that runs `walk_partition`."""
+    from recommendation_amd import _lib
+    L, s = _lib.lib(), _lib.cur_stream(xt.device)
+    o = _Out(g, d, form, a_in)
+    if g.hub is None:
+        ws = _nan(g.plan.n_slots, d)
+        _lib.check(L.gcr_spmm_rows_f32(*_head(g.plan, g), o.val_scale, _lib.dptr(xt), d, _lib.dptr(o.y), _lib.dptr(o.acc_in),
+                                       _lib.dptr(o.acc_out), o.acc_scale, _lib.dptr(ws), g.n_rows, g.n_cols, s), "gcr_spmm_rows_f32")
+        torch.cuda.synchronize()
+        return [o.y, o.acc_out, ws, None, None]
+    hub, H, main = g.hub, g.hub.H, g.hub.main
+    part, hws, mws = _nan(H.n_rows, d), _nan(H.plan.n_slots, d), _nan(main.n_slots, d)
+    _lib.check(L.gcr_spmm_windowed_f32(
+        *_head(H.plan, H), _lib.dptr(hws), *_head(main, g), _lib.dptr(mws), _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows,
+        _lib.dptr(part), _lib.dptr(xt), d, o.val_scale, _lib.dptr(o.y), _lib.dptr(o.acc_in), _lib.dptr(o.acc_out), o.acc_scale,
+        int(hub.main_first), g.n_rows, g.n_cols, s), "gcr_spmm_windowed_f32")
+    torch.cuda.synchronize()
+    return [o.y, o.acc_out, mws, part, hws]
+
+
+WHAT = ("y", "acc_out", "main workspace", "hub partials", "companion workspace")
+
+
+def _equal(got, want, what):
+    for g, w, name in zip(got, want, WHAT):
+        assert (g is None) == (w is None), f"{what} {name}"
+        if g is not None:
+            gi, wi = g.view(torch.int32), w.view(torch.int32)
+            assert torch.equal(gi, wi), f"{what} {name}: {int((gi != wi).sum())} of {gi.numel()} words differ"
+
+
+@pytest.mark.parametrize("has_val", [True, False], ids=["val", "ones"])
+@pytest.mark.parametrize("d", [64, 48, 4])
+@pytest.mark.parametrize("name,hub", CASES, ids=[f"{n}-{'hub' if h else 'plain'}" for n, h in CASES])
+def test_every_word_equals_the_generic_route(name, hub, d, has_val):
+    g = _graph(name, has_val, hub)
+    xt, a_in = _inputs(name, d)
+    for form in FORMS:
+        what = f"{name} hub={hub} d={d} {form}"
+        ref = _reference(g, xt, d, form, a_in)
+        for t, nm in zip(ref[:2], WHAT):
+            assert t is None or not bool(torch.isnan(t).any()), f"{what}: the reference left a word of {nm} unwritten"
+        first = _walk(g, xt, d, form, a_in)
+        _equal(first, ref, what)
+        _equal(_walk(g, xt, d, form, a_in), first, what + ", second launch")
