@@ -891,6 +891,52 @@ int32_t gcr_buir_bwd_f32(const float* on_user, const float* on_item, const float
 int32_t gcr_ema_rows_f32(float* target, const float* online, const int64_t* idx, int64_t n, int32_t d, int64_t n_rows,
                          double momentum, uint32_t* claim_bits, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Barlow Twins: redundancy reduction over two full-batch views (csrc/gcr_bt.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * mean[d], std[d] = the column mean and the UNBIASED standard deviation (divisor n - 1: torch.std's default) of the
+ * row-major x [n, d].  Every thread runs Welford's update over x - k with k its first row, never E[x^2] - E[x]^2; the
+ * (count, mean, M2) partials are merged by Chan's rule in a fixed order, inside a workgroup and then over the
+ * workgroups.  Two launches, bitwise reproducible.  n >= 2; d % 4 == 0, 4 <= d <= 1024 (GCR_EUNSUPPORTED otherwise);
+ * x 16-B aligned; workspace gcr_col_stats_workspace_bytes(n, d) bytes.
+ */
+int64_t gcr_col_stats_workspace_bytes(int64_t n, int32_t d);
+int32_t gcr_col_stats_f32(const float* x, int64_t n, int32_t d, float* mean, float* std, void* workspace, void* stream);
+/*
+ * replaces  bt_loss  univariate/gbt.py:203-217 and the second evaluation of WithinEmbedContrast.forward :392-395 (the
+ *           cross-correlation of (h2, h1) is c^T, whose diagonal and off-diagonal sum of squares are c's).
+ * h1, h2 [n, d] row-major float32, 16-B aligned.  batch_norm != 0:
+ *   stats [4 d] = mean1, std1, mean2, std2 (gcr_col_stats_f32's numbers),  z = (h - mean) / (std + eps), applied to the
+ *   operands as they are loaded and never written out,  c [d, d] = z1^T z2 / n;
+ * batch_norm == 0:  c = h1^T h2 / n, stats is neither read nor written.
+ *   loss[0] = sum_j (1 - c_jj)^2 + lambda sum_{j != k} c_jk^2        (the caller resolves lambda = None to 1 / d)
+ * The product runs on the f32-input MFMA with the rows split over min(ceil(n / 256), 1024) workgroups (d = 256: at most
+ * 256, times four 128 x 128 quadrants of c); the partials are summed in a fixed order, no float atomics, no host
+ * read-back: every output is bitwise reproducible.  Launches: 2 (statistics of both views), 1 (product), 2 (reduce + the
+ * loss terms, their sum).  stats and c are what the backward needs; nothing of size [n, d] is saved.
+ * Backward, for an upstream scalar g_loss[0] on the device.  With
+ *   G = g_loss * (2 lambda c off the diagonal, -2 (1 - c_jj) on it),
+ *   t1[j] = sum_k G[j,k] c[j,k],   t2[k] = sum_j G[j,k] c[j,k],   s = std, m = mean:
+ *   g_h1[n,j] = (z2 G^T)[n,j] / (n (s1_j + eps))  -  t1[j] (h1[n,j] - m1_j) / ((s1_j + eps) (n - 1) s1_j)
+ *   g_h2[n,k] = (z1 G  )[n,k] / (n (s2_k + eps))  -  t2[k] (h2[n,k] - m2_k) / ((s2_k + eps) (n - 1) s2_k)
+ * (the column sums of z G vanish because z is centred, and sum_n (z2 G^T)[n,j] z1[n,j] / n = t1[j]: the standardisation's
+ * backward needs no second reduction over n).  batch_norm == 0: only the first terms, with z = h and s + eps = 1.
+ * A column whose std is exactly 0 has z = 0 in the forward, as in the reference; its gradient column is WRITTEN AS 0 where
+ * the reference's autograd differentiates (h - mean) / (0 + eps): a column of magnitude 1 / eps, or NaN where std's
+ * backward is left as 0 / 0 (a stated deviation, like gcr_mim_fwd_f32's finite softplus).  Either gradient pointer may be NULL.  Two launches: one
+ * of d workgroups (G, G^T, t1, t2 into the workspace) and one over the rows.
+ * Supported (gcr_bt_supported): d in {32, 64, 96, 128, 256}; GCR_EUNSUPPORTED otherwise.  n >= 2 (n >= 1 without
+ * batch_norm).  workspace: gcr_bt_workspace_bytes(n, d) bytes, 16-B aligned, for either call.
+ */
+int32_t gcr_bt_supported(int32_t d);
+int64_t gcr_bt_workspace_bytes(int64_t n, int32_t d);
+int32_t gcr_bt_fwd_f32(const float* h1, const float* h2, int64_t n, int32_t d, float lambda, float eps, int32_t batch_norm,
+                       float* stats, float* c, float* loss, void* workspace, void* stream);
+int32_t gcr_bt_bwd_f32(const float* h1, const float* h2, int64_t n, int32_t d, float lambda, float eps, int32_t batch_norm,
+                       const float* stats, const float* c, const float* g_loss, float* g_h1, float* g_h2, void* workspace,
+                       void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

@@ -141,6 +141,12 @@ SIGNATURES = {
     "gcr_buir_bwd_f32": (c_int32, [_P, _P, _P, _P, c_int64, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P, _P, _P, _P, _P]),
     "gcr_ema_rows_f32": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int64, c_double, _P, _P]),
+    "gcr_col_stats_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "gcr_col_stats_f32": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P]),
+    "gcr_bt_supported": (c_int32, [c_int32]),
+    "gcr_bt_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "gcr_bt_fwd_f32": (c_int32, [_P, _P, c_int64, c_int32, c_float, c_float, c_int32, _P, _P, _P, _P, _P]),
+    "gcr_bt_bwd_f32": (c_int32, [_P, _P, c_int64, c_int32, c_float, c_float, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_mask_columns_f32":(c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "gcr_spgemm_expand_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_csr_lookup_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P]),

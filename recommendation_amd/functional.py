@@ -1844,3 +1844,129 @@ def ema_rows_(target, online, idx, momentum):
                                            idx.numel(), d, n_rows, float(momentum), _lib.dptr(claim),
                                            _lib.cur_stream(target.device)), "gcr_ema_rows_f32")
     return target
+
+
+# ---------------------------------------------------------------------------------------------
+# Barlow Twins: redundancy reduction over two full-batch views (univariate/gbt.py:203-228, 386-395)
+# ---------------------------------------------------------------------------------------------
+BT_WIDTHS = (32, 64, 96, 128, 256)
+
+
+def column_stats(x):
+    """(mean, std) of the columns of a float32 [n, d] device tensor, std unbiased (`x.mean(dim=0)`, `x.std(dim=0)`, gbt.py:
+    209-210) from one pass over the rows (gcr_col_stats_f32: Welford on shifted values per thread, Chan merges in a fixed order;
+    bitwise reproducible).  n >= 2, d % 4 == 0, d <= 1024.  Not differentiable."""
+    _lib.require_cuda(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[0] < 2:
+        raise ValueError("column_stats needs a float32 [n, d] tensor with n >= 2")
+    x = x.detach().contiguous()
+    n, d = x.shape
+    L = _lib.lib()
+    out = torch.empty(2, d, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(L.gcr_col_stats_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=x.device)
+    _lib.check(L.gcr_col_stats_f32(_lib.dptr(x), n, d, _lib.dptr(out[0]), _lib.dptr(out[1]), _lib.dptr(ws),
+                                   _lib.cur_stream(x.device)), "gcr_col_stats_f32")
+    return out[0], out[1]
+
+
+def bt_supported(d):
+    """True when the fused kernels (gcr_bt_*) serve views of width d: 32, 64, 96, 128 or 256."""
+    return int(d) in BT_WIDTHS
+
+
+def _bt_args(h1, h2, lambda_, batch_norm):
+    if h1.dim() != 2 or h1.shape != h2.shape or h1.dtype != h2.dtype or h1.device != h2.device:
+        raise ValueError("bt_loss needs two [n, d] views of one shape, dtype and device")
+    if h1.shape[0] < (2 if batch_norm else 1):
+        raise ValueError("bt_loss needs n >= 2 rows (n >= 1 without batch_norm)")
+    return 1.0 / h1.shape[1] if lambda_ is None else float(lambda_)
+
+
+def bt_cross_correlation_composed(h1, h2, batch_norm=True, eps=1e-15):
+    """c [d, d] of gbt.py:208-213 as the reference writes it: the standardised views' (or the raw views') product over n."""
+    batch_size = h1.size(0)
+    if batch_norm:
+        z1_norm = (h1 - h1.mean(dim=0)) / (h1.std(dim=0) + eps)
+        z2_norm = (h2 - h2.mean(dim=0)) / (h2.std(dim=0) + eps)
+        return (z1_norm.T @ z2_norm) / batch_size
+    return h1.T @ h2 / batch_size
+
+
+def bt_loss_composed(h1, h2, lambda_=None, batch_norm=True, eps=1e-15):
+    """`bt_loss` as the reference writes it (gbt.py:203-217), statement by statement in torch, on any device and dtype: the
+    path of widths outside `bt_supported` and the baseline of scripts/perf_bt_loss.py."""
+    lambda_ = _bt_args(h1, h2, lambda_, batch_norm)
+    feature_dim = h1.size(1)
+    c = bt_cross_correlation_composed(h1, h2, batch_norm, eps)
+    off_diagonal_mask = ~torch.eye(feature_dim, device=h1.device).bool()
+    loss = (1 - c.diagonal()).pow(2).sum()
+    return loss + lambda_ * c[off_diagonal_mask].pow(2).sum()
+
+
+def bt_forward_raw(h1, h2, lambda_, batch_norm=True, eps=1e-15):
+    """gcr_bt_fwd_f32 on contiguous float32 device views -> (loss [1], c [d, d], stats [4, d]: mean1, std1, mean2, std2;
+    not written without batch_norm)."""
+    L = _lib.lib()
+    n, d = h1.shape
+    dev = h1.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    c = torch.empty(d, d, dtype=torch.float32, device=dev)
+    stats = torch.zeros(4, d, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(int(L.gcr_bt_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=dev)
+    _lib.check(L.gcr_bt_fwd_f32(_lib.dptr(h1), _lib.dptr(h2), n, d, float(lambda_), float(eps), int(bool(batch_norm)),
+                                _lib.dptr(stats), _lib.dptr(c), _lib.dptr(loss), _lib.dptr(ws), _lib.cur_stream(dev)),
+               "gcr_bt_fwd_f32")
+    return loss, c, stats
+
+
+def bt_backward_raw(h1, h2, lambda_, batch_norm, eps, stats, c, g, want1=True, want2=True):
+    """gcr_bt_bwd_f32 -> (g_h1 or None, g_h2 or None) for the upstream device scalar g (float32 [1])."""
+    L = _lib.lib()
+    n, d = h1.shape
+    dev = h1.device
+    g1 = torch.empty_like(h1) if want1 else None
+    g2 = torch.empty_like(h2) if want2 else None
+    ws = torch.empty(max(int(L.gcr_bt_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=dev)
+    _lib.check(L.gcr_bt_bwd_f32(_lib.dptr(h1), _lib.dptr(h2), n, d, float(lambda_), float(eps), int(bool(batch_norm)),
+                                _lib.dptr(stats), _lib.dptr(c), _lib.dptr(g), _lib.dptr(g1), _lib.dptr(g2), _lib.dptr(ws),
+                                _lib.cur_stream(dev)), "gcr_bt_bwd_f32")
+    return g1, g2
+
+
+class _BtLoss(torch.autograd.Function):
+    """gcr_bt_fwd_f32 / gcr_bt_bwd_f32: beside the two inputs only stats [4, d] and c [d, d] are saved."""
+
+    @staticmethod
+    def forward(ctx, h1, h2, lambda_, batch_norm, eps):
+        h1, h2 = h1.contiguous(), h2.contiguous()
+        loss, c, stats = bt_forward_raw(h1, h2, lambda_, batch_norm, eps)
+        ctx.save_for_backward(h1, h2, stats, c)
+        ctx.hp = (lambda_, batch_norm, eps)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        h1, h2, stats, c = ctx.saved_tensors
+        g = g.to(torch.float32).reshape(1).contiguous()
+        g1, g2 = bt_backward_raw(h1, h2, *ctx.hp, stats, c, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return g1, g2, None, None, None
+
+
+def bt_loss(h1, h2, lambda_=None, batch_norm=True, eps=1e-15):
+    """The Barlow Twins loss of two float32 [n, d] device views, univariate/gbt.py:203-217:
+        z = (h - h.mean(0)) / (h.std(0) + eps)   (batch_norm; otherwise z = h),   c = z1^T z2 / n,
+        loss = sum_j (1 - c_jj)^2 + lambda_ sum_{j != k} c_jk^2,   lambda_ = None: 1 / d
+    as ONE autograd node over gcr_bt_fwd_f32 / gcr_bt_bwd_f32 (include/gcr.h has the backward's formulas): five launches
+    forward and two backward, three of them over the rows; z is never written and only the statistics and c are saved.
+    Returns a 0-d device tensor; every output is bitwise reproducible.  The loss of (h2, h1) is the same number (c^T has c's
+    diagonal and off-diagonal sum of squares), so `WithinEmbedContrast` needs one evaluation.  A column of exactly zero
+    std gets a zero gradient column where the reference's autograd gives one of magnitude 1 / eps (or NaN, by the torch
+    version's std backward); `bt_loss_composed` keeps the reference's behaviour.  Widths
+    outside `bt_supported(d)` run `bt_loss_composed`."""
+    _lib.require_cuda(h1, h2)
+    lam = _bt_args(h1, h2, lambda_, batch_norm)
+    if h1.dtype != torch.float32:
+        raise ValueError("bt_loss needs float32 views")
+    if not bt_supported(h1.shape[1]):
+        return bt_loss_composed(h1, h2, lam, batch_norm, eps)
+    return _BtLoss.apply(h1, h2, lam, bool(batch_norm), float(eps))

@@ -187,3 +187,41 @@ def grace_infonce_loss(h1, h2, tau, intraview_negs=True, exclude_self=False):
         return (torch.logaddexp(lse_inter, lse_intra) - pos).mean()
 
     return (one_direction(h1, h2) + one_direction(h2, h1)) * 0.5
+
+
+class BarlowTwins:
+    """univariate/gbt.py:220-228 with its call protocol (:198-200): `loss(anchor=h1, sample=h2)` -> `bt_loss(anchor, sample,
+    lambda_, batch_norm, eps).mean()`.  Note eps = 1e-5 here against `bt_loss`'s own default of 1e-15: both are the
+    reference's (:203, :221).  Float32 device views run the fused `Fn.bt_loss`; any other dtype or device runs the
+    reference's statements (`Fn.bt_loss_composed`)."""
+
+    def __init__(self, lambda_: float = None, batch_norm: bool = True, eps: float = 1e-5):
+        self.lambda_ = lambda_
+        self.batch_norm = batch_norm
+        self.eps = eps
+
+    def compute(self, anchor, sample, pos_mask=None, neg_mask=None, *args, **kwargs):
+        fn = Fn.bt_loss if anchor.is_cuda and anchor.dtype == torch.float32 else Fn.bt_loss_composed
+        return fn(anchor, sample, self.lambda_, self.batch_norm, self.eps).mean()
+
+    def __call__(self, anchor, sample, pos_mask=None, neg_mask=None, *args, **kwargs):
+        return self.compute(anchor, sample, pos_mask, neg_mask, *args, **kwargs)
+
+
+class WithinEmbedContrast(torch.nn.Module):
+    """univariate/gbt.py:386-395: `forward(h1, h2)` = (loss(anchor=h1, sample=h2) + loss(anchor=h2, sample=h1)) * 0.5.
+    With a `BarlowTwins` loss the second direction's cross-correlation is the transpose of the first's, and the loss reads
+    only the diagonal and the off-diagonal sum of squares, which a transpose keeps: one evaluation serves both, and
+    (l1 + l1) * 0.5 is l1 bit for bit.  Any other loss object is called in both directions as written."""
+
+    def __init__(self, loss, **kwargs):
+        super().__init__()
+        self.loss = loss
+        self.kwargs = kwargs
+
+    def forward(self, h1, h2):
+        l1 = self.loss(anchor=h1, sample=h2, **self.kwargs)
+        if isinstance(self.loss, BarlowTwins):
+            return (l1 + l1) * 0.5
+        l2 = self.loss(anchor=h2, sample=h1, **self.kwargs)
+        return (l1 + l2) * 0.5
