@@ -201,6 +201,20 @@ def dptr(t):
     return c_void_p(t.data_ptr())
 
 
+_SIZE_UNIT = {"_bytes": 1, "_floats": 4, "_words": 4}     # what a size export counts, by its name's ending
+
+
+def workspace(query, *args, device, dtype=torch.float32):
+    """The scratch buffer of an entry point: `query` names its size export (gcr_*_workspace_bytes, _workspace_floats or
+    _words), called with `args`.  Returns an uninitialised `dtype` tensor on `device` of at least that size and at least one
+    element, so that a query answering 0 (an empty or unsupported problem, which the entry point refuses itself) still
+    yields a pointer."""
+    unit = next(u for ending, u in _SIZE_UNIT.items() if query.endswith(ending))
+    nbytes = int(getattr(lib(), query)(*args)) * unit
+    item = torch.empty((), dtype=dtype).element_size()
+    return torch.empty(max(-(-nbytes // item), 1), dtype=dtype, device=device)
+
+
 def cur_stream(device=None):
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

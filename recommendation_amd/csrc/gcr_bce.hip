@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void bce_row_scales_kernel(const float* __rest
 template <int D>
 void launch_bce_row_scales(const float* x, int64_t rows, const float* w, float* inv, float* nrm, float* f, hipStream_t s) {
   const int64_t want = (rows + 4 * (1024 / D) - 1) / (4 * (1024 / D));
-  hipLaunchKernelGGL((bce_row_scales_kernel<D>), dim3((unsigned)(want < 1 ? 1 : (want > 8192 ? 8192 : want))), dim3(256), 0, s, x,
+  hipLaunchKernelGGL((bce_row_scales_kernel<D>), dim3((unsigned)gcr_grid(want, 8192)), dim3(256), 0, s, x,
                      rows, w, inv, nrm, f);
 }
 

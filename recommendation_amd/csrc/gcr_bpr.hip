@@ -21,20 +21,13 @@
 // on the item sides.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "gcr_common.h"
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 
 namespace {
 
 constexpr int kFwdThreads = 256;
 constexpr int kGroups = kFwdThreads / 16;
-
-__device__ __forceinline__ float group16_sum(float v) {
-  v += __shfl_xor(v, 8, 16);
-  v += __shfl_xor(v, 4, 16);
-  v += __shfl_xor(v, 2, 16);
-  v += __shfl_xor(v, 1, 16);
-  return v;
-}
 
 // d(loss)/dx and loss for x = pos - neg.  s = sigmoid(x) = 1 / (1 + e), e = exp(-x).  The subtraction 1 - s is exact, so
 // it carries s's rounding: 2^-25 absolute whatever x is.  That is within 2^-20 of 1 - s (the floor of the float64 pins'
@@ -114,11 +107,11 @@ __global__ __launch_bounds__(kFwdThreads) void bpr_fwd_kernel(const float* __res
         }
       }
     }
-    pos = group16_sum(pos);
-    neg = group16_sum(neg);
-    su = group16_sum(su);
-    sp = group16_sum(sp);
-    sn = group16_sum(sn);
+    pos = gcr_group16_sum(pos);
+    neg = gcr_group16_sum(neg);
+    su = gcr_group16_sum(su);
+    sp = gcr_group16_sum(sp);
+    sn = gcr_group16_sum(sn);
     float loss, dl;
     bpr_point(variant, pos - neg / (float)n_neg, loss, dl);
     if (l16 == 0) dloss_dx[b] = dl;
@@ -148,8 +141,7 @@ __global__ void bpr_reduce_kernel(const float* __restrict__ block_partials, int 
   const int lane = threadIdx.x & 63;
   double s = 0.0;
   for (int b = lane; b < n_blocks; b += 64) s += (double)block_partials[(int64_t)b * 5 + k];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = gcr_wave_sum_f64(s);
   if (lane == 0) sums[k] = (float)s;
 }
 
@@ -226,8 +218,6 @@ size_t sort_u32_temp_bytes(int64_t n) {
   (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)n, 0, 32, (hipStream_t)0);
   return bytes;
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // SIDE 0: rows of grad_user keyed by u; 1: rows of grad_item keyed by the positive item; 2: keyed by the
 // negative item (entries are the batch * n_neg negative slots).  Same arithmetic as bpr_bwd_kernel.
@@ -478,9 +468,23 @@ size_t sort_u32_u64_temp_bytes(int64_t n) {
   return bytes;
 }
 
-int fwd_blocks(int64_t batch) {
-  const int64_t want = (batch + kGroups - 1) / kGroups;
-  return (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+int fwd_blocks(int64_t batch) { return (int)gcr_grid((batch + kGroups - 1) / kGroups, 4096); }
+
+// the sorted kernels: a wave per 64-entry chunk, four waves per workgroup
+unsigned chunk_blocks(int64_t n_entries) { return (unsigned)gcr_grid(((n_entries + 63) / 64 + 3) / 4, 65536); }
+
+// gcr_sort_index's workspace in bytes: the unsorted keys and values, then rocPRIM's temporary storage
+struct SortIndexWorkspace {
+  int64_t key_in, val_in, tmp, total;
+};
+SortIndexWorkspace sort_index_layout(int64_t n) {
+  SortIndexWorkspace w;
+  WsCarve c;
+  w.key_in = c.take((int64_t)sizeof(uint32_t) * n, 256);
+  w.val_in = c.take((int64_t)sizeof(int32_t) * n, 256);
+  w.tmp = c.take((int64_t)sort_u32_temp_bytes(n), 1);
+  w.total = c.at;
+  return w;
 }
 
 }  // namespace
@@ -517,22 +521,17 @@ extern "C" int32_t gcr_bpr_bwd_f32(const float* user_tab, const float* item_tab,
   if (batch == 0) return GCR_OK;
   GCR_CHECK_ARG(user_tab && item_tab && u_idx && i_idx && j_idx && dloss_dx && grad_sums && grad_user && grad_item);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t want = (batch + 3) / 4;
-  const int blocks = (int)(want > 8192 ? 8192 : want);
-#define GCR_BWD(NV)                                                                                              \
-  hipLaunchKernelGGL((bpr_bwd_kernel<NV>), dim3(blocks), dim3(256), 0, s, user_tab, item_tab, d, u_idx, i_idx, \
-                     j_idx, batch, n_neg, n_users, n_items, dloss_dx, grad_sums, grad_user, grad_item)
-  if (d <= 64) GCR_BWD(1);
-  else if (d <= 128) GCR_BWD(2);
-  else if (d <= 192) GCR_BWD(3);
-  else GCR_BWD(4);
-#undef GCR_BWD
+  const int blocks = (int)gcr_grid((batch + 3) / 4, 8192);
+  dispatch_columns<1, 2, 3, 4>(d, [&](auto nv) {
+    hipLaunchKernelGGL((bpr_bwd_kernel<decltype(nv)::value>), dim3(blocks), dim3(256), 0, s, user_tab, item_tab, d, u_idx,
+                       i_idx, j_idx, batch, n_neg, n_users, n_items, dloss_dx, grad_sums, grad_user, grad_item);
+  });
   return GCR_LAUNCH_STATUS();
 }
 
 extern "C" int64_t gcr_sort_index_workspace_bytes(int64_t n) {
   if (n <= 0) return 0;
-  return (int64_t)(align256(sizeof(uint32_t) * (size_t)n) + align256(sizeof(int32_t) * (size_t)n) + sort_u32_temp_bytes(n));
+  return sort_index_layout(n).total;
 }
 
 extern "C" int32_t gcr_sort_index(const int64_t* idx, int64_t n, int64_t n_keys, uint32_t* keys_sorted, int32_t* perm,
@@ -541,13 +540,13 @@ extern "C" int32_t gcr_sort_index(const int64_t* idx, int64_t n, int64_t n_keys,
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(idx && keys_sorted && perm && workspace);
   hipStream_t s = (hipStream_t)stream;
+  const SortIndexWorkspace L = sort_index_layout(n);
   unsigned char* w = reinterpret_cast<unsigned char*>(workspace);
-  uint32_t* key_in = reinterpret_cast<uint32_t*>(w);
-  int32_t* val_in = reinterpret_cast<int32_t*>(w + align256(sizeof(uint32_t) * (size_t)n));
-  void* tmp = w + align256(sizeof(uint32_t) * (size_t)n) + align256(sizeof(int32_t) * (size_t)n);
-  size_t tmp_bytes = sort_u32_temp_bytes(n);
-  const int64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(sort_keys_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, s, idx, n, n_keys,
+  uint32_t* key_in = reinterpret_cast<uint32_t*>(w + L.key_in);
+  int32_t* val_in = reinterpret_cast<int32_t*>(w + L.val_in);
+  void* tmp = w + L.tmp;
+  size_t tmp_bytes = (size_t)(L.total - L.tmp);
+  hipLaunchKernelGGL(sort_keys_kernel, dim3((unsigned)gcr_grid((n + 255) / 256, 65536)), dim3(256), 0, s, idx, n, n_keys,
                      key_in, val_in);
   // only the bits that n_keys (the key of the invalid ids, which therefore sort last) needs
   int bits = 1;
@@ -573,43 +572,28 @@ extern "C" int32_t gcr_bpr_bwd_sorted_f32(const float* user_tab, const float* it
   const bool user_side = keys_u != nullptr;               // false (only without the positive parts): the caller adds the
   GCR_CHECK_ARG(!pos || (i_idx != nullptr && user_side)); // users' rows too (gcr_bpr_neg_block_f32 + one SpMM)
   hipStream_t s = (hipStream_t)stream;
-  auto blocks_for = [](int64_t n_entries) {
-    const int64_t want = ((n_entries + 63) / 64 + 3) / 4;
-    return (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
-  };
-#define GCR_SIDE(SIDE, NV, KEYS, PERM, NE, OUT)                                                                       \
-  if (n_neg == 1)                                                                                                     \
-    hipLaunchKernelGGL((bpr_bwd_sorted_kernel<SIDE, NV, true>), dim3(blocks_for(NE)), dim3(256), 0, s, user_tab,       \
-                       item_tab, d, u_idx, i_idx, j_idx, batch, n_neg, n_users, n_items, dloss_dx, grad_sums, KEYS,    \
-                       PERM, NE, OUT);                                                                                 \
-  else                                                                                                                \
-    hipLaunchKernelGGL((bpr_bwd_sorted_kernel<SIDE, NV, false>), dim3(blocks_for(NE)), dim3(256), 0, s, user_tab,      \
-                       item_tab, d, u_idx, i_idx, j_idx, batch, n_neg, n_users, n_items, dloss_dx, grad_sums, KEYS,    \
-                       PERM, NE, OUT)
-#define GCR_NEG0(NV)                                                                                                  \
-  if (n_neg == 1)                                                                                                     \
-    hipLaunchKernelGGL((bpr_bwd_sorted_kernel<0, NV, true, false>), dim3(blocks_for(batch)), dim3(256), 0, s, user_tab, \
-                       item_tab, d, u_idx, i_idx, j_idx, batch, n_neg, n_users, n_items, dloss_dx, grad_sums, keys_u, \
-                       perm_u, batch, grad_user);                                                                     \
-  else                                                                                                                \
-    hipLaunchKernelGGL((bpr_bwd_sorted_kernel<0, NV, false, false>), dim3(blocks_for(batch)), dim3(256), 0, s, user_tab, \
-                       item_tab, d, u_idx, i_idx, j_idx, batch, n_neg, n_users, n_items, dloss_dx, grad_sums, keys_u, \
-                       perm_u, batch, grad_user)
-#define GCR_ALL(NV)                                           \
-  if (pos) {                                                  \
-    GCR_SIDE(0, NV, keys_u, perm_u, batch, grad_user);        \
-    GCR_SIDE(1, NV, keys_i, perm_i, batch, grad_item);        \
-  } else if (user_side) {                                     \
-    GCR_NEG0(NV);                                             \
-  }                                                           \
-  if (keys_j != nullptr) { GCR_SIDE(2, NV, keys_j, perm_j, batch * n_neg, grad_item); }
-  if (d <= 64) { GCR_ALL(1); }
-  else if (d <= 128) { GCR_ALL(2); }
-  else if (d <= 192) { GCR_ALL(3); }
-  else { GCR_ALL(4); }
-#undef GCR_ALL
-#undef GCR_NEG0
-#undef GCR_SIDE
+  dispatch_columns<1, 2, 3, 4>(d, [&](auto nv) {
+    dispatch_bool(n_neg == 1, [&](auto one_neg) {
+      constexpr int NV = decltype(nv)::value;
+      constexpr bool ONE_NEG = decltype(one_neg)::value;
+      // one ordered side: SIDE's rows (POS = false: without the positive item's row) from `ne` sorted entries into `out`
+      auto side = [&](auto side_c, auto pos_c, const uint32_t* keys, const int32_t* perm, int64_t ne, float* out) {
+        hipLaunchKernelGGL((bpr_bwd_sorted_kernel<decltype(side_c)::value, NV, ONE_NEG, decltype(pos_c)::value>),
+                           dim3(chunk_blocks(ne)), dim3(256), 0, s, user_tab, item_tab, d, u_idx, i_idx, j_idx, batch, n_neg,
+                           n_users, n_items, dloss_dx, grad_sums, keys, perm, ne, out);
+      };
+      using Side0 = std::integral_constant<int, 0>;
+      using Side1 = std::integral_constant<int, 1>;
+      using Side2 = std::integral_constant<int, 2>;
+      if (pos) {
+        side(Side0{}, std::true_type{}, keys_u, perm_u, batch, grad_user);
+        side(Side1{}, std::true_type{}, keys_i, perm_i, batch, grad_item);
+      } else if (user_side) {
+        side(Side0{}, std::false_type{}, keys_u, perm_u, batch, grad_user);
+      }
+      if (keys_j != nullptr) side(Side2{}, std::true_type{}, keys_j, perm_j, batch * n_neg, grad_item);
+    });
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -619,9 +603,8 @@ extern "C" int32_t gcr_bpr_edge_values_f32(const float* dloss_dx, const int64_t*
   GCR_CHECK_ARG(n_pairs >= 0 && n_users >= 0 && n_pairs < (1ll << 40));
   if (n_pairs == 0) return GCR_OK;
   GCR_CHECK_ARG(dloss_dx && mirror && col && grad_sums && val && dropped_per_item);
-  const int64_t want = (2 * n_pairs + 255) / 256;
-  hipLaunchKernelGGL(bpr_edge_values_kernel, dim3((unsigned)(want > 65536 ? 65536 : want)), dim3(256), 0, (hipStream_t)stream,
-                     dloss_dx, mirror, col, n_users, n_pairs, grad_sums, val, dropped_per_item);
+  hipLaunchKernelGGL(bpr_edge_values_kernel, dim3((unsigned)gcr_grid((2 * n_pairs + 255) / 256, 65536)), dim3(256), 0,
+                     (hipStream_t)stream, dloss_dx, mirror, col, n_users, n_pairs, grad_sums, val, dropped_per_item);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -634,10 +617,9 @@ extern "C" int32_t gcr_bpr_neg_block_f32(const float* dloss_dx, const int64_t* j
   GCR_CHECK_ARG((col != nullptr) == (val != nullptr) && (col != nullptr) == (dropped_per_user != nullptr));
   GCR_CHECK_ARG((sort_key != nullptr) == (sort_payload != nullptr) && (!sort_key || n_items < 0xFFFFFFFFll));
   GCR_CHECK_ARG(col != nullptr || sort_key != nullptr);
-  const int64_t want = (batch * n_neg + 255) / 256;
-  hipLaunchKernelGGL(bpr_neg_block_kernel, dim3((unsigned)(want > 65536 ? 65536 : want)), dim3(256), 0, (hipStream_t)stream,
-                     dloss_dx, j_idx, u_idx, batch, (int)n_neg, n_items, grad_sums, col, val, dropped_per_user, sort_key,
-                     sort_payload);
+  hipLaunchKernelGGL(bpr_neg_block_kernel, dim3((unsigned)gcr_grid((batch * n_neg + 255) / 256, 65536)), dim3(256), 0,
+                     (hipStream_t)stream, dloss_dx, j_idx, u_idx, batch, (int)n_neg, n_items, grad_sums, col, val,
+                     dropped_per_user, sort_key, sort_payload);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -667,15 +649,10 @@ extern "C" int32_t gcr_bpr_neg_items_sorted_f32(const float* user_tab, const flo
                 n_items < 0xFFFFFFFFll);
   if (n_entries == 0) return GCR_OK;
   GCR_CHECK_ARG(user_tab && item_tab && keys_sorted && payload_sorted && grad_sums && grad_item);
-  const int64_t want = ((n_entries + 63) / 64 + 3) / 4;
-  const unsigned blocks = (unsigned)(want < 1 ? 1 : (want > 65536 ? 65536 : want));
-#define GCR_NIS(NV)                                                                                                  \
-  hipLaunchKernelGGL((bpr_neg_items_sorted_kernel<NV>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, user_tab,   \
-                     item_tab, d, keys_sorted, payload_sorted, n_entries, n_items, grad_sums, grad_item)
-  if (d <= 64) GCR_NIS(1);
-  else if (d <= 128) GCR_NIS(2);
-  else if (d <= 192) GCR_NIS(3);
-  else GCR_NIS(4);
-#undef GCR_NIS
+  dispatch_columns<1, 2, 3, 4>(d, [&](auto nv) {
+    hipLaunchKernelGGL((bpr_neg_items_sorted_kernel<decltype(nv)::value>), dim3(chunk_blocks(n_entries)), dim3(256), 0,
+                       (hipStream_t)stream, user_tab, item_tab, d, keys_sorted, payload_sorted, n_entries, n_items, grad_sums,
+                       grad_item);
+  });
   return GCR_LAUNCH_STATUS();
 }

@@ -17,25 +17,21 @@
 //               registers, the OTHER view's row tile is standardised into LDS, one 32 x 32 output tile per wave and
 //               tile on the MFMA, the own view's (h - mean) term added in the epilogue.
 // No float atomics, no host read-back; every sum has one order: outputs are bitwise reproducible.
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 #include "gcr_tile.h"   // f32x16, acc_row
 
 namespace {
 
 constexpr int kBtLossParts = 1024;                           // d * d / 64 <= 1024 reduce workgroups
 
-int stat_blocks(int64_t n) {
-  const int64_t want = (n + 255) / 256;                      // >= 256 rows per workgroup
-  return (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
-}
+int stat_blocks(int64_t n) { return (int)gcr_grid((n + 255) / 256, 1024); }      // >= 256 rows per workgroup
 
 bool bt_dim_ok(int d) { return d == 32 || d == 64 || d == 96 || d == 128 || d == 256; }
 
 // product launch: workgroups along the rows (times four quadrants at d = 256) and rows per workgroup (even: a row pair
 // never straddles two workgroups)
-int bt_blocks(int64_t n, int d) {
-  const int64_t want = (n + 255) / 256, cap = d == 256 ? 256 : 1024;
-  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
-}
+int bt_blocks(int64_t n, int d) { return (int)gcr_grid((n + 255) / 256, d == 256 ? 256 : 1024); }
 int64_t bt_rows(int64_t n, int nb) {
   const int64_t per = ((n + nb - 1) / nb + 1) & ~(int64_t)1;
   return per < 256 ? 256 : per;                              // below the cap: whole chunks of 256, the last one short
@@ -263,7 +259,7 @@ __global__ __launch_bounds__(256) void bt_product_kernel(const float* __restrict
   }
 }
 
-// c[e] = (sum over the workgroups' partials) / n, four lanes per output as gram_reduce_kernel of gcr_dense.hip, and
+// c[e] = (sum over the workgroups' partials) / n, four lanes per output (gcr_lanes.h: gcr_fold_partials4), and
 // loss_part[block] = the loss terms of the block's 64 outputs: (1 - c)^2 on the diagonal, lambda c^2 off it.
 __global__ __launch_bounds__(256) void bt_reduce_kernel(const float* __restrict__ part, int nblocks, int d, float inv_n,
                                                         float lambda, float* __restrict__ c, float* __restrict__ loss_part) {
@@ -271,22 +267,7 @@ __global__ __launch_bounds__(256) void bt_reduce_kernel(const float* __restrict_
   const int elems = d * d;
   const int k = blockIdx.x * 64 + (threadIdx.x >> 2);
   const int q = threadIdx.x & 3;
-  float s = 0.f;
-  if (k < elems) {
-    const int per = (nblocks + 3) / 4;
-    const int b0 = q * per, b1 = min(nblocks, b0 + per);
-    int b = b0;
-    for (; b + 8 <= b1; b += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(b + u) * elems + k];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; b < b1; ++b) s += part[(int64_t)b * elems + k];
-  }
-  s += __shfl_xor(s, 1, 4);
-  s += __shfl_xor(s, 2, 4);
+  const float s = gcr_fold_partials4(part, nblocks, elems, k, q, k < elems);
   float term = 0.f;
   if (k < elems && q == 0) {
     const float cv = s * inv_n;
@@ -469,6 +450,29 @@ int32_t launch_col_stats(const float* xa, const float* xb, int64_t n, int d, flo
 
 int64_t stats_part_floats(int64_t n, int d, int views) { return (int64_t)views * stat_blocks(n) * 2 * d; }
 
+// one workspace for both calls, offsets in floats; nothing is padded: the regions are multiples of four floats
+struct BtWorkspace {
+  int64_t part;        // product partials [bt_blocks][d, d]
+  int64_t stat_part;   // column-statistics partials of both views
+  int64_t loss_part;   // kBtLossParts loss terms
+  int64_t gmat;        // G, G^T [2][d, d]
+  int64_t coef;        // A1, B1, A2, B2 [4][d]
+  int64_t total;
+};
+
+BtWorkspace bt_layout(int64_t n, int d) {
+  BtWorkspace w;
+  WsCarve c;
+  const int64_t dd = (int64_t)d * d;
+  w.part = c.take(bt_blocks(n, d) * dd, 1);
+  w.stat_part = c.take(stats_part_floats(n, d, 2), 1);
+  w.loss_part = c.take(kBtLossParts, 1);
+  w.gmat = c.take(2 * dd, 1);
+  w.coef = c.take(4 * d, 1);
+  w.total = c.at;
+  return w;
+}
+
 }  // namespace
 
 extern "C" int64_t gcr_col_stats_workspace_bytes(int64_t n, int32_t d) {
@@ -487,11 +491,9 @@ extern "C" int32_t gcr_col_stats_f32(const float* x, int64_t n, int32_t d, float
 
 extern "C" int32_t gcr_bt_supported(int32_t d) { return bt_dim_ok(d); }
 
-// floats: [product partials nb d^2][stats partials 2 views][loss partials 1024][G, G^T 2 d^2][coef 4 d]
 extern "C" int64_t gcr_bt_workspace_bytes(int64_t n, int32_t d) {
   if (n < 1 || !bt_dim_ok(d)) return 0;
-  const int64_t dd = (int64_t)d * d;
-  return ((int64_t)bt_blocks(n, d) * dd + stats_part_floats(n, d, 2) + kBtLossParts + 2 * dd + 4 * d) * (int64_t)sizeof(float);
+  return bt_layout(n, d).total * (int64_t)sizeof(float);
 }
 
 extern "C" int32_t gcr_bt_fwd_f32(const float* h1, const float* h2, int64_t n, int32_t d, float lambda, float eps,
@@ -503,25 +505,20 @@ extern "C" int32_t gcr_bt_fwd_f32(const float* h1, const float* h2, int64_t n, i
   hipStream_t s = (hipStream_t)stream;
   const int nb = bt_blocks(n, d);
   const int64_t per = bt_rows(n, nb), dd = (int64_t)d * d;
-  float* part = reinterpret_cast<float*>(workspace);
-  float* stat_part = part + (int64_t)nb * dd;
-  float* loss_part = stat_part + stats_part_floats(n, d, 2);
+  const BtWorkspace w = bt_layout(n, d);
+  float* ws = reinterpret_cast<float*>(workspace);
+  float *part = ws + w.part, *stat_part = ws + w.stat_part, *loss_part = ws + w.loss_part;
   int32_t st;
   if (batch_norm) {
     st = launch_col_stats(h1, h2, n, d, stats, stats + d, stats + 2 * d, stats + 3 * d, stat_part, s);
     if (st != GCR_OK) return st;
   }
   const float* sp = batch_norm ? stats : nullptr;
-#define GCR_BT_PROD(T, GY) \
-  hipLaunchKernelGGL((bt_product_kernel<T, T>), dim3((unsigned)nb, GY), dim3(256), 0, s, h1, h2, n, (int)d, per, sp, eps, part)
-  switch (d) {
-    case 32: GCR_BT_PROD(1, 1); break;
-    case 64: GCR_BT_PROD(2, 1); break;
-    case 96: GCR_BT_PROD(3, 1); break;
-    case 128: GCR_BT_PROD(4, 1); break;
-    default: GCR_BT_PROD(4, 4); break;
-  }
-#undef GCR_BT_PROD
+  dispatch_value<32, 64, 96, 128, 256>(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value, T = D == 256 ? 4 : D / 32;      // d = 256: four quadrants of 128 x 128
+    hipLaunchKernelGGL((bt_product_kernel<T, T>), dim3((unsigned)nb, D == 256 ? 4 : 1), dim3(256), 0, s, h1, h2, n, (int)d, per,
+                       sp, eps, part);
+  });
   st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
   const int nred = (int)((dd + 63) / 64);
@@ -542,28 +539,18 @@ extern "C" int32_t gcr_bt_bwd_f32(const float* h1, const float* h2, int64_t n, i
   GCR_CHECK_ARG(h1 != nullptr && h2 != nullptr && c != nullptr && g_loss != nullptr && workspace != nullptr);
   GCR_CHECK_ARG(!batch_norm || stats != nullptr);
   hipStream_t s = (hipStream_t)stream;
-  const int64_t dd = (int64_t)d * d;
-  float* gmat = reinterpret_cast<float*>(workspace) + (int64_t)bt_blocks(n, d) * dd + stats_part_floats(n, d, 2) + kBtLossParts;
-  float* coef = gmat + 2 * dd;
+  const BtWorkspace w = bt_layout(n, d);
+  float *gmat = reinterpret_cast<float*>(workspace) + w.gmat, *coef = reinterpret_cast<float*>(workspace) + w.coef;
   hipLaunchKernelGGL(bt_prep_kernel, dim3((unsigned)d), dim3(256), 0, s, c, (int)d, n, lambda, eps, (int)batch_norm, stats,
                      g_loss, gmat, coef);
   int32_t st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
   const float* sp = batch_norm ? stats : gmat;               // never read without batch_norm
-#define GCR_BT_BWD(D, NW)                                                                                               \
-  do {                                                                                                                  \
-    const int64_t tiles = (n + 32 * (NW / (D / 32)) - 1) / (32 * (NW / (D / 32)));                                      \
-    const int64_t cap = D == 256 ? 512 : 1024;                                                                          \
-    hipLaunchKernelGGL((bt_bwd_kernel<D, NW>), dim3((unsigned)(tiles > cap ? cap : tiles), 2), dim3(64 * NW), 0, s, h1, \
-                       h2, n, sp, eps, (int)batch_norm, gmat, coef, g_h1, g_h2);                                        \
-  } while (0)
-  switch (d) {
-    case 32: GCR_BT_BWD(32, 4); break;
-    case 64: GCR_BT_BWD(64, 4); break;
-    case 96: GCR_BT_BWD(96, 3); break;
-    case 128: GCR_BT_BWD(128, 4); break;
-    default: GCR_BT_BWD(256, 8); break;
-  }
-#undef GCR_BT_BWD
+  dispatch_value<32, 64, 96, 128, 256>(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value, NW = D == 96 ? 3 : (D == 256 ? 8 : 4), ROWS = 32 * (NW / (D / 32));
+    const unsigned tiles = (unsigned)gcr_grid((n + ROWS - 1) / ROWS, D == 256 ? 512 : 1024);
+    hipLaunchKernelGGL((bt_bwd_kernel<D, NW>), dim3(tiles, 2), dim3(64 * NW), 0, s, h1, h2, n, sp, eps, (int)batch_norm, gmat,
+                       coef, g_h1, g_h2);
+  });
   return GCR_LAUNCH_STATUS();
 }

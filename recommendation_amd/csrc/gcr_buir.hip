@@ -20,6 +20,7 @@
 //             finish   waves of the first range: one per sorted position; the head of a run of equal ids adds the run's dx
 //                      rows in sorted (= position) order and WRITES the row.  The others add the S partials in split order.
 // One writer per word, fixed orders, no float atomics: every output is bitwise reproducible.
+#include "gcr_host.h"
 #include "gcr_tile.h"   // f32x16, acc_row, kTileJ = 32 rows of a tile
 
 namespace {
@@ -122,6 +123,8 @@ __global__ __launch_bounds__(256) void buir_loss_kernel(const float* __restrict_
   const float* c1 = stats + 5 * batch;
   double s = 0.0;
   for (int64_t b = threadIdx.x; b < batch; b += 256) s += (double)((2.0f - 2.0f * c0[b]) + (2.0f - 2.0f * c1[b]));
+  // gcr_lanes.h's gcr_wave_sum_f64, written out: through the call the compiler orders two instructions of this kernel the
+  // other way round, and the units of this family are held to their instructions
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, GCR_WAVE);
   if (lane == 0) part[wave] = s;
@@ -315,8 +318,6 @@ __global__ __launch_bounds__(256) void ema_rows_kernel(float* __restrict__ targe
   }
 }
 
-inline int64_t align64f(int64_t words) { return (words + 63) & ~(int64_t)63; }
-
 struct BuirWorkspace {
   int64_t dp, dx, dw_part, db_part, total;      // offsets in floats
   int n_splits, split_len;
@@ -335,15 +336,24 @@ BuirWorkspace buir_layout(int64_t batch, int d) {
   w.n_splits = (int)((2 * batch + len - 1) / len);
   if (w.n_splits < 1) w.n_splits = 1;
   w.split_len = (int)len;
-  w.dp = 0;
-  w.dx = w.dp + align64f(2 * batch * d);
-  w.dw_part = w.dx + align64f(2 * batch * d);
-  w.db_part = w.dw_part + align64f((int64_t)w.n_splits * d * d);
-  w.total = w.db_part + align64f((int64_t)w.n_splits * d);
+  WsCarve c;
+  w.dp = c.take(2 * batch * d);
+  w.dx = c.take(2 * batch * d);
+  w.dw_part = c.take((int64_t)w.n_splits * d * d);
+  w.db_part = c.take((int64_t)w.n_splits * d);
+  w.total = c.at;
   return w;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+BuirArgs buir_args(const float* on_user, const float* on_item, const float* tg_user, const float* tg_item, int64_t n_users,
+                   int64_t n_items, int d, const int64_t* u_idx, const int64_t* i_idx, int64_t batch, const float* w,
+                   const float* bias) {
+  BuirArgs A;
+  A.on[0] = on_user; A.on[1] = on_item; A.tg[0] = tg_user; A.tg[1] = tg_item;
+  A.idx[0] = u_idx; A.idx[1] = i_idx; A.n[0] = n_users; A.n[1] = n_items;
+  A.batch = batch; A.d = d; A.w = w; A.bias = bias;
+  return A;
+}
 
 bool buir_args_ok(int64_t n_users, int64_t n_items, int64_t batch) {
   return n_users >= 0 && n_users < (1ll << 31) && n_items >= 0 && n_items < (1ll << 31) && batch >= 0 && batch < (1ll << 24);
@@ -366,13 +376,9 @@ extern "C" int32_t gcr_buir_fwd_f32(const float* on_user, const float* on_item, 
   GCR_CHECK_ARG(buir_args_ok(n_users, n_items, batch));
   if (batch == 0) return GCR_OK;
   GCR_CHECK_ARG(on_user && on_item && tg_user && tg_item && u_idx && i_idx && w && bias && loss && stats);
-  GCR_CHECK_ARG(aligned16(on_user) && aligned16(on_item) && aligned16(tg_user) && aligned16(tg_item) && aligned16(w) &&
-                aligned16(bias));
+  GCR_CHECK_ARG(aligned16(on_user, on_item, tg_user, tg_item, w, bias));
   hipStream_t s = (hipStream_t)stream;
-  BuirArgs A;
-  A.on[0] = on_user; A.on[1] = on_item; A.tg[0] = tg_user; A.tg[1] = tg_item;
-  A.idx[0] = u_idx; A.idx[1] = i_idx; A.n[0] = n_users; A.n[1] = n_items;
-  A.batch = batch; A.d = d; A.w = w; A.bias = bias;
+  const BuirArgs A = buir_args(on_user, on_item, tg_user, tg_item, n_users, n_items, d, u_idx, i_idx, batch, w, bias);
   const unsigned n_tiles = (unsigned)((batch + kTileJ - 1) / kTileJ);
   hipLaunchKernelGGL(buir_fwd_rows_kernel, dim3(n_tiles, 2), dim3(256), 0, s, A, stats);
   hipLaunchKernelGGL(buir_loss_kernel, dim3(1), dim3(256), 0, s, stats, batch, loss);
@@ -390,13 +396,9 @@ extern "C" int32_t gcr_buir_bwd_f32(const float* on_user, const float* on_item, 
   if (batch == 0) return GCR_OK;
   GCR_CHECK_ARG(on_user && on_item && tg_user && tg_item && u_idx && i_idx && w && bias && stats && g && keys_u && perm_u &&
                 keys_i && perm_i && g_on_user && g_on_item && g_w && g_bias && workspace);
-  GCR_CHECK_ARG(aligned16(on_user) && aligned16(on_item) && aligned16(tg_user) && aligned16(tg_item) && aligned16(w) &&
-                aligned16(bias) && aligned16(workspace));
+  GCR_CHECK_ARG(aligned16(on_user, on_item, tg_user, tg_item, w, bias, workspace));
   hipStream_t s = (hipStream_t)stream;
-  BuirArgs A;
-  A.on[0] = on_user; A.on[1] = on_item; A.tg[0] = tg_user; A.tg[1] = tg_item;
-  A.idx[0] = u_idx; A.idx[1] = i_idx; A.n[0] = n_users; A.n[1] = n_items;
-  A.batch = batch; A.d = d; A.w = w; A.bias = bias;
+  const BuirArgs A = buir_args(on_user, on_item, tg_user, tg_item, n_users, n_items, d, u_idx, i_idx, batch, w, bias);
   BuirOrder O;
   O.keys[0] = keys_u; O.keys[1] = keys_i; O.perm[0] = perm_u; O.perm[1] = perm_i;
   O.grad[0] = g_on_user; O.grad[1] = g_on_item;
@@ -422,8 +424,7 @@ extern "C" int32_t gcr_ema_rows_f32(float* target, const float* online, const in
   hipStream_t s = (hipStream_t)stream;
   const int32_t st = gcr_hip_status(hipMemsetAsync(claim_bits, 0, (size_t)((n_rows + 31) / 32) * sizeof(uint32_t), s));
   if (st != GCR_OK) return st;
-  const int64_t want = (n + 3) / 4;
-  hipLaunchKernelGGL(ema_rows_kernel, dim3((unsigned)(want > 8192 ? 8192 : want)), dim3(256), 0, s, target, online, idx, n,
+  hipLaunchKernelGGL(ema_rows_kernel, dim3((unsigned)gcr_grid((n + 3) / 4, 8192)), dim3(256), 0, s, target, online, idx, n,
                      (int)d, n_rows, (float)momentum, (float)(1.0 - momentum), claim_bits);
   return GCR_LAUNCH_STATUS();
 }

@@ -19,6 +19,8 @@
 //                     mixed = sum_k score_k e_k (+ scale * extra: the `+ simple / 2` of mhcn.py:443) in one pass; the
 //                     backward gives d e_k = score_k g + dlogit_k v, d extra and the partial sums of d v in one pass
 //                     (torch: ~30 launches per call, three calls per step).
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 #include "gcr_tile.h"   // f32x16
 
 namespace {
@@ -138,29 +140,12 @@ __global__ __launch_bounds__(256) void gram_tn_kernel(const float* __restrict__ 
   }
 }
 
-// out[k] = sum over the workgroups' partials, four lanes per output (each a quarter of the partials, loads eight deep),
-// combined in a fixed order: bitwise reproducible.  (One thread per output walking all 1024 partials was a chain of 1024
-// dependent memory round trips: 229 us for the 64 x 64 case, ten times the product itself.)
+// out[k] = sum over the workgroups' partials, four lanes per output (gcr_lanes.h: gcr_fold_partials4)
 __global__ __launch_bounds__(256) void gram_reduce_kernel(const float* __restrict__ part, int nblocks, int elems,
                                                           float* __restrict__ out) {
   const int k = blockIdx.x * 64 + (threadIdx.x >> 2);
   const int q = threadIdx.x & 3;
-  float s = 0.f;
-  if (k < elems) {
-    const int per = (nblocks + 3) / 4;
-    const int b0 = q * per, b1 = min(nblocks, b0 + per);
-    int b = b0;
-    for (; b + 8 <= b1; b += 8) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(int64_t)(b + u) * elems + k];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; b < b1; ++b) s += part[(int64_t)b * elems + k];
-  }
-  s += __shfl_xor(s, 1, 4);
-  s += __shfl_xor(s, 2, 4);
+  const float s = gcr_fold_partials4(part, nblocks, elems, k, q, k < elems);
   if (k < elems && q == 0) out[k] = s;
 }
 
@@ -192,6 +177,7 @@ __global__ __launch_bounds__(256) void weighted_colsum_kernel(const float* __res
   }
 }
 
+// the gates' sigmoid as the reference writes it (gcr_mim.hip's stable_sigmoid_f32 is another formula and rounds differently)
 __device__ __forceinline__ float sigmoid_f32(float t) { return 1.0f / (1.0f + expf(-t)); }
 
 // thread t owns column t % DP of every (256 / DP)-th row (DP = d rounded up to a power of two <= 256): coalesced rows
@@ -237,15 +223,6 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
   }
 }
 
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // LPR lanes per row, float4 per lane (d = 4 LPR in {32, 64, 128, 256}); score [3, n]
 template <int LPR>
 __global__ __launch_bounds__(256) void channel_mix_fwd_kernel(const float* __restrict__ e1, const float* __restrict__ e2,
@@ -259,7 +236,7 @@ __global__ __launch_bounds__(256) void channel_mix_fwd_kernel(const float* __res
     const int64_t k = r * D + 4 * gl;
     const float4 a = *reinterpret_cast<const float4*>(e1 + k), b = *reinterpret_cast<const float4*>(e2 + k),
                  c = *reinterpret_cast<const float4*>(e3 + k);
-    const float l1 = group_sum<LPR>(dot4(a, v4)), l2 = group_sum<LPR>(dot4(b, v4)), l3 = group_sum<LPR>(dot4(c, v4));
+    const float l1 = gcr_group_sum<LPR>(gcr_dot4(a, v4)), l2 = gcr_group_sum<LPR>(gcr_dot4(b, v4)), l3 = gcr_group_sum<LPR>(gcr_dot4(c, v4));
     const float m = fmaxf(l1, fmaxf(l2, l3));
     const float p1 = expf(l1 - m), p2 = expf(l2 - m), p3 = expf(l3 - m);
     const float inv = 1.0f / (p1 + p2 + p3);
@@ -302,7 +279,7 @@ __global__ __launch_bounds__(256) void channel_mix_bwd_kernel(const float* __res
     const float4 a = *reinterpret_cast<const float4*>(e1 + k), b = *reinterpret_cast<const float4*>(e2 + k),
                  c = *reinterpret_cast<const float4*>(e3 + k);
     const float s1 = score[r], s2 = score[n + r], s3 = score[2 * n + r];
-    const float a1 = group_sum<LPR>(dot4(gv, a)), a2 = group_sum<LPR>(dot4(gv, b)), a3 = group_sum<LPR>(dot4(gv, c));
+    const float a1 = gcr_group_sum<LPR>(gcr_dot4(gv, a)), a2 = gcr_group_sum<LPR>(gcr_dot4(gv, b)), a3 = gcr_group_sum<LPR>(gcr_dot4(gv, c));
     const float abar = s1 * a1 + s2 * a2 + s3 * a3;
     const float q1 = s1 * (a1 - abar), q2 = s2 * (a2 - abar), q3 = s3 * (a3 - abar);
     *reinterpret_cast<float4*>(d1 + k) = make_float4(s1 * gv.x + q1 * v4.x, s1 * gv.y + q1 * v4.y, s1 * gv.z + q1 * v4.z, s1 * gv.w + q1 * v4.w);
@@ -327,10 +304,10 @@ __global__ __launch_bounds__(256) void channel_mix_bwd_kernel(const float* __res
   }
 }
 
-int gram_blocks(int64_t n) {
-  const int64_t want = (n + 255) / 256;                      // >= 256 rows per workgroup
-  return (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
-}
+int gram_blocks(int64_t n) { return (int)gcr_grid((n + 255) / 256, 1024); }      // >= 256 rows per workgroup
+
+// grid of the grid-stride row kernels: one workgroup per `rows` rows, at most 16384
+unsigned row_grid(int64_t n, int rows) { return (unsigned)gcr_grid((n + rows - 1) / rows, 16384); }
 
 bool gram_dim_ok(int d) { return d == 32 || d == 64 || d == 96 || d == 128; }
 
@@ -341,9 +318,8 @@ extern "C" int32_t gcr_normalize_bwd_n_f32(const float* n_rows_normalised, const
   GCR_CHECK_ARG(rows >= 0 && d >= 4 && d <= 256 && (d & 3) == 0);
   if (rows == 0) return GCR_OK;
   GCR_CHECK_ARG(n_rows_normalised != nullptr && inv_norm != nullptr && g_n != nullptr && out != nullptr);
-  const int64_t want = (rows + 15) / 16;
-  hipLaunchKernelGGL(normalize_bwd_n_kernel<false>, dim3((unsigned)(want > 16384 ? 16384 : want)), dim3(256), 0,
-                     (hipStream_t)stream, n_rows_normalised, inv_norm, g_n, g_raw, rows, d, out);
+  hipLaunchKernelGGL(normalize_bwd_n_kernel<false>, dim3(row_grid(rows, 16)), dim3(256), 0, (hipStream_t)stream,
+                     n_rows_normalised, inv_norm, g_n, g_raw, rows, d, out);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -352,9 +328,8 @@ extern "C" int32_t gcr_normalize_bwd_raw_f32(const float* z_raw, const float* in
   GCR_CHECK_ARG(rows >= 0 && d >= 4 && d <= 256 && (d & 3) == 0);
   if (rows == 0) return GCR_OK;
   GCR_CHECK_ARG(z_raw != nullptr && inv_norm != nullptr && g_n != nullptr && out != nullptr);
-  const int64_t want = (rows + 15) / 16;
-  hipLaunchKernelGGL(normalize_bwd_n_kernel<true>, dim3((unsigned)(want > 16384 ? 16384 : want)), dim3(256), 0,
-                     (hipStream_t)stream, z_raw, inv_norm, g_n, g_raw, rows, d, out);
+  hipLaunchKernelGGL(normalize_bwd_n_kernel<true>, dim3(row_grid(rows, 16)), dim3(256), 0, (hipStream_t)stream, z_raw,
+                     inv_norm, g_n, g_raw, rows, d, out);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -377,23 +352,12 @@ extern "C" int32_t gcr_gram_tn_f32(const float* x, const float* g, int64_t n, in
   const int nb = gram_blocks(n);
   const int64_t per = ((n + nb - 1) / nb + 1) & ~(int64_t)1;   // even: a row pair never straddles two workgroups
   float* part = reinterpret_cast<float*>(workspace);
-#define GCR_GRAM(TX, TG) \
-  hipLaunchKernelGGL((gram_tn_kernel<TX, TG>), dim3((unsigned)nb), dim3(256), 0, s, x, g, n, per, part)
-#define GCR_GRAM_ROW(TX)                 \
-  switch (dg / 32) {                     \
-    case 1: GCR_GRAM(TX, 1); break;      \
-    case 2: GCR_GRAM(TX, 2); break;      \
-    case 3: GCR_GRAM(TX, 3); break;      \
-    default: GCR_GRAM(TX, 4); break;     \
-  }
-  switch (dx / 32) {
-    case 1: GCR_GRAM_ROW(1); break;
-    case 2: GCR_GRAM_ROW(2); break;
-    case 3: GCR_GRAM_ROW(3); break;
-    default: GCR_GRAM_ROW(4); break;
-  }
-#undef GCR_GRAM_ROW
-#undef GCR_GRAM
+  dispatch_value<1, 2, 3, 4>(dx / 32, [&](auto tx) {
+    dispatch_value<1, 2, 3, 4>(dg / 32, [&](auto tg) {
+      hipLaunchKernelGGL((gram_tn_kernel<decltype(tx)::value, decltype(tg)::value>), dim3((unsigned)nb), dim3(256), 0, s, x, g,
+                         n, per, part);
+    });
+  });
   int32_t st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
   const int elems = dx * dg;
@@ -428,9 +392,7 @@ extern "C" int32_t gcr_rows_dot_vec_f32(const float* x, const float* v, int64_t 
   GCR_CHECK_ARG(n >= 0 && d >= 1);
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(x != nullptr && v != nullptr && out != nullptr);
-  const int64_t want = (n + 15) / 16;
-  hipLaunchKernelGGL(rows_dot_vec_kernel, dim3((unsigned)(want > 16384 ? 16384 : want)), dim3(256), 0, (hipStream_t)stream,
-                     x, v, n, (int)d, out);
+  hipLaunchKernelGGL(rows_dot_vec_kernel, dim3(row_grid(n, 16)), dim3(256), 0, (hipStream_t)stream, x, v, n, (int)d, out);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -441,9 +403,8 @@ extern "C" int32_t gcr_gate_fwd_f32(const float* em, const float* z, const float
   GCR_CHECK_ARG(em != nullptr && z != nullptr && out != nullptr);
   int dp = 1;
   while (dp < d) dp <<= 1;
-  const int64_t want = (n + (256 / dp) * 4 - 1) / ((256 / dp) * 4);
-  hipLaunchKernelGGL(gate_fwd_kernel, dim3((unsigned)(want > 16384 ? 16384 : want)), dim3(256), 0, (hipStream_t)stream, em, z,
-                     bias, n, (int)d, dp, out);
+  hipLaunchKernelGGL(gate_fwd_kernel, dim3(row_grid(n, (256 / dp) * 4)), dim3(256), 0, (hipStream_t)stream, em, z, bias, n,
+                     (int)d, dp, out);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -479,18 +440,11 @@ extern "C" int32_t gcr_channel_mix_fwd_f32(const float* e1, const float* e2, con
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(e1 && e2 && e3 && v && mixed && score);
   hipStream_t s = (hipStream_t)stream;
-  const int groups = 256 / (d / 4);
-  const int64_t want = (n + groups * 2 - 1) / (groups * 2);
-  const dim3 grid((unsigned)(want > 16384 ? 16384 : want));
-#define GCR_MIXF(LPR) \
-  hipLaunchKernelGGL((channel_mix_fwd_kernel<LPR>), grid, dim3(256), 0, s, e1, e2, e3, v, extra, extra_scale, n, mixed, score)
-  switch (d) {
-    case 32: GCR_MIXF(8); break;
-    case 64: GCR_MIXF(16); break;
-    case 128: GCR_MIXF(32); break;
-    default: GCR_MIXF(64); break;
-  }
-#undef GCR_MIXF
+  const dim3 grid(row_grid(n, 256 / (d / 4) * 2));
+  dispatch_value<32, 64, 128, 256>(d, [&](auto dc) {
+    hipLaunchKernelGGL((channel_mix_fwd_kernel<decltype(dc)::value / 4>), grid, dim3(256), 0, s, e1, e2, e3, v, extra,
+                       extra_scale, n, mixed, score);
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -510,16 +464,10 @@ extern "C" int32_t gcr_channel_mix_bwd_f32(const float* g, const float* e1, cons
   const int nb = gram_blocks(n);
   const int64_t per = (n + nb - 1) / nb;
   float* part = reinterpret_cast<float*>(workspace);
-#define GCR_MIXB(LPR)                                                                                                       \
-  hipLaunchKernelGGL((channel_mix_bwd_kernel<LPR>), dim3((unsigned)nb), dim3(256), 0, s, g, e1, e2, e3, v, score, extra_scale, \
-                     n, per, d_e1, d_e2, d_e3, d_extra, part)
-  switch (d) {
-    case 32: GCR_MIXB(8); break;
-    case 64: GCR_MIXB(16); break;
-    case 128: GCR_MIXB(32); break;
-    default: GCR_MIXB(64); break;
-  }
-#undef GCR_MIXB
+  dispatch_value<32, 64, 128, 256>(d, [&](auto dc) {
+    hipLaunchKernelGGL((channel_mix_bwd_kernel<decltype(dc)::value / 4>), dim3((unsigned)nb), dim3(256), 0, s, g, e1, e2, e3, v,
+                       score, extra_scale, n, per, d_e1, d_e2, d_e3, d_extra, part);
+  });
   int32_t st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
   hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)((d + 63) / 64)), dim3(256), 0, s, part, nb, (int)d, d_v);

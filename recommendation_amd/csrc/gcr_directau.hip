@@ -27,6 +27,8 @@
 // Backward: one launch, one wave per batch position.  From r, o, inv_norm and the table rows it forms the gradient with
 // respect to x^ of every set, applies the normalize backward and the 2 g_Q x term, and adds the row into the table
 // gradient with one float atomic per element (duplicate ids collide, as in gcr_scatter_add_rows_f32).
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 #include "gcr_tile.h"   // f32x16, acc_row, kTileJ = 32: rows of a tile (the MFMA's M and N)
 
 namespace {
@@ -37,12 +39,6 @@ constexpr int kWaves = 4;
 constexpr int kMaxPrepBlocks = 256;
 constexpr int kPrepVals = 5;         // A_pos, A_neg, Q_u, Q_p, Q_n
 constexpr float kNormEps = 1e-12f;   // F.normalize's eps
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, GCR_WAVE);
-  return v;
-}
 
 struct AuSets {
   const float* tab[3];
@@ -285,7 +281,7 @@ __global__ __launch_bounds__(256) void au_tile_kernel(const float* __restrict__ 
       const int col = k < 2 ? k : k - 3;                     // A_pos, A_neg | Q_u, Q_p, Q_n
       for (int i = lane; i < prep_blocks; i += 64) sum += (double)prep_part[(int64_t)i * kPrepVals + col];
     }
-    sum = wave_sum_f64(sum);
+    sum = gcr_wave_sum_f64(sum);
     if (lane == 0) sums[k] = (float)sum;
   }
 }
@@ -343,12 +339,7 @@ __global__ __launch_bounds__(256) void au_bwd_kernel(AuSets S, int d, int64_t ba
   }
 }
 
-int prep_blocks_for(int64_t batch) {
-  const int64_t want = (batch + kWaves - 1) / kWaves;
-  return (int)(want < 1 ? 1 : (want > kMaxPrepBlocks ? kMaxPrepBlocks : want));
-}
-
-inline int64_t align64f(int64_t floats) { return (floats + 63) & ~(int64_t)63; }
+int prep_blocks_for(int64_t batch) { return (int)gcr_grid((batch + kWaves - 1) / kWaves, kMaxPrepBlocks); }
 
 struct AuWorkspace {
   int64_t xhat, sqn, row_id, prep_part, r_part, ticket, total;      // offsets in floats (4-byte words)
@@ -356,15 +347,25 @@ struct AuWorkspace {
 
 AuWorkspace au_layout(int64_t batch, int d) {
   AuWorkspace w;
+  WsCarve c;
   const int64_t n_tiles = (batch + kTileJ - 1) / kTileJ;
-  w.xhat = 0;
-  w.sqn = w.xhat + align64f(3 * batch * d);
-  w.row_id = w.sqn + align64f(3 * batch);
-  w.prep_part = w.row_id + align64f(3 * batch);
-  w.r_part = w.prep_part + align64f((int64_t)kMaxPrepBlocks * kPrepVals);
-  w.ticket = w.r_part + align64f(3 * n_tiles);
-  w.total = w.ticket + 64;
+  w.xhat = c.take(3 * batch * d);
+  w.sqn = c.take(3 * batch);
+  w.row_id = c.take(3 * batch);
+  w.prep_part = c.take((int64_t)kMaxPrepBlocks * kPrepVals);
+  w.r_part = c.take(3 * n_tiles);
+  w.ticket = c.take(64);
+  w.total = c.at;
   return w;
+}
+
+AuSets au_sets(const float* user_tab, const float* item_tab, const int64_t* u_idx, const int64_t* i_idx, const int64_t* j_idx,
+               int64_t n_users, int64_t n_items) {
+  AuSets S;
+  S.tab[0] = user_tab; S.tab[1] = item_tab; S.tab[2] = item_tab;
+  S.idx[0] = u_idx; S.idx[1] = i_idx; S.idx[2] = j_idx;
+  S.n_rows[0] = n_users; S.n_rows[1] = n_items; S.n_rows[2] = n_items;
+  return S;
 }
 
 bool au_args_ok(int32_t d, int64_t batch, int32_t n_sets, int64_t n_users, int64_t n_items) {
@@ -394,20 +395,13 @@ extern "C" int32_t gcr_directau_fwd_f32(const float* user_tab, const float* item
   const AuWorkspace w = au_layout(batch, d);
   float* ws = reinterpret_cast<float*>(workspace);
   unsigned* ticket = reinterpret_cast<unsigned*>(ws + w.ticket);
-  AuSets S;
-  S.tab[0] = user_tab; S.tab[1] = item_tab; S.tab[2] = item_tab;
-  S.idx[0] = u_idx; S.idx[1] = i_idx; S.idx[2] = j_idx;
-  S.n_rows[0] = n_users; S.n_rows[1] = n_items; S.n_rows[2] = n_items;
+  const AuSets S = au_sets(user_tab, item_tab, u_idx, i_idx, j_idx, n_users, n_items);
   const int pb = prep_blocks_for(batch);
   int32_t* row_id = reinterpret_cast<int32_t*>(ws + w.row_id);
-#define GCR_AU_PREP(NV)                                                                                              \
-  hipLaunchKernelGGL((au_prepare_kernel<NV>), dim3(pb), dim3(256), 0, s, S, (int)d, batch, (int)n_sets, ws + w.xhat, \
-                     inv_norm, ws + w.sqn, row_id, ws + w.prep_part, ticket)
-  if (d <= 64) GCR_AU_PREP(1);
-  else if (d <= 128) GCR_AU_PREP(2);
-  else if (d <= 256) GCR_AU_PREP(4);
-  else GCR_AU_PREP(8);
-#undef GCR_AU_PREP
+  dispatch_columns<1, 2, 4, 8>(d, [&](auto nv) {
+    hipLaunchKernelGGL((au_prepare_kernel<decltype(nv)::value>), dim3(pb), dim3(256), 0, s, S, (int)d, batch, (int)n_sets,
+                       ws + w.xhat, inv_norm, ws + w.sqn, row_id, ws + w.prep_part, ticket);
+  });
   int32_t st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
   const unsigned n_tiles = (unsigned)((batch + kTileJ - 1) / kTileJ);
@@ -433,19 +427,11 @@ extern "C" int32_t gcr_directau_bwd_f32(const float* user_tab, const float* item
   GCR_CHECK_ARG(u_idx || n_users >= batch);
   GCR_CHECK_ARG(n_sets < 2 || i_idx || n_items >= batch);
   GCR_CHECK_ARG(n_sets < 3 || j_idx || n_items >= batch);
-  AuSets S;
-  S.tab[0] = user_tab; S.tab[1] = item_tab; S.tab[2] = item_tab;
-  S.idx[0] = u_idx; S.idx[1] = i_idx; S.idx[2] = j_idx;
-  S.n_rows[0] = n_users; S.n_rows[1] = n_items; S.n_rows[2] = n_items;
-  const int64_t want = (batch + kWaves - 1) / kWaves;
-  const unsigned blocks = (unsigned)(want > 8192 ? 8192 : want);
-#define GCR_AU_BWD(NV)                                                                                                 \
-  hipLaunchKernelGGL((au_bwd_kernel<NV>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, (int)d, batch, (int)n_sets, \
-                     t, inv_norm, r, o, g_sums, g_user_tab, g_item_tab)
-  if (d <= 64) GCR_AU_BWD(1);
-  else if (d <= 128) GCR_AU_BWD(2);
-  else if (d <= 256) GCR_AU_BWD(4);
-  else GCR_AU_BWD(8);
-#undef GCR_AU_BWD
+  const AuSets S = au_sets(user_tab, item_tab, u_idx, i_idx, j_idx, n_users, n_items);
+  const unsigned blocks = (unsigned)gcr_grid((batch + kWaves - 1) / kWaves, 8192);
+  dispatch_columns<1, 2, 4, 8>(d, [&](auto nv) {
+    hipLaunchKernelGGL((au_bwd_kernel<decltype(nv)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, S, (int)d, batch,
+                       (int)n_sets, t, inv_norm, r, o, g_sums, g_user_tab, g_item_tab);
+  });
   return GCR_LAUNCH_STATUS();
 }

@@ -11,6 +11,7 @@
 // regenerate it from (seed, p).  With d % 4 == 0 a lane's four columns are one counter block: one Philox call per view.
 // A recorded bitmap (keep_bits, [V, ceil(n * d / 32)] words in that bit order) replaces the draws when given.
 #include "gcr_common.h"
+#include "gcr_host.h"
 #include "gcr_philox.h"
 
 namespace {
@@ -148,12 +149,7 @@ __global__ __launch_bounds__(256) void gather_dropout_bwd_kernel(const float* __
   }
 }
 
-int dropout_grid(int64_t n) {
-  const int64_t g = (n + 3) / 4;
-  return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
-bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+int dropout_grid(int64_t n) { return (int)gcr_grid((n + 3) / 4, 8192); }
 
 }  // namespace
 
@@ -183,7 +179,7 @@ extern "C" int32_t gcr_gather_dropout_bwd_f32(const float* grad_out, const int64
   GCR_CHECK_ARG(grad_out && idx && grad_table);
   const float scale = p < 1.f ? 1.0f / (1.0f - p) : 0.f;      // p == 1: every view is zero, only block 0 has a gradient
   const int64_t n_words = (n * d + 31) / 32;
-  if (d % 4 == 0 && aligned16(grad_out, nullptr))
+  if (d % 4 == 0 && aligned16(grad_out))
     hipLaunchKernelGGL(gather_dropout_bwd_vec4_kernel, dim3(dropout_grid(n)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const float4*>(grad_out), idx, n, d, n_rows, p, scale, seed, n_views, keep_bits,
                        n_words, grad_table);

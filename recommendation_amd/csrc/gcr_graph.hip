@@ -16,6 +16,7 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 
 #include "gcr_common.h"
+#include "gcr_host.h"
 #include "gcr_philox.h"
 
 namespace {
@@ -23,8 +24,7 @@ namespace {
 constexpr int kBlock = 256;
 
 inline unsigned grid_for(int64_t n) {
-  const int64_t g = (n + kBlock - 1) / kBlock;
-  return (unsigned)(g < 1 ? 1 : (g > 262144 ? 262144 : g));
+  return (unsigned)gcr_grid((n + kBlock - 1) / kBlock, 262144);
 }
 
 inline int bits_for(uint64_t max_value) {
@@ -33,7 +33,6 @@ inline int bits_for(uint64_t max_value) {
   return b;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __global__ void iota_and_check_kernel(const int64_t* __restrict__ row, const int64_t* __restrict__ col, int64_t nnz,
                                       int64_t n_rows, int64_t n_cols, int64_t mul, int64_t* __restrict__ key,
@@ -165,7 +164,7 @@ struct Carve {
   template <class T>
   T* take(size_t n) {
     T* p = reinterpret_cast<T*>(base + off);
-    off += align256(n * sizeof(T));
+    off += gcr_align(n * sizeof(T), 256);
     return p;
   }
 };
@@ -192,8 +191,8 @@ extern "C" int64_t gcr_coo_to_csr_workspace_bytes(int64_t nnz) {
   if (nnz < 0) return 0;
   const size_t n = (size_t)(nnz > 0 ? nnz : 1);
   // keys in/out, idx in/out, sorted values, unique count, sort temp, reduce-by-key temp
-  return (int64_t)(4 * align256(n * 8) + 2 * align256(n * 4) + 256 + align256(sort_temp_bytes(nnz)) +
-                   align256(rbk_temp_bytes(nnz)) + 1024);
+  return (int64_t)(4 * gcr_align(n * 8, 256) + 2 * gcr_align(n * 4, 256) + 256 + gcr_align(sort_temp_bytes(nnz), 256) +
+                   gcr_align(rbk_temp_bytes(nnz), 256) + 1024);
 }
 
 extern "C" int32_t gcr_coo_to_csr(const int64_t* row, const int64_t* col, const float* val, int64_t nnz,
@@ -289,7 +288,7 @@ extern "C" int32_t gcr_csr_row_norm_f32(const int64_t* rowptr, const int32_t* co
 
 extern "C" int64_t gcr_edge_mask_exact_workspace_bytes(int64_t nnz) {
   if (nnz <= 0) return 256;
-  return (int64_t)(4 * align256((size_t)nnz * 8) + align256(sort_temp_bytes(nnz)) + 1024);
+  return (int64_t)(4 * gcr_align((size_t)nnz * 8, 256) + gcr_align(sort_temp_bytes(nnz), 256) + 1024);
 }
 
 extern "C" int32_t gcr_edge_mask_exact_bits(int64_t nnz, int64_t n_keep, uint64_t seed, uint32_t* bits,

@@ -14,16 +14,15 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gcr_common.h"
+#include "gcr_host.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 
 inline unsigned grid_for(int64_t n) {
-  const int64_t g = (n + kBlock - 1) / kBlock;
-  return (unsigned)(g < 1 ? 1 : (g > 262144 ? 262144 : g));
+  return (unsigned)gcr_grid((n + kBlock - 1) / kBlock, 262144);
 }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Carve {
   char* base;
@@ -31,7 +30,7 @@ struct Carve {
   template <class T>
   T* take(size_t n) {
     T* p = reinterpret_cast<T*>(base + off);
-    off += align256(n * sizeof(T));
+    off += gcr_align(n * sizeof(T), 256);
     return p;
   }
 };
@@ -105,7 +104,7 @@ __global__ void scatter_first_seen_kernel(const int64_t* __restrict__ is, const 
 extern "C" int64_t gcr_dense_ids_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
   const size_t m = (size_t)(n > 0 ? n : 1);
-  return (int64_t)(7 * align256(m * 8) + align256(sort_temp_bytes(n)) + align256(scan_temp_bytes(n)) + 1024);
+  return (int64_t)(7 * gcr_align(m * 8, 256) + gcr_align(sort_temp_bytes(n), 256) + gcr_align(scan_temp_bytes(n), 256) + 1024);
 }
 
 extern "C" int32_t gcr_dense_ids_u64(const uint64_t* keys, int64_t n, int32_t order, int64_t* dense, int64_t* first_pos,

@@ -9,6 +9,8 @@
 #include <type_traits>
 
 #include "gcr_b3.h"
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 #include "gcr_philox.h"
 
 namespace {
@@ -554,14 +556,6 @@ __global__ __launch_bounds__(256, LOWREG ? 4 : 2) void kmeans_search_img_kernel(
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kStreamSplit = 0x4B4D5350u;  // 'KMSP'
 
-__device__ __forceinline__ float group16_sum(float v) {
-  v += __shfl_xor(v, 8, 16);
-  v += __shfl_xor(v, 4, 16);
-  v += __shfl_xor(v, 2, 16);
-  v += __shfl_xor(v, 1, 16);
-  return v;
-}
-
 // sums[c] += x_i (256-B float-atomic rows), counts[c] += 1, one wave per point.  n_copies > 1: block b adds into private
 // copy b % n_copies of (sums, counts) — with a few hundred clusters every point of a 77K-point training set would
 // otherwise hit one of ~300 rows (the memory-side atomic unit serialises adds to one row); the finalize kernel sums the copies.
@@ -662,7 +656,7 @@ __global__ __launch_bounds__(256) void kmeans_finalize_kernel(const float* __res
       }
       ss += v * v;
     }
-    ss = group16_sum(ss);
+    ss = gcr_group16_sum(ss);
     if (l16 == 0) half_sq[c] = 0.5f * ss;
   }
 }
@@ -939,13 +933,12 @@ extern "C" int32_t gcr_kmeans_search_image_f32(const float* x, int64_t n, const 
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((n + 127) / 128));
   const bool low = (flags & GCR_KMEANS_SEARCH_LOW_REGISTERS) != 0;
-  if (d == 32) {
-    if (low) hipLaunchKernelGGL((kmeans_search_img_kernel<32, true>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-    else hipLaunchKernelGGL((kmeans_search_img_kernel<32, false>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-  } else {
-    if (low) hipLaunchKernelGGL((kmeans_search_img_kernel<64, true>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-    else hipLaunchKernelGGL((kmeans_search_img_kernel<64, false>), grid, dim3(256), 0, s, x, n, img, bias, k, assign, sums, counts, (int)n_copies);
-  }
+  dispatch_value<32, 64>(d, [&](auto dc) {
+    dispatch_bool(low, [&](auto lo) {
+      hipLaunchKernelGGL((kmeans_search_img_kernel<decltype(dc)::value, decltype(lo)::value>), grid, dim3(256), 0, s, x, n, img,
+                         bias, k, assign, sums, counts, (int)n_copies);
+    });
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -964,16 +957,13 @@ extern "C" int32_t gcr_kmeans_search_image_incr_f32(const float* x, int64_t n, c
   const dim3 grid((unsigned)((n + 127) / 128));
   const bool low = (flags & GCR_KMEANS_SEARCH_LOW_REGISTERS) != 0;
   long long* sq = reinterpret_cast<long long*>(sums_q);
-
-#define GCR_KMI(DD, LOW)                                                                                                \
-  hipLaunchKernelGGL((kmeans_search_img_kernel<DD, LOW, true>), grid, dim3(256), 0, s, x, n, img, bias, k, (int64_t*)nullptr, \
-                     (float*)nullptr, (float*)nullptr, (int)n_copies, prev_assign, qscale, sq, counts)
-  if (d == 32) {
-    if (low) GCR_KMI(32, true); else GCR_KMI(32, false);
-  } else {
-    if (low) GCR_KMI(64, true); else GCR_KMI(64, false);
-  }
-#undef GCR_KMI
+  dispatch_value<32, 64>(d, [&](auto dc) {
+    dispatch_bool(low, [&](auto lo) {
+      hipLaunchKernelGGL((kmeans_search_img_kernel<decltype(dc)::value, decltype(lo)::value, true>), grid, dim3(256), 0, s, x, n,
+                         img, bias, k, (int64_t*)nullptr, (float*)nullptr, (float*)nullptr, (int)n_copies, prev_assign, qscale,
+                         sq, counts);
+    });
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -984,23 +974,21 @@ extern "C" int32_t gcr_kmeans_assign_f32(const float* x, int64_t n, const float*
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(x && centroids && half_sqnorm && assign);
   hipStream_t s = (hipStream_t)stream;
-#define GCR_KM(DD)                                                                                             \
-  hipLaunchKernelGGL((kmeans_assign_kernel<DD>), dim3((unsigned)((n + Shape<DD>::ANCHORS_PER_BLOCK - 1) /      \
-                                                                 Shape<DD>::ANCHORS_PER_BLOCK)),               \
-                     dim3(256), 0, s, x, n, centroids, half_sqnorm, k, assign, best_score)
-#define GCR_KM3(DD)                                                                                            \
-  hipLaunchKernelGGL((kmeans_assign_b3_kernel<DD>), dim3((unsigned)((n + ShapeB3<DD>::ANCHORS_PER_BLOCK - 1) / \
-                                                                    ShapeB3<DD>::ANCHORS_PER_BLOCK)),          \
-                     dim3(256), 0, s, x, n, centroids, half_sqnorm, k, assign, best_score)
   const bool b3 = use_b3(d);
-  switch (d) {
-    case 32: if (b3) GCR_KM3(32); else GCR_KM(32); break;
-    case 64: if (b3) GCR_KM3(64); else GCR_KM(64); break;
-    case 128: if (b3) GCR_KM3(128); else GCR_KM(128); break;
-    default: GCR_KM(256); break;
-  }
-#undef GCR_KM
-#undef GCR_KM3
+  dispatch_value<32, 64, 128, 256>(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    if constexpr (D <= 128) {                                  // the split-operand engine has no d = 256 form
+      if (b3) {
+        constexpr int ROWS = ShapeB3<D>::ANCHORS_PER_BLOCK;
+        hipLaunchKernelGGL((kmeans_assign_b3_kernel<D>), dim3((unsigned)((n + ROWS - 1) / ROWS)), dim3(256), 0, s, x, n,
+                           centroids, half_sqnorm, k, assign, best_score);
+        return;
+      }
+    }
+    constexpr int ROWS = Shape<D>::ANCHORS_PER_BLOCK;
+    hipLaunchKernelGGL((kmeans_assign_kernel<D>), dim3((unsigned)((n + ROWS - 1) / ROWS)), dim3(256), 0, s, x, n, centroids,
+                       half_sqnorm, k, assign, best_score);
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -1012,16 +1000,11 @@ extern "C" int32_t gcr_kmeans_assign_accumulate_f32(const float* x, int64_t n, c
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(x && centroids && half_sqnorm && sums && counts);
   hipStream_t s = (hipStream_t)stream;
-#define GCR_KMA(DD)                                                                                            \
-  hipLaunchKernelGGL((kmeans_assign_b3_kernel<DD>), dim3((unsigned)((n + ShapeB3<DD>::ANCHORS_PER_BLOCK - 1) / \
-                                                                    ShapeB3<DD>::ANCHORS_PER_BLOCK)),          \
-                     dim3(256), 0, s, x, n, centroids, half_sqnorm, k, assign, (float*)nullptr, sums, counts, (int)n_copies)
-  switch (d) {
-    case 32: GCR_KMA(32); break;
-    case 64: GCR_KMA(64); break;
-    default: GCR_KMA(128); break;
-  }
-#undef GCR_KMA
+  dispatch_value<32, 64, 128>(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value, ROWS = ShapeB3<D>::ANCHORS_PER_BLOCK;
+    hipLaunchKernelGGL((kmeans_assign_b3_kernel<D>), dim3((unsigned)((n + ROWS - 1) / ROWS)), dim3(256), 0, s, x, n, centroids,
+                       half_sqnorm, k, assign, (float*)nullptr, sums, counts, (int)n_copies);
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -1036,12 +1019,10 @@ extern "C" int32_t gcr_kmeans_update_f32(const float* x, int64_t n, int32_t d, c
     hipError_t err = hipMemsetAsync(sums, 0, sizeof(float) * (size_t)(k * d), s);
     if (err == hipSuccess) err = hipMemsetAsync(counts, 0, sizeof(float) * (size_t)k, s);
     if (err != hipSuccess) return gcr_hip_status(err);
-    const int64_t want = (n + 3) / 4;
-    hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3((unsigned)(want > 16384 ? 16384 : want)), dim3(256), 0, s, x, n,
-                       d, assign, k, sums, counts, 1);
+    hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3((unsigned)gcr_grid((n + 3) / 4, 16384)), dim3(256), 0, s, x, n, d,
+                       assign, k, sums, counts, 1);
   }
-  const int64_t wantk = (k + 15) / 16;
-  hipLaunchKernelGGL(kmeans_finalize_kernel, dim3((unsigned)(wantk > 4096 ? 4096 : wantk)), dim3(256), 0, s, sums,
+  hipLaunchKernelGGL(kmeans_finalize_kernel, dim3((unsigned)gcr_grid((k + 15) / 16, 4096)), dim3(256), 0, s, sums,
                      n > 0 ? counts : nullptr, k, d, centroids, half_sqnorm);
   return GCR_LAUNCH_STATUS();
 }
@@ -1055,12 +1036,10 @@ extern "C" int32_t gcr_kmeans_update_sorted_f32(const float* x, int64_t n, int32
   hipError_t err = hipMemsetAsync(sums, 0, sizeof(float) * (size_t)(k * d), s);
   if (err == hipSuccess) err = hipMemsetAsync(counts, 0, sizeof(float) * (size_t)k, s);
   if (err != hipSuccess) return gcr_hip_status(err);
-  const int64_t want = ((n + 63) / 64 + 3) / 4;
-  hipLaunchKernelGGL(kmeans_accumulate_sorted_kernel, dim3((unsigned)(want > 65536 ? 65536 : want)), dim3(256), 0, s, x, n,
-                     d, keys_sorted, perm, k, sums, counts);
-  const int64_t wantk = (k + 15) / 16;
-  hipLaunchKernelGGL(kmeans_finalize_kernel, dim3((unsigned)(wantk > 4096 ? 4096 : wantk)), dim3(256), 0, s, sums, counts,
-                     k, d, centroids, half_sqnorm);
+  hipLaunchKernelGGL(kmeans_accumulate_sorted_kernel, dim3((unsigned)gcr_grid(((n + 63) / 64 + 3) / 4, 65536)), dim3(256), 0,
+                     s, x, n, d, keys_sorted, perm, k, sums, counts);
+  hipLaunchKernelGGL(kmeans_finalize_kernel, dim3((unsigned)gcr_grid((k + 15) / 16, 4096)), dim3(256), 0, s, sums, counts, k,
+                     d, centroids, half_sqnorm);
   return GCR_LAUNCH_STATUS();
 }
 
@@ -1078,12 +1057,10 @@ extern "C" int32_t gcr_kmeans_lloyd_update_f32(const float* x, int64_t n, int32_
   if (keys_sorted == nullptr && assign == nullptr) {
     // sums / counts already hold this iteration's accumulation (gcr_kmeans_assign_accumulate_f32)
   } else if (keys_sorted != nullptr) {
-    const int64_t want = ((n + 63) / 64 + 3) / 4;
-    hipLaunchKernelGGL(kmeans_accumulate_sorted_kernel, dim3((unsigned)(want > 65536 ? 65536 : want)), dim3(256), 0, s, x,
-                       n, d, keys_sorted, perm, k, sums, counts);
+    hipLaunchKernelGGL(kmeans_accumulate_sorted_kernel, dim3((unsigned)gcr_grid(((n + 63) / 64 + 3) / 4, 65536)), dim3(256), 0,
+                       s, x, n, d, keys_sorted, perm, k, sums, counts);
   } else {
-    const int64_t want = (n + 3) / 4;
-    hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3((unsigned)(want > 16384 ? 16384 : want)), dim3(256), 0, s, x, n, d,
+    hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3((unsigned)gcr_grid((n + 3) / 4, 16384)), dim3(256), 0, s, x, n, d,
                        assign, k, sums, counts, (int)n_copies);
   }
   GCR_CHECK_ARG(256 % d == 0 && k * (int64_t)d < (1ll << 39));       // rows must not straddle workgroups (d in 32..256)

@@ -23,26 +23,12 @@
 //
 // Every indexed row is read only if 0 <= idx < n; an index outside (or a slot of q that no p_k fills, when p_k is not a
 // permutation) contributes a zero row and a zero coefficient.
-#include "gcr_common.h"
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 
 namespace {
 
 constexpr int kMaxBlocks = 1024;
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, GCR_WAVE);
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, GCR_WAVE);
-  return v;
-}
 
 // row `idx` of x as this lane's float4, a zero row for an index outside [0, n)
 template <int LPR>
@@ -51,9 +37,10 @@ __device__ __forceinline__ float4 row4(const float* __restrict__ x, int64_t idx,
   return *reinterpret_cast<const float4*>(x + idx * (4 * LPR) + 4 * gl);
 }
 
-// sp(x) = log(1 + e^x) and sigmoid(x) without overflow at either end
+// sp(x) = log(1 + e^x) and sigmoid(x) without overflow at either end (not gcr_dense.hip's sigmoid_f32, 1 / (1 + e^-x): the two
+// round differently)
 __device__ __forceinline__ float softplus_f32(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigmoid_f32(float x) {
+__device__ __forceinline__ float stable_sigmoid_f32(float x) {
   const float e = expf(-fabsf(x));
   return (x >= 0.f ? 1.0f : e) / (1.0f + e);
 }
@@ -169,13 +156,14 @@ __global__ __launch_bounds__(256) void mim_rows_kernel(const float* __restrict__
     const float4 u0 = row4<LPR>(em, p0[r], n, gl);
     const float4 e1 = row4<LPR>(edge, p1[r], n, gl);
     const float4 e2 = row4<LPR>(edge, p2[r], n, gl);
-    const float pos = group_sum<LPR>(dot4(u, e)), neg1 = group_sum<LPR>(dot4(u0, e)), neg2 = group_sum<LPR>(dot4(e1, u));
-    const float gpos = group_sum<LPR>(dot4(e, g4)), gneg = group_sum<LPR>(dot4(e2, g4));
+    const float pos = gcr_group_sum<LPR>(gcr_dot4(u, e)), neg1 = gcr_group_sum<LPR>(gcr_dot4(u0, e));
+    const float neg2 = gcr_group_sum<LPR>(gcr_dot4(e1, u));
+    const float gpos = gcr_group_sum<LPR>(gcr_dot4(e, g4)), gneg = gcr_group_sum<LPR>(gcr_dot4(e2, g4));
     const float x1 = neg1 - pos, x2 = neg2 - neg1, x3 = gneg - gpos;
-    const float c = -sigmoid_f32(x3);
+    const float c = -stable_sigmoid_f32(x3);
     if (gl == 0) {
-      coef[r] = -sigmoid_f32(x1);
-      coef[n + r] = -sigmoid_f32(x2);
+      coef[r] = -stable_sigmoid_f32(x1);
+      coef[n + r] = -stable_sigmoid_f32(x2);
       coef[2 * n + r] = c;
       lsum += (double)softplus_f32(x1) + (double)softplus_f32(x2) + (double)softplus_f32(x3);
     }
@@ -195,7 +183,7 @@ __global__ __launch_bounds__(256) void mim_rows_kernel(const float* __restrict__
   const int nb = (int)gridDim.x;
   fold_columns(dg_part, nb, D, 1.0, gvec + D, red);
   if (threadIdx.x < GCR_WAVE) {
-    const double t = wave_sum_f64(fold_strided(loss_part, (int)threadIdx.x, GCR_WAVE, nb, 1));
+    const double t = gcr_wave_sum_f64(fold_strided(loss_part, (int)threadIdx.x, GCR_WAVE, nb, 1));
     if (threadIdx.x == 0) *loss = (float)t;
   }
 }
@@ -252,11 +240,8 @@ __global__ __launch_bounds__(256) void mim_bwd_kernel(const float* __restrict__ 
 }
 
 int mim_blocks(int64_t n) {
-  const int64_t want = (n + 255) / 256;                      // >= 256 rows per workgroup
-  return (int)(want < 1 ? 1 : (want > kMaxBlocks ? kMaxBlocks : want));
+  return (int)gcr_grid((n + 255) / 256, kMaxBlocks);         // >= 256 rows per workgroup
 }
-
-inline int64_t align64(int64_t bytes) { return (bytes + 63) & ~(int64_t)63; }
 
 struct MimWorkspace {
   int64_t ticket, cs_part, dg_part, loss_part, q, total;     // byte offsets
@@ -264,13 +249,14 @@ struct MimWorkspace {
 
 MimWorkspace mim_layout(int64_t n, int d) {
   MimWorkspace w;
+  WsCarve c;
   const int64_t nb = mim_blocks(n);
-  w.ticket = 0;                                              // two counters: colsum, rows
-  w.cs_part = 64;
-  w.dg_part = w.cs_part + align64(nb * d * (int64_t)sizeof(double));
-  w.loss_part = w.dg_part + align64(nb * d * (int64_t)sizeof(double));
-  w.q = w.loss_part + align64(nb * (int64_t)sizeof(double));
-  w.total = w.q + align64(3 * n * (int64_t)sizeof(int64_t));
+  w.ticket = c.take(64);                                     // two counters: colsum, rows
+  w.cs_part = c.take(nb * d * (int64_t)sizeof(double));
+  w.dg_part = c.take(nb * d * (int64_t)sizeof(double));
+  w.loss_part = c.take(nb * (int64_t)sizeof(double));
+  w.q = c.take(3 * n * (int64_t)sizeof(int64_t));
+  w.total = c.at;
   return w;
 }
 
@@ -300,19 +286,12 @@ extern "C" int32_t gcr_mim_fwd_f32(const float* em, const float* edge, const int
   const int64_t per = (n + nb - 1) / nb;
   hipError_t err = hipMemsetAsync(ticket, 0, 64, s);
   if (err != hipSuccess) return gcr_hip_status(err);
-#define GCR_MIM_FWD(LPR)                                                                                                  \
-  do {                                                                                                                    \
-    hipLaunchKernelGGL((mim_colsum_kernel<LPR>), dim3((unsigned)nb), dim3(256), 0, s, edge, n, per, cs_part, ticket, gvec); \
-    hipLaunchKernelGGL((mim_rows_kernel<LPR>), dim3((unsigned)nb), dim3(256), 0, s, em, edge, p0, p1, p2, n, per, coef,     \
-                       loss_part, dg_part, ticket + 1, loss, gvec);                                                       \
-  } while (0)
-  switch (d) {
-    case 32: GCR_MIM_FWD(8); break;
-    case 64: GCR_MIM_FWD(16); break;
-    case 128: GCR_MIM_FWD(32); break;
-    default: GCR_MIM_FWD(64); break;
-  }
-#undef GCR_MIM_FWD
+  dispatch_value<32, 64, 128, 256>(d, [&](auto dc) {
+    constexpr int LPR = decltype(dc)::value / 4;
+    hipLaunchKernelGGL((mim_colsum_kernel<LPR>), dim3((unsigned)nb), dim3(256), 0, s, edge, n, per, cs_part, ticket, gvec);
+    hipLaunchKernelGGL((mim_rows_kernel<LPR>), dim3((unsigned)nb), dim3(256), 0, s, em, edge, p0, p1, p2, n, per, coef,
+                       loss_part, dg_part, ticket + 1, loss, gvec);
+  });
   return GCR_LAUNCH_STATUS();
 }
 
@@ -328,21 +307,14 @@ extern "C" int32_t gcr_mim_bwd_f32(const float* em, const float* edge, const int
   int64_t* q = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + w.q);
   hipError_t err = hipMemsetAsync(q, 0xFF, sizeof(int64_t) * (size_t)(3 * n), s);       // -1: no row maps here
   if (err != hipSuccess) return gcr_hip_status(err);
-  const int64_t want_inv = (3 * n + 255) / 256;
-  hipLaunchKernelGGL(mim_inverse_kernel, dim3((unsigned)(want_inv > 16384 ? 16384 : want_inv)), dim3(256), 0, s, p0, p1, p2, n, q);
+  hipLaunchKernelGGL(mim_inverse_kernel, dim3((unsigned)gcr_grid((3 * n + 255) / 256, 16384)), dim3(256), 0, s, p0, p1, p2, n, q);
   int32_t st = GCR_LAUNCH_STATUS();
   if (st != GCR_OK) return st;
   const int groups = 256 / (d / 4);
-  const int64_t want = (n + groups * 2 - 1) / (groups * 2);
-  const dim3 grid((unsigned)(want > 16384 ? 16384 : want));
-#define GCR_MIM_BWD(LPR) \
-  hipLaunchKernelGGL((mim_bwd_kernel<LPR>), grid, dim3(256), 0, s, em, edge, p0, p1, q, n, coef, gvec, g_out, d_em, d_edge)
-  switch (d) {
-    case 32: GCR_MIM_BWD(8); break;
-    case 64: GCR_MIM_BWD(16); break;
-    case 128: GCR_MIM_BWD(32); break;
-    default: GCR_MIM_BWD(64); break;
-  }
-#undef GCR_MIM_BWD
+  const dim3 grid((unsigned)gcr_grid((n + groups * 2 - 1) / (groups * 2), 16384));
+  dispatch_value<32, 64, 128, 256>(d, [&](auto dc) {
+    hipLaunchKernelGGL((mim_bwd_kernel<decltype(dc)::value / 4>), grid, dim3(256), 0, s, em, edge, p0, p1, q, n, coef, gvec,
+                       g_out, d_em, d_edge);
+  });
   return GCR_LAUNCH_STATUS();
 }

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "gcr_b3.h"
+#include "gcr_host.h"   // dispatch_value, dispatch_bool, gcr_align
 
 namespace {
 
@@ -523,20 +524,10 @@ bool h2_eight_waves(int d, const FwdPlan& p8) { return d == 64 && p8.tiles_per_s
 bool bce_pipe(int d, bool force_f32) { return d <= 64 && use_b3(d, force_f32); }
 
 // ------------------------------------------------------------------------------------------
-// Dispatch: a runtime width / flag becomes a compile-time constant handed to a generic lambda.  The `if constexpr` guards
-// at the call sites keep the combinations that have no kernel from being instantiated.
+// Dispatch over the four widths of the all-pairs kernels (gcr_host.h: dispatch_value, dispatch_bool).
 // ------------------------------------------------------------------------------------------
 template <class F>
-auto dispatch_dim(int d, F&& f) {
-  switch (d) {
-    case 32: return f(std::integral_constant<int, 32>{});
-    case 64: return f(std::integral_constant<int, 64>{});
-    case 128: return f(std::integral_constant<int, 128>{});
-    default: return f(std::integral_constant<int, 256>{});
-  }
-}
-template <class F>
-void dispatch_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+auto dispatch_dim(int d, F&& f) { return dispatch_value<32, 64, 128, 256>(d, std::forward<F>(f)); }
 // the lse forward's (COLSUM, EXD): plain, column sums or excluded diagonal — the last two never meet
 template <class F>
 void dispatch_lse_mode(bool exd, bool colsum, F&& f) {
@@ -577,8 +568,6 @@ struct PairsPlan {
 template <class T>
 T* ws_at(void* workspace, int64_t offset) { return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset); }
 
-constexpr int64_t align256_i64(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 // lse-only forward: (max, sum) pairs per split and anchor
 enum { kLseF32, kLseSplit, kLseSplit8, kLsePaths };
 PairsPlan<kLsePaths> plan_lse_fwd(int64_t m, int64_t n, int d) {
@@ -618,7 +607,7 @@ PairsPlan<kFlashPaths> plan_flash_fwd(int64_t m, int64_t n, int d) {
 constexpr int64_t kBwdHeader = 256;
 constexpr int64_t fold_rows(int64_t ny) { return (ny + kTileJ - 1) / kTileJ * kTileJ; }
 constexpr int64_t bwd_header_bytes(int64_t ny, int d) {
-  return d <= 128 ? kBwdHeader + align256_i64(fold_rows(ny) * (2 + d) * (int64_t)sizeof(float)) : 0;
+  return d <= 128 ? kBwdHeader + gcr_align(fold_rows(ny) * (2 + d) * (int64_t)sizeof(float), 256) : 0;
 }
 enum { kBwdF32, kBwdSplit, kBwdPaths };
 PairsPlan<kBwdPaths> plan_infonce_bwd(int64_t mx, int64_t ny, int d) {
@@ -641,11 +630,11 @@ PairsPlan<kBwdPaths> plan_infonce_bwd(int64_t mx, int64_t ny, int d) {
 // two-plane format (d <= 64): inv / nrm of both sides, f of the streamed side, hw[2]
 enum { kBceLoop, kBceF32, kBcePaths };
 void bce_scratch_behind(PairsPlan<kBcePaths>& pl, int64_t m, int64_t n, int d) {
-  const int64_t core = align256_i64(pl.bytes());
+  const int64_t core = gcr_align(pl.bytes(), 256);
   for (PairsPath& q : pl.path) {
     q.scales = core;
     q.hw = core + (2 * m + 3 * n) * (int64_t)sizeof(float);
-    q.bytes = core + (d <= 64 ? align256_i64((2 * m + 3 * n + 8) * (int64_t)sizeof(float)) : 0);
+    q.bytes = core + (d <= 64 ? gcr_align((2 * m + 3 * n + 8) * (int64_t)sizeof(float), 256) : 0);
   }
 }
 

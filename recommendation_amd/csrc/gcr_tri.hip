@@ -29,6 +29,8 @@
 // gcr_directau.hip.  Per-split partials are added in split (and view) order by the last kernel, which applies the
 // normalisation backward and writes row uniq[i] of each gradient table: one writer per row, no float atomics, bitwise
 // reproducible.
+#include "gcr_host.h"
+#include "gcr_lanes.h"
 #include "gcr_tile.h"   // f32x16, acc_row, kTileJ = 32 rows of a tile
 
 namespace {
@@ -39,12 +41,6 @@ constexpr int kMaxK = 32;
 constexpr float kNormEps = 1e-12f;   // F.normalize's eps
 constexpr int kNoCol = 0x7fffffff;
 constexpr float kMaxInvT = 40.f;    // e = exp((S - 1) / t) >= exp(-2 / t) stays a normal f32
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, GCR_WAVE);
-  return v;
-}
 
 struct TriTabs {
   const float* tab[4];     // friend, sharing, rec, augmented
@@ -296,7 +292,7 @@ __global__ __launch_bounds__(192) void tri_reduce_kernel(const float* __restrict
   const int lane = threadIdx.x & 63, v = threadIdx.x >> 6;
   double s = 0.0;
   for (int64_t i = lane; i < m; i += 64) s += (double)row_loss[(int64_t)v * m + i];
-  s = wave_sum_f64(s);
+  s = gcr_wave_sum_f64(s);
   if (lane == 0) loss[v] = (float)s;
 }
 
@@ -419,8 +415,6 @@ __global__ __launch_bounds__(256) void tri_bwd_rows_kernel(const float* __restri
   }
 }
 
-inline int64_t align64f(int64_t words) { return (words + 63) & ~(int64_t)63; }
-
 int splits_for(int64_t n_tiles) {
   int64_t want = (256 + n_tiles - 1) / n_tiles;
   if (want > kMaxSplits) want = kMaxSplits;
@@ -434,29 +428,33 @@ struct TriWorkspace {
 
 TriWorkspace tri_layout(int64_t m, int d, int k) {
   TriWorkspace w;
+  WsCarve c;
   const int64_t n_tiles = (m + kTileJ - 1) / kTileJ;
   const int ns = splits_for(n_tiles < 1 ? 1 : n_tiles);
-  w.xhat = 0;
-  w.inv_norm = w.xhat + align64f(4 * m * d);
-  w.z1 = w.inv_norm + align64f(4 * m);
-  w.zt = w.z1 + align64f((int64_t)ns * kViews * m);
-  w.row_loss = w.zt + align64f(2 * (int64_t)ns * kViews * m);                                // doubles
-  w.cand_val = w.row_loss + align64f(kViews * m);
-  w.cand_col = w.cand_val + align64f((int64_t)kViews * m * 2 * ns * k);
-  w.part_e = w.cand_col + align64f((int64_t)kViews * m * 2 * ns * k);
-  w.part_a = w.part_e + align64f((int64_t)ns * kViews * m * d);
-  w.total = w.part_a + align64f((int64_t)ns * kViews * m * d);
+  w.xhat = c.take(4 * m * d);
+  w.inv_norm = c.take(4 * m);
+  w.z1 = c.take((int64_t)ns * kViews * m);
+  w.zt = c.take(2 * (int64_t)ns * kViews * m);                                               // doubles
+  w.row_loss = c.take(kViews * m);
+  w.cand_val = c.take((int64_t)kViews * m * 2 * ns * k);
+  w.cand_col = c.take((int64_t)kViews * m * 2 * ns * k);
+  w.part_e = c.take((int64_t)ns * kViews * m * d);
+  w.part_a = c.take((int64_t)ns * kViews * m * d);
+  w.total = c.at;
   return w;
+}
+
+TriTabs tri_tabs(const float* x_f, const float* x_s, const float* x_r, const float* aug) {
+  TriTabs T;
+  T.tab[0] = x_f; T.tab[1] = x_s; T.tab[2] = x_r; T.tab[3] = aug;
+  return T;
 }
 
 bool tri_args_ok(int64_t n_rows, int64_t m, int32_t k) {
   return n_rows >= 0 && n_rows < (1ll << 31) && m >= 0 && m < (1ll << 22) && k >= 1 && k <= kMaxK;
 }
 
-unsigned row_blocks(int64_t waves) {
-  const int64_t want = (waves + 3) / 4;
-  return (unsigned)(want > 8192 ? 8192 : (want < 1 ? 1 : want));
-}
+unsigned row_blocks(int64_t waves) { return (unsigned)gcr_grid((waves + 3) / 4, 8192); }
 
 }  // namespace
 
@@ -473,17 +471,6 @@ extern "C" int64_t gcr_tri_member_words(int64_t m) {
   return m < 1 ? 0 : kViews * m * ((m + kTileJ - 1) / kTileJ);
 }
 
-#define GCR_TRI_BY_D(CALL) \
-  do {                     \
-    if (d == 32) {         \
-      CALL(32);            \
-    } else if (d == 64) {  \
-      CALL(64);            \
-    } else {               \
-      CALL(128);           \
-    }                      \
-  } while (0)
-
 extern "C" int32_t gcr_tri_fwd_f32(const float* x_f, const float* x_s, const float* x_r, const float* aug, int64_t n_rows,
                                    int32_t d, const int64_t* uniq, int64_t m, int32_t k, float inv_t, int32_t replay,
                                    float* loss, int64_t* positive, float* rsum, float* inv_norm, uint32_t* member,
@@ -498,31 +485,29 @@ extern "C" int32_t gcr_tri_fwd_f32(const float* x_f, const float* x_s, const flo
   float* ws = reinterpret_cast<float*>(workspace);
   const int n_tiles = (int)((m + kTileJ - 1) / kTileJ);
   const int ns = splits_for(n_tiles);
-  TriTabs T;
-  T.tab[0] = x_f; T.tab[1] = x_s; T.tab[2] = x_r; T.tab[3] = aug;
+  const TriTabs T = tri_tabs(x_f, x_s, x_r, aug);
   int32_t st = gcr_hip_status(hipMemsetAsync(member, 0, (size_t)gcr_tri_member_words(m) * sizeof(uint32_t), s));
   if (st != GCR_OK) return st;
   const dim3 grid((unsigned)n_tiles, (unsigned)ns);
   const size_t lds_sel = (size_t)(kViews * 16 * 64 + 2 * kViews * k * 64) * sizeof(float);
   int* cand_col = reinterpret_cast<int*>(ws + w.cand_col);
   double* zt = reinterpret_cast<double*>(ws + w.zt);             // every offset is a multiple of 64 words
-#define GCR_TRI_FWD(D)                                                                                                     \
-  hipLaunchKernelGGL((tri_prepare_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, T, uniq, m, n_rows, ws + w.xhat,   \
-                     inv_norm);                                                                                            \
-  if (replay) {                                                                                                            \
-    hipLaunchKernelGGL((tri_sweep_kernel<D, 1>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,        \
-                       (const float*)nullptr, zt, (float*)nullptr, (int*)nullptr);                                         \
-  } else {                                                                                                                 \
-    hipLaunchKernelGGL((tri_sweep_kernel<D, 0>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,        \
-                       (const float*)nullptr, ws + w.z1, (float*)nullptr, (int*)nullptr);                                  \
-    hipLaunchKernelGGL((tri_sweep_kernel<D, 2>), grid, dim3(192), lds_sel, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,  \
-                       ws + w.z1, zt, ws + w.cand_val, cand_col);                                                          \
-  }                                                                                                                        \
-  hipLaunchKernelGGL((tri_finish_kernel<D>), dim3(row_blocks(kViews * m)), dim3(256), 0, s, ws + w.xhat, m, n_tiles, ns,   \
-                     (int)k, inv_t, (int)replay, zt, ws + w.cand_val, cand_col, positive, rsum, ws + w.row_loss,           \
-                     member)
-  GCR_TRI_BY_D(GCR_TRI_FWD);
-#undef GCR_TRI_FWD
+  dispatch_value<32, 64, 128>(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    hipLaunchKernelGGL((tri_prepare_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, T, uniq, m, n_rows, ws + w.xhat,
+                       inv_norm);
+    if (replay) {
+      hipLaunchKernelGGL((tri_sweep_kernel<D, 1>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,
+                         (const float*)nullptr, zt, (float*)nullptr, (int*)nullptr);
+    } else {
+      hipLaunchKernelGGL((tri_sweep_kernel<D, 0>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,
+                         (const float*)nullptr, ws + w.z1, (float*)nullptr, (int*)nullptr);
+      hipLaunchKernelGGL((tri_sweep_kernel<D, 2>), grid, dim3(192), lds_sel, s, ws + w.xhat, m, n_tiles, ns, (int)k, inv_t,
+                         ws + w.z1, zt, ws + w.cand_val, cand_col);
+    }
+    hipLaunchKernelGGL((tri_finish_kernel<D>), dim3(row_blocks(kViews * m)), dim3(256), 0, s, ws + w.xhat, m, n_tiles, ns,
+                       (int)k, inv_t, (int)replay, zt, ws + w.cand_val, cand_col, positive, rsum, ws + w.row_loss, member);
+  });
   hipLaunchKernelGGL(tri_reduce_kernel, dim3(1), dim3(192), 0, s, ws + w.row_loss, m, loss);
   return GCR_LAUNCH_STATUS();
 }
@@ -540,21 +525,20 @@ extern "C" int32_t gcr_tri_bwd_f32(const float* x_f, const float* x_s, const flo
   float* ws = reinterpret_cast<float*>(workspace);
   const int n_tiles = (int)((m + kTileJ - 1) / kTileJ);
   const int ns = splits_for(n_tiles);
-  TriTabs T;
-  T.tab[0] = x_f; T.tab[1] = x_s; T.tab[2] = x_r; T.tab[3] = aug;
+  const TriTabs T = tri_tabs(x_f, x_s, x_r, aug);
   TriGrads G;
   G.tab[0] = d_f; G.tab[1] = d_s; G.tab[2] = d_r; G.tab[3] = d_aug;
   const dim3 grid((unsigned)n_tiles, (unsigned)ns);
-#define GCR_TRI_BWD(D)                                                                                                      \
-  hipLaunchKernelGGL((tri_prepare_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, T, uniq, m, n_rows, ws + w.xhat,    \
-                     ws + w.inv_norm);                                                                                      \
-  hipLaunchKernelGGL((tri_bwd_sweep_kernel<D, false>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, inv_t, rsum,     \
-                     member, g, ws + w.part_e);                                                                             \
-  hipLaunchKernelGGL((tri_bwd_sweep_kernel<D, true>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, inv_t, rsum,      \
-                     member, g, ws + w.part_a);                                                                             \
-  hipLaunchKernelGGL((tri_bwd_rows_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, ws + w.xhat, ws + w.inv_norm,      \
-                     uniq, m, n_rows, ns, ws + w.part_e, ws + w.part_a, G)
-  GCR_TRI_BY_D(GCR_TRI_BWD);
-#undef GCR_TRI_BWD
+  dispatch_value<32, 64, 128>(d, [&](auto dc) {
+    constexpr int D = decltype(dc)::value;
+    hipLaunchKernelGGL((tri_prepare_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, T, uniq, m, n_rows, ws + w.xhat,
+                       ws + w.inv_norm);
+    hipLaunchKernelGGL((tri_bwd_sweep_kernel<D, false>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, inv_t, rsum,
+                       member, g, ws + w.part_e);
+    hipLaunchKernelGGL((tri_bwd_sweep_kernel<D, true>), grid, dim3(192), 0, s, ws + w.xhat, m, n_tiles, ns, inv_t, rsum,
+                       member, g, ws + w.part_a);
+    hipLaunchKernelGGL((tri_bwd_rows_kernel<D>), dim3(row_blocks(4 * m)), dim3(256), 0, s, ws + w.xhat, ws + w.inv_norm,
+                       uniq, m, n_rows, ns, ws + w.part_e, ws + w.part_a, G);
+  });
   return GCR_LAUNCH_STATUS();
 }

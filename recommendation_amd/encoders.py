@@ -61,7 +61,7 @@ def dense_ids_device(keys, device, order="sorted"):
     L = _lib.lib()
     n, words = keys.shape
     dev = torch.device(device)
-    ws = torch.empty(int(L.gcr_dense_ids_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("gcr_dense_ids_workspace_bytes", n, device=dev, dtype=torch.uint8)
     n_unique = torch.zeros(1, dtype=torch.int64, device=dev)
 
     def call(k, mode):

@@ -58,7 +58,7 @@ def rank_topk(user_emb, item_emb, user_ids, user_rowptr, user_items_sorted, top_
         _rank_two_call(L, ue, ie, user_ids, user_rowptr, user_items_sorted, top_n, top_items, top_scores, chunk_bytes)
         return top_items, top_scores
     chunk = min(q, FUSED_CHUNK_USERS)
-    ws = torch.empty(int(L.gcr_rank_fused_workspace_bytes(chunk)), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("gcr_rank_fused_workspace_bytes", chunk, device=dev, dtype=torch.uint8)
     status = torch.empty(q, dtype=torch.int32, device=dev)
     stream = _lib.cur_stream(dev)
     for s in range(0, q, chunk):

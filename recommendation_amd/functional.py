@@ -288,7 +288,7 @@ def gram_tn(x, g):
         return x.t() @ g
     L = _lib.lib()
     out = torch.empty(dx, dg, dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(L.gcr_gram_tn_workspace_bytes(n, dx, dg)), 4) // 4, dtype=torch.float32, device=x.device)
+    ws = _lib.workspace("gcr_gram_tn_workspace_bytes", n, dx, dg, device=x.device)
     _lib.check(L.gcr_gram_tn_f32(_lib.dptr(x), _lib.dptr(g), n, dx, dg, _lib.dptr(out), _lib.dptr(ws), _lib.cur_stream(x.device)),
                "gcr_gram_tn_f32")
     return out
@@ -342,7 +342,7 @@ class _RowsDotVec(torch.autograd.Function):
             L = _lib.lib()
             n, d = em.shape
             gv = torch.empty(d, dtype=torch.float32, device=em.device)
-            ws = torch.empty(max(int(L.gcr_weighted_colsum_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=em.device)
+            ws = _lib.workspace("gcr_weighted_colsum_workspace_bytes", n, d, device=em.device)
             _lib.check(L.gcr_weighted_colsum_f32(_lib.dptr(em), _lib.dptr(g), n, d, _lib.dptr(gv), _lib.dptr(ws),
                                                  _lib.cur_stream(em.device)), "gcr_weighted_colsum_f32")
         return gem, gv
@@ -379,7 +379,7 @@ class _Gate(torch.autograd.Function):
         g = g.contiguous()
         d_em, d_z = torch.empty_like(em), torch.empty_like(z)
         d_b = torch.empty(d, dtype=torch.float32, device=em.device)
-        ws = torch.empty(max(int(L.gcr_gate_bwd_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=em.device)
+        ws = _lib.workspace("gcr_gate_bwd_workspace_bytes", n, d, device=em.device)
         _lib.check(L.gcr_gate_bwd_f32(_lib.dptr(g), _lib.dptr(em), _lib.dptr(z), _lib.dptr(b), n, d, _lib.dptr(d_em),
                                       _lib.dptr(d_z), _lib.dptr(d_b), _lib.dptr(ws), _lib.cur_stream(em.device)),
                    "gcr_gate_bwd_f32")
@@ -423,7 +423,7 @@ class _ChannelMix(torch.autograd.Function):
         d1, d2, d3 = torch.empty_like(e1), torch.empty_like(e1), torch.empty_like(e1)
         dx = torch.empty_like(e1) if ctx.has_extra else None
         dv = torch.empty(d, dtype=torch.float32, device=e1.device)
-        ws = torch.empty(max(int(L.gcr_channel_mix_bwd_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=e1.device)
+        ws = _lib.workspace("gcr_channel_mix_bwd_workspace_bytes", n, d, device=e1.device)
         _lib.check(L.gcr_channel_mix_bwd_f32(_lib.dptr(g), _lib.dptr(e1), _lib.dptr(e2), _lib.dptr(e3), _lib.dptr(v),
                                              _lib.dptr(score), ctx.extra_scale, n, d, _lib.dptr(d1), _lib.dptr(d2),
                                              _lib.dptr(d3), _lib.dptr(dx), _lib.dptr(dv), _lib.dptr(ws),
@@ -459,7 +459,7 @@ class _MimLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         coef = torch.empty(3, n, dtype=torch.float32, device=dev)
         gvec = torch.empty(2, d, dtype=torch.float32, device=dev)
-        ws = torch.empty(max(int(L.gcr_mim_workspace_bytes(n, d)), 8) // 8, dtype=torch.float64, device=dev)
+        ws = _lib.workspace("gcr_mim_workspace_bytes", n, d, device=dev, dtype=torch.float64)
         _lib.check(L.gcr_mim_fwd_f32(_lib.dptr(em), _lib.dptr(edge), _lib.dptr(p0), _lib.dptr(p1), _lib.dptr(p2), n, d,
                                      _lib.dptr(loss), _lib.dptr(coef), _lib.dptr(gvec), _lib.dptr(ws), _lib.cur_stream(dev)),
                    "gcr_mim_fwd_f32")
@@ -473,7 +473,7 @@ class _MimLoss(torch.autograd.Function):
         n, d = em.shape
         g = g.to(torch.float32).contiguous()
         d_em, d_edge = torch.empty_like(em), torch.empty_like(edge)
-        ws = torch.empty(max(int(L.gcr_mim_workspace_bytes(n, d)), 8) // 8, dtype=torch.float64, device=em.device)
+        ws = _lib.workspace("gcr_mim_workspace_bytes", n, d, device=em.device, dtype=torch.float64)
         _lib.check(L.gcr_mim_bwd_f32(_lib.dptr(em), _lib.dptr(edge), _lib.dptr(p0), _lib.dptr(p1), _lib.dptr(p2), n, d,
                                      _lib.dptr(coef), _lib.dptr(gvec), _lib.dptr(g), _lib.dptr(d_em), _lib.dptr(d_edge),
                                      _lib.dptr(ws), _lib.cur_stream(em.device)), "gcr_mim_bwd_f32")
@@ -731,7 +731,7 @@ def _sorted_order(idx, n_keys, cache=False):
     n = idx.numel()
     keys = torch.empty(n, dtype=torch.int32, device=idx.device)
     perm = torch.empty(n, dtype=torch.int32, device=idx.device)
-    ws = torch.empty(int(L.gcr_sort_index_workspace_bytes(n)), dtype=torch.uint8, device=idx.device)
+    ws = _lib.workspace("gcr_sort_index_workspace_bytes", n, device=idx.device, dtype=torch.uint8)
     _lib.check(L.gcr_sort_index(_lib.dptr(idx), n, int(n_keys), _lib.dptr(keys), _lib.dptr(perm), _lib.dptr(ws),
                                 _lib.cur_stream(idx.device)), "gcr_sort_index")
     if cache:
@@ -765,7 +765,7 @@ class _BprSums(torch.autograd.Function):
         dev = user_tab.device
         dldx = torch.empty(max(batch, 1), dtype=torch.float32, device=dev)
         sums = torch.zeros(5, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.gcr_bpr_workspace_floats(batch)), dtype=torch.float32, device=dev)
+        ws = _lib.workspace("gcr_bpr_workspace_floats", batch, device=dev)
         _lib.check(L.gcr_bpr_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
                                      _lib.dptr(j_idx), batch, n_neg, variant, user_tab.shape[0], item_tab.shape[0],
                                      _lib.dptr(dldx), _lib.dptr(sums), _lib.dptr(ws), _lib.cur_stream(dev)),
@@ -813,7 +813,7 @@ class _BprSums(torch.autograd.Function):
                                                    _lib.dptr(gs), None, None, None, _lib.dptr(skey), _lib.dptr(spay), stream),
                            "gcr_bpr_neg_block_f32")
                 ks, ps = torch.empty_like(skey), torch.empty_like(spay)
-                ws = torch.empty(int(L.gcr_sort_pairs_u64_workspace_bytes(slots)), dtype=torch.uint8, device=dev)
+                ws = _lib.workspace("gcr_sort_pairs_u64_workspace_bytes", slots, device=dev, dtype=torch.uint8)
                 _lib.check(L.gcr_sort_pairs_u64(_lib.dptr(skey), _lib.dptr(spay), slots, n_items, _lib.dptr(ks), _lib.dptr(ps),
                                                 _lib.dptr(ws), stream), "gcr_sort_pairs_u64")
                 _lib.check(L.gcr_bpr_neg_items_sorted_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), user_tab.shape[1],
@@ -847,7 +847,7 @@ class _BprEdgeSums(torch.autograd.Function):
         user_tab, item_tab = table[:n_users], table[n_users:]
         dldx = torch.empty(max(batch, 1), dtype=torch.float32, device=dev)
         sums = torch.zeros(5, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.gcr_bpr_workspace_floats(batch)), dtype=torch.float32, device=dev)
+        ws = _lib.workspace("gcr_bpr_workspace_floats", batch, device=dev)
         _lib.check(L.gcr_bpr_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
                                      _lib.dptr(j_idx), batch, n_neg, variant, n_users, n_items, _lib.dptr(dldx),
                                      _lib.dptr(sums), _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_bpr_fwd_f32")
@@ -902,7 +902,7 @@ class _BprEdgeSums(torch.autograd.Function):
         # the key, so the scatter streams its three arrays instead of chasing perm -> sample -> (u_idx, dloss_dx)
         if payload_sort:
             ks, ps = torch.empty_like(skey), torch.empty_like(spay)
-            ws = torch.empty(int(L.gcr_sort_pairs_u64_workspace_bytes(batch * n_neg)), dtype=torch.uint8, device=table.device)
+            ws = _lib.workspace("gcr_sort_pairs_u64_workspace_bytes", batch * n_neg, device=table.device, dtype=torch.uint8)
             _lib.check(L.gcr_sort_pairs_u64(_lib.dptr(skey), _lib.dptr(spay), batch * n_neg, n_items, _lib.dptr(ks),
                                             _lib.dptr(ps), _lib.dptr(ws), _lib.cur_stream(table.device)), "gcr_sort_pairs_u64")
             _lib.check(L.gcr_bpr_neg_items_sorted_f32(_lib.dptr(table[:n_users]), _lib.dptr(table[n_users:]), table.shape[1],
@@ -979,7 +979,7 @@ class _AuSums(torch.autograd.Function):
         inv = torch.empty(3 * batch, dtype=torch.float32, device=dev)
         r = torch.empty(3 * batch, dtype=torch.float32, device=dev) if want_grad else None
         o = torch.empty(3 * batch, d, dtype=torch.float32, device=dev) if want_grad else None
-        ws = torch.empty(int(L.gcr_directau_workspace_bytes(batch, d)) // 4, dtype=torch.float32, device=dev)
+        ws = _lib.workspace("gcr_directau_workspace_bytes", batch, d, device=dev)
         _lib.check(L.gcr_directau_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
                                           _lib.dptr(j_idx), batch, n_sets, user_tab.shape[0], n_items, float(t),
                                           _lib.dptr(sums), _lib.dptr(inv), _lib.dptr(r), _lib.dptr(o), _lib.dptr(ws),
@@ -1144,7 +1144,7 @@ def infonce_lse_raw(a, a_scale, b, b_scale, inv_tau, col_bound=None, exclude_dia
     n = b.shape[0]
     lse = torch.empty(m, dtype=torch.float32, device=a.device)
     col_sum = torch.empty(n, dtype=torch.float32, device=a.device) if col_bound is not None else None
-    ws = torch.empty(max(int(L.gcr_infonce_fwd_workspace_bytes(m, n, d)), 8) // 4, dtype=torch.float32, device=a.device)
+    ws = _lib.workspace("gcr_infonce_fwd_workspace_bytes", m, n, d, device=a.device)
     _lib.check(L.gcr_infonce_fwd_ex_f32(_lib.dptr(a), _lib.dptr(a_scale), m, _lib.dptr(b), _lib.dptr(b_scale), n, d,
                                         float(inv_tau), _lib.dptr(lse), _lib.dptr(col_sum),
                                         float(col_bound) if col_bound is not None else 0.0, _lib.dptr(ws),
@@ -1176,7 +1176,7 @@ def infonce_fwd_o_raw(a, a_scale, b, b_scale, inv_tau, exclude_diagonal=False, e
     o = torch.empty(m, d, dtype=torch.float32, device=a.device) if o_out is None else o_out
     if lse.shape != (m,) or o.shape != (m, d) or lse.dtype != torch.float32 or o.dtype != torch.float32:
         raise ValueError("lse_out [M] / o_out [M, d] must be float32")
-    ws = torch.empty(max(int(L.gcr_infonce_fwd_o_workspace_bytes(m, n, d)), 8) // 4, dtype=torch.float32, device=a.device)
+    ws = _lib.workspace("gcr_infonce_fwd_o_workspace_bytes", m, n, d, device=a.device)
     _lib.check(L.gcr_infonce_fwd_o_f32(_lib.dptr(a), _lib.dptr(a_scale), m, _lib.dptr(b), _lib.dptr(b_scale), n, d,
                                        float(inv_tau), _lib.dptr(lse), _lib.dptr(o), _lib.dptr(ws),
                                        (INFONCE_EXCLUDE_DIAGONAL if exclude_diagonal else 0) |
@@ -1364,7 +1364,7 @@ def bce_fwd_raw(a, b, want_o=False, engine_flag=0):
     n = b.shape[0]
     rows = torch.empty(m, dtype=torch.float32, device=a.device)
     o = torch.empty(m, d, dtype=torch.float32, device=a.device) if want_o else None
-    ws = torch.empty(max(int(L.gcr_bce_fwd_workspace_bytes(m, n, d)), 8) // 4, dtype=torch.float32, device=a.device)
+    ws = _lib.workspace("gcr_bce_fwd_workspace_bytes", m, n, d, device=a.device)
     _lib.check(L.gcr_bce_fwd_f32(_lib.dptr(a), m, _lib.dptr(b), n, d, _lib.dptr(rows), _lib.dptr(o), _lib.dptr(ws),
                                  int(engine_flag), _lib.cur_stream(a.device)), "gcr_bce_fwd_f32")
     return rows, o
@@ -1487,7 +1487,7 @@ def edge_mask_exact_bits(nnz, n_keep, seed, device):
     (univariate/sept.py:55-61: `np.random.choice(idx, int(len(idx) * (1 - drop_rate)), replace=False)`)."""
     L = _lib.lib()
     bits = torch.empty((nnz + 31) // 32, dtype=torch.int32, device=device)
-    ws = torch.empty(int(L.gcr_edge_mask_exact_workspace_bytes(nnz)), dtype=torch.uint8, device=device)
+    ws = _lib.workspace("gcr_edge_mask_exact_workspace_bytes", nnz, device=device, dtype=torch.uint8)
     _lib.check(L.gcr_edge_mask_exact_bits(int(nnz), int(n_keep), int(seed) & (2 ** 64 - 1), _lib.dptr(bits),
                                           _lib.dptr(ws), _lib.cur_stream(device)), "gcr_edge_mask_exact_bits")
     return bits
@@ -1644,8 +1644,8 @@ class _TriTraining(torch.autograd.Function):
         pos = positives if replay else torch.empty(3, m, k, dtype=torch.int64, device=dev)
         rsum = torch.empty(2, 3, m, dtype=torch.float32, device=dev)
         inv_norm = torch.empty(4, m, dtype=torch.float32, device=dev)
-        member = torch.empty(int(L.gcr_tri_member_words(m)), dtype=torch.int32, device=dev)
-        ws = torch.empty(max(int(L.gcr_tri_workspace_bytes(m, d, k)), 4) // 4, dtype=torch.float32, device=dev)
+        member = _lib.workspace("gcr_tri_member_words", m, device=dev, dtype=torch.int32)
+        ws = _lib.workspace("gcr_tri_workspace_bytes", m, d, k, device=dev)
         _lib.check(L.gcr_tri_fwd_f32(*(_lib.dptr(t) for t in tabs), n_rows, d, _lib.dptr(uniq), m, k, inv_t, int(replay),
                                      _lib.dptr(loss), _lib.dptr(pos), _lib.dptr(rsum), _lib.dptr(inv_norm), _lib.dptr(member),
                                      _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_tri_fwd_f32")
@@ -1663,7 +1663,7 @@ class _TriTraining(torch.autograd.Function):
         m, dev = uniq.numel(), tabs[0].device
         g = g.to(torch.float32).contiguous()
         grads = [torch.zeros_like(t) for t in tabs]
-        ws = torch.empty(max(int(L.gcr_tri_workspace_bytes(m, d, k)), 4) // 4, dtype=torch.float32, device=dev)
+        ws = _lib.workspace("gcr_tri_workspace_bytes", m, d, k, device=dev)
         _lib.check(L.gcr_tri_bwd_f32(*(_lib.dptr(t) for t in tabs), n_rows, d, _lib.dptr(uniq), m, k, inv_t, _lib.dptr(rsum),
                                      _lib.dptr(member), _lib.dptr(g), *(_lib.dptr(t) for t in grads), _lib.dptr(ws),
                                      _lib.cur_stream(dev)), "gcr_tri_bwd_f32")
@@ -1766,7 +1766,7 @@ class _BuirLoss(torch.autograd.Function):
         if batch:
             ku, pu, _ = _sorted_order(u_idx, n_users)
             ki, pi, _ = _sorted_order(i_idx, n_items)
-            ws = torch.empty(int(L.gcr_buir_workspace_bytes(batch, d)) // 4, dtype=torch.float32, device=dev)
+            ws = _lib.workspace("gcr_buir_workspace_bytes", batch, d, device=dev)
             g = g.to(torch.float32).reshape(1).contiguous()
             _lib.check(L.gcr_buir_bwd_f32(
                 _lib.dptr(on_user), _lib.dptr(on_item), _lib.dptr(tg_user), _lib.dptr(tg_item), n_users, n_items, d,
@@ -1863,7 +1863,7 @@ def column_stats(x):
     n, d = x.shape
     L = _lib.lib()
     out = torch.empty(2, d, dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(L.gcr_col_stats_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=x.device)
+    ws = _lib.workspace("gcr_col_stats_workspace_bytes", n, d, device=x.device)
     _lib.check(L.gcr_col_stats_f32(_lib.dptr(x), n, d, _lib.dptr(out[0]), _lib.dptr(out[1]), _lib.dptr(ws),
                                    _lib.cur_stream(x.device)), "gcr_col_stats_f32")
     return out[0], out[1]
@@ -1912,7 +1912,7 @@ def bt_forward_raw(h1, h2, lambda_, batch_norm=True, eps=1e-15):
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     c = torch.empty(d, d, dtype=torch.float32, device=dev)
     stats = torch.zeros(4, d, dtype=torch.float32, device=dev)
-    ws = torch.empty(max(int(L.gcr_bt_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("gcr_bt_workspace_bytes", n, d, device=dev)
     _lib.check(L.gcr_bt_fwd_f32(_lib.dptr(h1), _lib.dptr(h2), n, d, float(lambda_), float(eps), int(bool(batch_norm)),
                                 _lib.dptr(stats), _lib.dptr(c), _lib.dptr(loss), _lib.dptr(ws), _lib.cur_stream(dev)),
                "gcr_bt_fwd_f32")
@@ -1926,7 +1926,7 @@ def bt_backward_raw(h1, h2, lambda_, batch_norm, eps, stats, c, g, want1=True, w
     dev = h1.device
     g1 = torch.empty_like(h1) if want1 else None
     g2 = torch.empty_like(h2) if want2 else None
-    ws = torch.empty(max(int(L.gcr_bt_workspace_bytes(n, d)), 4) // 4, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("gcr_bt_workspace_bytes", n, d, device=dev)
     _lib.check(L.gcr_bt_bwd_f32(_lib.dptr(h1), _lib.dptr(h2), n, d, float(lambda_), float(eps), int(bool(batch_norm)),
                                 _lib.dptr(stats), _lib.dptr(c), _lib.dptr(g), _lib.dptr(g1), _lib.dptr(g2), _lib.dptr(ws),
                                 _lib.cur_stream(dev)), "gcr_bt_bwd_f32")

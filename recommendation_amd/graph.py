@@ -466,7 +466,7 @@ def coo_to_csr_device(row, col, val, n_rows, n_cols, device, coalesce=False, wan
     val_out = torch.empty(max(nnz, 1), dtype=torch.float32, device=device) if keep_val else None
     perm = torch.empty(max(nnz, 1), dtype=torch.int64, device=device) if (want_perm and not coalesce) else None
     meta = torch.zeros(2, dtype=torch.int64, device=device)
-    ws = torch.empty(int(L.gcr_coo_to_csr_workspace_bytes(nnz)), dtype=torch.uint8, device=device)
+    ws = _lib.workspace("gcr_coo_to_csr_workspace_bytes", nnz, device=device, dtype=torch.uint8)
     _lib.check(L.gcr_coo_to_csr(_lib.dptr(row), _lib.dptr(col), _lib.dptr(val), nnz, n_rows, n_cols, int(coalesce),
                                 _lib.dptr(rowptr), _lib.dptr(col_out), _lib.dptr(val_out), _lib.dptr(perm),
                                 _lib.dptr(meta[0:1]), _lib.dptr(meta[1:2]), _lib.dptr(ws), _lib.cur_stream(device)),

@@ -176,7 +176,7 @@ class FusedNCLStep:
         # ---- BPR + the three squared norms of l2_reg_loss (ncl.py:314-317,116-123) ----
         dldx = torch.empty(max(bsz, 1), dtype=torch.float32, device=dev)
         sums = torch.zeros(5, dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.gcr_bpr_workspace_floats(bsz)), dtype=torch.float32, device=dev)
+        ws = _lib.workspace("gcr_bpr_workspace_floats", bsz, device=dev)
         _lib.check(L.gcr_bpr_fwd_f32(_lib.dptr(fu), _lib.dptr(fi), d, _lib.dptr(user_idx), _lib.dptr(pos_idx), _lib.dptr(neg_idx),
                                      bsz, 1, Fn.BPR_NCL, n_u, n_i, _lib.dptr(dldx), _lib.dptr(sums), _lib.dptr(ws), stream),
                    "gcr_bpr_fwd_f32")
