@@ -9,12 +9,14 @@ import ctypes
 import os
 from ctypes import c_char_p, c_double, c_float, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
+import numpy as np
 import torch
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libgcr.so")
 
 _P = c_void_p  # every device / host buffer crosses the ABI as a plain pointer
+_Tensor = torch.Tensor
 
 # name -> (restype, argtypes); mirrors include/gcr.h one to one
 SIGNATURES = {
@@ -163,25 +165,65 @@ SIGNATURES = {
 }
 
 _lib = None
+_exports = {}   # name -> (converter without a stream, converter with one, is the return a status code): `call`'s table
+
+# int32 is libgcr's status code, except for these exports, whose int32 is the answer
+INT32_ANSWERS = ("gcr_version", "gcr_infonce_engine", "gcr_infonce_fwd_o_supported", "gcr_channel_mix_supported",
+                 "gcr_mim_supported", "gcr_bce_fwd_o_supported", "gcr_rank_fused_supported", "gcr_tri_supported",
+                 "gcr_buir_supported", "gcr_bt_supported")
 
 
 class GcrError(RuntimeError):
     pass
 
 
+def _converter(name, argtypes, with_stream):
+    """One export's argument converter, `name(a0, a1, ...[, stream]) -> tuple`, as straight-line code generated from its
+    argtypes when the library loads (the last slot is the stream's, passed through, when with_stream).  A loop over the
+    kinds at every call does the same and costs about 1 us more on a 19-argument launch (EXPERIMENTS.md)."""
+    n = len(argtypes) - with_stream
+    names = [f"a{i}" for i in range(n)]
+    src = [f"def {name}({', '.join(names + ['stream'] * with_stream)}):"]
+    for i, a in enumerate(names):
+        if argtypes[i] is _P:
+            src += [f"    if {a} is not None:",
+                    f"        if isinstance({a}, Tensor):",
+                    f"            if not {a}.is_contiguous():",
+                    "                raise GcrError('libgcr needs contiguous tensors')",
+                    f"            {a} = {a}.data_ptr()",
+                    "        else:",
+                    f"            {a} = other_pointer('{name}', {i}, {a})"]
+        else:
+            src += [f"    if isinstance({a}, Tensor):",
+                    f"        raise TypeError('{name}: argument {i} is a number, got a tensor')"]
+    src.append(f"    return ({''.join(x + ', ' for x in names + ['stream'] * with_stream)})")
+    scope = {"Tensor": torch.Tensor, "GcrError": GcrError, "other_pointer": _other_pointer}
+    exec("\n".join(src), scope)
+    return scope[name]
+
+
+def _bind(handle, signatures):
+    """Resolves every export and sets its ctypes prototype (from here on the handle holds the function as a plain
+    attribute) and builds `call`'s table, once per load."""
+    exports = {}
+    for name, (res, args) in signatures.items():
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = res, args
+        plain = _converter(name, args, False)
+        exports[name] = (plain, _converter(name, args, True) if args else plain, res is c_int32 and name not in INT32_ANSWERS)
+    return exports
+
+
 def lib():
     """Loads libgcr.so once; raises loudly when the HIP extension has not been built."""
-    global _lib
+    global _lib, _exports
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise GcrError(
                 f"{LIB_PATH} is missing: the HIP extension is not built "
                 "(run `python -c 'import __graft_entry__ as g; g.build()'`); there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
+        _lib, _exports = handle, _bind(handle, SIGNATURES)
     return _lib
 
 
@@ -201,6 +243,45 @@ def dptr(t):
     return c_void_p(t.data_ptr())
 
 
+def _other_pointer(name, pos, a):
+    """The pointer kinds `call` meets rarely: a C-contiguous numpy array as its host address (the _host planners), or a
+    c_void_p as it is.  Anything else, a plain int included, is refused."""
+    if isinstance(a, np.ndarray):
+        if not a.flags.c_contiguous:
+            raise GcrError("libgcr needs contiguous tensors")
+        return a.ctypes.data
+    if isinstance(a, c_void_p):
+        return a
+    raise TypeError(f"{name}: argument {pos} is a pointer (a tensor, a numpy array, a c_void_p or None), got {type(a).__name__}")
+
+
+def call(name, *args, on=None):
+    """The one way the package calls an export of libgcr.so: `name` with `args` converted by the kinds of SIGNATURES[name].
+
+    A pointer slot takes a contiguous tensor (its data_ptr()), None (NULL), a C-contiguous numpy array (its host address) or
+    a c_void_p, and refuses a plain int; a numeric slot takes Python and numpy scalars and refuses a tensor.  `on` names the
+    stream, which every launch takes as its last argument: a tensor or a device stands for the current stream of that
+    device, a pointer from `cur_stream` goes in as it is (loops fetch it once), None appends nothing (host planners, size
+    and _supported queries).  A wrong argument count is the converter's own TypeError, before the function is entered.  A
+    status return other than 0 raises GcrError under the export's name; any other return (sizes and INT32_ANSWERS) is handed
+    back."""
+    try:
+        plain, streamed, status = _exports[name]
+    except KeyError:
+        lib()                                    # first call: load and bind (an unknown name is a KeyError again)
+        plain, streamed, status = _exports[name]
+    if on is None:
+        conv = plain(*args)
+    else:
+        conv = streamed(*args, on if isinstance(on, c_void_p) else cur_stream(on.device if isinstance(on, _Tensor) else on))
+    rc = getattr(_lib, name)(*conv)          # the attribute `_bind` resolved; a test may have put a spy in its place
+    if status:
+        if rc != 0:
+            check(rc, name)
+        return None
+    return rc
+
+
 _SIZE_UNIT = {"_bytes": 1, "_floats": 4, "_words": 4}     # what a size export counts, by its name's ending
 
 
@@ -210,7 +291,7 @@ def workspace(query, *args, device, dtype=torch.float32):
     element, so that a query answering 0 (an empty or unsupported problem, which the entry point refuses itself) still
     yields a pointer."""
     unit = next(u for ending, u in _SIZE_UNIT.items() if query.endswith(ending))
-    nbytes = int(getattr(lib(), query)(*args)) * unit
+    nbytes = int(call(query, *args)) * unit
     item = torch.empty((), dtype=dtype).element_size()
     return torch.empty(max(-(-nbytes // item), 1), dtype=dtype, device=device)
 

@@ -389,17 +389,12 @@ class _ShardedSymInfoNCE(torch.autograd.Function):
         lse12_f, lse21_f = ctx.gather(lse12), ctx.gather(lse21)
         ga = Fn._infonce_bwd_raw(a, sa, b_f, sb_f, inv_tau, lse12, w_local, lse21_f, w_full, False, eng)
         gb = Fn._infonce_bwd_raw(b, sb, a_f, sa_f, inv_tau, lse21, w_local, lse12_f, w_full, False, eng)
-        L = _lib.lib()
         stream = _lib.cur_stream(a.device)
-        _lib.check(L.gcr_infonce_pos_bwd_f32(_lib.dptr(a), _lib.dptr(sa), _lib.dptr(b), _lib.dptr(sb), _lib.dptr(idx),
-                                             _lib.dptr((-2.0 * w_local).contiguous()), m_local, m_local, a.shape[1],
-                                             float(inv_tau), _lib.dptr(ga), _lib.dptr(gb), stream), "gcr_infonce_pos_bwd_f32")
+        _lib.call("gcr_infonce_pos_bwd_f32", a, sa, b, sb, idx, (-2.0 * w_local).contiguous(), m_local, m_local, a.shape[1],
+                  inv_tau, ga, gb, on=stream)
         for x, sc, gx in ((a, sa, ga), (b, sb, gb)):
-            _lib.check(L.gcr_normalize_bwd_f32(_lib.dptr(x), _lib.dptr(sc), _lib.dptr(gx), x.shape[0], x.shape[1],
-                                               _lib.dptr(gx), stream), "gcr_normalize_bwd_f32")
-        if ga.shape[1] != ctx.d:
-            ga, gb = ga[:, :ctx.d].contiguous(), gb[:, :ctx.d].contiguous()
-        return ga, gb, None, None
+            _lib.call("gcr_normalize_bwd_f32", x, sc, gx, x.shape[0], x.shape[1], gx, on=stream)
+        return Fn._unpad(ga, ctx.d), Fn._unpad(gb, ctx.d), None, None
 
 
 def sharded_info_nce_loss(z1_local, z2_local, temp=0.2, group=None, stats_fn=None):

@@ -58,7 +58,6 @@ def dense_ids_device(keys, device, order="sorted"):
     """(dense int64 [n] on the device, first_pos int64 [m] on the host) of the records' uint64 keys [n, W]:
     gcr_dense_ids_u64; ids wider than one word are folded word by word through their sorted ranks."""
     from . import _lib
-    L = _lib.lib()
     n, words = keys.shape
     dev = torch.device(device)
     ws = _lib.workspace("gcr_dense_ids_workspace_bytes", n, device=dev, dtype=torch.uint8)
@@ -67,8 +66,7 @@ def dense_ids_device(keys, device, order="sorted"):
     def call(k, mode):
         dense = torch.empty(n, dtype=torch.int64, device=dev)
         first = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        _lib.check(L.gcr_dense_ids_u64(_lib.dptr(k), n, mode, _lib.dptr(dense), _lib.dptr(first), _lib.dptr(n_unique),
-                                       _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_dense_ids_u64")
+        _lib.call("gcr_dense_ids_u64", k, n, mode, dense, first, n_unique, ws, on=dev)
         return dense, first
 
     mode = {"sorted": 0, "first_seen": 1}[order]

@@ -21,7 +21,7 @@ FUSED_RANK = True
 FUSED_CHUNK_USERS = 16384          # 48 KB of workspace per user (sample scores + candidate regions)
 
 
-def _rank_two_call(L, ue, ie, user_ids, user_rowptr, user_items_sorted, top_n, top_items, top_scores, chunk_bytes):
+def _rank_two_call(ue, ie, user_ids, user_rowptr, user_items_sorted, top_n, top_items, top_scores, chunk_bytes):
     """[chunk, I] scores at a time through gcr_score_rows_f32 + gcr_topk_masked_f32."""
     dev = ue.device
     q, n_items, d = user_ids.numel(), ie.shape[0], ue.shape[1]
@@ -31,12 +31,9 @@ def _rank_two_call(L, ue, ie, user_ids, user_rowptr, user_items_sorted, top_n, t
     for s in range(0, q, chunk):
         ids = user_ids[s:s + chunk]
         n = ids.numel()
-        _lib.check(L.gcr_score_rows_f32(_lib.dptr(ue), _lib.dptr(ids), n, ue.shape[0], _lib.dptr(ie), n_items, d,
-                                        _lib.dptr(scores), stream), "gcr_score_rows_f32")
-        _lib.check(L.gcr_topk_masked_f32(_lib.dptr(scores), n, n_items, _lib.dptr(ids), ue.shape[0],
-                                         _lib.dptr(user_rowptr), _lib.dptr(user_items_sorted), int(top_n),
-                                         _lib.dptr(top_items[s:s + n]), _lib.dptr(top_scores[s:s + n]), stream),
-                   "gcr_topk_masked_f32")
+        _lib.call("gcr_score_rows_f32", ue, ids, n, ue.shape[0], ie, n_items, d, scores, on=stream)
+        _lib.call("gcr_topk_masked_f32", scores, n, n_items, ids, ue.shape[0], user_rowptr, user_items_sorted, top_n,
+                  top_items[s:s + n], top_scores[s:s + n], on=stream)
 
 
 def rank_topk(user_emb, item_emb, user_ids, user_rowptr, user_items_sorted, top_n, chunk_bytes=4 << 30):
@@ -47,15 +44,14 @@ def rank_topk(user_emb, item_emb, user_ids, user_rowptr, user_items_sorted, top_
     filter in one kernel: no U x I matrix, not even chunk-wise); a user whose candidate list overflowed or came
     up short is re-ranked through the two-call path, as are small catalogues."""
     _lib.require_cuda(user_emb, item_emb)
-    L = _lib.lib()
     dev = user_emb.device
     ue, ie = Fn._pad_dim(user_emb.detach()).contiguous(), Fn._pad_dim(item_emb.detach()).contiguous()
     user_ids = torch.as_tensor(user_ids, device=dev, dtype=torch.int64).contiguous()
     q, n_items, d = user_ids.numel(), ie.shape[0], ue.shape[1]
     top_items = torch.empty(q, top_n, dtype=torch.int64, device=dev)
     top_scores = torch.empty(q, top_n, dtype=torch.float32, device=dev)
-    if not (FUSED_RANK and q > 0 and L.gcr_rank_fused_supported(n_items, d, int(top_n))):
-        _rank_two_call(L, ue, ie, user_ids, user_rowptr, user_items_sorted, top_n, top_items, top_scores, chunk_bytes)
+    if not (FUSED_RANK and q > 0 and _lib.call("gcr_rank_fused_supported", n_items, d, top_n)):
+        _rank_two_call(ue, ie, user_ids, user_rowptr, user_items_sorted, top_n, top_items, top_scores, chunk_bytes)
         return top_items, top_scores
     chunk = min(q, FUSED_CHUNK_USERS)
     ws = _lib.workspace("gcr_rank_fused_workspace_bytes", chunk, device=dev, dtype=torch.uint8)
@@ -63,15 +59,13 @@ def rank_topk(user_emb, item_emb, user_ids, user_rowptr, user_items_sorted, top_
     stream = _lib.cur_stream(dev)
     for s in range(0, q, chunk):
         n = min(chunk, q - s)
-        _lib.check(L.gcr_rank_fused_f32(_lib.dptr(ue), _lib.dptr(user_ids[s:s + n]), n, ue.shape[0], _lib.dptr(ie), n_items,
-                                        d, _lib.dptr(user_rowptr), _lib.dptr(user_items_sorted), int(top_n),
-                                        _lib.dptr(top_items[s:s + n]), _lib.dptr(top_scores[s:s + n]),
-                                        _lib.dptr(status[s:s + n]), _lib.dptr(ws), stream), "gcr_rank_fused_f32")
+        _lib.call("gcr_rank_fused_f32", ue, user_ids[s:s + n], n, ue.shape[0], ie, n_items, d, user_rowptr, user_items_sorted,
+                  top_n, top_items[s:s + n], top_scores[s:s + n], status[s:s + n], ws, on=stream)
     redo = torch.nonzero(status).flatten()
     if redo.numel():
         ti = torch.empty(redo.numel(), top_n, dtype=torch.int64, device=dev)
         ts = torch.empty(redo.numel(), top_n, dtype=torch.float32, device=dev)
-        _rank_two_call(L, ue, ie, user_ids[redo].contiguous(), user_rowptr, user_items_sorted, top_n, ti, ts, chunk_bytes)
+        _rank_two_call(ue, ie, user_ids[redo].contiguous(), user_rowptr, user_items_sorted, top_n, ti, ts, chunk_bytes)
         top_items[redo], top_scores[redo] = ti, ts
     return top_items, top_scores
 
@@ -93,7 +87,6 @@ def rank_metric_terms(top_items, test_rowptr, test_items_sorted, cutoffs):
     """The per-user terms behind every metric definition, on the device (gcr_rank_metrics): returns (cut-offs int32 [C],
     ascending; hits int32 [Q, C]; DCG float64 [Q, C]; IDCG float64 [Q, C]).  Row q counts the distinct test items of
     query row q among its first n ranked items (-1 = padding) and sums 1 / log2(p + 2) over the hit positions p."""
-    L = _lib.lib()
     dev = top_items.device
     q, k = top_items.shape
     cut = torch.tensor(sorted(int(n) for n in cutoffs), dtype=torch.int32, device=dev)
@@ -103,9 +96,7 @@ def rank_metric_terms(top_items, test_rowptr, test_items_sorted, cutoffs):
     idcg = torch.empty(q, nc, dtype=torch.float64, device=dev)
     test_rowptr = torch.as_tensor(test_rowptr, device=dev, dtype=torch.int64).contiguous()
     test_items_sorted = torch.as_tensor(test_items_sorted, device=dev, dtype=torch.int32).contiguous()
-    _lib.check(L.gcr_rank_metrics(_lib.dptr(top_items.contiguous()), q, k, _lib.dptr(test_rowptr), _lib.dptr(test_items_sorted),
-                                  _lib.dptr(cut), nc, _lib.dptr(hits), _lib.dptr(dcg), _lib.dptr(idcg), _lib.cur_stream(dev)),
-               "gcr_rank_metrics")
+    _lib.call("gcr_rank_metrics", top_items.contiguous(), q, k, test_rowptr, test_items_sorted, cut, nc, hits, dcg, idcg, on=dev)
     return cut, hits, dcg, idcg
 
 

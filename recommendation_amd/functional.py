@@ -29,8 +29,21 @@ def _check_dense(x, n_rows, name):
 
 def _plan_head(graph, plan):
     """The eight arguments every SpMM entry point of gcr.h starts with: a launch plan and the CSR it partitions."""
-    return (_lib.dptr(plan.desc), plan.n_parts, _lib.dptr(plan.long_row), _lib.dptr(plan.long_slot0), plan.n_long,
-            _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val))
+    return (plan.desc, plan.n_parts, plan.long_row, plan.long_slot0, plan.n_long, graph.rowptr, graph.col, graph.val)
+
+
+def _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, **outputs):
+    """What every raw SpMM launch asks of its caller-allocated buffers: each output that is given contiguous float32
+    [n_rows, d], keep_bits an int32 bitmap over the non-zeros, inv_norm_out float32 [n_rows]."""
+    for nm, t in outputs.items():
+        if t is not None:
+            _check_dense(t, graph.n_rows, nm)
+            if t.shape[1] != d or not t.is_contiguous():
+                raise ValueError(f"{nm} must be contiguous [{graph.n_rows}, {d}]")
+    if keep_bits is not None and (keep_bits.dtype != torch.int32 or keep_bits.numel() * 32 < graph.nnz):
+        raise ValueError("keep_bits must be an int32 bitmap with >= nnz bits")
+    if inv_norm_out is not None and (inv_norm_out.dtype != torch.float32 or inv_norm_out.numel() != graph.n_rows):
+        raise ValueError("inv_norm_out must be float32 [n_rows]")
 
 
 def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scale=1.0, val_scale=1.0,
@@ -46,19 +59,11 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
     x = x.contiguous()
     _check_dense(x, graph.n_cols, "x")
     d = x.shape[1]
-    for t, nm in ((y, "y"), (acc_in, "acc_in"), (acc_out, "acc_out"), (acc_in2, "acc_in2")):
-        if t is not None:
-            _check_dense(t, graph.n_rows, nm)
-            if t.shape[1] != d or not t.is_contiguous():
-                raise ValueError(f"{nm} must be contiguous [{graph.n_rows}, {d}]")
     if y is None and acc_out is None:
         raise ValueError("need y and/or acc_out")
     if acc_in2 is not None and acc_out is None:
         raise ValueError("acc_in2 needs acc_out")
-    if keep_bits is not None and (keep_bits.dtype != torch.int32 or keep_bits.numel() * 32 < graph.nnz):
-        raise ValueError("keep_bits must be an int32 bitmap with >= nnz bits")
-    if inv_norm_out is not None and (inv_norm_out.dtype != torch.float32 or inv_norm_out.numel() != graph.n_rows):
-        raise ValueError("inv_norm_out must be float32 [n_rows]")
+    _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, y=y, acc_in=acc_in, acc_out=acc_out, acc_in2=acc_in2)
     p = graph.plan
     ws = graph.workspace(d)
     sink = EVENT_SINK
@@ -67,37 +72,30 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
         ev0.record()
     # plain launches: no mask (a predicate per stored non-zero of the classic order), no second addend, no row normalise
     plain = keep_bits is None and col_active_bits is None and acc_in2 is None and not l2norm and inv_norm_out is None
-    L, stream = _lib.lib(), _lib.cur_stream(x.device)
+    stream = _lib.cur_stream(x.device)
     # the heaviest rows by column window (graph.HubPlan): plain launches only
     hub = graph.hub if plain and graph.hub is not None and graph.hub.eligible(d) else None
     if hub is not None and d <= WINDOWED_MAX_D:
         # both walks in one grid, both plans' split rows in another, then the hub reduction: the words of the branch below
         H = hub.H
-        _lib.check(L.gcr_spmm_windowed_f32(
-            *_plan_head(H, H.plan), _lib.dptr(H.workspace(d)), *_plan_head(graph, hub.main), _lib.dptr(ws),
-            _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(hub.partials(d)), _lib.dptr(x), d, float(val_scale),
-            _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), int(hub.main_first), graph.n_rows,
-            graph.n_cols, stream), "gcr_spmm_windowed_f32")
+        _lib.call("gcr_spmm_windowed_f32", *_plan_head(H, H.plan), H.workspace(d), *_plan_head(graph, hub.main), ws,
+                  hub.hub_row, hub.n_hub, hub.n_windows, hub.partials(d), x, d, val_scale, y, acc_in, acc_out, acc_scale,
+                  hub.main_first, graph.n_rows, graph.n_cols, on=stream)
     else:
         if hub is not None:               # d > 64: the companion through the generic kernel, the reduction, then `main`
             H, part = hub.H, hub.partials(d)
-            _lib.check(L.gcr_spmm_csr_acc2_f32(
-                *_plan_head(H, H.plan), None, 1.0, _lib.dptr(x), d, _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None,
-                _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
-            _lib.check(L.gcr_spmm_hub_reduce_f32(
-                _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, float(val_scale), _lib.dptr(y),
-                _lib.dptr(acc_in), _lib.dptr(acc_out), float(acc_scale), graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
+            _lib.call("gcr_spmm_csr_acc2_f32", *_plan_head(H, H.plan), None, 1.0, x, d, part, None, None, 0.0, None, 1.0, 0,
+                      None, H.workspace(d), H.n_rows, H.n_cols, None, on=stream)
+            _lib.call("gcr_spmm_hub_reduce_f32", hub.hub_row, hub.n_hub, hub.n_windows, part, d, val_scale, y, acc_in, acc_out,
+                      acc_scale, graph.n_rows, on=stream)
             p = hub.main                  # every other row: the classic walk with the hub rows skipped
         if plain and d <= ROWS_MAX_D:     # the plain launch's own kernel: the same words on another schedule
-            _lib.check(L.gcr_spmm_rows_f32(
-                *_plan_head(graph, p), float(val_scale), _lib.dptr(x), d, _lib.dptr(y), _lib.dptr(acc_in), _lib.dptr(acc_out),
-                float(acc_scale), _lib.dptr(ws), graph.n_rows, graph.n_cols, stream), "gcr_spmm_rows_f32")
+            _lib.call("gcr_spmm_rows_f32", *_plan_head(graph, p), val_scale, x, d, y, acc_in, acc_out, acc_scale, ws,
+                      graph.n_rows, graph.n_cols, on=stream)
         else:
-            _lib.check(L.gcr_spmm_csr_acc2_f32(
-                *_plan_head(graph, p), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y),
-                _lib.dptr(acc_in), _lib.dptr(acc_in2), float(acc_in2_scale), _lib.dptr(acc_out), float(acc_scale),
-                SPMM_ROW_L2NORM if l2norm else 0, _lib.dptr(inv_norm_out), _lib.dptr(ws), graph.n_rows, graph.n_cols,
-                _lib.dptr(col_active_bits), stream), "gcr_spmm_csr_acc2_f32")
+            _lib.call("gcr_spmm_csr_acc2_f32", *_plan_head(graph, p), keep_bits, val_scale, x, d, y, acc_in, acc_in2,
+                      acc_in2_scale, acc_out, acc_scale, SPMM_ROW_L2NORM if l2norm else 0, inv_norm_out, ws, graph.n_rows,
+                      graph.n_cols, col_active_bits, on=stream)
     if sink is not None:
         ev1.record()
         sink.append((ev0, ev1))
@@ -110,9 +108,23 @@ def active_rows_bitmap(idx, n_rows):
     idx = _as_index(idx, idx.device if isinstance(idx, torch.Tensor) else None).reshape(-1)
     _lib.require_cuda(idx)
     bits = torch.zeros((int(n_rows) + 31) // 32, dtype=torch.int32, device=idx.device)
-    _lib.check(_lib.lib().gcr_bitmap_set(_lib.dptr(idx), idx.numel(), int(n_rows), _lib.dptr(bits), _lib.cur_stream(idx.device)),
-               "gcr_bitmap_set")
+    _lib.call("gcr_bitmap_set", idx, idx.numel(), n_rows, bits, on=idx)
     return bits
+
+
+def _spmm_t(graph, dz, **mask):
+    """A^T dz into a fresh [n_cols, d] tensor: the product every SpMM backward ends with (`mask`: the launch's keep_bits in
+    A^T's non-zero order and val_scale)."""
+    gt = graph.t
+    dx = torch.empty(gt.n_rows, dz.shape[1], dtype=torch.float32, device=dz.device)
+    return spmm_into(gt, dz.contiguous(), y=dx, **mask)
+
+
+def _need_mask_t(x, or_else=""):
+    """The rule of every masked product: a gradient through it needs the mask in A^T's non-zero order."""
+    if x.requires_grad and torch.is_grad_enabled():
+        raise ValueError("backward through a masked graph needs keep_bits_t (the mask in A^T's non-zero order); "
+                         "for a symmetric graph build it with graph.mirror_perm()" + or_else)
 
 
 class _SpMM(torch.autograd.Function):
@@ -124,10 +136,7 @@ class _SpMM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        gt = ctx.graph.t
-        dx = torch.empty(gt.n_rows, dy.shape[1], dtype=torch.float32, device=dy.device)
-        spmm_into(gt, dy.contiguous(), y=dx, keep_bits=ctx.keep_bits_t, val_scale=ctx.val_scale)
-        return dx, None, None, None, None
+        return _spmm_t(ctx.graph, dy, keep_bits=ctx.keep_bits_t, val_scale=ctx.val_scale), None, None, None, None
 
 
 def spmm(graph: CsrGraph, x, keep_bits=None, keep_bits_t=None, val_scale=1.0, mask_symmetric=False):
@@ -144,10 +153,8 @@ def spmm(graph: CsrGraph, x, keep_bits=None, keep_bits_t=None, val_scale=1.0, ma
     if keep_bits is not None and keep_bits_t is None:
         if mask_symmetric and graph.symmetric:
             keep_bits_t = keep_bits
-        elif x.requires_grad and torch.is_grad_enabled():
-            raise ValueError("backward through a masked graph needs keep_bits_t (the mask in A^T's non-zero order); "
-                             "for a symmetric graph build it with graph.mirror_perm(), or pass mask_symmetric=True "
-                             "if the mask itself is symmetric")
+        else:
+            _need_mask_t(x, ", or pass mask_symmetric=True if the mask itself is symmetric")
     return _SpMM.apply(x, graph, keep_bits, keep_bits_t, float(val_scale))
 
 
@@ -246,9 +253,8 @@ def lightgcn_propagate(graph: CsrGraph, x0, n_layers: int, combine: str = "mean"
     if keep_bits is None:
         if keep_bits_t is not None:
             raise ValueError("keep_bits_t without keep_bits")
-    elif keep_bits_t is None and x0.requires_grad and torch.is_grad_enabled():
-        raise ValueError("backward through a masked graph needs keep_bits_t (the mask in A^T's non-zero order); "
-                         "for a symmetric graph build it with graph.mirror_perm()")
+    elif keep_bits_t is None:
+        _need_mask_t(x0)
     out = _Propagate.apply(x0, graph, int(n_layers), scale, bool(return_layers), keep_bits, keep_bits_t, float(val_scale))
     if return_layers:
         return out[0], [x0, *out[1:]]
@@ -268,9 +274,7 @@ def normalize_bwd_n(nrm, inv, g_n, g_raw=None, out=None, from_raw=False):
     rows, d = nrm.shape
     if g_n.shape != nrm.shape or out.shape != nrm.shape or (g_raw is not None and g_raw.shape != nrm.shape) or d % 4 or d > 256:
         raise ValueError("normalize_bwd_n: [rows, d] float32 tensors of one shape, d a multiple of 4 and <= 256")
-    fn = _lib.lib().gcr_normalize_bwd_raw_f32 if from_raw else _lib.lib().gcr_normalize_bwd_n_f32
-    _lib.check(fn(_lib.dptr(nrm), _lib.dptr(inv), _lib.dptr(g_n), _lib.dptr(g_raw), rows, d, _lib.dptr(out),
-                  _lib.cur_stream(nrm.device)), "gcr_normalize_bwd_raw_f32" if from_raw else "gcr_normalize_bwd_n_f32")
+    _lib.call("gcr_normalize_bwd_raw_f32" if from_raw else "gcr_normalize_bwd_n_f32", nrm, inv, g_n, g_raw, rows, d, out, on=nrm)
     return out
 
 
@@ -286,11 +290,9 @@ def gram_tn(x, g):
     dg = g.shape[1]
     if dx not in _GRAM_DIMS or dg not in _GRAM_DIMS or g.shape[0] != n:
         return x.t() @ g
-    L = _lib.lib()
     out = torch.empty(dx, dg, dtype=torch.float32, device=x.device)
     ws = _lib.workspace("gcr_gram_tn_workspace_bytes", n, dx, dg, device=x.device)
-    _lib.check(L.gcr_gram_tn_f32(_lib.dptr(x), _lib.dptr(g), n, dx, dg, _lib.dptr(out), _lib.dptr(ws), _lib.cur_stream(x.device)),
-               "gcr_gram_tn_f32")
+    _lib.call("gcr_gram_tn_f32", x, g, n, dx, dg, out, ws, on=x)
     return out
 
 
@@ -328,8 +330,7 @@ class _RowsDotVec(torch.autograd.Function):
         ctx.save_for_backward(em, v)
         v = v.contiguous()
         out = torch.empty(em.shape[0], dtype=torch.float32, device=em.device)
-        _lib.check(_lib.lib().gcr_rows_dot_vec_f32(_lib.dptr(em), _lib.dptr(v), em.shape[0], em.shape[1], _lib.dptr(out),
-                                                   _lib.cur_stream(em.device)), "gcr_rows_dot_vec_f32")
+        _lib.call("gcr_rows_dot_vec_f32", em, v, em.shape[0], em.shape[1], out, on=em)
         return out
 
     @staticmethod
@@ -339,12 +340,10 @@ class _RowsDotVec(torch.autograd.Function):
         gem = torch.outer(g, v) if ctx.needs_input_grad[0] else None
         gv = None
         if ctx.needs_input_grad[1]:
-            L = _lib.lib()
             n, d = em.shape
             gv = torch.empty(d, dtype=torch.float32, device=em.device)
             ws = _lib.workspace("gcr_weighted_colsum_workspace_bytes", n, d, device=em.device)
-            _lib.check(L.gcr_weighted_colsum_f32(_lib.dptr(em), _lib.dptr(g), n, d, _lib.dptr(gv), _lib.dptr(ws),
-                                                 _lib.cur_stream(em.device)), "gcr_weighted_colsum_f32")
+            _lib.call("gcr_weighted_colsum_f32", em, g, n, d, gv, ws, on=em)
         return gem, gv
 
 
@@ -365,8 +364,7 @@ class _Gate(torch.autograd.Function):
         b = None if bias is None else bias.reshape(-1).contiguous()
         out = torch.empty_like(em)
         n, d = em.shape
-        _lib.check(_lib.lib().gcr_gate_fwd_f32(_lib.dptr(em), _lib.dptr(z), _lib.dptr(b), n, d, _lib.dptr(out),
-                                               _lib.cur_stream(em.device)), "gcr_gate_fwd_f32")
+        _lib.call("gcr_gate_fwd_f32", em, z, b, n, d, out, on=em)
         ctx.save_for_backward(em, z, b)
         ctx.bias_shape = None if bias is None else bias.shape
         return out
@@ -374,15 +372,12 @@ class _Gate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         em, z, b = ctx.saved_tensors
-        L = _lib.lib()
         n, d = em.shape
         g = g.contiguous()
         d_em, d_z = torch.empty_like(em), torch.empty_like(z)
         d_b = torch.empty(d, dtype=torch.float32, device=em.device)
         ws = _lib.workspace("gcr_gate_bwd_workspace_bytes", n, d, device=em.device)
-        _lib.check(L.gcr_gate_bwd_f32(_lib.dptr(g), _lib.dptr(em), _lib.dptr(z), _lib.dptr(b), n, d, _lib.dptr(d_em),
-                                      _lib.dptr(d_z), _lib.dptr(d_b), _lib.dptr(ws), _lib.cur_stream(em.device)),
-                   "gcr_gate_bwd_f32")
+        _lib.call("gcr_gate_bwd_f32", g, em, z, b, n, d, d_em, d_z, d_b, ws, on=em)
         return d_em, d_z, (None if ctx.bias_shape is None else d_b.reshape(ctx.bias_shape))
 
 
@@ -400,15 +395,12 @@ class _ChannelMix(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, e1, e2, e3, v, extra, extra_scale):
-        L = _lib.lib()
         e1, e2, e3, v = e1.contiguous(), e2.contiguous(), e3.contiguous(), v.contiguous()
         ex = None if extra is None else extra.contiguous()
         n, d = e1.shape
         mixed = torch.empty_like(e1)
         score = torch.empty(3, n, dtype=torch.float32, device=e1.device)
-        _lib.check(L.gcr_channel_mix_fwd_f32(_lib.dptr(e1), _lib.dptr(e2), _lib.dptr(e3), _lib.dptr(v), _lib.dptr(ex),
-                                             float(extra_scale), n, d, _lib.dptr(mixed), _lib.dptr(score),
-                                             _lib.cur_stream(e1.device)), "gcr_channel_mix_fwd_f32")
+        _lib.call("gcr_channel_mix_fwd_f32", e1, e2, e3, v, ex, extra_scale, n, d, mixed, score, on=e1)
         ctx.save_for_backward(e1, e2, e3, v, score)
         ctx.extra_scale, ctx.has_extra = float(extra_scale), extra is not None
         ctx.mark_non_differentiable(score)
@@ -417,17 +409,13 @@ class _ChannelMix(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_score):
         e1, e2, e3, v, score = ctx.saved_tensors
-        L = _lib.lib()
         n, d = e1.shape
         g = g.contiguous()
         d1, d2, d3 = torch.empty_like(e1), torch.empty_like(e1), torch.empty_like(e1)
         dx = torch.empty_like(e1) if ctx.has_extra else None
         dv = torch.empty(d, dtype=torch.float32, device=e1.device)
         ws = _lib.workspace("gcr_channel_mix_bwd_workspace_bytes", n, d, device=e1.device)
-        _lib.check(L.gcr_channel_mix_bwd_f32(_lib.dptr(g), _lib.dptr(e1), _lib.dptr(e2), _lib.dptr(e3), _lib.dptr(v),
-                                             _lib.dptr(score), ctx.extra_scale, n, d, _lib.dptr(d1), _lib.dptr(d2),
-                                             _lib.dptr(d3), _lib.dptr(dx), _lib.dptr(dv), _lib.dptr(ws),
-                                             _lib.cur_stream(e1.device)), "gcr_channel_mix_bwd_f32")
+        _lib.call("gcr_channel_mix_bwd_f32", g, e1, e2, e3, v, score, ctx.extra_scale, n, d, d1, d2, d3, dx, dv, ws, on=e1)
         return d1, d2, d3, dv, dx, None
 
 
@@ -437,7 +425,7 @@ def channel_mix(e1, e2, e3, v, extra=None, extra_scale=0.0):
     (+ extra_scale * extra).  Widths other than 32 / 64 / 128 / 256 and CPU tensors take the torch expression."""
     fused = e1.is_cuda and e1.dim() == 2 and e1.dtype == torch.float32 and e2.shape == e1.shape and e3.shape == e1.shape \
         and v.dim() == 1 and v.numel() == e1.shape[1] and (extra is None or extra.shape == e1.shape) \
-        and bool(_lib.lib().gcr_channel_mix_supported(e1.shape[1]))
+        and bool(_lib.call("gcr_channel_mix_supported", e1.shape[1]))
     if not fused:
         logits = torch.stack([rows_dot_vec(e, v) for e in (e1, e2, e3)])
         score = torch.softmax(logits, dim=0)
@@ -452,7 +440,6 @@ class _MimLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, em, edge, p0, p1, p2):
-        L = _lib.lib()
         em, edge = em.contiguous(), edge.contiguous()
         n, d = em.shape
         dev = em.device
@@ -460,29 +447,24 @@ class _MimLoss(torch.autograd.Function):
         coef = torch.empty(3, n, dtype=torch.float32, device=dev)
         gvec = torch.empty(2, d, dtype=torch.float32, device=dev)
         ws = _lib.workspace("gcr_mim_workspace_bytes", n, d, device=dev, dtype=torch.float64)
-        _lib.check(L.gcr_mim_fwd_f32(_lib.dptr(em), _lib.dptr(edge), _lib.dptr(p0), _lib.dptr(p1), _lib.dptr(p2), n, d,
-                                     _lib.dptr(loss), _lib.dptr(coef), _lib.dptr(gvec), _lib.dptr(ws), _lib.cur_stream(dev)),
-                   "gcr_mim_fwd_f32")
+        _lib.call("gcr_mim_fwd_f32", em, edge, p0, p1, p2, n, d, loss, coef, gvec, ws, on=dev)
         ctx.save_for_backward(em, edge, p0, p1, p2, coef, gvec)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         em, edge, p0, p1, p2, coef, gvec = ctx.saved_tensors
-        L = _lib.lib()
         n, d = em.shape
         g = g.to(torch.float32).contiguous()
         d_em, d_edge = torch.empty_like(em), torch.empty_like(edge)
         ws = _lib.workspace("gcr_mim_workspace_bytes", n, d, device=em.device, dtype=torch.float64)
-        _lib.check(L.gcr_mim_bwd_f32(_lib.dptr(em), _lib.dptr(edge), _lib.dptr(p0), _lib.dptr(p1), _lib.dptr(p2), n, d,
-                                     _lib.dptr(coef), _lib.dptr(gvec), _lib.dptr(g), _lib.dptr(d_em), _lib.dptr(d_edge),
-                                     _lib.dptr(ws), _lib.cur_stream(em.device)), "gcr_mim_bwd_f32")
+        _lib.call("gcr_mim_bwd_f32", em, edge, p0, p1, p2, n, d, coef, gvec, g, d_em, d_edge, ws, on=em)
         return d_em, d_edge, None, None, None
 
 
 def mim_supported(em):
     """True when `mim_loss` runs these rows: float32 [n, d] on the GPU with d in {32, 64, 128, 256}."""
-    return bool(em.is_cuda and em.dim() == 2 and em.dtype == torch.float32 and _lib.lib().gcr_mim_supported(em.shape[1]))
+    return bool(em.is_cuda and em.dim() == 2 and em.dtype == torch.float32 and _lib.call("gcr_mim_supported", em.shape[1]))
 
 
 def mim_loss(em, edge, perms=None):
@@ -505,7 +487,7 @@ def mim_loss(em, edge, perms=None):
         for k, p in enumerate(perms):
             if p.shape != (n,) or not torch.equal(torch.sort(p).values, rows):
                 raise ValueError(f"perms[{k}] is not a permutation of the {n} rows")
-    if not _lib.lib().gcr_mim_supported(em.shape[1]):
+    if not _lib.call("gcr_mim_supported", em.shape[1]):
         raise _lib.GcrError(f"mim_loss: unsupported width {em.shape[1]} (32, 64, 128 or 256)")
     if n == 0:
         return (em.sum() + edge.sum()) * 0.0
@@ -528,11 +510,7 @@ class _NormProp(torch.autograd.Function):
     def backward(ctx, dy):
         y, inv = ctx.saved_tensors
         # d(Ax) = (dy - y <y, dy>) / max(||Ax||, eps); rows clamped by eps have inv = 1e12 and y = 0
-        dz = normalize_bwd_n(y, inv, dy)
-        gt = ctx.graph.t
-        dx = torch.empty(gt.n_rows, dy.shape[1], dtype=torch.float32, device=dy.device)
-        spmm_into(gt, dz, y=dx)
-        return dx, None
+        return _spmm_t(ctx.graph, normalize_bwd_n(y, inv, dy)), None
 
 
 def spmm_l2norm(graph: CsrGraph, x):
@@ -549,21 +527,11 @@ def spmm_dual_into(graph: CsrGraph, x, y_raw, y_norm, inv_norm_out=None, keep_bi
     x = x.contiguous()
     _check_dense(x, graph.n_cols, "x")
     d = x.shape[1]
-    for t, nm in ((y_raw, "y_raw"), (y_norm, "y_norm")):
-        _check_dense(t, graph.n_rows, nm)
-        if t.shape[1] != d or not t.is_contiguous():
-            raise ValueError(f"{nm} must be contiguous [{graph.n_rows}, {d}]")
+    _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, y_raw=y_raw, y_norm=y_norm)
     if y_raw.data_ptr() == y_norm.data_ptr():
         raise ValueError("y_raw and y_norm must be different buffers")
-    if keep_bits is not None and (keep_bits.dtype != torch.int32 or keep_bits.numel() * 32 < graph.nnz):
-        raise ValueError("keep_bits must be an int32 bitmap with >= nnz bits")
-    if inv_norm_out is not None and (inv_norm_out.dtype != torch.float32 or inv_norm_out.numel() != graph.n_rows):
-        raise ValueError("inv_norm_out must be float32 [n_rows]")
-    rc = _lib.lib().gcr_spmm_csr_dual_f32(
-        *_plan_head(graph, graph.plan), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y_raw),
-        _lib.dptr(y_norm), _lib.dptr(inv_norm_out), _lib.dptr(graph.workspace(d)), graph.n_rows, graph.n_cols,
-        _lib.cur_stream(x.device))
-    _lib.check(rc, "gcr_spmm_csr_dual_f32")
+    _lib.call("gcr_spmm_csr_dual_f32", *_plan_head(graph, graph.plan), keep_bits, val_scale, x, d, y_raw, y_norm, inv_norm_out,
+              graph.workspace(d), graph.n_rows, graph.n_cols, on=x)
     return y_raw, y_norm
 
 
@@ -574,21 +542,13 @@ def spmm_dual_acc_into(graph: CsrGraph, x, y_raw, acc_in, acc_out, inv_norm_out,
     x = x.contiguous()
     _check_dense(x, graph.n_cols, "x")
     d = x.shape[1]
-    for t, nm in ((y_raw, "y_raw"), (acc_out, "acc_out"), (acc_in, "acc_in"), (y_norm, "y_norm")):
-        if t is None:
-            continue
-        _check_dense(t, graph.n_rows, nm)
-        if t.shape[1] != d or not t.is_contiguous():
-            raise ValueError(f"{nm} must be contiguous [{graph.n_rows}, {d}]")
+    if inv_norm_out is None:
+        raise ValueError("inv_norm_out must be float32 [n_rows]")
+    _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, y_raw=y_raw, acc_out=acc_out, acc_in=acc_in, y_norm=y_norm)
     if y_raw.data_ptr() == acc_out.data_ptr() or (y_norm is not None and y_norm.data_ptr() == y_raw.data_ptr()):
         raise ValueError("y_raw, y_norm and acc_out must be different buffers")
-    if inv_norm_out is None or inv_norm_out.dtype != torch.float32 or inv_norm_out.numel() != graph.n_rows:
-        raise ValueError("inv_norm_out must be float32 [n_rows]")
-    rc = _lib.lib().gcr_spmm_csr_dual_acc_f32(
-        *_plan_head(graph, graph.plan), _lib.dptr(keep_bits), float(val_scale), _lib.dptr(x), d, _lib.dptr(y_raw),
-        _lib.dptr(y_norm), _lib.dptr(acc_in), _lib.dptr(acc_out), _lib.dptr(inv_norm_out), _lib.dptr(graph.workspace(d)),
-        graph.n_rows, graph.n_cols, _lib.cur_stream(x.device))
-    _lib.check(rc, "gcr_spmm_csr_dual_acc_f32")
+    _lib.call("gcr_spmm_csr_dual_acc_f32", *_plan_head(graph, graph.plan), keep_bits, val_scale, x, d, y_raw, y_norm, acc_in,
+              acc_out, inv_norm_out, graph.workspace(d), graph.n_rows, graph.n_cols, on=x)
     return y_raw, acc_out
 
 
@@ -615,10 +575,7 @@ class _NormPropDual(torch.autograd.Function):
             return None, None
         # dz = gz + (gn - n <n, gn>) / max(||z||, eps); rows clamped by eps have inv = 1e12 and n = 0
         dz = normalize_bwd_n(n, inv, gn, gz) if gn is not None else gz
-        gt = ctx.graph.t
-        dx = torch.empty(gt.n_rows, dz.shape[1], dtype=torch.float32, device=dz.device)
-        spmm_into(gt, dz.contiguous(), y=dx)
-        return dx, None
+        return _spmm_t(ctx.graph, dz), None
 
 
 def spmm_l2norm_dual(graph: CsrGraph, x):
@@ -649,10 +606,7 @@ class _NormPropDualAcc(torch.autograd.Function):
         if gz is None and gs is None:
             return None, None, None
         dz = normalize_bwd_n(z, inv, gs, gz, from_raw=True) if gs is not None else gz
-        gt = ctx.graph.t
-        dx = torch.empty(gt.n_rows, dz.shape[1], dtype=torch.float32, device=dz.device)
-        spmm_into(gt, dz.contiguous(), y=dx)
-        return dx, gs, None
+        return _spmm_t(ctx.graph, dz), gs, None
 
 
 def spmm_l2norm_dual_acc(graph: CsrGraph, x, acc):
@@ -727,13 +681,11 @@ def _sorted_order(idx, n_keys, cache=False):
     key = (idx.data_ptr(), idx.numel(), idx._version, int(n_keys))
     if cache and key in _ORDER_CACHE:
         return _ORDER_CACHE[key]
-    L = _lib.lib()
     n = idx.numel()
     keys = torch.empty(n, dtype=torch.int32, device=idx.device)
     perm = torch.empty(n, dtype=torch.int32, device=idx.device)
     ws = _lib.workspace("gcr_sort_index_workspace_bytes", n, device=idx.device, dtype=torch.uint8)
-    _lib.check(L.gcr_sort_index(_lib.dptr(idx), n, int(n_keys), _lib.dptr(keys), _lib.dptr(perm), _lib.dptr(ws),
-                                _lib.cur_stream(idx.device)), "gcr_sort_index")
+    _lib.call("gcr_sort_index", idx, n, n_keys, keys, perm, ws, on=idx)
     if cache:
         if len(_ORDER_CACHE) >= 8:
             _ORDER_CACHE.pop(next(iter(_ORDER_CACHE)))
@@ -752,26 +704,50 @@ def _halves_of_one_table(top, bot):
         and bot.data_ptr() == base.data_ptr() + top.numel() * base.element_size()
 
 
+def _table_grads(user_tab, item_tab, stacked):
+    """Zeroed gradients (gu, gi) of two tables: for the halves of one stacked table (`_halves_of_one_table`) the two row
+    blocks of ONE [U + I, d] buffer, which _SplitRows.backward hands on without a copy; else one tensor each (gi None for an
+    absent item table)."""
+    if stacked:
+        n_users = user_tab.shape[0]
+        gfull = torch.zeros(n_users + item_tab.shape[0], user_tab.shape[1], dtype=torch.float32, device=user_tab.device)
+        return gfull[:n_users], gfull[n_users:]
+    return torch.zeros_like(user_tab), None if item_tab is None else torch.zeros_like(item_tab)
+
+
+def _bpr_forward(user_tab, item_tab, u_idx, i_idx, j_idx, variant):
+    """The forward launch of both BPR nodes (gcr_bpr_fwd_f32) -> (sums [5], dL/dx per sample, n_neg)."""
+    batch, dev = u_idx.numel(), user_tab.device
+    n_neg = 1 if j_idx.dim() == 1 else j_idx.shape[1]
+    dldx = torch.empty(max(batch, 1), dtype=torch.float32, device=dev)
+    sums = torch.zeros(5, dtype=torch.float32, device=dev)
+    ws = _lib.workspace("gcr_bpr_workspace_floats", batch, device=dev)
+    _lib.call("gcr_bpr_fwd_f32", user_tab, item_tab, user_tab.shape[1], u_idx, i_idx, j_idx, batch, n_neg, variant,
+              user_tab.shape[0], item_tab.shape[0], dldx, sums, ws, on=dev)
+    return sums, dldx, n_neg
+
+
+def _bpr_neg_items(user_tab, item_tab, skey, spay, gs, gi):
+    """The negatives' item rows from the (key j, payload (user, coefficient)) pairs gcr_bpr_neg_block_f32 wrote.  They are
+    fresh every step, so their sort carries the payload with the key (gcr_sort_pairs_u64) and the scatter into gi streams
+    sorted arrays (gcr_bpr_neg_items_sorted_f32) instead of chasing perm -> sample -> (u_idx, dloss_dx)."""
+    slots, n_items = skey.numel(), item_tab.shape[0]
+    ks, ps = torch.empty_like(skey), torch.empty_like(spay)
+    ws = _lib.workspace("gcr_sort_pairs_u64_workspace_bytes", slots, device=skey.device, dtype=torch.uint8)
+    stream = _lib.cur_stream(skey.device)
+    _lib.call("gcr_sort_pairs_u64", skey, spay, slots, n_items, ks, ps, ws, on=stream)
+    _lib.call("gcr_bpr_neg_items_sorted_f32", user_tab, item_tab, user_tab.shape[1], ks, ps, slots, user_tab.shape[0], n_items,
+              gs, gi, on=stream)
+
+
 class _BprSums(torch.autograd.Function):
     """sums = [sum_b loss_b, sum|U[u]|^2, sum|I[i]|^2, sum|I[j]|^2] through gcr_bpr_fwd/bwd_f32."""
 
     @staticmethod
     def forward(ctx, user_tab, item_tab, u_idx, i_idx, j_idx, variant):
-        L = _lib.lib()
         user_tab, item_tab = user_tab.contiguous(), item_tab.contiguous()
-        batch = u_idx.numel()
-        n_neg = 1 if j_idx.dim() == 1 else j_idx.shape[1]
-        d = user_tab.shape[1]
-        dev = user_tab.device
-        dldx = torch.empty(max(batch, 1), dtype=torch.float32, device=dev)
-        sums = torch.zeros(5, dtype=torch.float32, device=dev)
-        ws = _lib.workspace("gcr_bpr_workspace_floats", batch, device=dev)
-        _lib.check(L.gcr_bpr_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
-                                     _lib.dptr(j_idx), batch, n_neg, variant, user_tab.shape[0], item_tab.shape[0],
-                                     _lib.dptr(dldx), _lib.dptr(sums), _lib.dptr(ws), _lib.cur_stream(dev)),
-                   "gcr_bpr_fwd_f32")
+        sums, dldx, ctx.n_neg = _bpr_forward(user_tab, item_tab, u_idx, i_idx, j_idx, variant)
         ctx.save_for_backward(user_tab, item_tab, u_idx, i_idx, j_idx, dldx)
-        ctx.n_neg = n_neg
         # the two tables are the halves of one stacked [N, d] table (split_rows): the backward then writes both
         # gradients into one buffer, which _SplitRows.backward hands on without a copy
         ctx.stacked = _halves_of_one_table(user_tab, item_tab)
@@ -782,48 +758,26 @@ class _BprSums(torch.autograd.Function):
     def backward(ctx, g_sums):
         user_tab, item_tab, u_idx, i_idx, j_idx, dldx = ctx.saved_tensors
         gs = g_sums.contiguous().to(torch.float32)
-        if ctx.stacked:
-            gfull = torch.zeros(user_tab.shape[0] + item_tab.shape[0], user_tab.shape[1], dtype=torch.float32,
-                                device=user_tab.device)
-            gu, gi = gfull[: user_tab.shape[0]], gfull[user_tab.shape[0]:]
-        else:
-            gu = torch.zeros_like(user_tab)
-            gi = torch.zeros_like(item_tab)
-        batch = u_idx.numel()
+        gu, gi = _table_grads(user_tab, item_tab, ctx.stacked)
+        batch, d, n_users, n_items = u_idx.numel(), user_tab.shape[1], user_tab.shape[0], item_tab.shape[0]
         if batch >= BPR_SORTED_MIN_BATCH and batch * ctx.n_neg < 2 ** 31:
-            ku, pu, _ = _sorted_order(u_idx, user_tab.shape[0], cache=True)
-            ki, pi, _ = _sorted_order(i_idx, item_tab.shape[0], cache=True)
-            L = _lib.lib()
+            ku, pu, _ = _sorted_order(u_idx, n_users, cache=True)
+            ki, pi, _ = _sorted_order(i_idx, n_items, cache=True)
             dev, stream = user_tab.device, _lib.cur_stream(user_tab.device)
-            n_users, n_items, slots = user_tab.shape[0], item_tab.shape[0], batch * ctx.n_neg
             kj = pj = None
             if not BPR_NEG_PAYLOAD_SORT:
                 kj, pj, _ = _sorted_order(j_idx.reshape(-1), n_items)             # fresh negatives every step
-            _lib.check(L.gcr_bpr_bwd_sorted_f32(
-                _lib.dptr(user_tab), _lib.dptr(item_tab), user_tab.shape[1], _lib.dptr(u_idx), _lib.dptr(i_idx),
-                _lib.dptr(j_idx), batch, ctx.n_neg, n_users, n_items, _lib.dptr(dldx),
-                _lib.dptr(gs), _lib.dptr(ku), _lib.dptr(pu), _lib.dptr(ki), _lib.dptr(pi), _lib.dptr(kj), _lib.dptr(pj),
-                _lib.dptr(gu), _lib.dptr(gi), stream), "gcr_bpr_bwd_sorted_f32")
+            _lib.call("gcr_bpr_bwd_sorted_f32", user_tab, item_tab, d, u_idx, i_idx, j_idx, batch, ctx.n_neg, n_users, n_items,
+                      dldx, gs, ku, pu, ki, pi, kj, pj, gu, gi, on=stream)
             if BPR_NEG_PAYLOAD_SORT:
-                # the negatives' item rows: fresh every step, so their sort carries (user, coefficient) with the key and the
-                # scatter streams sorted arrays (gcr_bpr_neg_items_sorted_f32) instead of gathering through a sorted index
-                skey = torch.empty(slots, dtype=torch.int32, device=dev)
-                spay = torch.empty(slots, dtype=torch.int64, device=dev)
-                _lib.check(L.gcr_bpr_neg_block_f32(_lib.dptr(dldx), _lib.dptr(j_idx), _lib.dptr(u_idx), batch, ctx.n_neg, n_items,
-                                                   _lib.dptr(gs), None, None, None, _lib.dptr(skey), _lib.dptr(spay), stream),
-                           "gcr_bpr_neg_block_f32")
-                ks, ps = torch.empty_like(skey), torch.empty_like(spay)
-                ws = _lib.workspace("gcr_sort_pairs_u64_workspace_bytes", slots, device=dev, dtype=torch.uint8)
-                _lib.check(L.gcr_sort_pairs_u64(_lib.dptr(skey), _lib.dptr(spay), slots, n_items, _lib.dptr(ks), _lib.dptr(ps),
-                                                _lib.dptr(ws), stream), "gcr_sort_pairs_u64")
-                _lib.check(L.gcr_bpr_neg_items_sorted_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), user_tab.shape[1],
-                                                          _lib.dptr(ks), _lib.dptr(ps), slots, n_users, n_items, _lib.dptr(gs),
-                                                          _lib.dptr(gi), stream), "gcr_bpr_neg_items_sorted_f32")
+                skey = torch.empty(batch * ctx.n_neg, dtype=torch.int32, device=dev)
+                spay = torch.empty(batch * ctx.n_neg, dtype=torch.int64, device=dev)
+                _lib.call("gcr_bpr_neg_block_f32", dldx, j_idx, u_idx, batch, ctx.n_neg, n_items, gs, None, None, None, skey, spay,
+                          on=stream)
+                _bpr_neg_items(user_tab, item_tab, skey, spay, gs, gi)
             return gu, gi, None, None, None, None
-        _lib.check(_lib.lib().gcr_bpr_bwd_f32(
-            _lib.dptr(user_tab), _lib.dptr(item_tab), user_tab.shape[1], _lib.dptr(u_idx), _lib.dptr(i_idx),
-            _lib.dptr(j_idx), u_idx.numel(), ctx.n_neg, user_tab.shape[0], item_tab.shape[0], _lib.dptr(dldx),
-            _lib.dptr(gs), _lib.dptr(gu), _lib.dptr(gi), _lib.cur_stream(user_tab.device)), "gcr_bpr_bwd_f32")
+        _lib.call("gcr_bpr_bwd_f32", user_tab, item_tab, d, u_idx, i_idx, j_idx, batch, ctx.n_neg, n_users, n_items, dldx, gs,
+                  gu, gi, on=user_tab)
         return gu, gi, None, None, None, None
 
 
@@ -836,21 +790,9 @@ class _BprEdgeSums(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, graph, n_users, j_idx, variant):
-        L = _lib.lib()
         table = table.contiguous()
-        n_items = table.shape[0] - n_users
         u_idx, i_idx = graph.user_major_edges(n_users)
-        batch = u_idx.numel()
-        n_neg = 1 if j_idx.dim() == 1 else j_idx.shape[1]
-        d = table.shape[1]
-        dev = table.device
-        user_tab, item_tab = table[:n_users], table[n_users:]
-        dldx = torch.empty(max(batch, 1), dtype=torch.float32, device=dev)
-        sums = torch.zeros(5, dtype=torch.float32, device=dev)
-        ws = _lib.workspace("gcr_bpr_workspace_floats", batch, device=dev)
-        _lib.check(L.gcr_bpr_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
-                                     _lib.dptr(j_idx), batch, n_neg, variant, n_users, n_items, _lib.dptr(dldx),
-                                     _lib.dptr(sums), _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_bpr_fwd_f32")
+        sums, dldx, n_neg = _bpr_forward(table[:n_users], table[n_users:], u_idx, i_idx, j_idx, variant)
         ctx.save_for_backward(table, j_idx, dldx)
         ctx.graph, ctx.n_users, ctx.n_neg = graph, n_users, n_neg
         ctx.mark_non_differentiable(j_idx)
@@ -867,9 +809,7 @@ class _BprEdgeSums(torch.autograd.Function):
         # positive pairs: G = C_sym [U; I], C_sym = the graph's pattern with c_ui at (u, i) and (i, u)
         val = torch.empty(2 * batch, dtype=torch.float32, device=table.device)
         dropped = torch.zeros(n_items, dtype=torch.float32, device=table.device)   # samples the forward dropped, per positive item
-        _lib.check(_lib.lib().gcr_bpr_edge_values_f32(_lib.dptr(dldx), _lib.dptr(graph.mirror_perm()), _lib.dptr(graph.col),
-                                                      n_users, batch, _lib.dptr(gs), _lib.dptr(val), _lib.dptr(dropped),
-                                                      _lib.cur_stream(table.device)), "gcr_bpr_edge_values_f32")
+        _lib.call("gcr_bpr_edge_values_f32", dldx, graph.mirror_perm(), graph.col, n_users, batch, gs, val, dropped, on=table)
         gfull = torch.empty_like(table)
         spmm_into(graph.with_values(val), table, y=gfull)
         gu, gi = gfull[:n_users], gfull[n_users:]
@@ -880,7 +820,6 @@ class _BprEdgeSums(torch.autograd.Function):
         # the negatives' USER side: the edges are in user-major order, so this step's negatives are a CSR block [U x I] on the
         # graph's own user row pointer (x n_neg) — one more SpMM on a cached work plan instead of a sorted scatter over E
         # samples (0.84 -> ~0.4 ms at cfg2); its |U[u]|^2 term counts the live samples of every user
-        L = _lib.lib()
         n_neg = ctx.n_neg
         nb = graph.negatives_user_block(n_users, n_items, n_neg)
         ncol = torch.empty(batch * n_neg, dtype=torch.int32, device=table.device)
@@ -891,31 +830,18 @@ class _BprEdgeSums(torch.autograd.Function):
         if payload_sort:                     # the same walk also writes the item side's (key j, payload (u, value)) pairs
             skey = torch.empty(batch * n_neg, dtype=torch.int32, device=table.device)
             spay = torch.empty(batch * n_neg, dtype=torch.int64, device=table.device)
-        _lib.check(L.gcr_bpr_neg_block_f32(_lib.dptr(dldx), _lib.dptr(j_idx), _lib.dptr(u_idx), batch, n_neg, n_items,
-                                           _lib.dptr(gs), _lib.dptr(ncol), _lib.dptr(nval), _lib.dptr(dropped_u),
-                                           _lib.dptr(skey), _lib.dptr(spay), _lib.cur_stream(table.device)),
-                   "gcr_bpr_neg_block_f32")
+        _lib.call("gcr_bpr_neg_block_f32", dldx, j_idx, u_idx, batch, n_neg, n_items, gs, ncol, nval, dropped_u, skey, spay,
+                  on=table)
         nb.col, nb.val = ncol, nval
         spmm_into(nb, table[n_users:], acc_in=gu, acc_out=gu)
         gu.addcmul_(table[:n_users], (2.0 * gs[1] * (graph.row_degrees()[:n_users] - dropped_u)).unsqueeze(1))
-        # the negatives' item rows (fresh every step: one sort, one sorted scatter).  The sort carries (user, value) with
-        # the key, so the scatter streams its three arrays instead of chasing perm -> sample -> (u_idx, dloss_dx)
+        # the negatives' item rows
         if payload_sort:
-            ks, ps = torch.empty_like(skey), torch.empty_like(spay)
-            ws = _lib.workspace("gcr_sort_pairs_u64_workspace_bytes", batch * n_neg, device=table.device, dtype=torch.uint8)
-            _lib.check(L.gcr_sort_pairs_u64(_lib.dptr(skey), _lib.dptr(spay), batch * n_neg, n_items, _lib.dptr(ks),
-                                            _lib.dptr(ps), _lib.dptr(ws), _lib.cur_stream(table.device)), "gcr_sort_pairs_u64")
-            _lib.check(L.gcr_bpr_neg_items_sorted_f32(_lib.dptr(table[:n_users]), _lib.dptr(table[n_users:]), table.shape[1],
-                                                      _lib.dptr(ks), _lib.dptr(ps), batch * n_neg, n_users, n_items,
-                                                      _lib.dptr(gs), _lib.dptr(gi), _lib.cur_stream(table.device)),
-                       "gcr_bpr_neg_items_sorted_f32")
+            _bpr_neg_items(table[:n_users], table[n_users:], skey, spay, gs, gi)
             return gfull, None, None, None, None
         kj, pj, _ = _sorted_order(j_idx.reshape(-1), n_items)
-        _lib.check(L.gcr_bpr_bwd_sorted_f32(
-            _lib.dptr(table[:n_users]), _lib.dptr(table[n_users:]), table.shape[1], _lib.dptr(u_idx), None,
-            _lib.dptr(j_idx), batch, n_neg, n_users, n_items, _lib.dptr(dldx), _lib.dptr(gs), None,
-            None, None, None, _lib.dptr(kj), _lib.dptr(pj), _lib.dptr(gu), _lib.dptr(gi),
-            _lib.cur_stream(table.device)), "gcr_bpr_bwd_sorted_f32")
+        _lib.call("gcr_bpr_bwd_sorted_f32", table[:n_users], table[n_users:], table.shape[1], u_idx, None, j_idx, batch, n_neg,
+                  n_users, n_items, dldx, gs, None, None, None, None, kj, pj, gu, gi, on=table)
         return gfull, None, None, None, None
 
 
@@ -968,7 +894,6 @@ class _AuSums(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, user_tab, item_tab, u_idx, i_idx, j_idx, n_sets, t):
-        L = _lib.lib()
         user_tab = user_tab.contiguous()
         item_tab = None if item_tab is None else item_tab.contiguous()
         batch = u_idx.numel() if u_idx is not None else user_tab.shape[0]
@@ -980,10 +905,8 @@ class _AuSums(torch.autograd.Function):
         r = torch.empty(3 * batch, dtype=torch.float32, device=dev) if want_grad else None
         o = torch.empty(3 * batch, d, dtype=torch.float32, device=dev) if want_grad else None
         ws = _lib.workspace("gcr_directau_workspace_bytes", batch, d, device=dev)
-        _lib.check(L.gcr_directau_fwd_f32(_lib.dptr(user_tab), _lib.dptr(item_tab), d, _lib.dptr(u_idx), _lib.dptr(i_idx),
-                                          _lib.dptr(j_idx), batch, n_sets, user_tab.shape[0], n_items, float(t),
-                                          _lib.dptr(sums), _lib.dptr(inv), _lib.dptr(r), _lib.dptr(o), _lib.dptr(ws),
-                                          _lib.cur_stream(dev)), "gcr_directau_fwd_f32")
+        _lib.call("gcr_directau_fwd_f32", user_tab, item_tab, d, u_idx, i_idx, j_idx, batch, n_sets, user_tab.shape[0], n_items, t,
+                  sums, inv, r, o, ws, on=dev)
         if want_grad:
             ctx.save_for_backward(user_tab, item_tab, u_idx, i_idx, j_idx, inv, r, o)
             ctx.n_sets, ctx.t, ctx.batch = n_sets, float(t), batch
@@ -995,20 +918,9 @@ class _AuSums(torch.autograd.Function):
     def backward(ctx, g_sums):
         user_tab, item_tab, u_idx, i_idx, j_idx, inv, r, o = ctx.saved_tensors
         gs = g_sums.contiguous().to(torch.float32)
-        gi = None
-        if ctx.stacked:             # the halves of one stacked table: one gradient buffer (_SplitRows.backward hands it on)
-            gfull = torch.zeros(user_tab.shape[0] + item_tab.shape[0], user_tab.shape[1], dtype=torch.float32,
-                                device=user_tab.device)
-            gu, gi = gfull[: user_tab.shape[0]], gfull[user_tab.shape[0]:]
-        else:
-            gu = torch.zeros_like(user_tab)
-            if item_tab is not None:
-                gi = torch.zeros_like(item_tab)
-        _lib.check(_lib.lib().gcr_directau_bwd_f32(
-            _lib.dptr(user_tab), _lib.dptr(item_tab), user_tab.shape[1], _lib.dptr(u_idx), _lib.dptr(i_idx), _lib.dptr(j_idx),
-            ctx.batch, ctx.n_sets, user_tab.shape[0], 0 if item_tab is None else item_tab.shape[0], ctx.t, _lib.dptr(inv),
-            _lib.dptr(r), _lib.dptr(o), _lib.dptr(gs), _lib.dptr(gu), _lib.dptr(gi), _lib.cur_stream(user_tab.device)),
-            "gcr_directau_bwd_f32")
+        gu, gi = _table_grads(user_tab, item_tab, ctx.stacked)
+        _lib.call("gcr_directau_bwd_f32", user_tab, item_tab, user_tab.shape[1], u_idx, i_idx, j_idx, ctx.batch, ctx.n_sets,
+                  user_tab.shape[0], 0 if item_tab is None else item_tab.shape[0], ctx.t, inv, r, o, gs, gu, gi, on=user_tab)
         return gu, gi, None, None, None, None, None
 
 
@@ -1060,10 +972,8 @@ def neg_sample(user_rowptr, user_items_sorted, u_idx, n_negs, num_items, seed, o
     dev = u_idx.device
     u_idx = _as_index(u_idx, dev)
     out = torch.empty(u_idx.numel() * n_negs, dtype=torch.int64, device=dev)
-    _lib.check(_lib.lib().gcr_neg_sample(_lib.dptr(user_rowptr), _lib.dptr(user_items_sorted), _lib.dptr(u_idx),
-                                         u_idx.numel(), int(n_negs), user_rowptr.numel() - 1, int(num_items),
-                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(max_trials),
-                                         _lib.dptr(out), _lib.cur_stream(dev)), "gcr_neg_sample")
+    _lib.call("gcr_neg_sample", user_rowptr, user_items_sorted, u_idx, u_idx.numel(), n_negs, user_rowptr.numel() - 1, num_items,
+              int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), max_trials, out, on=dev)
     return out
 
 
@@ -1073,8 +983,7 @@ def edge_mask_bits(nnz, pe, seed, device, edge_id=None):
     bits = torch.zeros((nnz + 31) // 32, dtype=torch.int32, device=device)
     if edge_id is not None:
         edge_id = _as_index(edge_id, device)
-    _lib.check(_lib.lib().gcr_edge_mask_bits(int(nnz), float(pe), int(seed) & (2 ** 64 - 1), _lib.dptr(edge_id),
-                                             _lib.dptr(bits), _lib.cur_stream(device)), "gcr_edge_mask_bits")
+    _lib.call("gcr_edge_mask_bits", nnz, pe, int(seed) & (2 ** 64 - 1), edge_id, bits, on=device)
     return bits
 
 
@@ -1100,6 +1009,11 @@ def _pad_dim(x):
     raise ValueError("embedding dim must be <= 256")
 
 
+def _unpad(g, d):
+    """The first d columns of a gradient computed on `_pad_dim`'s width (None stays None)."""
+    return g if g is None or g.shape[1] == d else g[:, :d].contiguous()
+
+
 def row_inv_norm(x, eps=1e-12, out=None):
     """1 / max(||x_r||, eps) per row — F.normalize's denominator (ncl.py:127, gcl.py:29-30)."""
     _lib.require_cuda(x)
@@ -1108,8 +1022,7 @@ def row_inv_norm(x, eps=1e-12, out=None):
         out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     elif out.shape != (x.shape[0],) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
         raise ValueError("row_inv_norm: out must be a contiguous float32 [rows] tensor on x's device")
-    _lib.check(_lib.lib().gcr_row_inv_norm_f32(_lib.dptr(x), x.shape[0], x.shape[1], float(eps), _lib.dptr(out),
-                                               _lib.cur_stream(x.device)), "gcr_row_inv_norm_f32")
+    _lib.call("gcr_row_inv_norm_f32", x, x.shape[0], x.shape[1], eps, out, on=x)
     return out
 
 
@@ -1134,23 +1047,23 @@ def _resolve_engine(engine=None, unit_rows=False):
     return INFONCE_UNIT_ROWS if (unit_rows and e == "auto") else 0
 
 
+def _infonce_flags(exclude_diagonal, engine_flag):
+    """The flag word of an InfoNCE launch: the diagonal's bit and the engine (None: `_resolve_engine()`'s)."""
+    return (INFONCE_EXCLUDE_DIAGONAL if exclude_diagonal else 0) | (_resolve_engine() if engine_flag is None else engine_flag)
+
+
 def infonce_lse_raw(a, a_scale, b, b_scale, inv_tau, col_bound=None, exclude_diagonal=False, engine_flag=None):
     """lse[i] = log sum_j exp(inv_tau * a_scale[i] b_scale[j] <a_i, b_j>) (no autograd).
     col_bound (an upper bound of every logit, e.g. inv_tau for unit rows): also return the column
     logsumexp over the anchors [N] from the same pass (float atomics) as a second value.
     exclude_diagonal: the sum runs over j != i (grace.py:396-404, intra-view negatives)."""
-    L = _lib.lib()
     m, d = a.shape
     n = b.shape[0]
     lse = torch.empty(m, dtype=torch.float32, device=a.device)
     col_sum = torch.empty(n, dtype=torch.float32, device=a.device) if col_bound is not None else None
     ws = _lib.workspace("gcr_infonce_fwd_workspace_bytes", m, n, d, device=a.device)
-    _lib.check(L.gcr_infonce_fwd_ex_f32(_lib.dptr(a), _lib.dptr(a_scale), m, _lib.dptr(b), _lib.dptr(b_scale), n, d,
-                                        float(inv_tau), _lib.dptr(lse), _lib.dptr(col_sum),
-                                        float(col_bound) if col_bound is not None else 0.0, _lib.dptr(ws),
-                                        (INFONCE_EXCLUDE_DIAGONAL if exclude_diagonal else 0) |
-                                        (_resolve_engine() if engine_flag is None else engine_flag),
-                                        _lib.cur_stream(a.device)), "gcr_infonce_fwd_ex_f32")
+    _lib.call("gcr_infonce_fwd_ex_f32", a, a_scale, m, b, b_scale, n, d, inv_tau, lse, col_sum,
+              0.0 if col_bound is None else col_bound, ws, _infonce_flags(exclude_diagonal, engine_flag), on=a)
     if col_bound is None:
         return lse
     return lse, torch.log(col_sum) + float(col_bound)
@@ -1163,13 +1076,12 @@ FWD_O = True
 
 
 def infonce_fwd_o_supported(d, engine_flag=0):
-    return bool(_lib.lib().gcr_infonce_fwd_o_supported(int(d), int(engine_flag)))
+    return bool(_lib.call("gcr_infonce_fwd_o_supported", d, engine_flag))
 
 
 def infonce_fwd_o_raw(a, a_scale, b, b_scale, inv_tau, exclude_diagonal=False, engine_flag=None, lse_out=None, o_out=None):
     """(lse [M], o [M, d]): lse[i] = log sum_j exp(s_ij), o[i] = sum_j softmax(s_i.)_j * (b_scale[j] b_j)
     (no autograd).  lse_out / o_out: caller-owned contiguous outputs (e.g. slices of one stacked buffer)."""
-    L = _lib.lib()
     m, d = a.shape
     n = b.shape[0]
     lse = torch.empty(m, dtype=torch.float32, device=a.device) if lse_out is None else lse_out
@@ -1177,20 +1089,15 @@ def infonce_fwd_o_raw(a, a_scale, b, b_scale, inv_tau, exclude_diagonal=False, e
     if lse.shape != (m,) or o.shape != (m, d) or lse.dtype != torch.float32 or o.dtype != torch.float32:
         raise ValueError("lse_out [M] / o_out [M, d] must be float32")
     ws = _lib.workspace("gcr_infonce_fwd_o_workspace_bytes", m, n, d, device=a.device)
-    _lib.check(L.gcr_infonce_fwd_o_f32(_lib.dptr(a), _lib.dptr(a_scale), m, _lib.dptr(b), _lib.dptr(b_scale), n, d,
-                                       float(inv_tau), _lib.dptr(lse), _lib.dptr(o), _lib.dptr(ws),
-                                       (INFONCE_EXCLUDE_DIAGONAL if exclude_diagonal else 0) |
-                                       (_resolve_engine() if engine_flag is None else engine_flag),
-                                       _lib.cur_stream(a.device)), "gcr_infonce_fwd_o_f32")
+    _lib.call("gcr_infonce_fwd_o_f32", a, a_scale, m, b, b_scale, n, d, inv_tau, lse, o, ws,
+              _infonce_flags(exclude_diagonal, engine_flag), on=a)
     return lse, o
 
 
 def pos_logit_raw(a, a_scale, b, b_scale, pos, scale, out=None):
     m, d = a.shape
     out = torch.empty(m, dtype=torch.float32, device=a.device) if out is None else out
-    _lib.check(_lib.lib().gcr_pos_logit_f32(_lib.dptr(a), _lib.dptr(a_scale), _lib.dptr(b), _lib.dptr(b_scale),
-                                            _lib.dptr(pos), m, b.shape[0], d, float(scale), _lib.dptr(out),
-                                            _lib.cur_stream(a.device)), "gcr_pos_logit_f32")
+    _lib.call("gcr_pos_logit_f32", a, a_scale, b, b_scale, pos, m, b.shape[0], d, scale, out, on=a)
     return out
 
 
@@ -1198,20 +1105,13 @@ def _infonce_bwd_raw(x, x_scale, y, y_scale, inv_tau, lse_x, w_x, lse_y, w_y, ex
                      out=None):
     """g = inv_tau * sum_j P_ij yhat_j (see gcr_infonce_bwd_f32): gradient w.r.t. the scaled rows of x.
     out: caller-owned contiguous [Mx, d] (e.g. one half of a stacked gradient table)."""
-    L = _lib.lib()
     mx, d = x.shape
     g = torch.empty_like(x) if out is None else out
     if g.shape != x.shape or g.dtype != torch.float32:
         raise ValueError("out must be float32 with x's shape")
-    nbytes = int(L.gcr_infonce_bwd_workspace_bytes(mx, y.shape[0], d))
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    _lib.check(L.gcr_infonce_bwd_ex_f32(_lib.dptr(x), _lib.dptr(x_scale), mx, _lib.dptr(y), _lib.dptr(y_scale), y.shape[0],
-                                        d, float(inv_tau), _lib.dptr(lse_x), _lib.dptr(w_x), _lib.dptr(lse_y),
-                                        _lib.dptr(w_y), _lib.dptr(g), _lib.dptr(ws),
-                                        (INFONCE_EXCLUDE_DIAGONAL if exclude_diagonal else 0) |
-                                        (_resolve_engine() if engine_flag is None else engine_flag),
-                                        _lib.cur_stream(x.device)),
-               "gcr_infonce_bwd_ex_f32")
+    ws = _lib.workspace("gcr_infonce_bwd_workspace_bytes", mx, y.shape[0], d, device=x.device)
+    _lib.call("gcr_infonce_bwd_ex_f32", x, x_scale, mx, y, y_scale, y.shape[0], d, inv_tau, lse_x, w_x, lse_y, w_y, g, ws,
+              _infonce_flags(exclude_diagonal, engine_flag), on=x)
     return g
 
 
@@ -1239,7 +1139,7 @@ class _InfoNCEStats(torch.autograd.Function):
         # (two passes vs one: 11.5 vs 11.2 ms on three bf16 planes, 8.2 vs 13.6 ms on two f16 planes at 100K x 100K;
         # 0.34-0.49 vs 0.62-0.89 ms at 20K x 20K; scripts/perf_infonce_sym.py)
         eng = _resolve_engine(unit_rows=normalize)   # once per problem: the backward runs on the same engine
-        on_f32 = bool(eng & INFONCE_ENGINE_F32) or _lib.lib().gcr_infonce_engine(a_p.shape[1]) == 0
+        on_f32 = bool(eng & INFONCE_ENGINE_F32) or _lib.call("gcr_infonce_engine", a_p.shape[1]) == 0
         diag = pos is None and not exd and a_p.shape[0] == b_p.shape[0] >= 2
         kex = exd or diag                            # the kernels leave the diagonal out
         one_pass = want_col and normalize and inv_tau <= 40.0 and not COL_DETERMINISTIC and not kex and on_f32
@@ -1270,7 +1170,6 @@ class _InfoNCEStats(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lse, g_pos, g_col=None):
         a, b, pos, sa, sb, lse, col, o, q, q_col = ctx.saved_tensors
-        L = _lib.lib()
         inv_tau = ctx.inv_tau
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         g_lse = g_lse.contiguous().float() if g_lse is not None else None
@@ -1300,21 +1199,13 @@ class _InfoNCEStats(torch.autograd.Function):
                 total, corr = total + g_col, corr + g_col * q_col
             g_pos = total - corr
         if g_pos is not None and (need_a or need_b):
-            _lib.check(L.gcr_infonce_pos_bwd_f32(_lib.dptr(a), _lib.dptr(sa), _lib.dptr(b), _lib.dptr(sb), _lib.dptr(pos),
-                                                 _lib.dptr(g_pos.contiguous().float()), a.shape[0], b.shape[0], a.shape[1],
-                                                 float(inv_tau), _lib.dptr(ga), _lib.dptr(gb), stream),
-                       "gcr_infonce_pos_bwd_f32")
+            _lib.call("gcr_infonce_pos_bwd_f32", a, sa, b, sb, pos, g_pos.contiguous().float(), a.shape[0], b.shape[0], a.shape[1],
+                      inv_tau, ga, gb, on=stream)
         if sa is not None:
             for x, s, g in ((a, sa, ga), (b, sb, gb)):
                 if g is not None:
-                    _lib.check(L.gcr_normalize_bwd_f32(_lib.dptr(x), _lib.dptr(s), _lib.dptr(g), x.shape[0], x.shape[1],
-                                                       _lib.dptr(g), stream), "gcr_normalize_bwd_f32")
-        d = ctx.d
-        if ga is not None and ga.shape[1] != d:
-            ga = ga[:, :d].contiguous()
-        if gb is not None and gb.shape[1] != d:
-            gb = gb[:, :d].contiguous()
-        return ga, gb, None, None, None, None, None, None
+                    _lib.call("gcr_normalize_bwd_f32", x, s, g, x.shape[0], x.shape[1], g, on=stream)
+        return _unpad(ga, ctx.d), _unpad(gb, ctx.d), None, None, None, None, None, None
 
 
 def infonce_stats(a, b, pos=None, temperature=0.2, normalize=True, want_col=False, exclude_diagonal=False):
@@ -1359,26 +1250,21 @@ def _bce_flags(engine=None):
 
 def bce_fwd_raw(a, b, want_o=False, engine_flag=0):
     """(rowsum [M], o [M, d] or None): rowsum[i] = sum_j softplus(<a_i, b_j>), o[i] = sum_j sigmoid(<a_i, b_j>) b_j (no autograd)."""
-    L = _lib.lib()
     m, d = a.shape
     n = b.shape[0]
     rows = torch.empty(m, dtype=torch.float32, device=a.device)
     o = torch.empty(m, d, dtype=torch.float32, device=a.device) if want_o else None
     ws = _lib.workspace("gcr_bce_fwd_workspace_bytes", m, n, d, device=a.device)
-    _lib.check(L.gcr_bce_fwd_f32(_lib.dptr(a), m, _lib.dptr(b), n, d, _lib.dptr(rows), _lib.dptr(o), _lib.dptr(ws),
-                                 int(engine_flag), _lib.cur_stream(a.device)), "gcr_bce_fwd_f32")
+    _lib.call("gcr_bce_fwd_f32", a, m, b, n, d, rows, o, ws, engine_flag, on=a)
     return rows, o
 
 
 def bce_bwd_raw(x, y, w_x=None, w_y=None, engine_flag=0, out=None):
     """g[i] = sum_j (w_x[i] | w_y[j]) sigmoid(<x_i, y_j>) y_j (exactly one of the weight vectors; gcr_bce_bwd_f32)."""
-    L = _lib.lib()
     mx, d = x.shape
     g = torch.empty_like(x) if out is None else out
-    nbytes = int(L.gcr_bce_bwd_workspace_bytes(mx, y.shape[0], d))
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
-    _lib.check(L.gcr_bce_bwd_f32(_lib.dptr(x), mx, _lib.dptr(y), y.shape[0], d, _lib.dptr(w_x), _lib.dptr(w_y), _lib.dptr(g),
-                                 _lib.dptr(ws), int(engine_flag), _lib.cur_stream(x.device)), "gcr_bce_bwd_f32")
+    ws = _lib.workspace("gcr_bce_bwd_workspace_bytes", mx, y.shape[0], d, device=x.device)
+    _lib.call("gcr_bce_bwd_f32", x, mx, y, y.shape[0], d, w_x, w_y, g, ws, engine_flag, on=x)
     return g
 
 
@@ -1388,7 +1274,7 @@ class _BceRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, eng, grad_a):
         a_p, b_p = _pad_dim(a).contiguous(), _pad_dim(b).contiguous()
-        want_o = bool(grad_a and a_p.shape[0] > 0 and _lib.lib().gcr_bce_fwd_o_supported(a_p.shape[1], eng))
+        want_o = bool(grad_a and a_p.shape[0] > 0 and _lib.call("gcr_bce_fwd_o_supported", a_p.shape[1], eng))
         rows, o = bce_fwd_raw(a_p, b_p, want_o, eng)
         ctx.save_for_backward(a_p, b_p, o)
         ctx.eng, ctx.d = eng, a.shape[1]
@@ -1403,12 +1289,7 @@ class _BceRows(torch.autograd.Function):
             ga = o * g.unsqueeze(1) if o is not None else bce_bwd_raw(a, b, w_x=g, engine_flag=ctx.eng)
         if ctx.needs_input_grad[1]:
             gb = bce_bwd_raw(b, a, w_y=g, engine_flag=ctx.eng)
-        d = ctx.d
-        if ga is not None and ga.shape[1] != d:
-            ga = ga[:, :d].contiguous()
-        if gb is not None and gb.shape[1] != d:
-            gb = gb[:, :d].contiguous()
-        return ga, gb, None, None
+        return _unpad(ga, ctx.d), _unpad(gb, ctx.d), None, None
 
 
 def bce_softplus_rowsum(a, b, engine=None):
@@ -1437,7 +1318,7 @@ class _BceEdgeLoss(torch.autograd.Function):
         ue, ie = table[:n_users], table[n_users:]
         n_edges = graph.user_major_edges(n_users)[0].numel()
         deg = graph.row_degrees()[:n_users].contiguous()
-        want_o = bool(_lib.lib().gcr_bce_fwd_o_supported(table.shape[1], eng))
+        want_o = bool(_lib.call("gcr_bce_fwd_o_supported", table.shape[1], eng))
         rows, o = bce_fwd_raw(ue, ie, want_o, eng)
         ones = getattr(graph, "_unit_values", None)
         if ones is None:
@@ -1485,11 +1366,9 @@ def bce_edge_loss(graph, table, n_users, engine=None):
 def edge_mask_exact_bits(nnz, n_keep, seed, device):
     """Keep bitmap with exactly n_keep of nnz bits set, a uniformly random subset without replacement
     (univariate/sept.py:55-61: `np.random.choice(idx, int(len(idx) * (1 - drop_rate)), replace=False)`)."""
-    L = _lib.lib()
     bits = torch.empty((nnz + 31) // 32, dtype=torch.int32, device=device)
     ws = _lib.workspace("gcr_edge_mask_exact_workspace_bytes", nnz, device=device, dtype=torch.uint8)
-    _lib.check(L.gcr_edge_mask_exact_bits(int(nnz), int(n_keep), int(seed) & (2 ** 64 - 1), _lib.dptr(bits),
-                                          _lib.dptr(ws), _lib.cur_stream(device)), "gcr_edge_mask_exact_bits")
+    _lib.call("gcr_edge_mask_exact_bits", nnz, n_keep, int(seed) & (2 ** 64 - 1), bits, ws, on=device)
     return bits
 
 
@@ -1514,8 +1393,7 @@ def mask_columns_raw(x, keep_bits):
     if x.dim() != 2 or x.dtype != torch.float32 or keep_bits.dtype != torch.int32 or keep_bits.numel() * 32 < x.shape[1]:
         raise ValueError("x float32 [n, d]; keep_bits int32 bitmap with >= d bits")
     out = torch.empty_like(x)
-    _lib.check(_lib.lib().gcr_mask_columns_f32(_lib.dptr(x), x.shape[0], x.shape[1], _lib.dptr(keep_bits), _lib.dptr(out),
-                                               _lib.cur_stream(x.device)), "gcr_mask_columns_f32")
+    _lib.call("gcr_mask_columns_f32", x, x.shape[0], x.shape[1], keep_bits, out, on=x)
     return out
 
 
@@ -1537,8 +1415,7 @@ class _GatherRows(torch.autograd.Function):
     def forward(ctx, table, idx):
         table = table.contiguous()
         out = torch.empty(idx.numel(), table.shape[1], dtype=torch.float32, device=table.device)
-        _lib.check(_lib.lib().gcr_gather_rows_f32(_lib.dptr(table), _lib.dptr(idx), idx.numel(), table.shape[1], table.shape[0],
-                                                  _lib.dptr(out), _lib.cur_stream(table.device)), "gcr_gather_rows_f32")
+        _lib.call("gcr_gather_rows_f32", table, idx, idx.numel(), table.shape[1], table.shape[0], out, on=table)
         ctx.save_for_backward(idx)
         ctx.shape = table.shape
         return out
@@ -1548,8 +1425,7 @@ class _GatherRows(torch.autograd.Function):
         (idx,) = ctx.saved_tensors
         gt = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
         g = g.contiguous()
-        _lib.check(_lib.lib().gcr_scatter_add_rows_f32(_lib.dptr(g), _lib.dptr(idx), idx.numel(), g.shape[1], ctx.shape[0],
-                                                       _lib.dptr(gt), _lib.cur_stream(g.device)), "gcr_scatter_add_rows_f32")
+        _lib.call("gcr_scatter_add_rows_f32", g, idx, idx.numel(), g.shape[1], ctx.shape[0], gt, on=g)
         return gt, None
 
 
@@ -1585,9 +1461,7 @@ class _GatherDropoutViews(torch.autograd.Function):
         table = table.contiguous()
         n, d = idx.numel(), table.shape[1]
         out = torch.empty((1 + n_views) * n, d, dtype=torch.float32, device=table.device)
-        _lib.check(_lib.lib().gcr_gather_dropout_f32(_lib.dptr(table), _lib.dptr(idx), n, d, table.shape[0], p, seed, n_views,
-                                                     _lib.dptr(keep_bits), _lib.dptr(out), _lib.cur_stream(table.device)),
-                   "gcr_gather_dropout_f32")
+        _lib.call("gcr_gather_dropout_f32", table, idx, n, d, table.shape[0], p, seed, n_views, keep_bits, out, on=table)
         ctx.save_for_backward(idx, *(() if keep_bits is None else (keep_bits,)))      # no mask of its own: (p, seed)
         ctx.args = (table.shape, p, seed, n_views)
         return out
@@ -1598,9 +1472,8 @@ class _GatherDropoutViews(torch.autograd.Function):
         shape, p, seed, n_views = ctx.args
         gt = torch.zeros(shape, dtype=torch.float32, device=g.device)
         g = g.contiguous()
-        _lib.check(_lib.lib().gcr_gather_dropout_bwd_f32(_lib.dptr(g), _lib.dptr(idx), idx.numel(), shape[1], shape[0], p, seed,
-                                                         n_views, _lib.dptr(bits[0] if bits else None), _lib.dptr(gt),
-                                                         _lib.cur_stream(g.device)), "gcr_gather_dropout_bwd_f32")
+        _lib.call("gcr_gather_dropout_bwd_f32", g, idx, idx.numel(), shape[1], shape[0], p, seed, n_views,
+                  bits[0] if bits else None, gt, on=g)
         return gt, None, None, None, None, None
 
 
@@ -1635,7 +1508,6 @@ class _TriTraining(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_f, x_s, x_r, aug, uniq, k, inv_t, positives):
-        L = _lib.lib()
         tabs = [t.contiguous() for t in (x_f, x_s, x_r, aug)]
         n_rows, d = tabs[0].shape
         m, dev = uniq.numel(), tabs[0].device
@@ -1646,9 +1518,7 @@ class _TriTraining(torch.autograd.Function):
         inv_norm = torch.empty(4, m, dtype=torch.float32, device=dev)
         member = _lib.workspace("gcr_tri_member_words", m, device=dev, dtype=torch.int32)
         ws = _lib.workspace("gcr_tri_workspace_bytes", m, d, k, device=dev)
-        _lib.check(L.gcr_tri_fwd_f32(*(_lib.dptr(t) for t in tabs), n_rows, d, _lib.dptr(uniq), m, k, inv_t, int(replay),
-                                     _lib.dptr(loss), _lib.dptr(pos), _lib.dptr(rsum), _lib.dptr(inv_norm), _lib.dptr(member),
-                                     _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_tri_fwd_f32")
+        _lib.call("gcr_tri_fwd_f32", *tabs, n_rows, d, uniq, m, k, inv_t, replay, loss, pos, rsum, inv_norm, member, ws, on=dev)
         ctx.save_for_backward(*tabs, uniq, rsum, member)
         ctx.args = (k, inv_t)
         ctx.mark_non_differentiable(pos)
@@ -1658,21 +1528,18 @@ class _TriTraining(torch.autograd.Function):
     def backward(ctx, g, _g_pos):
         *tabs, uniq, rsum, member = ctx.saved_tensors
         k, inv_t = ctx.args
-        L = _lib.lib()
         n_rows, d = tabs[0].shape
         m, dev = uniq.numel(), tabs[0].device
         g = g.to(torch.float32).contiguous()
         grads = [torch.zeros_like(t) for t in tabs]
         ws = _lib.workspace("gcr_tri_workspace_bytes", m, d, k, device=dev)
-        _lib.check(L.gcr_tri_bwd_f32(*(_lib.dptr(t) for t in tabs), n_rows, d, _lib.dptr(uniq), m, k, inv_t, _lib.dptr(rsum),
-                                     _lib.dptr(member), _lib.dptr(g), *(_lib.dptr(t) for t in grads), _lib.dptr(ws),
-                                     _lib.cur_stream(dev)), "gcr_tri_bwd_f32")
+        _lib.call("gcr_tri_bwd_f32", *tabs, n_rows, d, uniq, m, k, inv_t, rsum, member, g, *grads, ws, on=dev)
         return (*grads, None, None, None, None)
 
 
 def tri_training_supported(d, k):
     """True when the fused kernels (gcr_tri_*) serve rows of width d with k pseudo-labels: d in {32, 64, 128}, 1 <= k <= 32."""
-    return bool(_lib.lib().gcr_tri_supported(int(d), int(k)))
+    return bool(_lib.call("gcr_tri_supported", d, k))
 
 
 def tri_training_loss_composed(x_f, x_s, x_r, aug, uniq, k, temperature=0.1, positives=None):
@@ -1738,15 +1605,13 @@ class _BuirLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias):
-        L = _lib.lib()
         tabs = [t.contiguous() for t in (on_user, on_item, tg_user, tg_item)]
         weight, bias = weight.contiguous(), bias.contiguous()
         d, batch, dev = weight.shape[0], u_idx.numel(), weight.device
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
         stats = torch.empty(2, 3, batch, dtype=torch.float32, device=dev)
-        _lib.check(L.gcr_buir_fwd_f32(*(_lib.dptr(t) for t in tabs), tabs[0].shape[0], tabs[1].shape[0], d, _lib.dptr(u_idx),
-                                      _lib.dptr(i_idx), batch, _lib.dptr(weight), _lib.dptr(bias), _lib.dptr(loss),
-                                      _lib.dptr(stats), _lib.cur_stream(dev)), "gcr_buir_fwd_f32")
+        _lib.call("gcr_buir_fwd_f32", *tabs, tabs[0].shape[0], tabs[1].shape[0], d, u_idx, i_idx, batch, weight, bias, loss, stats,
+                  on=dev)
         ctx.save_for_backward(*tabs, u_idx, i_idx, weight, bias, stats)
         ctx.stacked = _halves_of_one_table(tabs[0], tabs[1])
         return loss.reshape(())
@@ -1754,31 +1619,23 @@ class _BuirLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias, stats = ctx.saved_tensors
-        L = _lib.lib()
         d, batch, dev = weight.shape[0], u_idx.numel(), weight.device
         n_users, n_items = on_user.shape[0], on_item.shape[0]
-        if ctx.stacked:                                     # one buffer for both halves: _SplitRows.backward hands it on
-            gfull = torch.zeros(n_users + n_items, d, dtype=torch.float32, device=dev)
-            gu, gi = gfull[:n_users], gfull[n_users:]
-        else:
-            gu, gi = torch.zeros_like(on_user), torch.zeros_like(on_item)
+        gu, gi = _table_grads(on_user, on_item, ctx.stacked)
         gw, gb = torch.zeros_like(weight), torch.zeros_like(bias)
         if batch:
             ku, pu, _ = _sorted_order(u_idx, n_users)
             ki, pi, _ = _sorted_order(i_idx, n_items)
             ws = _lib.workspace("gcr_buir_workspace_bytes", batch, d, device=dev)
             g = g.to(torch.float32).reshape(1).contiguous()
-            _lib.check(L.gcr_buir_bwd_f32(
-                _lib.dptr(on_user), _lib.dptr(on_item), _lib.dptr(tg_user), _lib.dptr(tg_item), n_users, n_items, d,
-                _lib.dptr(u_idx), _lib.dptr(i_idx), batch, _lib.dptr(weight), _lib.dptr(bias), _lib.dptr(stats), _lib.dptr(g),
-                _lib.dptr(ku), _lib.dptr(pu), _lib.dptr(ki), _lib.dptr(pi), _lib.dptr(gu), _lib.dptr(gi), _lib.dptr(gw),
-                _lib.dptr(gb), _lib.dptr(ws), _lib.cur_stream(dev)), "gcr_buir_bwd_f32")
+            _lib.call("gcr_buir_bwd_f32", on_user, on_item, tg_user, tg_item, n_users, n_items, d, u_idx, i_idx, batch, weight,
+                      bias, stats, g, ku, pu, ki, pi, gu, gi, gw, gb, ws, on=dev)
         return gu, gi, None, None, None, None, gw, gb
 
 
 def buir_supported(d):
     """True when the fused kernels (gcr_buir_*) serve rows of width d: a multiple of 16 in [16, 512]."""
-    return bool(_lib.lib().gcr_buir_supported(int(d)))
+    return bool(_lib.call("gcr_buir_supported", d))
 
 
 def _buir_args(on_user, on_item, tg_user, tg_item, u_idx, i_idx, weight, bias):
@@ -1840,9 +1697,7 @@ def ema_rows_(target, online, idx, momentum):
     idx = _as_index(idx, target.device).reshape(-1)
     n_rows, d = target.shape
     claim = torch.empty((n_rows + 31) // 32, dtype=torch.int32, device=target.device)
-    _lib.check(_lib.lib().gcr_ema_rows_f32(_lib.dptr(target), _lib.dptr(online.detach().contiguous()), _lib.dptr(idx),
-                                           idx.numel(), d, n_rows, float(momentum), _lib.dptr(claim),
-                                           _lib.cur_stream(target.device)), "gcr_ema_rows_f32")
+    _lib.call("gcr_ema_rows_f32", target, online.detach().contiguous(), idx, idx.numel(), d, n_rows, momentum, claim, on=target)
     return target
 
 
@@ -1861,11 +1716,9 @@ def column_stats(x):
         raise ValueError("column_stats needs a float32 [n, d] tensor with n >= 2")
     x = x.detach().contiguous()
     n, d = x.shape
-    L = _lib.lib()
     out = torch.empty(2, d, dtype=torch.float32, device=x.device)
     ws = _lib.workspace("gcr_col_stats_workspace_bytes", n, d, device=x.device)
-    _lib.check(L.gcr_col_stats_f32(_lib.dptr(x), n, d, _lib.dptr(out[0]), _lib.dptr(out[1]), _lib.dptr(ws),
-                                   _lib.cur_stream(x.device)), "gcr_col_stats_f32")
+    _lib.call("gcr_col_stats_f32", x, n, d, out[0], out[1], ws, on=x)
     return out[0], out[1]
 
 
@@ -1906,30 +1759,24 @@ def bt_loss_composed(h1, h2, lambda_=None, batch_norm=True, eps=1e-15):
 def bt_forward_raw(h1, h2, lambda_, batch_norm=True, eps=1e-15):
     """gcr_bt_fwd_f32 on contiguous float32 device views -> (loss [1], c [d, d], stats [4, d]: mean1, std1, mean2, std2;
     not written without batch_norm)."""
-    L = _lib.lib()
     n, d = h1.shape
     dev = h1.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     c = torch.empty(d, d, dtype=torch.float32, device=dev)
     stats = torch.zeros(4, d, dtype=torch.float32, device=dev)
     ws = _lib.workspace("gcr_bt_workspace_bytes", n, d, device=dev)
-    _lib.check(L.gcr_bt_fwd_f32(_lib.dptr(h1), _lib.dptr(h2), n, d, float(lambda_), float(eps), int(bool(batch_norm)),
-                                _lib.dptr(stats), _lib.dptr(c), _lib.dptr(loss), _lib.dptr(ws), _lib.cur_stream(dev)),
-               "gcr_bt_fwd_f32")
+    _lib.call("gcr_bt_fwd_f32", h1, h2, n, d, lambda_, eps, bool(batch_norm), stats, c, loss, ws, on=dev)
     return loss, c, stats
 
 
 def bt_backward_raw(h1, h2, lambda_, batch_norm, eps, stats, c, g, want1=True, want2=True):
     """gcr_bt_bwd_f32 -> (g_h1 or None, g_h2 or None) for the upstream device scalar g (float32 [1])."""
-    L = _lib.lib()
     n, d = h1.shape
     dev = h1.device
     g1 = torch.empty_like(h1) if want1 else None
     g2 = torch.empty_like(h2) if want2 else None
     ws = _lib.workspace("gcr_bt_workspace_bytes", n, d, device=dev)
-    _lib.check(L.gcr_bt_bwd_f32(_lib.dptr(h1), _lib.dptr(h2), n, d, float(lambda_), float(eps), int(bool(batch_norm)),
-                                _lib.dptr(stats), _lib.dptr(c), _lib.dptr(g), _lib.dptr(g1), _lib.dptr(g2), _lib.dptr(ws),
-                                _lib.cur_stream(dev)), "gcr_bt_bwd_f32")
+    _lib.call("gcr_bt_bwd_f32", h1, h2, n, d, lambda_, eps, bool(batch_norm), stats, c, g, g1, g2, ws, on=dev)
     return g1, g2
 
 

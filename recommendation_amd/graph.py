@@ -11,8 +11,6 @@ partial-sum workspace [n_slots, d].
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
@@ -63,25 +61,19 @@ class SpmmPlan:
         (reorder.xcd_grouped_order), and its rows stay in that XCD's L2 between the gathers that share them; without it
         the partitions keep row order and consecutive workgroups alternate over the XCDs.
         skip (optional bool / uint8 array [n_rows]): rows that get no partition and no long-row entry (HubPlan's)."""
-        L = _lib.lib()
         rowptr_host = np.ascontiguousarray(rowptr_host, dtype=np.int64)
         n_rows = rowptr_host.size - 1
         if skip is not None:
             skip = np.ascontiguousarray(skip, dtype=np.uint8)
             if skip.shape != (n_rows,):
                 raise ValueError("skip must have one entry per row")
-        skip_p = None if skip is None else skip.ctypes.data
-        sizes = (ctypes.c_int64 * 3)()
-        p = ctypes.addressof(sizes)
-        _lib.check(L.gcr_spmm_plan_size_skip_host(rowptr_host.ctypes.data, n_rows, nnz_per_part, skip_p, p, p + 8, p + 16),
-                   "gcr_spmm_plan_size_skip_host")
+        sizes = np.zeros(3, np.int64)
+        _lib.call("gcr_spmm_plan_size_skip_host", rowptr_host, n_rows, nnz_per_part, skip, sizes[0:1], sizes[1:2], sizes[2:3])
         self.n_parts, self.n_long, self.n_slots = int(sizes[0]), int(sizes[1]), int(sizes[2])
         desc = np.empty((max(self.n_parts, 1), 4), dtype=np.int64)
         long_row = np.zeros(max(self.n_long, 1), dtype=np.int32)
         long_slot0 = np.zeros(self.n_long + 1, dtype=np.int32)
-        _lib.check(L.gcr_spmm_plan_fill_skip_host(rowptr_host.ctypes.data, n_rows, nnz_per_part, skip_p, desc.ctypes.data,
-                                                  long_row.ctypes.data, long_slot0.ctypes.data),
-                   "gcr_spmm_plan_fill_skip_host")
+        _lib.call("gcr_spmm_plan_fill_skip_host", rowptr_host, n_rows, nnz_per_part, skip, desc, long_row, long_slot0)
         self.nnz_per_part = nnz_per_part
         self.grouped = row_group is not None and self.n_parts > 0
         if self.grouped:
@@ -240,8 +232,7 @@ class CsrGraph:
     def validate(self):
         """Device-side structural check before any kernel trusts the indices."""
         errs = torch.zeros(1, dtype=torch.int64, device=self.device)
-        _lib.check(_lib.lib().gcr_csr_validate(_lib.dptr(self.rowptr), _lib.dptr(self.col), self.n_rows, self.n_cols,
-                                               self.nnz, _lib.dptr(errs), _lib.cur_stream(self.device)), "gcr_csr_validate")
+        _lib.call("gcr_csr_validate", self.rowptr, self.col, self.n_rows, self.n_cols, self.nnz, errs, on=self.device)
         n = int(errs.item())
         if n:
             raise ValueError(f"CSR graph is malformed: {n} structural errors (rowptr order / column range)")
@@ -421,8 +412,7 @@ class CsrGraph:
         rp, c, v, _ = coo_to_csr_device(row, col, val, n_rows, n_cols, device, coalesce=True)
         rinv = torch.empty(n_rows, dtype=torch.float32, device=rp.device)
         out = torch.empty_like(v)
-        _lib.check(_lib.lib().gcr_csr_row_norm_f32(_lib.dptr(rp), _lib.dptr(c), _lib.dptr(v), n_rows, _lib.dptr(rinv),
-                                                   _lib.dptr(out), _lib.cur_stream(rp.device)), "gcr_csr_row_norm_f32")
+        _lib.call("gcr_csr_row_norm_f32", rp, c, v, n_rows, rinv, out, on=rp)
         return cls(rp, c, out, n_rows, n_cols, device, symmetric=False, **kw)
 
     @classmethod
@@ -453,7 +443,6 @@ def _dev_i64(a, device):
 def coo_to_csr_device(row, col, val, n_rows, n_cols, device, coalesce=False, want_perm=False):
     """gcr_coo_to_csr: returns (rowptr int64 [n_rows+1], col int32 [nnz'], val fp32 [nnz'] or None,
     perm int64 [nnz'] or None) as device tensors.  Raises on ids outside the matrix."""
-    L = _lib.lib()
     row, col = _dev_i64(row, device), _dev_i64(col, device)
     nnz = row.numel()
     if col.numel() != nnz:
@@ -467,10 +456,8 @@ def coo_to_csr_device(row, col, val, n_rows, n_cols, device, coalesce=False, wan
     perm = torch.empty(max(nnz, 1), dtype=torch.int64, device=device) if (want_perm and not coalesce) else None
     meta = torch.zeros(2, dtype=torch.int64, device=device)
     ws = _lib.workspace("gcr_coo_to_csr_workspace_bytes", nnz, device=device, dtype=torch.uint8)
-    _lib.check(L.gcr_coo_to_csr(_lib.dptr(row), _lib.dptr(col), _lib.dptr(val), nnz, n_rows, n_cols, int(coalesce),
-                                _lib.dptr(rowptr), _lib.dptr(col_out), _lib.dptr(val_out), _lib.dptr(perm),
-                                _lib.dptr(meta[0:1]), _lib.dptr(meta[1:2]), _lib.dptr(ws), _lib.cur_stream(device)),
-               "gcr_coo_to_csr")
+    _lib.call("gcr_coo_to_csr", row, col, val, nnz, n_rows, n_cols, coalesce, rowptr, col_out, val_out, perm,
+              meta[0:1], meta[1:2], ws, on=device)
     n_out, n_err = (int(v) for v in meta.tolist())
     if n_err:
         raise ValueError(f"{n_err} COO entries have a row / column outside [{n_rows}, {n_cols}]")
@@ -482,9 +469,7 @@ def sym_norm_device(rowptr, col, val, n):
     """gcr_csr_sym_norm_f32 on a square symmetric operator: D^-1/2 A D^-1/2 (val None = ones)."""
     dinv = torch.empty(n, dtype=torch.float32, device=rowptr.device)
     out = torch.empty(col.numel(), dtype=torch.float32, device=rowptr.device)
-    _lib.check(_lib.lib().gcr_csr_sym_norm_f32(_lib.dptr(rowptr), _lib.dptr(col), _lib.dptr(val), n, n, None, None,
-                                               _lib.dptr(dinv), None, _lib.dptr(out), _lib.cur_stream(rowptr.device)),
-               "gcr_csr_sym_norm_f32")
+    _lib.call("gcr_csr_sym_norm_f32", rowptr, col, val, n, n, None, None, dinv, None, out, on=rowptr)
     return out
 
 

@@ -65,7 +65,6 @@ class Sp:
         """A @ B (scipy `.dot`)."""
         if self.n_cols != other.n_rows:
             raise ValueError("shape mismatch")
-        L = _lib.lib()
         dev = self.device
         if self.nnz == 0 or other.nnz == 0:
             return Sp.from_coo(torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
@@ -77,10 +76,8 @@ class Sp:
         out_row = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
         out_col = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
         out_val = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
-        _lib.check(L.gcr_spgemm_expand_f32(_lib.dptr(self.rowptr), _lib.dptr(self.col), _lib.dptr(self.val), self.n_rows, self.nnz,
-                                           _lib.dptr(self.row_of()), _lib.dptr(other.rowptr), _lib.dptr(other.col),
-                                           _lib.dptr(other.val), _lib.dptr(offset), _lib.dptr(out_row), _lib.dptr(out_col),
-                                           _lib.dptr(out_val), _lib.cur_stream(dev)), "gcr_spgemm_expand_f32")
+        _lib.call("gcr_spgemm_expand_f32", self.rowptr, self.col, self.val, self.n_rows, self.nnz, self.row_of(), other.rowptr,
+                  other.col, other.val, offset, out_row, out_col, out_val, on=dev)
         return Sp.from_coo(out_row[:total], out_col[:total], out_val[:total], self.n_rows, other.n_cols, dev)
 
     def __mul__(self, mask):
@@ -91,9 +88,7 @@ class Sp:
             return Sp(torch.zeros(self.n_rows + 1, dtype=torch.int64, device=self.device), self.col[:0], self.val[:0],
                       self.n_rows, self.n_cols)
         m = torch.empty(max(self.nnz, 1), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().gcr_csr_lookup_f32(_lib.dptr(self.row_of()), _lib.dptr(self.col), self.nnz, _lib.dptr(mask.rowptr),
-                                                 _lib.dptr(mask.col), _lib.dptr(mask.val), _lib.dptr(m),
-                                                 _lib.cur_stream(self.device)), "gcr_csr_lookup_f32")
+        _lib.call("gcr_csr_lookup_f32", self.row_of(), self.col, self.nnz, mask.rowptr, mask.col, mask.val, m, on=self.device)
         return Sp(self.rowptr, self.col, self.val * m[: self.nnz], self.n_rows, self.n_cols)._drop_zeros()
 
     def __add__(self, other):

@@ -67,11 +67,9 @@ def _perm_prefix(n, count, seed, device):
 
 
 def kmeans_assign(x, centroids, half_sq):
-    L = _lib.lib()
     n, d = x.shape
     assign = torch.empty(n, dtype=torch.int64, device=x.device)
-    _lib.check(L.gcr_kmeans_assign_f32(_lib.dptr(x), n, _lib.dptr(centroids), _lib.dptr(half_sq), centroids.shape[0], d,
-                                       _lib.dptr(assign), None, _lib.cur_stream(x.device)), "gcr_kmeans_assign_f32")
+    _lib.call("gcr_kmeans_assign_f32", x, n, centroids, half_sq, centroids.shape[0], d, assign, None, on=x)
     return assign
 
 
@@ -117,7 +115,6 @@ def run_kmeans(x, k, niter=FAISS_NITER, seed=FAISS_SEED, init_centroids=None,
         cent = Fn._pad_dim(init_centroids.detach().to(torch.float32)).contiguous().clone()
     k = cent.shape[0]
     d = xp.shape[1]
-    L = _lib.lib()
     dev = x.device
     half_sq = torch.empty(k, dtype=torch.float32, device=dev)
     use_sorted = n_train >= SORTED_UPDATE_MIN_POINTS
@@ -128,14 +125,13 @@ def run_kmeans(x, k, niter=FAISS_NITER, seed=FAISS_SEED, init_centroids=None,
     n_split = torch.zeros(1, dtype=torch.int32, device=dev)
     stream = _lib.cur_stream(dev)
     # 0.5 |c|^2 of the initial centroids (n = 0: refresh only)
-    _lib.check(L.gcr_kmeans_update_f32(None, 0, d, None, k, _lib.dptr(cent), _lib.dptr(half_sq), None, None, stream),
-               "gcr_kmeans_update_f32")
-    fused = not use_sorted and bool(L.gcr_infonce_engine(d))       # search + accumulate in one launch (d <= 128)
+    _lib.call("gcr_kmeans_update_f32", None, 0, d, None, k, cent, half_sq, None, None, on=stream)
+    fused = not use_sorted and bool(_lib.call("gcr_infonce_engine", d))       # search + accumulate in one launch (d <= 128)
     # small problems (the e_step: 76.8 K sampled points, a few hundred centroids) are latency-bound: wave-independent search
     # over a pre-split centroid image (gcr_kmeans_search_image_f32), the image rebuilt once per iteration
     image = None
     if fused and d in (32, 64) and IMAGE_SEARCH and n_train * k <= IMAGE_SEARCH_MAX_PAIRS:
-        image = torch.empty(int(L.gcr_kmeans_image_bytes(k, d)), dtype=torch.uint8, device=dev)
+        image = torch.empty(_lib.call("gcr_kmeans_image_bytes", k, d), dtype=torch.uint8, device=dev)
     incremental = image is not None and INCREMENTAL_UPDATE
     if incremental:
         # fixed-point scale 2^e with max |x| * 2^e in [2^29, 2^30): exact in f32, computed on the device (no read-back).
@@ -150,39 +146,28 @@ def run_kmeans(x, k, niter=FAISS_NITER, seed=FAISS_SEED, init_centroids=None,
         counts_f = torch.zeros(k, dtype=torch.float32, device=dev)
         flags = 1 if IMAGE_SEARCH_LOW_REGISTERS else 0
         # the operand image is built once; every iteration's update keeps it current (no image launch per iteration)
-        _lib.check(L.gcr_kmeans_centroid_image_f32(_lib.dptr(cent), _lib.dptr(half_sq), k, d, _lib.dptr(image), stream),
-                   "gcr_kmeans_centroid_image_f32")
+        _lib.call("gcr_kmeans_centroid_image_f32", cent, half_sq, k, d, image, on=stream)
         for it in range(int(niter)):
-            _lib.check(L.gcr_kmeans_search_image_incr_f32(_lib.dptr(xt), n_train, _lib.dptr(image), k, d, _lib.dptr(prev),
-                                                          _lib.dptr(qscale), _lib.dptr(sums_q), _lib.dptr(counts_i), copies, flags, stream),
-                       "gcr_kmeans_search_image_incr_f32")
-            _lib.check(L.gcr_kmeans_lloyd_update_q_f32(_lib.dptr(sums_q), _lib.dptr(counts_i), _lib.dptr(qscale), k, d,
-                                                       _lib.dptr(cent), _lib.dptr(half_sq), _lib.dptr(counts_f), n_train,
-                                                       int(seed) & (2 ** 64 - 1), it, _lib.dptr(n_split), _lib.dptr(image), copies,
-                                                       stream),
-                       "gcr_kmeans_lloyd_update_q_f32")
+            _lib.call("gcr_kmeans_search_image_incr_f32", xt, n_train, image, k, d, prev, qscale, sums_q, counts_i, copies, flags,
+                      on=stream)
+            _lib.call("gcr_kmeans_lloyd_update_q_f32", sums_q, counts_i, qscale, k, d, cent, half_sq, counts_f, n_train,
+                      int(seed) & (2 ** 64 - 1), it, n_split, image, copies, on=stream)
         niter = 0
     for it in range(int(niter)):
         keys = perm = assign = None
         if image is not None:
-            _lib.check(L.gcr_kmeans_centroid_image_f32(_lib.dptr(cent), _lib.dptr(half_sq), k, d, _lib.dptr(image), stream),
-                       "gcr_kmeans_centroid_image_f32")
-            _lib.check(L.gcr_kmeans_search_image_f32(_lib.dptr(xt), n_train, _lib.dptr(image), k, d, None, _lib.dptr(sums),
-                                                     _lib.dptr(counts), copies, 1 if IMAGE_SEARCH_LOW_REGISTERS else 0, stream),
-                       "gcr_kmeans_search_image_f32")
+            _lib.call("gcr_kmeans_centroid_image_f32", cent, half_sq, k, d, image, on=stream)
+            _lib.call("gcr_kmeans_search_image_f32", xt, n_train, image, k, d, None, sums, counts, copies,
+                      1 if IMAGE_SEARCH_LOW_REGISTERS else 0, on=stream)
         elif fused:
-            _lib.check(L.gcr_kmeans_assign_accumulate_f32(_lib.dptr(xt), n_train, _lib.dptr(cent), _lib.dptr(half_sq), k, d, None,
-                                                          _lib.dptr(sums), _lib.dptr(counts), copies, stream),
-                       "gcr_kmeans_assign_accumulate_f32")
+            _lib.call("gcr_kmeans_assign_accumulate_f32", xt, n_train, cent, half_sq, k, d, None, sums, counts, copies, on=stream)
         else:
             assign = kmeans_assign(xt, cent, half_sq)
             if use_sorted:
                 # points ordered by cluster: one row atomic per run instead of one per point
                 keys, perm, _ = Fn._sorted_order(assign, k)
-        _lib.check(L.gcr_kmeans_lloyd_update_f32(_lib.dptr(xt), n_train, d, _lib.dptr(assign), _lib.dptr(keys), _lib.dptr(perm),
-                                                 k, _lib.dptr(cent), _lib.dptr(half_sq), _lib.dptr(sums), _lib.dptr(counts),
-                                                 copies, int(seed) & (2 ** 64 - 1), it, _lib.dptr(n_split), stream),
-                   "gcr_kmeans_lloyd_update_f32")
+        _lib.call("gcr_kmeans_lloyd_update_f32", xt, n_train, d, assign, keys, perm, k, cent, half_sq, sums, counts, copies,
+                  int(seed) & (2 ** 64 - 1), it, n_split, on=stream)
     # kmeans.index.search(x, 1) against the final centroids
     assign = kmeans_assign(xp, cent, half_sq) if assign_points else None
     cent = cent[:, :d_orig].contiguous()

@@ -93,7 +93,6 @@ class FusedNCLStep:
         (rec_loss, ssl_loss, proto_loss, total) as device scalars; the parameters are updated."""
         o_ = self.owner
         enc, graph, n_u, n_i = self.enc, self.graph, self.n_u, self.n_i
-        L = _lib.lib()
         if self._cuda_graph is not None and not enc._aliased():
             raise RuntimeError("the encoder's parameters were re-bound (deepcopy / load_state_dict(assign=True) / .data = ...) "
                                "after this step was captured: call capture() again")
@@ -125,8 +124,8 @@ class FusedNCLStep:
         Fn.row_inv_norm(x0, out=sb)                                                # F.normalize(iu) / F.normalize(ii)
 
         def contrast_rows(ctx):                                                    # the small launches stay on the main stream:
-            _lib.check(L.gcr_gather_rows_f32(_lib.dptr(ctx), _lib.dptr(gat), 2 * bsz, d, n, _lib.dptr(rows_c), stream),
-                       "gcr_gather_rows_f32")                                      # the fork releases the two big ones together
+            # (the fork releases the two big ones together)
+            _lib.call("gcr_gather_rows_f32", ctx, gat, 2 * bsz, d, n, rows_c, on=stream)
             Fn.row_inv_norm(rows_c, out=sa)
 
         def structure_contrast():
@@ -177,9 +176,7 @@ class FusedNCLStep:
         dldx = torch.empty(max(bsz, 1), dtype=torch.float32, device=dev)
         sums = torch.zeros(5, dtype=torch.float32, device=dev)
         ws = _lib.workspace("gcr_bpr_workspace_floats", bsz, device=dev)
-        _lib.check(L.gcr_bpr_fwd_f32(_lib.dptr(fu), _lib.dptr(fi), d, _lib.dptr(user_idx), _lib.dptr(pos_idx), _lib.dptr(neg_idx),
-                                     bsz, 1, Fn.BPR_NCL, n_u, n_i, _lib.dptr(dldx), _lib.dptr(sums), _lib.dptr(ws), stream),
-                   "gcr_bpr_fwd_f32")
+        _lib.call("gcr_bpr_fwd_f32", fu, fi, d, user_idx, pos_idx, neg_idx, bsz, 1, Fn.BPR_NCL, n_u, n_i, dldx, sums, ws, on=stream)
         rec_loss = sums[0] / bsz
         roots = sums[1:4].sqrt()
         l2 = o_.reg * roots.sum() / bsz                                            # l2_reg_loss(reg, u, p, n)
@@ -215,11 +212,9 @@ class FusedNCLStep:
             Fn._infonce_bwd_raw(xu, sbu, rows_c[:bsz], sa[:bsz], inv_tau, None, None, lse[:bsz], w[:bsz], engine_flag=eng, out=g0[:n_u])
             Fn._infonce_bwd_raw(xi, sbi, rows_c[bsz:], sa[bsz:], inv_tau, None, None, lse[bsz:], w[bsz:], engine_flag=eng, out=g0[n_u:])
             for a_sl, tab, stab, pos, g_tab in ((slice(0, bsz), xu, sbu, user_idx, g0[:n_u]), (slice(bsz, 2 * bsz), xi, sbi, pos_idx, g0[n_u:])):
-                _lib.check(L.gcr_infonce_pos_bwd_f32(_lib.dptr(rows_c[a_sl]), _lib.dptr(sa[a_sl]), _lib.dptr(tab), _lib.dptr(stab),
-                                                     _lib.dptr(pos), _lib.dptr(neg_w[a_sl]), bsz, tab.shape[0], d, inv_tau,
-                                                     None, _lib.dptr(g_tab), st), "gcr_infonce_pos_bwd_f32")
-            _lib.check(L.gcr_normalize_bwd_f32(_lib.dptr(x0), _lib.dptr(sb), _lib.dptr(g0), n, d, _lib.dptr(g0), st),
-                       "gcr_normalize_bwd_f32")
+                _lib.call("gcr_infonce_pos_bwd_f32", rows_c[a_sl], sa[a_sl], tab, stab, pos, neg_w[a_sl], bsz, tab.shape[0], d,
+                          inv_tau, None, g_tab, on=st)
+            _lib.call("gcr_normalize_bwd_f32", x0, sb, g0, n, d, g0, on=st)
 
         neg_w = -w
         if side is not None:
@@ -232,24 +227,20 @@ class FusedNCLStep:
         # anchor side: softmax part = w * inv_tau * o (the flash forward kept o), positives added, then F.normalize backward
         ga = o * (w * inv_tau).unsqueeze(1)
         for a_sl, tab, stab, pos in ((slice(0, bsz), xu, sbu, user_idx), (slice(bsz, 2 * bsz), xi, sbi, pos_idx)):
-            _lib.check(L.gcr_infonce_pos_bwd_f32(_lib.dptr(rows_c[a_sl]), _lib.dptr(sa[a_sl]), _lib.dptr(tab), _lib.dptr(stab),
-                                                 _lib.dptr(pos), _lib.dptr(neg_w[a_sl]), bsz, tab.shape[0], d, inv_tau,
-                                                 _lib.dptr(ga[a_sl]), None, stream), "gcr_infonce_pos_bwd_f32")
-        _lib.check(L.gcr_normalize_bwd_f32(_lib.dptr(rows_c), _lib.dptr(sa), _lib.dptr(ga), 2 * bsz, d, _lib.dptr(ga), stream),
-                   "gcr_normalize_bwd_f32")
+            _lib.call("gcr_infonce_pos_bwd_f32", rows_c[a_sl], sa[a_sl], tab, stab, pos, neg_w[a_sl], bsz, tab.shape[0], d, inv_tau,
+                      ga[a_sl], None, on=stream)
+        _lib.call("gcr_normalize_bwd_f32", rows_c, sa, ga, 2 * bsz, d, ga, on=stream)
 
         # Zg: d total / d final (BPR rows), the only zero-filled [N, d] buffer of the step
         zg = torch.zeros_like(x0)
-        _lib.check(L.gcr_bpr_bwd_f32(_lib.dptr(fu), _lib.dptr(fi), d, _lib.dptr(user_idx), _lib.dptr(pos_idx), _lib.dptr(neg_idx),
-                                     bsz, 1, n_u, n_i, _lib.dptr(dldx), _lib.dptr(gs), _lib.dptr(zg[:n_u]), _lib.dptr(zg[n_u:]),
-                                     stream), "gcr_bpr_bwd_f32")
+        _lib.call("gcr_bpr_bwd_f32", fu, fi, d, user_idx, pos_idx, neg_idx, bsz, 1, n_u, n_i, dldx, gs, zg[:n_u], zg[n_u:],
+                  on=stream)
         # Horner recurrence on A^T in h' = h / c:  h'_K = Zg + g_K / c,  h'_k = Zg + g_k / c + A^T h'_{k+1},  dx0 = c h'_0 + G0
         gt = graph.t
         ga_c = ga * inv_c
 
         def add_ctx(buf):
-            _lib.check(L.gcr_scatter_add_rows_f32(_lib.dptr(ga_c), _lib.dptr(gat), 2 * bsz, d, n, _lib.dptr(buf), stream),
-                       "gcr_scatter_add_rows_f32")
+            _lib.call("gcr_scatter_add_rows_f32", ga_c, gat, 2 * bsz, d, n, buf, on=stream)
 
         h = zg
         # h_K is zero outside the batch rows (<= 3 B, + 2 B context rows when the context layer is the last): the first
@@ -277,13 +268,11 @@ class FusedNCLStep:
 
         # ---- prototype contrast (ncl.py:369-375): InfoNCE(e0[idx], centroid of idx's cluster) * batch_size ----
         rows_0 = torch.empty(2 * bsz, d, dtype=torch.float32, device=dev)
-        _lib.check(L.gcr_gather_rows_f32(_lib.dptr(x0), _lib.dptr(gat), 2 * bsz, d, n, _lib.dptr(rows_0), stream),
-                   "gcr_gather_rows_f32")
+        _lib.call("gcr_gather_rows_f32", x0, gat, 2 * bsz, d, n, rows_0, on=stream)
         # kmeans.index.search(x, 1) for the batch's rows only (ncl.py:371-372 read user_2cluster[user_idx] / item_2cluster[item_idx])
         from .kmeans import assign_to_centroids
         rows_f = torch.empty(2 * bsz, d, dtype=torch.float32, device=dev)
-        _lib.check(L.gcr_gather_rows_f32(_lib.dptr(final), _lib.dptr(gat), 2 * bsz, d, n, _lib.dptr(rows_f), stream),
-                   "gcr_gather_rows_f32")
+        _lib.call("gcr_gather_rows_f32", final, gat, 2 * bsz, d, n, rows_f, on=stream)
         cents = torch.cat([o_.user_centroids[assign_to_centroids(rows_f[:bsz], o_.user_centroids)],
                            o_.item_centroids[assign_to_centroids(rows_f[bsz:], o_.item_centroids)]])
         s0, sc = Fn.row_inv_norm(rows_0), Fn.row_inv_norm(cents)
@@ -301,15 +290,12 @@ class FusedNCLStep:
         neg_wp = torch.full((2 * bsz,), -wp, dtype=torch.float32, device=dev)
         for lo in (0, bsz):
             sl = slice(lo, lo + bsz)
-            _lib.check(L.gcr_infonce_pos_bwd_f32(_lib.dptr(rows_0[sl]), _lib.dptr(s0[sl]), _lib.dptr(cents[sl]), _lib.dptr(sc[sl]),
-                                                 None, _lib.dptr(neg_wp[sl]), bsz, bsz, d, inv_tau, _lib.dptr(gp[sl]), None,
-                                                 stream), "gcr_infonce_pos_bwd_f32")
-        _lib.check(L.gcr_normalize_bwd_f32(_lib.dptr(rows_0), _lib.dptr(s0), _lib.dptr(gp), 2 * bsz, d, _lib.dptr(gp), stream),
-                   "gcr_normalize_bwd_f32")
+            _lib.call("gcr_infonce_pos_bwd_f32", rows_0[sl], s0[sl], cents[sl], sc[sl], None, neg_wp[sl], bsz, bsz, d, inv_tau,
+                      gp[sl], None, on=stream)
+        _lib.call("gcr_normalize_bwd_f32", rows_0, s0, gp, 2 * bsz, d, gp, on=stream)
         if side is not None:
             main.wait_stream(side)                 # G0 complete
-        _lib.check(L.gcr_scatter_add_rows_f32(_lib.dptr(gp), _lib.dptr(gat), 2 * bsz, d, n, _lib.dptr(g0), stream),
-                   "gcr_scatter_add_rows_f32")
+        _lib.call("gcr_scatter_add_rows_f32", gp, gat, 2 * bsz, d, n, g0, on=stream)
         dx0 = torch.empty_like(x0)
         Fn.spmm_into(gt, h, acc_in=zg, acc_in2=g0, acc_in2_scale=inv_c, acc_out=dx0, acc_scale=c, col_active_bits=bits)
 

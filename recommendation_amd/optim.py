@@ -28,7 +28,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
@@ -53,23 +52,20 @@ class FusedAdam(torch.optim.Optimizer):
                     raise ValueError("at most two extra gradient pieces")
                 g = p.grad.contiguous()
                 ex = [e.contiguous() for e in extra] + [None, None]
+                # the group's values and `step` are user and state_dict data (torch.optim.Adam allows a tensor lr and keeps
+                # `step` as a tensor): these float() / int() convert, they are not wrappers around call-site numbers
+                lr, eps, wd = float(group["lr"]), float(group["eps"]), float(group["weight_decay"])
                 if group.get("capturable"):
                     if "step_dev" not in st:               # state loaded from a non-capturable run
                         if torch.cuda.is_current_stream_capturing():
                             raise RuntimeError("FusedAdam: no device step count yet; run one eager step() before capturing")
                         st["step_dev"] = torch.full((1,), st["step"] - 1, dtype=torch.int64, device=p.device)
                     st["step_dev"].add_(1)
-                    _lib.check(L.gcr_adam_step_dev_f32(_lib.dptr(p), _lib.dptr(g), _lib.dptr(ex[0]), _lib.dptr(ex[1]),
-                                                       _lib.dptr(st["exp_avg"]), _lib.dptr(st["exp_avg_sq"]), p.numel(),
-                                                       float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                                       float(group["weight_decay"]), _lib.dptr(st["step_dev"]), 1.0,
-                                                       _lib.cur_stream(p.device)), "gcr_adam_step_dev_f32")
+                    _lib.call("gcr_adam_step_dev_f32", p, g, ex[0], ex[1], st["exp_avg"], st["exp_avg_sq"], p.numel(), lr,
+                              float(b1), float(b2), eps, wd, st["step_dev"], 1.0, on=p)
                     continue
-                _lib.check(L.gcr_adam_step_f32(_lib.dptr(p), _lib.dptr(g), _lib.dptr(ex[0]), _lib.dptr(ex[1]),
-                                               _lib.dptr(st["exp_avg"]), _lib.dptr(st["exp_avg_sq"]), p.numel(),
-                                               float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                               float(group["weight_decay"]), int(st["step"]), 1.0, _lib.cur_stream(p.device)),
-                           "gcr_adam_step_f32")
+                _lib.call("gcr_adam_step_f32", p, g, ex[0], ex[1], st["exp_avg"], st["exp_avg_sq"], p.numel(), lr,
+                          float(b1), float(b2), eps, wd, int(st["step"]), 1.0, on=p)
         return loss
 
     def sync_step_counts(self):
@@ -123,7 +119,6 @@ class FusedSGD(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
         for group in self.param_groups:
             mu = float(group["momentum"])
             # a torch.optim.SGD state_dict can load these into the group: the kernel implements one setting of them
@@ -143,7 +138,6 @@ class FusedSGD(torch.optim.Optimizer):
                     if first:
                         buf = st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)
                 g = p.grad.contiguous()
-                _lib.check(L.gcr_sgd_momentum_step_f32(_lib.dptr(p), _lib.dptr(g), _lib.dptr(buf), p.numel(),
-                                                       float(group["lr"]), mu, float(group["weight_decay"]), int(first),
-                                                       _lib.cur_stream(p.device)), "gcr_sgd_momentum_step_f32")
+                _lib.call("gcr_sgd_momentum_step_f32", p, g, buf, p.numel(), float(group["lr"]), mu, float(group["weight_decay"]),
+                          first, on=p)
         return loss

@@ -34,6 +34,75 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert lib.gcr_version() >= 100 and lib.gcr_arch() == b"gfx950"
 
 
+def header_prototypes():
+    """{name: (return type, [parameter types], [parameter names])} of every prototype of include/gcr.h, the types as ctypes:
+    any `*` is a pointer (c_void_p; `const char*` as a return type c_char_p), the fixed-width integers, float and double
+    are their ctypes."""
+    import ctypes
+    scalars = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+               "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+
+    def ctype(decl, is_return=False):
+        if "*" in decl:
+            return ctypes.c_char_p if is_return and decl.replace(" ", "") == "constchar*" else ctypes.c_void_p
+        return scalars[decl.replace("const", "").strip()]
+
+    text = open(os.path.join(ROOT, "include", "gcr.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(gcr_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        assert name not in protos, f"{name} is declared twice"
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        split = [re.fullmatch(r"(.*?)(\w+)", p, flags=re.S) for p in params]
+        protos[name] = (ctype(ret, True), [ctype(m.group(1)) for m in split], [m.group(2) for m in split])
+    return protos
+
+
+def package_calls():
+    """{export: whether the call passes on=} for every `_lib.call("gcr_...", ...)` site of the package's sources."""
+    pkg = os.path.join(ROOT, "recommendation_amd")
+    calls = {}
+    for fname in sorted(os.listdir(pkg)):
+        if not fname.endswith(".py"):
+            continue
+        text = open(os.path.join(pkg, fname)).read()
+        for m in re.finditer(r'\bcall\(\s*"(gcr_[a-z0-9_]+)"', text):
+            depth, k = 0, m.end()
+            while depth >= 0:                         # to the call's closing bracket
+                depth += {"(": 1, "[": 1, ")": -1, "]": -1}.get(text[k], 0)
+                k += 1
+            calls.setdefault(m.group(1), set()).add(re.search(r"\bon=", text[m.end():k]) is not None)
+    return calls
+
+
+def test_signature_table_matches_the_header_entry_by_entry():
+    from recommendation_amd import _lib
+    protos = header_prototypes()
+    assert len(protos) >= 123 and sorted(protos) == sorted(_lib.SIGNATURES)
+    for name, (res, args, _) in protos.items():
+        assert _lib.SIGNATURES[name] == (res, args), f"{name}: the table disagrees with include/gcr.h"
+
+
+def test_stream_is_the_last_parameter_exactly_where_the_package_passes_one():
+    from recommendation_amd import _lib
+    protos = header_prototypes()
+    calls = package_calls()
+    assert len(calls) > 60, "the package's call sites were not found"
+    for name, with_on in calls.items():
+        assert len(with_on) == 1, f"{name} is called both with and without on="
+        names = protos[name][2]
+        assert (bool(names) and names[-1] == "stream") == with_on.pop(), f"{name}: on= and the header's `stream` disagree"
+    # the name of a conditional or computed export is not a literal at its call site: those are launches too
+    for name in ("gcr_normalize_bwd_n_f32", "gcr_normalize_bwd_raw_f32"):
+        assert protos[name][2][-1] == "stream"
+    # ... and no export takes a stream anywhere but last
+    for name, (_, _, names) in protos.items():
+        assert "stream" not in names[:-1], name
+        assert name in _lib.SIGNATURES
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from recommendation_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
