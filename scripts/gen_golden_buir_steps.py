@@ -2,8 +2,8 @@
 """TEST INFRASTRUCTURE ONLY — write tests/golden/buir_steps.npz: six training steps of univariate/buir.py run by the
 reference itself.
 
-Runs ONLY where the reference sources are (like scripts/gen_golden_sept_steps.py; the data helpers are
-scripts/gen_golden_mhcn_steps.py's); the fixture is plain data.  buir.py imports as-is.  Per step the statements
+Runs ONLY where the reference sources are (like scripts/gen_golden_sept_steps.py; the data set and the helpers are
+scripts/step_golden.py's); the fixture is plain data.  buir.py imports as-is.  Per step the statements
 buir.py:194-203 of `BUIR.train` (forward, get_loss, zero_grad, backward, Adam step, update_target) are lifted with
 `oracle.gen_golden.load_stmts` and executed unchanged on a `BUIR_NB` and ONE `torch.optim.Adam`; every
 `np.random.random()` rate and `torch.rand` draw of `LGCN_Encoder.forward` is recorded (the way `gen_buir` records one).
@@ -17,39 +17,29 @@ and without the `loss_iu` term (what a dropped part moves).  The keep masks are 
 The seed of the initial state is scanned from 3 + c upward for the first at which no non-zero element of the float64 run's
 FIRST-step gradient is smaller than 10 x Adam's eps (scripts/gen_golden_sept_steps.py says why; rows the batch does not
 reach have a gradient of exactly 0 in either precision and do not move).
-Asserted when the file is written: f32 and f64 losses within 1e-5 relative; each tensor moves by more than
-50 x max(4 x slack, 1e-7) when either part is dropped.
+Asserted when the file is written: f32 and f64 losses within 1e-5 relative; the sensitivity rule of
+tests/step_pins.py for either dropped part.
 
 One component case for the kernel test: B = 130 positions with recurring ids over 70 x 50 rows of the first configuration's
 propagated tables, d = 64: the reference's predictor and `get_loss` on the gathered rows, its autograd gradients in float64
-(dW, dbias, the two table gradients), and the float32 drift of each (max |f32 - f64| / S, S = max |f64|; 4 for the loss).
-
-Usage:  python scripts/gen_golden_buir_steps.py [--out DIR]
-"""
+(dW, dbias, the two table gradients), and the float32 drift of each (max |f32 - f64| / S, S = max |f64|; 4 for the loss)."""
 import os
 import random
-import sys
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
-sys.path.insert(0, HERE)
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, load_stmts  # noqa: E402
-import gen_golden_mhcn_steps as mh  # noqa: E402
+from step_pins import BUIR_TENSORS as TENSORS  # noqa: E402
 import buir  # noqa: E402   (oracle.gen_golden puts the reference's univariate/ on sys.path)
 
-OUT = os.path.join(HERE, "..", "tests", "golden")
 PATH = os.path.join(REF, "univariate", "buir.py")
 
 BATCH, STEPS, BATCH_SEED, DRAW_SEED = 128, 6, 5, 23
 MIN_FIRST_GRAD = 1e-7       # 10 x Adam's eps
 BASE = {"lr": 1e-3, "drop_rate": 0.2}
 CONFIGS = [dict(n_layer=2, d=64, tau=0.5), dict(n_layer=3, d=32, tau=0.1)]
-TENSORS = ("online_encoder.embedding_dict.user_emb", "online_encoder.embedding_dict.item_emb",
-           "target_encoder.embedding_dict.user_emb", "target_encoder.embedding_dict.item_emb", "predictor.weight",
-           "predictor.bias")
 BODY = load_stmts(PATH, "BUIR.train", 194, 203)
 
 
@@ -120,13 +110,7 @@ def keep_of(rate, rand):
 
 def reference_batches(data, seed):
     random.seed(seed)
-    out = []
-    for u, i, j in buir.next_batch_pairwise(data, BATCH):
-        if len(out) == STEPS:
-            break
-        assert len(u) == BATCH
-        out.append((list(u), list(i), list(j)))
-    return out
+    return sg.first_batches(buir.next_batch_pairwise(data, BATCH), STEPS, BATCH, lambda b: tuple(list(t) for t in b))
 
 
 def component_case(data, out):
@@ -169,19 +153,16 @@ def component_case(data, out):
 
 def main(out_dir):
     rng = np.random.default_rng(20261018)
-    train, _ = mh.synthetic_lists(rng)
+    train, _ = sg.synthetic_lists(rng)
     data = buir.Interaction({}, train, train[:10])
-    assert (data.user_num, data.item_num) == (mh.N_USERS, mh.N_ITEMS)
+    assert (data.user_num, data.item_num) == (sg.N_USERS, sg.N_ITEMS)
     assert len(set((t[0], t[1]) for t in train)) < len(train), "expected a duplicate interaction"
     batches = reference_batches(data, BATCH_SEED)
-    out = dict(train_user=np.array([t[0] for t in train]), train_item=np.array([t[1] for t in train]),
-               user_ids=np.array([data.id2user[k] for k in range(mh.N_USERS)]),
-               item_ids=np.array([data.id2item[k] for k in range(mh.N_ITEMS)]),
+    out = dict(sg.id_arrays(train, data),
                steps=STEPS, batch_size=BATCH, configs=len(CONFIGS), batch_seed=BATCH_SEED, draw_seed=DRAW_SEED,
                **{f"hp/{k}": v for k, v in BASE.items()})
-    for n, (u, i, _) in enumerate(batches):
-        out[f"batch{n}_users"], out[f"batch{n}_items"] = np.array(u, dtype=np.int16), np.array(i, dtype=np.int16)
-        assert len(set(u)) < len(u) or len(set(i)) < len(i)
+    sg.store_batches(out, batches, ("users", "items"), np.int16)
+    assert all(len(set(u)) < len(u) or len(set(i)) < len(i) for u, i, _ in batches)
 
     for c, cfg in enumerate(CONFIGS):
         pre = f"c{c}/"
@@ -207,31 +188,13 @@ def main(out_dir):
                   "iu": run(data, cfg, torch.float64, seed, batches, drop="iu")[1]}
         init = {k: v.detach().numpy().copy() for k, v in build(data, cfg, torch.float32, seed).state_dict().items()}
         for k in TENSORS:
-            assert init[k].dtype == np.float32
-            delta = (p64[k] - init[k].astype(np.float64)).astype(np.float32)
-            assert np.abs(init[k].astype(np.float64) + delta.astype(np.float64) - p64[k]).max() < 2e-9
-            if not k.startswith("target_encoder"):                          # _init_target: the targets start as copies
-                out[f"{pre}init/{k}"] = init[k]
-            else:
-                assert np.array_equal(init[k], init[k.replace("target_encoder", "online_encoder")])
-            out[f"{pre}f64/delta/{k}"] = delta
-            slack = out[f"{pre}slack/{k}"] = float(np.abs(p32[k] - p64[k]).max())
-            atol = max(4 * slack, 1e-7)
-            row = [f"{k:45s} slack {slack:.3g}"]
-            for part, final in finals.items():
-                d = out[f"{pre}delta_{part}/{k}"] = float(np.abs(final[k] - p64[k]).max())
-                row.append(f"d_{part} {d:.3g} ({d / atol:.0f}x)")
-                assert d > 50 * atol, (k, part, d, atol)
-            print("  " + "  ".join(row))
+            online = k.replace("target_encoder", "online_encoder")          # _init_target: the targets start as copies,
+            assert np.array_equal(init[k], init[online])                    # so only the online ones are stored
+            sg.record_table(out, pre, "buir", k, p64[k], p32[k], finals, init=init[k], store_init=k == online)
 
     component_case(data, out)
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "buir_steps.npz")
-    np.savez_compressed(path, **out)
-    size = os.path.getsize(path)
-    print("wrote", os.path.abspath(path), size, "bytes")
-    assert size < 1_000_000
+    sg.save(out_dir, "buir_steps", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

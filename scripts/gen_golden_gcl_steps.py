@@ -9,25 +9,19 @@ EdgeRemoving views, forward, symmetric InfoNCE over all users and all items, BPR
 
 Two runs from the same initial weights and batches:
   * float64 — the reference functions are dtype-agnostic; this is the trajectory tests compare against;
-  * float32 — kept for information: how far plain fp32 arithmetic drifts from float64 over the same five steps (the
-    tests size their parameter tolerance from it).
-EdgeRemoving's draws do not reach the outputs: GRACEModel.encode ignores its edges (gcl.py:53-57), so z1 == z2.
-
-Usage:  python scripts/gen_golden_gcl_steps.py [--out DIR]
-"""
+  * float32 — kept whole: how far plain fp32 arithmetic drifts from float64 over the same five steps is the slack the
+    tests size their parameter tolerance from (tests/step_pins.py; this fixture stores f32/final in place of a slack).
+EdgeRemoving's draws do not reach the outputs: GRACEModel.encode ignores its edges (gcl.py:53-57), so z1 == z2."""
 import os
-import sys
 import tempfile
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, load_stmts  # noqa: E402  (puts the reference directory on sys.path)
-
-OUT = os.path.join(HERE, "..", "tests", "golden")
+from step_pins import GCL_TERMS as TERMS  # noqa: E402
 
 N_USERS, N_ITEMS, N_TRAIN, N_TEST = 300, 200, 3000, 400
 EMB, LAYERS, STEPS = 64, 2, 5
@@ -71,11 +65,8 @@ def main(out_dir):
 
     # the batches: the reference's own sampler (gcl.py:111-125), seeded
     np.random.seed(7)
-    batches = []
-    for n, b in enumerate(gcl.next_batch_pairwise(train_df, CONFIG["batch_size"], num_users, num_items, user_pos)):
-        if n == STEPS:
-            break
-        batches.append(tuple(t.clone() for t in b))
+    batches = sg.first_batches(gcl.next_batch_pairwise(train_df, CONFIG["batch_size"], num_users, num_items, user_pos), STEPS,
+                               CONFIG["batch_size"], lambda b: tuple(t.clone() for t in b))
 
     torch.manual_seed(11)
     init = gcl.GRACEModel(num_users, num_items, emb_size=EMB, num_layers=LAYERS)
@@ -87,8 +78,7 @@ def main(out_dir):
                **{f"config_{k}": v for k, v in CONFIG.items()})
     for k, v in init_state.items():
         out[f"init/{k}"] = v.numpy()
-    for n, (u, p, q) in enumerate(batches):
-        out[f"batch{n}_users"], out[f"batch{n}_pos"], out[f"batch{n}_neg"] = u.numpy(), p.numpy(), q.numpy()
+    sg.store_batches(out, batches, ("users", "pos", "neg"), np.int64)
 
     for tag, dtype in (("f64", torch.float64), ("f32", torch.float32)):
         model = gcl.GRACEModel(num_users, num_items, emb_size=EMB, num_layers=LAYERS)
@@ -100,7 +90,7 @@ def main(out_dir):
                   info_nce_loss=gcl.info_nce_loss, config=dict(CONFIG))
         torch.manual_seed(3)                                  # EdgeRemoving's draws (no effect on the outputs)
         model.train()
-        rec = {k: [] for k in ("ssl_loss", "bpr_loss", "reg_loss", "total_loss")}
+        rec = {k: [] for k in TERMS}
         for n, (u, p, q) in enumerate(batches):
             ns.update(n=n, users=u, pos_items=p, neg_items=q)
             exec(body, ns)
@@ -114,11 +104,8 @@ def main(out_dir):
 
     drift = {k: float(np.abs(out[f"f32/final/{k}"] - out[f"f64/final/{k}"]).max()) for k in init_state}
     print("max |f32 - f64| of the final parameters:", drift)
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "gcl_steps.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", os.path.abspath(path), os.path.getsize(path), "bytes")
+    sg.save(out_dir, "gcl_steps", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

@@ -35,7 +35,7 @@ Per configuration, from the same float32 xavier tables (one pair per width):
   * float64 reruns with reg_weight = 0 (and for B with weight_decay = 0): max |delta final| per table, what a dropped term
     would move.
 Asserted here and stored: every table moved by more than 100 x max(slack, 1e-7); every sensitivity figure is above
-40 x max(slack, 1e-7), ten times the tests' tolerance 4 x max(slack, 1e-7).
+DROPPED_CPU = 10 times the tests' tolerance (`atol_floor_4` of tests/step_pins.py).
 
 The seed of a width's tables is scanned from 100 + d upward for the first at which, in every Adam configuration of that
 width, no element of the gradient that Adam's first step sees (the float64 run's step-0 gradient plus weight_decay x the
@@ -47,13 +47,9 @@ one with |g| = 1.6e-7, against 3e-8 to 5e-8 where no such element decides (D, pl
 one draw of that lottery is no yardstick for another float32 implementation, in either direction
 (scripts/gen_golden_sept_steps.py, which scans at 1e-7 for lr = 1e-3; the amplification grows with lr / |g|^2, so
 lr = 1e-2 takes sqrt(10) x 1e-7).  About 4400 seeds are tried at d = 64 (a minute in all); the seeds kept and the smallest
-|g| are stored.
-
-Usage:  python scripts/gen_golden_lightgcn_steps.py [--out DIR]
-"""
+|g| are stored."""
 import ast
 import os
-import sys
 import tempfile
 import zipfile
 
@@ -61,11 +57,11 @@ import numpy as np
 import pandas as pd
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, load_defs, load_stmts  # noqa: E402
+import step_pins as sp  # noqa: E402
+from step_pins import LIGHTGCN_TABLES as TABLES  # noqa: E402
 
-OUT = os.path.join(HERE, "..", "tests", "golden")
 PATH = os.path.join(REF, "lightgcn.py")
 
 N_USERS, N_ITEMS, N_TRAIN, N_DUP, STEPS = 120, 72, 1200, 8, 6
@@ -73,7 +69,6 @@ ISO_USER, ISO_ITEM = 57, 30
 HEAVY_USER, HEAVY_USER_DEG, HUB_DEGREE = 7, 45, 40
 NEG_SEED = 7
 MIN_FIRST_GRAD = 3.2e-7     # see the module docstring
-FLOOR = 1e-7
 # every value is one of lightgcn.py:143-152's param_grid; A is its default_config
 CONFIGS = {
     "A": dict(embedding_dim=64, num_layers=3, loss_type="bpr", n_neg=1, optimizer="Adam", lr=0.01, reg_weight=1e-4,
@@ -85,7 +80,6 @@ CONFIGS = {
     "D": dict(embedding_dim=64, num_layers=4, loss_type="bpr", n_neg=1, optimizer="SGD", lr=0.05, reg_weight=1e-4,
               weight_decay=0.0),
 }
-TABLES = ("user", "item")
 
 
 class LGConv(torch.nn.Module):
@@ -259,31 +253,17 @@ def main(out_dir):
         if cfg["weight_decay"]:
             reruns["wd"] = ref.run(dict(cfg, weight_decay=0.0), init, torch.float64)[3]
         for k in TABLES:
-            i64 = init[k].numpy().astype(np.float64)
-            delta = (p64[k] - i64).astype(np.float32)
-            assert np.abs(i64 + delta.astype(np.float64) - p64[k]).max() < 4e-9
-            out[f"{pre}f64/grad0/{k}"], out[f"{pre}f64/delta/{k}"] = g64[k], delta
-            slack = out[f"{pre}slack/{k}"] = float(np.abs(p32[k] - p64[k]).max())
+            out[f"{pre}f64/grad0/{k}"] = g64[k]
             drift = out[f"{pre}drift/{k}"] = float(np.abs(g32[k] - g64[k]).max() / np.abs(g64[k]).max())
-            moved = out[f"{pre}moved/{k}"] = float(np.abs(p64[k] - i64).max())
-            unit = max(slack, FLOOR)
-            assert moved > 100 * unit, (c, k, moved, slack)
-            row = [f"{k:4s} slack {slack:.3g} grad drift {drift:.3g} moved {moved:.3g} ({moved / unit:.0f}x)"]
-            for term, final in reruns.items():
-                dlt = out[f"{pre}delta_{term}/{k}"] = float(np.abs(final[k] - p64[k]).max())
-                row.append(f"d_{term} {dlt:.3g} ({dlt / (4 * unit):.0f}x tol)")
-                assert dlt > 40 * unit, (c, k, term, dlt, slack)
-            print("  " + "  ".join(row))
+            moved = out[f"{pre}moved/{k}"] = float(np.abs(p64[k] - init[k].numpy().astype(np.float64)).max())
+            slack = sg.record_table(out, pre, "lightgcn", k, p64[k], p32[k], reruns, init=init[k].numpy(), store_init=False,
+                                    exact=4e-9, factor=sp.DROPPED_CPU, extra=f" grad drift {drift:.3g} moved {moved:.3g}")
+            assert sp.has_moved(moved, max(slack, sp.FLOOR)), (c, k, moved, slack)
         # the isolated user: no gradient at all; the isolated item: a gradient that comes through no edge
         assert not g64["user"][ISO_USER].any() and g64["item"][ISO_ITEM].any()
 
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "lightgcn_steps.npz")
-    save_npz(path, out)
-    size = os.path.getsize(path)
-    print("wrote", os.path.abspath(path), size, "bytes")
-    assert size < 1_000_000
+    sg.save(out_dir, "lightgcn_steps", out, write=save_npz)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

@@ -18,86 +18,33 @@ The data: 200 users, 120 items with a planted group structure; one repeated inte
 pair (2 in S), two social pairs naming a user that is not in the training set (dropped by `Relation.__initialize`).
 Asserted: H_p is not empty, and every channel operator has users with an empty row.
 
-Per configuration, from the same float32 initial parameters:
-  * float64 (parameters and operators cast): per-step losses and the final value of all 20 parameters — stored as
-    `delta = float32(final - init)`: |delta| < 1e-2, so `init + delta` gives the float64 final value to 1e-9 absolute,
-    in half the bytes;
-  * float32: per-step losses, and one number per parameter, slack = max |f32 - f64| of its final value;
-  * float64 with ss_rate = 0 and with reg_lambda = 0: max |delta final| per parameter — what a dropped term would move.
-Asserted when the file is written: losses of f32 and f64 within 1e-5 relative; every parameter a term reaches moves by
-more than 50 x max(4 x slack, 1e-7) when the term is dropped; `sgating_bias.4` stays exactly 0 and `sgating_weights.4`
-moves through the regulariser alone.
-
-Usage:  python scripts/gen_golden_mhcn_steps.py [--out DIR]
-"""
+Per configuration, from the same float32 initial parameters, what tests/step_pins.py describes: a float64 run (operators
+cast too; the 20 finals as float32(final - init), |delta| < 1e-2, exact to 1e-9), a float32 run, float64 reruns with
+ss_rate = 0 and with reg_lambda = 0.  Asserted when the file is written: losses of f32 and f64 within 1e-5 relative; its
+sensitivity rule; `sgating_bias.4` stays exactly 0 and `sgating_weights.4` moves through the regulariser alone."""
 import copy
 import math
 import os
 import random
-import sys
 from collections import defaultdict
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, _lift_class_methods, load_stmts  # noqa: E402
+from step_golden import N_ITEMS, N_TRAIN, N_USERS  # noqa: E402
+from step_pins import MHCN_TERMS as TERMS, MHCN_UNREACHED as UNREACHED  # noqa: E402
 
-OUT = os.path.join(HERE, "..", "tests", "golden")
 PATH = os.path.join(REF, "univariate", "mhcn.py")
 
-N_USERS, N_ITEMS, N_TRAIN, BATCH, STEPS, GROUPS = 200, 120, 1400, 128, 6, 5
+BATCH, STEPS = 128, 6
 # mhcn.py:564-571's grid; reg_lambda = 1e-2 so that the 20 norms move every parameter well past float32 rounding
 BASE = {"lr": 1e-3, "reg_lambda": 1e-2, "ss_rate": 0.01}
 CONFIGS = [dict(n_layer=2, d=64), dict(n_layer=3, d=32)]
-TERMS = ("rec_loss", "reg_loss", "ss_loss", "total_loss")
 METHODS = {"build", "build_hyper_adj_mats", "self_gating", "self_supervised_gating", "channel_attention", "forward",
            "hierarchical_self_supervision", "sparse_mx_to_torch_sparse_tensor"}
-UNREACHED = {"ss": {"sgating_weights.4", "sgating_bias.4"}, "reg": {"sgating_bias.4"}}
-
-
-def synthetic_lists(rng):
-    """(train triples, social triples) over raw integer ids."""
-    raw_u = np.sort(rng.choice(np.arange(10_000, 99_999), N_USERS + 2, replace=False))
-    ghosts, raw_u = raw_u[[7, 150]], np.delete(raw_u, [7, 150])           # two ids that never interact
-    raw_i = np.sort(rng.choice(np.arange(100_000, 999_999), N_ITEMS, replace=False))
-    pairs = {(u, int(rng.integers(0, N_ITEMS))) for u in range(N_USERS)}
-    pairs |= {(int(rng.integers(0, N_USERS)), i) for i in range(N_ITEMS)}
-    while len(pairs) < N_TRAIN:
-        u = int(rng.integers(0, N_USERS))
-        i = int(rng.integers(0, N_ITEMS // GROUPS)) * GROUPS + u % GROUPS if rng.random() < 0.8 \
-            else int(rng.integers(0, N_ITEMS))
-        pairs.add((u, i))
-    pairs = sorted(pairs)
-    rng.shuffle(pairs)
-    train = [[int(raw_u[u]), int(raw_i[i]), 1.0] for u, i in pairs]
-    train.append(list(train[0]))                                           # a repeated interaction: 2 in Y
-    soc = set()
-    while len(soc) < 1200:
-        a = int(rng.integers(0, N_USERS))
-        b = (a + GROUPS * int(rng.integers(1, 12))) % N_USERS if rng.random() < 0.7 else int(rng.integers(0, N_USERS))
-        if a != b:
-            soc.add((a, b))
-    soc = sorted(soc)
-    rng.shuffle(soc)
-    have = set(soc)
-    soc = soc + [(b, a) for a, b in soc[:400] if (b, a) not in have]       # reciprocated pairs (B of mhcn.py:343)
-    social = [[int(raw_u[a]), int(raw_u[b]), 1.0] for a, b in soc]
-    social.insert(100, list(social[3]))                                    # a repeated social pair: 2 in S
-    social.insert(50, [int(ghosts[0]), int(raw_u[1]), 1.0])                # unknown follower
-    social.append([int(raw_u[2]), int(ghosts[1]), 1.0])                    # unknown followee
-    return train, social
-
-
-def csr_dict(prefix, m):
-    m = m.tocsr().astype(np.float32)
-    m.sum_duplicates()
-    m.sort_indices()
-    m.eliminate_zeros()
-    return {f"{prefix}_indptr": m.indptr.astype(np.int32), f"{prefix}_indices": m.indices.astype(np.int16),
-            f"{prefix}_data": m.data.astype(np.float32), f"{prefix}_shape": np.array(m.shape, dtype=np.int32)}
 
 
 class Reference:
@@ -152,7 +99,7 @@ class Reference:
 def main(out_dir):
     ref = Reference()
     rng = np.random.default_rng(20261018)
-    train, social = synthetic_lists(rng)
+    train, social = sg.synthetic_lists(rng)
     probe = ref.model(train, social, CONFIGS[0], BASE, torch.float32, 0)
     data = probe.data
     assert (data.user_num, data.item_num) == (N_USERS, N_ITEMS) and len(train) == N_TRAIN + 1
@@ -163,27 +110,18 @@ def main(out_dir):
 
     # the batches: the reference's own sampler (mhcn.py:13-31), seeded; the first six (all full)
     random.seed(7)
-    batches = []
-    for u, p, q in ref.ns["next_batch_pairwise"](data, BATCH):
-        if len(batches) == STEPS:
-            break
-        assert len(u) == BATCH
-        batches.append((u, p, q))
+    batches = sg.first_batches(ref.ns["next_batch_pairwise"](data, BATCH), STEPS, BATCH)
 
-    out = dict(train_user=np.array([t[0] for t in train]), train_item=np.array([t[1] for t in train]),
-               social_follower=np.array([t[0] for t in social]), social_followee=np.array([t[1] for t in social]),
-               user_ids=np.array([data.id2user[k] for k in range(N_USERS)]),
-               item_ids=np.array([data.id2item[k] for k in range(N_ITEMS)]),
+    out = dict(sg.id_arrays(train, data, social),
                S_row=np.array([data.user[p[0]] for p in kept], dtype=np.int16),
                S_col=np.array([data.user[p[1]] for p in kept], dtype=np.int16),
                steps=STEPS, batch_size=BATCH, configs=len(CONFIGS), **{f"hp/{k}": v for k, v in BASE.items()})
-    for n, (u, p, q) in enumerate(batches):
-        out[f"batch{n}_users"], out[f"batch{n}_pos"], out[f"batch{n}_neg"] = (t.numpy().astype(np.int16) for t in (u, p, q))
+    sg.store_batches(out, batches, ("users", "pos", "neg"), np.int16)
     nnz = {}
     for name in ("H_s", "H_j", "H_p", "R"):
         t = getattr(probe, name).coalesce()
         mat = sp.csr_matrix((t.values().numpy(), tuple(t.indices().numpy())), shape=tuple(t.shape))
-        out.update(csr_dict(name, mat))
+        out.update(sg.csr_dict(name, mat))
         nnz[name] = int(out[f"{name}_data"].size)
         if name != "R":
             assert nnz[name] > 0 and (np.diff(out[f"{name}_indptr"]) == 0).any(), f"{name}: needs entries and an empty row"
@@ -206,32 +144,13 @@ def main(out_dir):
         finals = {"ss": ref.run(train, social, cfg, dict(BASE, ss_rate=0.0), torch.float64, seed, batches)[1],
                   "reg": ref.run(train, social, cfg, dict(BASE, reg_lambda=0.0), torch.float64, seed, batches)[1]}
         for k in names:
-            assert init[k].dtype == np.float32
-            delta = (p64[k] - init[k].astype(np.float64)).astype(np.float32)
-            assert np.abs(delta).max() < 1e-2 or k == "sgating_bias.4"
-            assert np.abs(init[k].astype(np.float64) + delta.astype(np.float64) - p64[k]).max() < 1e-9
-            out[f"{pre}init/{k}"], out[f"{pre}f64/delta/{k}"] = init[k], delta
-            slack = out[f"{pre}slack/{k}"] = float(np.abs(p32[k] - p64[k]).max())
-            atol = max(4 * slack, 1e-7)
-            row = [f"{k:20s} slack {slack:.3g}"]
-            for term, final in finals.items():
-                d = out[f"{pre}delta_{term}/{k}"] = float(np.abs(final[k] - p64[k]).max())
-                row.append(f"d_{term} {d:.3g} ({d / atol:.0f}x)")
-                if k in UNREACHED[term]:
-                    assert d == 0.0, (k, term, d)
-                else:
-                    assert d > 50 * atol, (k, term, d, atol)
-            print("  " + "  ".join(row))
+            sg.record_table(out, pre, "mhcn", k, p64[k], p32[k], finals, init=init[k], exact=1e-9, unreached=UNREACHED)
+            assert np.abs(out[f"{pre}f64/delta/{k}"]).max() < 1e-2 or k == "sgating_bias.4"
         assert not p64["sgating_bias.4"].any() and not init["sgating_bias.4"].any()
         assert np.abs(p64["sgating_weights.4"] - init["sgating_weights.4"]).max() > 1e-3
 
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "mhcn_steps.npz")
-    np.savez_compressed(path, **out)
-    size = os.path.getsize(path)
-    print("wrote", os.path.abspath(path), size, "bytes")
-    assert size < 1_000_000
+    sg.save(out_dir, "mhcn_steps", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

@@ -22,23 +22,17 @@ Per configuration, two runs from the same float32 initial tables (the sparse adj
   * float64: the trajectory tests compare against (per-step losses and the final tables);
   * float32: kept as one number per table, slack = max |f32 - f64| of the final table (tests size their tolerance on it).
 Then three float64 reruns with ssl_reg = 0, proto_reg = 0 and reg = 0 store max |delta final| per table: what a dropped
-term would move, so that a test can show its tolerance would see it.
-
-Usage:  python scripts/gen_golden_ncl_steps.py [--out DIR]
-"""
+term would move; the sensitivity rule of tests/step_pins.py is asserted on them when the file is written."""
 import os
 import random
-import sys
 import types
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, load_defs, load_stmts  # noqa: E402  (puts the reference directory on sys.path)
-
-OUT = os.path.join(HERE, "..", "tests", "golden")
+from step_pins import NCL_TERMS as TERMS  # noqa: E402
 
 N_USERS, N_ITEMS, N_TRAIN, BATCH, STEPS = 200, 120, 1000, 128, 6
 # the raw 0/1 adjacency (ncl.py:76-85) multiplies row norms by about the degree per layer: the xavier tables are scaled
@@ -57,21 +51,6 @@ CONFIGS = [dict(n_layers=3, hyper_layers=1, d=64),      # context = emb_list[2],
            dict(n_layers=3, hyper_layers=2, d=64),      # hyper_layers * 2 >= len(emb_list): emb_list[-1]
            dict(n_layers=2, hyper_layers=1, d=128)]     # emb_list[2] is the last layer, reached by index; d = 128 engine
 SENSITIVITY = ("ssl_reg", "proto_reg", "reg")
-
-
-def synthetic_pairs(rng):
-    """Unique (user, item) pairs with a planted group structure; every user and every item occurs."""
-    groups = 5
-    pairs = {(u, int(rng.integers(0, N_ITEMS))) for u in range(N_USERS)}
-    pairs |= {(int(rng.integers(0, N_USERS)), i) for i in range(N_ITEMS)}
-    while len(pairs) < N_TRAIN:
-        u = int(rng.integers(0, N_USERS))
-        i = int(rng.integers(0, N_ITEMS // groups)) * groups + u % groups if rng.random() < 0.8 \
-            else int(rng.integers(0, N_ITEMS))
-        pairs.add((u, i))
-    pairs = sorted(pairs)
-    rng.shuffle(pairs)
-    return np.array(pairs, dtype=np.int64)
 
 
 def nearest(x, cent):
@@ -122,7 +101,7 @@ def run(ref, directau, data, cfg, hp, init, cents, batches, dtype):
     body = load_stmts(os.path.join(REF, "ncl.py"), "NCLModel.train", 311, 329)
     ns = dict(ref, model=model, optimizer=optimizer, self=self, device=torch.device("cpu"))
     model.train()
-    losses = {k: [] for k in ("rec_loss", "ssl_loss", "proto_loss", "total_loss")}
+    losses = {k: [] for k in TERMS}
     score_gap = 0.0
     for n, batch in enumerate(batches):
         state["batch"] = batch
@@ -142,7 +121,7 @@ def main(out_dir):
                     methods={"NCLModel.ssl_layer_loss", "NCLModel.ProtoNCE_loss"})
     ref.update(shuffle=random.shuffle, choice=random.choice)     # ncl.py:5 `from random import shuffle, choice`
     rng = np.random.default_rng(20261016)
-    pairs = synthetic_pairs(rng)
+    pairs = sg.synthetic_pairs(rng, N_USERS, N_ITEMS, N_TRAIN, 5)
     raw_u = rng.choice(np.arange(10_000, 99_999), N_USERS, replace=False)      # raw ids: their sorted order is the dense one
     raw_i = rng.choice(np.arange(100_000, 999_999), N_ITEMS, replace=False)
     train = [[int(raw_u[u]), int(raw_i[i]), 1.0] for u, i in pairs]
@@ -151,20 +130,13 @@ def main(out_dir):
 
     # the batches: the reference's own sampler (ncl.py:91-114), seeded; full batches only (len(batch) == batch.size)
     random.seed(7)
-    batches = []
-    for u, p, q in ref["next_batch_pairwise"](data, BATCH):
-        if len(batches) == STEPS:
-            break
-        assert len(u) == BATCH
-        batches.append(tuple(torch.tensor(t, dtype=torch.int64) for t in (u, p, q)))
+    batches = sg.first_batches(ref["next_batch_pairwise"](data, BATCH), STEPS, BATCH,
+                               lambda b: tuple(torch.tensor(t, dtype=torch.int64) for t in b))
 
-    out = dict(train_user=np.array([t[0] for t in train]), train_item=np.array([t[1] for t in train]),
-               user_ids=np.array([data.id2user[k] for k in range(N_USERS)]),
-               item_ids=np.array([data.id2item[k] for k in range(N_ITEMS)]),
+    out = dict(sg.id_arrays(train, data),
                steps=STEPS, batch_size=BATCH, init_scale=INIT_SCALE, min_gap_required=MIN_GAP, configs=len(CONFIGS),
                **{f"hp/{k}": v for k, v in BASE.items()})
-    for n, (u, p, q) in enumerate(batches):
-        out[f"batch{n}_users"], out[f"batch{n}_pos"], out[f"batch{n}_neg"] = u.numpy(), p.numpy(), q.numpy()
+    sg.store_batches(out, batches, ("users", "pos", "neg"), np.int64)
 
     inits = {}
     for c, cfg in enumerate(CONFIGS):
@@ -203,27 +175,15 @@ def main(out_dir):
         for k in res["f64"][0]:
             out[f"{pre}f64/{k}"] = np.array(res["f64"][0][k], dtype=np.float64)
             out[f"{pre}f32/{k}"] = np.array(res["f32"][0][k], dtype=np.float64)
-        slack = {}
-        for k, v in res["f64"][1].items():
-            out[f"{pre}f64/final/{k}"] = v
-            slack[k] = out[f"{pre}slack/{k}"] = float(np.abs(res["f32"][1][k] - v).max())
         print(f"config {c} {cfg}: min assignment gap {gap:.3g}, max |pos - neg score| {out[pre + 'max_score_diff']:.3g}")
         print("  f64 losses", {k: [f"{x:.6f}" for x in v] for k, v in res["f64"][0].items()})
-        print("  slack max |f32 - f64|:", {k: f"{v:.3g}" for k, v in slack.items()})
-        for term in SENSITIVITY:
-            hp = dict(BASE, **{("reg.lambda" if term == "reg" else f"NCL.{term}"): 0.0})
-            _, final, _, _, _ = run(ref, directau, data, cfg, hp, init, cents, batches, torch.float64)
-            row = []
-            for k, v in final.items():
-                delta = out[f"{pre}delta_{term}/{k}"] = float(np.abs(v - res["f64"][1][k]).max())
-                row.append(f"{k} {delta:.3g} ({delta / max(4 * slack[k], 1e-7):.0f}x tol)")
-            print(f"  sensitivity {term} = 0: max |delta final|", ", ".join(row))
+        reruns = {term: run(ref, directau, data, cfg, dict(BASE, **{("reg.lambda" if term == "reg" else f"NCL.{term}"): 0.0}),
+                            init, cents, batches, torch.float64)[1] for term in SENSITIVITY}
+        for k, v in res["f64"][1].items():
+            sg.record_table(out, pre, "ncl", k, v, res["f32"][1][k], reruns)
 
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "ncl_steps.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", os.path.abspath(path), os.path.getsize(path), "bytes")
+    sg.save(out_dir, "ncl_steps", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

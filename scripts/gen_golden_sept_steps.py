@@ -2,8 +2,8 @@
 """TEST INFRASTRUCTURE ONLY — write tests/golden/sept_steps.npz: eight training steps of univariate/sept_social.py run by
 the reference itself.
 
-Runs ONLY where the reference sources are (like scripts/gen_golden_mhcn_steps.py, whose data and helpers it shares); the
-fixture is plain data.  sept_social.py does not import (tensorflow), so its pieces are taken out of its AST and executed
+Runs ONLY where the reference sources are (the data set and the helpers are scripts/step_golden.py's, shared with the MHCN
+and BUIR fixtures); the fixture is plain data.  sept_social.py does not import (tensorflow), so its pieces are taken out of its AST and executed
 unchanged:
   * `TFGraphInterface`, `GraphAugmentor`, `Graph`, `Relation`, `Interaction`, `bpr_loss`, `next_batch_pairwise` (top level);
   * SEPT's `build`, `get_social_related_views`, `encoder`, `social_encoder`, `label_prediction`, `sampling`,
@@ -31,36 +31,27 @@ is below the median error of its whole user gradient (1.3e-10) and still moved t
 yardstick for another float32 implementation, in either direction; with the element excluded it measures the precision of a
 step, and the tolerance that follows from it is the tighter one.
 Asserted when the file is written: f32 and f64 terms within 1e-5 relative; the f32 run selects the f64 run's label sets; the
-gap and the first-step gradient condition; each table moves by more than 50 x max(4 x slack, 1e-7) when either term is dropped.
-
-Usage:  python scripts/gen_golden_sept_steps.py [--out DIR]
-"""
+gap and the first-step gradient condition; the sensitivity rule of tests/step_pins.py for either dropped term."""
 import copy
 import math
 import os
 import random
-import sys
 from collections import defaultdict
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
-sys.path.insert(0, HERE)
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, _lift_class_methods, load_stmts  # noqa: E402
-import gen_golden_mhcn_steps as mh  # noqa: E402
+from step_pins import SEPT_TABLES as TABLES  # noqa: E402
 
-OUT = os.path.join(HERE, "..", "tests", "golden")
 PATH = os.path.join(REF, "univariate", "sept_social.py")
 
 BATCH, STEPS, PLAIN_STEPS, MAX_EPOCH, TRI_EPOCH, DROP_SEED, MIN_GAP = 128, 8, 2, 6, 3, 11, 1e-5
 MIN_FIRST_GRAD = 1e-7       # 10 x Adam's eps
 BASE = {"lr": 1e-3, "reg_lambda": 1e-4, "ss_rate": 0.005, "drop_rate": 0.3}
 CONFIGS = [dict(n_layer=2, d=64, ins_cnt=10), dict(n_layer=3, d=32, ins_cnt=5)]
-TERMS = ("rec_loss", "neighbor_dis_loss", "total_loss")
-TABLES = ("user_embeddings", "item_embeddings")
 METHODS = {"build", "get_social_related_views", "encoder", "social_encoder", "label_prediction", "sampling",
            "generate_pesudo_labels", "neighbor_discrimination"}
 
@@ -124,22 +115,16 @@ class Reference:
 
     def batches(self, data, seed):
         random.seed(seed)
-        out = []
-        for u, p, q in self.ns["next_batch_pairwise"](data, BATCH):
-            if len(out) == STEPS:
-                break
-            assert len(u) == BATCH
-            out.append((u, p, q))
-        return out
+        return sg.first_batches(self.ns["next_batch_pairwise"](data, BATCH), STEPS, BATCH)
 
 
 def main(out_dir):
     ref = Reference()
     rng = np.random.default_rng(20261018)
-    train, social = mh.synthetic_lists(rng)
+    train, social = sg.synthetic_lists(rng)
     probe = ref.model(train, social, CONFIGS[0], BASE, torch.float32, 0)
     data = probe.data
-    assert (data.user_num, data.item_num) == (mh.N_USERS, mh.N_ITEMS)
+    assert (data.user_num, data.item_num) == (sg.N_USERS, sg.N_ITEMS)
     kept = probe.social_data.relation
     assert len(kept) == len(social) - 2, "the two pairs naming unknown users must be dropped"
     assert probe.social_data.get_social_mat().max() == 2.0 and data.interaction_mat.max() == 2.0
@@ -149,10 +134,7 @@ def main(out_dir):
     n_pairs = len(data.interaction_mat.nonzero()[0])
     assert len(kept_u) == int(n_pairs * (1 - BASE["drop_rate"])) and dropped.max() == 1.0
 
-    out = dict(train_user=np.array([t[0] for t in train]), train_item=np.array([t[1] for t in train]),
-               social_follower=np.array([t[0] for t in social]), social_followee=np.array([t[1] for t in social]),
-               user_ids=np.array([data.id2user[k] for k in range(mh.N_USERS)]),
-               item_ids=np.array([data.id2item[k] for k in range(mh.N_ITEMS)]),
+    out = dict(sg.id_arrays(train, data, social),
                S_row=np.array([data.user[p[0]] for p in kept], dtype=np.int16),
                S_col=np.array([data.user[p[1]] for p in kept], dtype=np.int16),
                Y_row=np.array([data.user[t[0]] for t in train], dtype=np.int16),
@@ -163,7 +145,7 @@ def main(out_dir):
     for name in ("social", "sharing"):
         t = getattr(probe, f"{name}_mat").coalesce()
         mat = sp.csr_matrix((t.values().numpy(), tuple(t.indices().numpy())), shape=tuple(t.shape))
-        out.update(mh.csr_dict(name, mat))
+        out.update(sg.csr_dict(name, mat))
         assert (mat != mat.T).nnz > 0, f"{name}: expected a non-symmetric operator"
 
     for c, cfg in enumerate(CONFIGS):
@@ -185,9 +167,7 @@ def main(out_dir):
             raise AssertionError("no table seed satisfies the first-step gradient condition")
         out[pre + "table_seed"], out[pre + "first_grad"] = seed, first_grad
         out[pre + "batch_seed"], out[pre + "gaps"] = bseed, gaps
-        for n, (u, p, q) in enumerate(batches):
-            out[f"{pre}batch{n}_users"], out[f"{pre}batch{n}_pos"], out[f"{pre}batch{n}_neg"] = \
-                (t.numpy().astype(np.int16) for t in (u, p, q))
+        sg.store_batches(out, batches, ("users", "pos", "neg"), np.int16, prefix=pre)
         l32, p32, lab32, _, _ = ref.run(train, social, cfg, BASE, torch.float32, seed, batches, dropped)
         same = all(np.array_equal(a, b) for a, b in zip(lab64, lab32))
         assert same, "the float32 run selected other label sets than the float64 run"
@@ -205,27 +185,11 @@ def main(out_dir):
         m0 = ref.model(train, social, cfg, BASE, torch.float32, seed)
         for k in TABLES:
             init = getattr(m0, k).detach().numpy().copy()
-            assert init.dtype == np.float32
-            delta = (p64[k] - init.astype(np.float64)).astype(np.float32)
-            assert np.abs(delta).max() < 2e-2
-            assert np.abs(init.astype(np.float64) + delta.astype(np.float64) - p64[k]).max() < 2e-9
-            out[f"{pre}init/{k}"], out[f"{pre}f64/delta/{k}"] = init, delta
-            slack = out[f"{pre}slack/{k}"] = float(np.abs(p32[k] - p64[k]).max())
-            atol = max(4 * slack, 1e-7)
-            row = [f"{k:16s} slack {slack:.3g}"]
-            for term, final in finals.items():
-                d = out[f"{pre}delta_{term}/{k}"] = float(np.abs(final[k] - p64[k]).max())
-                row.append(f"d_{term} {d:.3g} ({d / atol:.0f}x)")
-                assert d > 50 * atol, (k, term, d, atol)
-            print("  " + "  ".join(row))
+            sg.record_table(out, pre, "sept", k, p64[k], p32[k], finals, init=init)
+            assert np.abs(out[f"{pre}f64/delta/{k}"]).max() < 2e-2
 
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "sept_steps.npz")
-    np.savez_compressed(path, **out)
-    size = os.path.getsize(path)
-    print("wrote", os.path.abspath(path), size, "bytes")
-    assert size < 1_000_000
+    sg.save(out_dir, "sept_steps", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

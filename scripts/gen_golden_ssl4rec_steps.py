@@ -26,14 +26,10 @@ parameter with delta >= 10 x (4 x max(slack, 1e-7)); every parameter moved by mo
 The initial draw of a configuration is the first (seeds tried in order) for which that holds and for which slack is a
 stable measure: four more float32 runs of the reference with the rows of every batch permuted — the same sums in another
 order, which is all that the HIP step is — stay within 2 x max(slack, 1e-7) of the float64 run.  Both criteria read the
-reference's runs only.  learning.rate is 1e-5: see the comment at `LR`.
-
-Usage:  python scripts/gen_golden_ssl4rec_steps.py [--out DIR]
-"""
+reference's runs only.  learning.rate is 1e-5: see the comment at `LR`."""
 import ast
 import os
 import random
-import sys
 import types
 from collections import defaultdict
 
@@ -41,13 +37,11 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, ".."))
-sys.path.insert(0, os.path.join(HERE, "..", "tests"))
+import step_golden as sg  # noqa: E402  (puts the repository root and tests/ on sys.path)
 from oracle.gen_golden import REF, load_defs, load_stmts  # noqa: E402  (puts the reference directory on sys.path)
 import ssl4rec_fixture as fx  # noqa: E402
+import step_pins as pins  # noqa: E402
 
-OUT = os.path.join(HERE, "..", "tests", "golden")
 SRC = os.path.join(REF, "ssl4rec.py")
 
 N_USERS, N_ITEMS, N_TRAIN, BATCH, STEPS = 160, 96, 1000, 128, 6
@@ -75,21 +69,6 @@ def load_classes(ns, names):
     wanted = [node for node in tree.body if isinstance(node, ast.ClassDef) and node.name in names]
     assert len(wanted) == len(names)
     exec(compile(ast.Module(body=wanted, type_ignores=[]), SRC, "exec"), ns)
-
-
-def synthetic_pairs(rng):
-    """Unique (user, item) pairs with a planted group structure; every user and every item occurs."""
-    groups = 4
-    pairs = {(u, int(rng.integers(0, N_ITEMS))) for u in range(N_USERS)}
-    pairs |= {(int(rng.integers(0, N_USERS)), i) for i in range(N_ITEMS)}
-    while len(pairs) < N_TRAIN:
-        u = int(rng.integers(0, N_USERS))
-        i = int(rng.integers(0, N_ITEMS // groups)) * groups + u % groups if rng.random() < 0.8 \
-            else int(rng.integers(0, N_ITEMS))
-        pairs.add((u, i))
-    pairs = sorted(pairs)
-    rng.shuffle(pairs)
-    return np.array(pairs, dtype=np.int64)
 
 
 class RecordedDropout(torch.nn.Module):
@@ -147,7 +126,7 @@ def main(out_dir):
     ref.update(shuffle=random.shuffle, choice=random.choice, sp=sp, defaultdict=defaultdict)   # ssl4rec.py:6-8
     load_classes(ref, {"DNNEncoder", "Interaction"})
     rng = np.random.default_rng(20261017)
-    pairs = synthetic_pairs(rng)
+    pairs = sg.synthetic_pairs(rng, N_USERS, N_ITEMS, N_TRAIN, 4)
     raw_u = rng.choice(np.arange(10_000, 99_999), N_USERS, replace=False)       # raw ids in no order: first-seen ids
     raw_i = rng.choice(np.arange(100_000, 999_999), N_ITEMS, replace=False)     # differ from the sorted ones
     train = [[str(raw_u[u]), str(raw_i[i]), 1.0] for u, i in pairs]
@@ -156,19 +135,11 @@ def main(out_dir):
 
     # the batches: the reference's own sampler (ssl4rec.py:33-50), seeded; full batches only
     random.seed(11)
-    batches = []
-    for u, i, j in ref["next_batch_pairwise"](data, BATCH):
-        if len(batches) == STEPS:
-            break
-        assert len(u) == BATCH
-        batches.append((list(u), list(i), list(j)))
+    batches = sg.first_batches(ref["next_batch_pairwise"](data, BATCH), STEPS, BATCH, lambda b: tuple(list(t) for t in b))
 
-    out = dict(train_user=np.array([t[0] for t in train]), train_item=np.array([t[1] for t in train]),
-               user_ids=np.array([data.id2user[k] for k in range(N_USERS)]),
-               item_ids=np.array([data.id2item[k] for k in range(N_ITEMS)]),
+    out = dict(sg.id_arrays(train, data),
                steps=STEPS, batch_size=BATCH, learning_rate=LR, configs=len(CONFIGS))
-    for n, (u, i, _) in enumerate(batches):
-        out[f"batch{n}_users"], out[f"batch{n}_items"] = np.array(u, dtype=np.int64), np.array(i, dtype=np.int64)
+    sg.store_batches(out, batches, ("users", "items"), np.int64)
 
     for c, cfg in enumerate(CONFIGS):
         pre = f"c{c}/"
@@ -202,7 +173,7 @@ def main(out_dir):
             cf = fx.Config({k: np.asarray(v) for k, v in out.items()}, c)      # the reader's view of what is stored so far
             slack = {k: float(np.abs(f32[k] - f64[k]).max()) for k in names}
             moved = {k: float(np.abs(cf.at(k, f64[k]) - cf.at(k, init[k])).max()) for k in names}
-            if not all(moved[k] > 100 * slack[k] for k in names):
+            if not all(pins.has_moved(moved[k], slack[k]) for k in names):
                 print(f"config {c} draw {attempt}: worst slack / moved", max(slack[k] / moved[k] for k in names))
                 continue
             loss_rel = max(float(np.max(np.abs(np.array(l32[k]) - np.array(l64[k])) / np.abs(np.array(l64[k])))) for k in fx.TERMS)
@@ -212,7 +183,7 @@ def main(out_dir):
             # ... and until that slack is a stable measure of float32 drift: the same float32 run with the rows of every
             # batch in another order (the same sums, added in another order) must stay within 2 x slack of float64
             spread = permuted_drift(ref, data, cfg, init, masks, batches, f64)
-            worst = max(spread[k] / max(slack[k], 1e-7) for k in names)
+            worst = max(spread[k] / max(slack[k], pins.FLOOR) for k in names)
             if worst <= 2.0:
                 break
             print(f"config {c} draw {attempt}: a reordered float32 run drifts {worst:.2f} x slack")
@@ -234,17 +205,14 @@ def main(out_dir):
             ratios = []
             for k in names:
                 delta = out[f"{pre}delta_{term}/{k}"] = float(np.abs(cf.at(k, final[k]) - cf.at(k, f64[k])).max())
-                ratios.append(delta / (4 * max(slack[k], 1e-7)))
+                ratios.append(delta / pins.atol_floor_4(slack[k]))
             print(f"  sensitivity {term} = 0: max |delta final| / tolerance per parameter:", [f"{r:.1f}" for r in ratios])
             # at the default reg.weight = 1e-4 the regulariser is below the tolerance (config 0): no claim made there
             if term == "alpha" or cfg["reg_weight"] >= 1e-3:
-                assert max(ratios) >= 10, f"config {c}: dropping {term} stays inside 10 x the tolerance"
+                assert max(ratios) >= pins.DROPPED_CPU, f"config {c}: dropping {term} stays inside 10 x the tolerance"
 
-    os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, "ssl4rec_steps.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", os.path.abspath(path), os.path.getsize(path), "bytes")
+    sg.save(out_dir, "ssl4rec_steps", out)
 
 
 if __name__ == "__main__":
-    main(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT)
+    main(sg.out_dir())

@@ -18,6 +18,8 @@ import zlib
 
 import numpy as np
 
+import step_pins as sp
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "directau_steps.npz")
 GRID = 2.0 ** -12
 SAMPLE = 1024
@@ -139,17 +141,17 @@ class Config:
     def init(self, table):
         return self.g[f"{self.pre}init/{table}"]
 
-    def final(self, table):
-        return self.g[f"{self.pre}f64/final/{table}"]
-
-    def slack(self, table):
-        return float(self.g[f"{self.pre}slack/{table}"])
-
-    def delta(self, term, table):
-        return float(self.g[f"{self.pre}delta_{term}/{table}"])
-
-    def losses(self, run, term):
-        return self.g[f"{self.pre}{run}/{term}"]
+    def record(self):
+        """The trajectory of this configuration as tests/step_pins.py takes it.  pos_loss, neg_loss and l2 at rtol; `loss`,
+        their difference, within REL x (|pos_loss| + |neg_loss|); the MOVED rule; the deltas for the CPU test's claim."""
+        g, p = self.g, self.pre
+        f64, f32 = sp.stack_terms(g, p, TERMS)
+        tol = sp.term_tol(f64)
+        tol[:, TERMS.index("loss")] = sp.difference_tol(f64[:, TERMS.index("pos_loss")], f64[:, TERMS.index("neg_loss")])
+        slack = {k: float(g[f"{p}slack/{k}"]) for k in TABLES}
+        return sp.Record("directau", repr(self), TERMS, f64, f32, {k: g[f"{p}f64/final/{k}"] for k in TABLES}, slack, tol=tol,
+                         dropped={k: {t: float(g[f"{p}delta_{t}/{k}"]) for t in DROPPED} for k in TABLES}, factor=None,
+                         moved={k: (self.init(k), slack[k]) for k in TABLES})
 
 
 def batches(g):

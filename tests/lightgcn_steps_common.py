@@ -5,12 +5,13 @@ import os
 
 import numpy as np
 
+import step_pins as sp
+from step_pins import LIGHTGCN_TABLES as TABLES  # noqa: F401
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lightgcn_steps.npz")
 SIZE_CAP = 1_000_000
 CONFIGS = ("A", "B", "C", "D")
-TABLES = ("user", "item")
 HYPER = ("embedding_dim", "num_layers", "loss_type", "n_neg", "optimizer", "lr", "reg_weight", "weight_decay")
-FLOOR = 1e-7            # of a table's slack: the reference's own |f32 - f64| can be at the rounding level by chance
 _cache = {}
 
 
@@ -32,12 +33,7 @@ def init_table(g, c, k):
 
 def final_table(g, c, k):
     """The float64 run's final table: stored as float32(final - init), exact to 4e-9 (asserted by the generator)."""
-    return init_table(g, c, k).astype(np.float64) + g[f"{c}/f64/delta/{k}"].astype(np.float64)
-
-
-def atol(g, c, k):
-    """4 x the reference's own float32 slack on the table, floored (tests/test_gcl_model_gpu.py explains the rule)."""
-    return 4.0 * max(float(g[f"{c}/slack/{k}"]), FLOOR)
+    return sp.record("lightgcn", g, c).tables[k]
 
 
 def sensitivity_terms(g, c):

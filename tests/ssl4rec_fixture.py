@@ -14,6 +14,8 @@ import zlib
 
 import numpy as np
 
+import step_pins as sp
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ssl4rec_steps.npz")
 GRID = 2.0 ** -12
 SAMPLE = 4096
@@ -96,17 +98,14 @@ class Config:
         full = np.asarray(full)
         return full if idx is None else full.reshape(-1)[idx]
 
-    def final(self, name):
-        return self.g[f"{self.pre}f64/final/{name}"]
-
-    def slack(self, name):
-        return float(self.g[f"{self.pre}slack/{name}"])
-
-    def delta(self, term, name):
-        return float(self.g[f"{self.pre}delta_{term}/{name}"])
-
-    def losses(self, run, term):
-        return self.g[f"{self.pre}{run}/{term}"]
+    def record(self):
+        """The trajectory of this configuration as tests/step_pins.py takes it: finals at the stored entries (`at`), the
+        MOVED rule against the initial values there, the dropped-term deltas for the CPU test's DROPPED_CPU claim."""
+        g, p, names = self.g, self.pre, self.names
+        slack = {k: float(g[f"{p}slack/{k}"]) for k in names}
+        return sp.Record("ssl4rec", f"config {p[1:-1]}", TERMS, *sp.stack_terms(g, p, TERMS), {k: g[f"{p}f64/final/{k}"] for k in names},
+                         slack, dropped={k: {t: float(g[f"{p}delta_{t}/{k}"]) for t in SENSITIVITY} for k in names}, factor=None,
+                         moved={k: (self.at(k, self.init(k)), slack[k]) for k in names})
 
 
 def load():

@@ -3,26 +3,23 @@ tests/golden/buir_steps.npz, written by scripts/gen_golden_buir_steps.py.  Six b
 fixture's initial state with the reference's recorded dropout draws, two configurations (2 layers, d = 64, tau 0.5;
 3 layers, d = 32, tau 0.1).
 
-Tolerances are those of tests/test_sept_model_gpu.py: a loss within max(1e-5 rel, 4 x the reference's own |f32 - f64|), each
-of the six final tensors within 4 x the reference's own f32 slack on it (floored at 1e-7), that tolerance at most 1/50 of
-what dropping `update_target` or the `loss_iu` term moves the tensor."""
-import os
-
+The rule is tests/step_pins.py's (family "buir"): the loss against the reference's float64 and float32 runs, each of the six
+final tensors within `atol_floor_1` of the reference's own f32 slack, that tolerance at most 1/50 of what dropping
+`update_target` or the `loss_iu` term moves the tensor."""
 import numpy as np
 import pytest
 import torch
 
+import step_pins as sp
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "buir_steps.npz")
-NAMES = {"online_encoder.embedding_dict.user_emb": "online_user", "online_encoder.embedding_dict.item_emb": "online_item",
-         "target_encoder.embedding_dict.user_emb": "target_user", "target_encoder.embedding_dict.item_emb": "target_item",
-         "predictor.weight": "weight", "predictor.bias": "bias"}
+NAMES = dict(zip(sp.BUIR_TENSORS, ("online_user", "online_item", "target_user", "target_item", "weight", "bias")))
 
 
 @pytest.fixture(scope="module")
 def steps():
-    return np.load(GOLDEN)
+    return sp.load("buir")
 
 
 def _conf(g, c, batch_size=None):
@@ -31,23 +28,15 @@ def _conf(g, c, batch_size=None):
             "BUIR": {"n_layer": int(g[f"c{c}/n_layer"]), "tau": float(g[f"c{c}/tau"]), "drop_rate": float(g["hp/drop_rate"])}}
 
 
-def _triples(g):
-    return [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
-
-
 def _init_state(g, c):
-    state = {}
-    for k in NAMES:
-        state[k] = g[f"c{c}/init/" + k.replace("target_encoder", "online_encoder")]     # _init_target: copies
-    return state
+    return {k: sp.buir_init(g, c, k) for k in NAMES}
 
 
 def _model(g, c):
     from recommendation_amd.buir import BUIRModel
-    train = _triples(g)
+    train = sp.triples(g)
     m = BUIRModel(_conf(g, c), train, train[:10], device="cuda")
-    assert [m.data.id2user[k] for k in range(m.data.user_num)] == g["user_ids"].tolist()
-    assert [m.data.id2item[k] for k in range(m.data.item_num)] == g["item_ids"].tolist()
+    sp.assert_dense_id_order(m, g)
     assert torch.equal(m.target_user, m.online_user.detach()) and torch.equal(m.target_item, m.online_item.detach())
     m.load_reference_state(_init_state(g, c))
     return m
@@ -75,8 +64,7 @@ def _run(g, c):
     m = _model(g, c)
     got = []
     for n in range(int(g["steps"])):
-        batch = tuple(torch.from_numpy(g[f"batch{n}_{s}"].astype(np.int64)).cuda() for s in ("users", "items"))
-        got.append(m.train_step(batch, views=_views(g, c, m, n)))
+        got.append(m.train_step(sp.batch(g, n, ("users", "items")), views=_views(g, c, m, n)))
     return torch.stack(got).cpu().numpy().astype(np.float64), m
 
 
@@ -84,30 +72,7 @@ def _run(g, c):
 def test_buir_trajectory_matches_reference_float64(steps, c):
     g = steps
     got, m = _run(g, c)
-    report, failures = [f"config {c}:"], []
-    ref, f32 = g[f"c{c}/f64/losses"], g[f"c{c}/f32/losses"]
-    tol = np.maximum(1e-5 * np.abs(ref), 4 * np.abs(f32 - ref))
-    err = np.abs(got - ref)
-    report.append(f"  loss: max err {err.max():.3g} (max rel {np.max(err / np.abs(ref)):.3g})")
-    if not np.all(err <= tol):
-        failures.append(f"loss: got {got.tolist()} reference {ref.tolist()}")
-    init = _init_state(g, c)
-    for k, attr in NAMES.items():
-        final = getattr(m, attr).detach().cpu().numpy().astype(np.float64)
-        assert np.isfinite(final).all(), k
-        want = init[k].astype(np.float64) + g[f"c{c}/f64/delta/{k}"].astype(np.float64)
-        slack = float(g[f"c{c}/slack/{k}"])
-        atol = max(4 * slack, 1e-7)
-        err = float(np.abs(final - want).max())
-        deltas = {t: float(g[f"c{c}/delta_{t}/{k}"]) for t in ("update", "iu")}
-        report.append(f"  {k}: max err {err:.3g} ({err / atol:.2f} x atol {atol:.3g}, reference f32 slack {slack:.3g}); a dropped "
-                      "part moves it by " + ", ".join(f"{t} {v:.3g}" for t, v in deltas.items()))
-        for t, v in deltas.items():                             # a tolerance that would not see a missing part checks nothing
-            assert v > 50 * atol, (k, t, v, atol)
-        if err > atol:
-            failures.append(f"{k}: max |final - f64| = {err:.3g} > atol {atol:.3g}")
-    print("\n".join(report))
-    assert not failures, "\n".join(report + failures)
+    sp.check(sp.record("buir", g, c), got, {k: getattr(m, attr).detach().cpu().numpy() for k, attr in NAMES.items()})
 
     # get_embedding / predict on the final state: the dense float64 formula
     st = {a: getattr(m, a).detach().cpu().double() for a in NAMES.values()}
@@ -159,7 +124,7 @@ def test_the_models_own_draws(steps):
 def test_train_end_to_end_and_state_round_trip(steps):
     from recommendation_amd.buir import BUIRModel
     g = steps
-    train = _triples(g)
+    train = sp.triples(g)
     m = BUIRModel(_conf(g, 1, batch_size=256), train[:1200], train[1200:], device="cuda", seed=2)
     before = m.target_user.clone()
     metrics = m.train()

@@ -4,7 +4,7 @@ steps per configuration, evaluate() and one end-to-end run.
 
 Tolerances.  Values: rtol 1e-5, the project's parity bound.  Gradients and final tables: 4 x max(slack, floor), slack
 being the drift of the reference's OWN float32 run from its float64 run, floor 1e-7 x max |ref| for a gradient tensor and
-1e-7 for a table (the rule of tests/test_gcl_model_gpu.py).  In the two zero-row cases the all-zero row, whose gradient
+1e-7 for a table (the trajectory rule of tests/step_pins.py, family "directau").  In the two zero-row cases the all-zero row, whose gradient
 is ~1e10 (F.normalize divides by eps), is bounded apart from the other rows: slack and max |ref| of the other rows
 exclude it, so the rows it is paired with are held to a bound of their own size.  calculate_loss, the training loss and `mix` are differences
 of an alignment (> 0) and uniformities (< 0): like `loss` in the trajectories they are held to 1e-5 x the sum of the
@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import directau_fixture as fx
+import step_pins as sp
 
 pytestmark = pytest.mark.gpu
 
@@ -101,7 +102,7 @@ def test_components_against_reference_float64(k):
     for obj in fx.OBJECTIVES:
         for tab in fx.TABLES:
             assert np.all(np.isfinite(grads[obj][tab]))
-            tol = 4 * max(c.grad_slack(obj, tab), 1e-7 * c.grad_max(obj, tab))
+            tol = sp.F32 * max(c.grad_slack(obj, tab), sp.FLOOR * c.grad_max(obj, tab))
             err = float(np.abs(c.at(tab, grads[obj][tab]) - c.grad(obj, tab)).max())
             report.append(f"{c}: grad {obj}/{tab} max err {err:.3g}, tolerance {tol:.3g} ({err / tol:.3f}x), max |ref| {c.grad_max(obj, tab):.3g}")
             if err > tol:
@@ -110,7 +111,7 @@ def test_components_against_reference_float64(k):
                 # the all-zero row on its own: F.normalize's backward multiplies its gradient by 1 / eps = 1e12, so it
                 # gets a bound from its own slack and size and takes no part in the bound of the rows above
                 zg, zslack, zmax = c.zero_grad(obj, tab)
-                ztol = 4 * max(zslack, 1e-7 * zmax)
+                ztol = sp.F32 * max(zslack, sp.FLOOR * zmax)
                 zerr = float(np.abs(grads[obj][tab][c.zero_index(tab)] - zg).max())
                 report.append(f"{c}: grad {obj}/{tab} ZERO ROW max err {zerr:.3g}, tolerance {ztol:.3g} ({zerr / ztol:.3f}x), max |ref| {zmax:.3g}")
                 if zerr > ztol:
@@ -232,46 +233,26 @@ def test_fused_sgd_against_float64_torch_sgd(weight_decay):
 
 @pytest.mark.parametrize("c", range(len(CONFIGS)), ids=[repr(c) for c in CONFIGS])
 def test_trajectory_matches_reference_float64(c):
-    """Six train_steps from the fixture's state on its batches: pos_loss, neg_loss and l2 at rtol 1e-5 of the reference's
-    float64 run, loss (their difference) within 1e-5 x (|pos_loss| + |neg_loss|); both tables within 4 x max(slack, 1e-7)
-    of their float64 finals and moved by more than 100 x slack.  The fixture runs at learning.rate 5e-3, the largest
+    """Six train_steps from the fixture's state on its batches, by the rule of tests/step_pins.py: pos_loss, neg_loss and l2
+    at rtol 1e-5 of the reference's float64 run, loss (their difference) within 1e-5 x (|pos_loss| + |neg_loss|); both
+    tables within 4 x max(slack, 1e-7) of their float64 finals and moved by more than 100 x slack.  The fixture runs at learning.rate 5e-3, the largest
     value of the reference's grid (scripts/gen_golden_directau.py, `LR_GRID`)."""
     from recommendation_amd.directau import DirectAUModel
     g = np.load(fx.GOLDEN, allow_pickle=False)
     cf = CONFIGS[c]
     model = DirectAUModel(cf.conf(), fx.train_records(g), [], device="cuda")
     # sorted dense ids (directau.py:116-117): the fixture's batches index these rows
-    assert [model.data.id2user[k] for k in range(model.data.user_num)] == [str(s) for s in g["user_ids"]]
-    assert [model.data.id2item[k] for k in range(model.data.item_num)] == [str(s) for s in g["item_ids"]]
+    sp.assert_dense_id_order(model, g)
     assert type(model.optimizer).__name__ == {"adam": "FusedAdam", "sgd": "FusedSGD"}[cf.optimizer]
     with torch.no_grad():
         for k in fx.TABLES:
             model.model.embedding_dict[k].copy_(_dev(cf.init(k)))
-    got = {k: [] for k in fx.TERMS}
+    got = []
     for batch in fx.batches(g):
         out = model.train_step(tuple(_dev(b) for b in batch))
-        for k, v in zip(fx.TERMS, out):
-            assert not v.requires_grad
-            got[k].append(v)
-    vals = {k: torch.stack(got[k]).cpu().numpy().astype(np.float64) for k in fx.TERMS}
-    ref = {k: cf.losses("f64", k) for k in fx.TERMS}
-    for k in ("pos_loss", "neg_loss", "l2"):
-        print(f"{cf} {k}: max rel err / 1e-5 = {(np.abs(vals[k] - ref[k]) / np.abs(ref[k])).max() / 1e-5:.3f}")
-    size = np.abs(ref["pos_loss"]) + np.abs(ref["neg_loss"])
-    print(f"{cf} loss: max err / (1e-5 x (|pos| + |neg|)) = {(np.abs(vals['loss'] - ref['loss']) / (1e-5 * size)).max():.3f}")
-    final = {k: _np(model.model.embedding_dict[k]) for k in fx.TABLES}
-    report = []
-    for k in fx.TABLES:
-        err, slack = float(np.abs(final[k] - cf.final(k)).max()), max(cf.slack(k), 1e-7)
-        report.append(f"{cf} {k}: max err {err:.3g}, tolerance {4 * slack:.3g} ({err / (4 * slack):.3f}x), "
-                      f"moved {np.abs(final[k] - cf.init(k)).max():.3g}")
-    print("\n".join(report))
-    for k in ("pos_loss", "neg_loss", "l2"):
-        np.testing.assert_allclose(vals[k], ref[k], rtol=1e-5, atol=0, err_msg=k)
-    assert np.all(np.abs(vals["loss"] - ref["loss"]) <= 1e-5 * size)
-    for k in fx.TABLES:
-        assert np.abs(final[k] - cf.init(k)).max() > 100 * cf.slack(k), k
-        np.testing.assert_allclose(final[k], cf.final(k), rtol=0, atol=4 * max(cf.slack(k), 1e-7), err_msg="\n".join(report))
+        assert not any(v.requires_grad for v in out)
+        got.append(torch.stack([v.reshape(()) for v in out]))
+    sp.check(cf.record(), torch.stack(got).cpu().numpy(), {k: _np(model.model.embedding_dict[k]) for k in fx.TABLES})
 
 
 def _numpy_ranking_evaluation(query, items, train, test, top_n):

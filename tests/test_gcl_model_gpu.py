@@ -6,35 +6,34 @@
   * the lightgcn form: one step against the autograd composition of the library's differentiable ops on explicitly
     masked operators, and drop_edge = 0 giving two identical views;
   * convergence: train() on a planted-structure graph beats a random ranking by a wide margin."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import step_pins as sp
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gcl_steps.npz")
 CONFIG_KEYS = ("embedding_size", "num_layers", "lr", "weight_decay", "ssl_temp", "drop_edge", "reg_weight", "ssl_weight",
                "batch_size", "max_epoch")
-TERMS = ("ssl_loss", "bpr_loss", "reg_loss", "total_loss")
 
 
 @pytest.fixture(scope="module")
 def golden():
-    return np.load(GOLDEN)
+    return sp.load("gcl")
 
 
 def test_trajectory_matches_reference_float64(golden):
     """Five train_steps of GCLModel(encoder="linear") from the fixture's weights on its batches: every loss term at
-    rel 1e-5 of the float64 reference run, and the final parameters.
+    rel 1e-5 of the float64 reference run, and the final parameters, by the rule of tests/step_pins.py (family "gcl").
 
     Parameter tolerance: Adam divides by sqrt(v), so an element whose gradient is near zero moves by up to lr per step
     whatever its size, and fp32 rounding of such a gradient is amplified instead of damped.  How much that is over these
     five steps is measured, not guessed: the fixture's float32 run of the reference itself drifts from the float64 run
     by `slack` (max |f32 - f64| per parameter).  The HIP step is another fp32 evaluation of the same arithmetic in a
     different summation order, so its drift is allowed 4 x the reference's own (floored at 1e-7 for the biases, whose
-    reference drift is at the rounding level).  A wrong gradient moves an element by O(lr) = 5e-3 — far outside that."""
+    reference drift is at the rounding level: `atol_floor_4`).  A wrong gradient moves an element by O(lr) = 5e-3 — far
+    outside that; and every parameter moved by more than 100 x that slack (the step is not a no-op)."""
     from recommendation_amd.gcl import GCLModel
     g = golden
     config = {k: g[f"config_{k}"].item() for k in CONFIG_KEYS}
@@ -42,28 +41,12 @@ def test_trajectory_matches_reference_float64(golden):
                      encoder="linear", num_users=int(g["num_users"]), num_items=int(g["num_items"]))
     names = [k for k in model.model.state_dict()]
     model.model.load_state_dict({k: torch.from_numpy(g[f"init/{k}"]) for k in names})
-    got = {k: [] for k in TERMS}
+    got = []
     for n in range(int(g["steps"])):
-        out = model.train_step(*(torch.from_numpy(g[f"batch{n}_{s}"]).cuda() for s in ("users", "pos", "neg")))
-        for k, v in zip(TERMS, out):
-            got[k].append(v)
-    for k in TERMS:
-        vals = torch.stack(got[k]).cpu().numpy().astype(np.float64)
-        np.testing.assert_allclose(vals, g[f"f64/{k}"], rtol=1e-5, err_msg=k)
-    final = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in model.model.state_dict().items()}
-    report = []
-    for k in names:
-        ref = g[f"f64/final/{k}"]
-        slack = max(float(np.abs(g[f"f32/final/{k}"] - ref).max()), 1e-7)
-        err = float(np.abs(final[k] - ref).max())
-        report.append(f"{k}: max err {err:.3g}, reference f32 slack {slack:.3g} ({err / slack:.2f}x)")
-        # every parameter moved (the step is not a no-op) ...
-        assert np.abs(final[k] - g[f"init/{k}"]).max() > 100 * slack, k
-    print("\n".join(report))
-    for k in names:
-        ref = g[f"f64/final/{k}"]
-        slack = max(float(np.abs(g[f"f32/final/{k}"] - ref).max()), 1e-7)
-        np.testing.assert_allclose(final[k], ref, rtol=0, atol=4 * slack, err_msg="\n".join(report))
+        out = model.train_step(*sp.batch(g, n, ("users", "pos", "neg")))
+        got.append(torch.stack([v.reshape(()) for v in out]))
+    final = {k: v.detach().cpu().numpy() for k, v in model.model.state_dict().items()}
+    sp.check(sp.record("gcl", g), torch.stack(got).cpu().numpy(), final)
 
 
 def _numpy_gcl_evaluate(user_emb, item_emb, test_u, test_i, train_u, train_i, ks):

@@ -6,8 +6,9 @@ import os
 import numpy as np
 import pytest
 
-from lightgcn_steps_common import (CONFIGS, FLOOR, GOLDEN, HYPER, SIZE_CAP, TABLES, adam_on_weight_decay_only, atol, config,
-                                   final_table, fixture, init_table, sensitivity_terms, user_major_perm)
+import step_pins as sp
+from lightgcn_steps_common import (CONFIGS, GOLDEN, HYPER, SIZE_CAP, TABLES, adam_on_weight_decay_only, config, final_table,
+                                   fixture, init_table, sensitivity_terms, user_major_perm)
 from oracle import oracle_np as onp
 
 
@@ -78,16 +79,15 @@ def test_graph_has_the_edge_cases():
 def test_tolerances_would_see_a_dropped_term():
     g = fixture()
     for c in CONFIGS:
+        rec = sp.record("lightgcn", g, c)
+        assert rec.factor == sp.DROPPED_CPU and all(tuple(rec.dropped[k]) == sensitivity_terms(g, c) for k in TABLES)
+        rec.assert_sensitivity()                                           # every dropped term: more than DROPPED_CPU x atol
         for k in TABLES:
-            slack, tol = float(g[f"{c}/slack/{k}"]), atol(g, c, k)
-            final, init = final_table(g, c, k), init_table(g, c, k).astype(np.float64)
-            moved = float(np.abs(final - init).max())
+            moved = float(np.abs(rec.tables[k] - init_table(g, c, k).astype(np.float64)).max())
             assert moved == pytest.approx(float(g[f"{c}/moved/{k}"]), abs=4e-9)
-            assert moved > 100 * max(slack, FLOOR), (c, k, moved, slack)
-            for t in sensitivity_terms(g, c):
-                assert float(g[f"{c}/delta_{t}/{k}"]) > 10 * tol, (c, k, t)
+            assert sp.has_moved(moved, max(rec.slack[k], sp.FLOOR)), (c, k, moved, rec.slack[k])
             assert 0 < float(g[f"{c}/drift/{k}"]) < 2.5e-6                 # 4 x drift stays under the 1e-5 of the pin rule
-        assert np.all(np.abs(g[f"{c}/f32/loss"] - g[f"{c}/f64/loss"]) <= 1e-5 * np.abs(g[f"{c}/f64/loss"]))
+        assert np.all(np.abs(rec.f32 - rec.f64) <= sp.REL * np.abs(rec.f64))
     assert sensitivity_terms(g, "B") == ("reg", "wd")
     # the Adam configurations start without a gradient element of Adam's eps' size (the generator's seed scan)
     for c in "ABC":

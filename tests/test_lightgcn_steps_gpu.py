@@ -15,12 +15,11 @@ The recorded negatives are in the reference's file order; the loss wants them in
 (`graph.user_major_edges`), which the test derives from the file by a stable sort and checks against the graph.
 
 Everything is compared with the reference's float64 run, never with another path of ours:
-  * the loss of every step at 1e-5 relative;
+  * the loss of every step at 1e-5 relative and the final tables by the rule of tests/step_pins.py (family "lightgcn":
+    `atol_floor_4` of slack = the reference's own max |f32 - f64|); tests/test_lightgcn_steps_cpu.py shows that this is
+    under a tenth of what a dropped regulariser or weight decay moves;
   * the step-0 gradient of each table by the rule of tests/f64_pins.py: err = max|got - f64| / max|f64| <=
     max(4 x drift, 2^-20) and <= 1e-5 (a trajectory under Adam cannot see a wrong global factor such as a missing 1 / E);
-  * the final tables at atol = 4 x max(slack, 1e-7), slack = the reference's own max |f32 - f64| (tests/test_gcl_model_gpu.py
-    explains the rule); tests/test_lightgcn_steps_cpu.py shows that this is under a tenth of what a dropped regulariser
-    or weight decay moves;
   * the isolated user's row: gradient exactly 0, the row unchanged at the end (A, C, D) or moved by weight decay alone (B).
     The isolated ITEM is no such case, in the reference either: `torch.randint` draws it as a negative and the BCE branch
     scores every item, so it has a gradient (through no edge) and is covered by the table checks.
@@ -34,8 +33,8 @@ import numpy as np
 import pytest
 import torch
 
-from lightgcn_steps_common import (TABLES, adam_on_weight_decay_only, atol, config, final_table, fixture, init_table,
-                                   user_major_perm)
+import step_pins as sp
+from lightgcn_steps_common import TABLES, adam_on_weight_decay_only, config, fixture, init_table, user_major_perm
 from oracle import oracle_np as onp
 from spmm_window_common import HUB_MIN_DEGREE, WINDOW_ROWS
 
@@ -128,13 +127,8 @@ def test_trajectory_matches_reference_float64(monkeypatch, c, path):
     cfg = config(g, c)
     losses, grad0, final = _replay(g, c, path, _set_path(monkeypatch, path))
     tag = f"LGNPIN {c}:{path}"
+    rec = sp.record("lightgcn", g, c, path)
     report, failures = [], []
-
-    ref = g[f"{c}/f64/loss"]
-    err = np.abs(losses - ref) / np.abs(ref)
-    report.append(f"{tag} loss err={err.max():.3e} bound={NORTH_STAR:.3e} ratio={err.max() / NORTH_STAR:.3f}")
-    if not np.all(err <= NORTH_STAR):
-        failures.append(f"loss: got {losses.tolist()} reference {ref.tolist()}")
 
     for k in TABLES:
         ref = g[f"{c}/f64/grad0/{k}"]
@@ -145,14 +139,6 @@ def test_trajectory_matches_reference_float64(monkeypatch, c, path):
         if err > bound:
             failures.append(f"grad0/{k}: err {err:.3e} > bound {bound:.3e}")
 
-    for k in TABLES:
-        ref, tol = final_table(g, c, k), atol(g, c, k)
-        err = float(np.abs(final[k] - ref).max())
-        report.append(f"{tag} final/{k} err={err:.3e} bound={tol:.3e} ratio={err / tol:.3f} "
-                      f"(reference f32 slack {float(g[f'{c}/slack/{k}']):.3e})")
-        if err > tol:
-            failures.append(f"final/{k}: max |final - f64| = {err:.3e} > atol {tol:.3e}")
-
     # the isolated user: no edge, never a negative, not among the BCE branch's users
     iso = int(g["iso_user"])
     row0 = init_table(g, c, "user")[iso].astype(np.float64)
@@ -160,14 +146,14 @@ def test_trajectory_matches_reference_float64(monkeypatch, c, path):
         failures.append(f"isolated user's step-0 gradient is not zero: max {np.abs(grad0['user'][iso]).max():.3e}")
     if cfg["weight_decay"]:
         want = adam_on_weight_decay_only(row0, cfg["lr"], cfg["weight_decay"], int(g["steps"]))
-        err, tol = float(np.abs(final["user"][iso] - want).max()), atol(g, c, "user")
+        err, tol = float(np.abs(final["user"][iso] - want).max()), rec.atol["user"]
         report.append(f"{tag} isolated user, weight decay alone err={err:.3e} bound={tol:.3e} ratio={err / tol:.3f}")
         if err > tol:
             failures.append(f"isolated user's row is not Adam on weight decay alone: err {err:.3e} > {tol:.3e}")
     elif not np.array_equal(final["user"][iso], row0):
         failures.append(f"isolated user's row moved by {np.abs(final['user'][iso] - row0).max():.3e}")
     print("\n".join(report))
-    assert not failures, "\n".join(report + failures)
+    sp.check(rec, losses, final, failures)             # the losses and the final tables, and one message for everything
 
 
 def test_edge_path_losses_are_reproducible(monkeypatch):

@@ -2,25 +2,22 @@
 tests/golden/mhcn_steps.npz, written by scripts/gen_golden_mhcn_steps.py.  Six batches of the reference's sampler with the
 recorded torch.randperm draws, from the fixture's initial parameters, two configurations (2 layers at d = 64, 3 at d = 32).
 
-Tolerances follow tests/test_ncl_steps_gpu.py: a loss term within max(1e-5 rel, 4 x the reference's own |f32 - f64|), each
-of the 20 final parameters within 4 x the reference's own f32 slack on it (floored at 1e-7), and that tolerance at most
-1/50 of what dropping the self-supervision or the regulariser would move the parameter."""
-import os
-
+The rule is tests/step_pins.py's (family "mhcn"): terms against the reference's float64 and float32 runs, each of the 20
+final parameters within `atol_floor_1` of the reference's own f32 slack, and that tolerance at most 1/50 of what dropping
+the self-supervision or the regulariser would move the parameter (exactly 0 for the parameters no term reaches)."""
 import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+import step_pins as sp
+from step_pins import MHCN_TERMS as TERMS  # noqa: F401  (tests/test_prepared_models_gpu.py reads it from here)
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mhcn_steps.npz")
-TERMS = ("rec_loss", "reg_loss", "ss_loss", "total_loss")
-UNREACHED = {"ss": {"sgating_weights.4", "sgating_bias.4"}, "reg": {"sgating_bias.4"}}
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def steps():
-    return np.load(GOLDEN)
+    return sp.load("mhcn")
 
 
 def _conf(g, c):
@@ -31,12 +28,9 @@ def _conf(g, c):
 
 def _model(g, c):
     from recommendation_amd.mhcn import MHCNModel
-    train = [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
-    social = [[int(a), int(b), 1.0] for a, b in zip(g["social_follower"], g["social_followee"])]
-    m = MHCNModel(_conf(g, c), train, train[:10], social, device="cuda")
-    # the fixture's batches, permutations and tables are indexed by the reference's dense ids (sorted raw ids, mhcn.py:232)
-    assert [m.data.id2user[k] for k in range(m.data.user_num)] == g["user_ids"].tolist()
-    assert [m.data.id2item[k] for k in range(m.data.item_num)] == g["item_ids"].tolist()
+    train = sp.triples(g)
+    m = MHCNModel(_conf(g, c), train, train[:10], sp.social(g), device="cuda")
+    sp.assert_dense_id_order(m, g)                                  # sorted raw ids, mhcn.py:232
     return m
 
 
@@ -54,38 +48,15 @@ def test_mhcn_trajectory_matches_reference_float64(steps, c):
             p.copy_(torch.from_numpy(g[f"c{c}/init/{k}"]))
     got = []
     for n in range(int(g["steps"])):
-        batch = tuple(torch.from_numpy(g[f"batch{n}_{s}"].astype(np.int64)).cuda() for s in ("users", "pos", "neg"))
+        batch = sp.batch(g, n, ("users", "pos", "neg"))
         perms = [torch.from_numpy(p.astype(np.int64)).cuda() for p in g[f"c{c}/perms"][n]]
         got.append(torch.stack([t.reshape(()) for t in m.train_step(batch, perms)]))
     got = torch.stack(got).cpu().numpy().astype(np.float64)      # [steps, 4]
 
-    report, failures = [f"config {c}:"], []
-    ref, f32 = g[f"c{c}/f64/losses"], g[f"c{c}/f32/losses"]
-    for j, k in enumerate(TERMS):
-        tol = np.maximum(1e-5 * np.abs(ref[:, j]), 4 * np.abs(f32[:, j] - ref[:, j]))
-        err = np.abs(got[:, j] - ref[:, j])
-        report.append(f"  {k}: max err {err.max():.3g} ({(err / tol).max():.2f} x tol)")
-        if not np.all(err <= tol):
-            failures.append(f"{k}: got {got[:, j].tolist()} reference {ref[:, j].tolist()}")
-    for k, p in params.items():
-        final = p.detach().cpu().numpy().astype(np.float64)
-        assert np.isfinite(final).all(), k
-        want = g[f"c{c}/init/{k}"].astype(np.float64) + g[f"c{c}/f64/delta/{k}"].astype(np.float64)
-        slack = float(g[f"c{c}/slack/{k}"])
-        atol = max(4 * slack, 1e-7)
-        err = float(np.abs(final - want).max())
-        deltas = {t: float(g[f"c{c}/delta_{t}/{k}"]) for t in ("ss", "reg")}
-        report.append(f"  {k}: max err {err:.3g} ({err / atol:.2f} x atol {atol:.3g}, reference f32 slack {slack:.3g}); a dropped "
-                      "term moves it by " + ", ".join(f"{t} {v:.3g}" for t, v in deltas.items()))
-        for t, v in deltas.items():                             # a tolerance that would not see a missing term checks nothing
-            assert (v == 0.0) if k in UNREACHED[t] else (v > 50 * atol), (k, t, v, atol)
-        if err > atol:
-            failures.append(f"{k}: max |final - f64| = {err:.3g} > atol {atol:.3g}")
-    print("\n".join(report))
+    sp.check(sp.record("mhcn", g, c), got, {k: p.detach().cpu().numpy() for k, p in params.items()})
     assert not bool(params["sgating_bias.4"].any())             # no term reaches it, and the norm's gradient at 0 is 0
     moved = float((params["sgating_weights.4"].detach().cpu() - torch.from_numpy(g[f"c{c}/init/sgating_weights.4"])).abs().max())
     assert moved > 1e-3                                          # the regulariser alone moves it
-    assert not failures, "\n".join(report + failures)
 
 
 def test_operators_built_from_the_raw_lists_equal_the_references(steps):
@@ -105,17 +76,8 @@ def test_operators_built_from_the_raw_lists_equal_the_references(steps):
 def test_train_end_to_end_on_a_planted_group_graph():
     from recommendation_amd.evaluate import ranking_evaluation, test as rank_test
     from recommendation_amd.mhcn import MHCNModel
-    rng = np.random.default_rng(5)
-    n_u, n_i, groups = 150, 200, 5
-    train, test, social = [], [], []
-    for u in range(n_u):
-        own = rng.permutation(np.arange(u % groups, n_i, groups))[:15]          # items of the user's group
-        train += [[f"u{u:03d}", f"i{int(i):03d}", 1.0] for i in own[:12]]
-        test += [[f"u{u:03d}", f"i{int(i):03d}", 1.0] for i in own[12:]]
-        for v in rng.choice(np.arange(u % groups, n_u, groups), 6, replace=False):
-            if v != u:
-                social.append([f"u{u:03d}", f"u{int(v):03d}", 1.0])
-    social += [[b, a, w] for a, b, w in social[:300]] + [["nobody", "u001", 1.0]]
+    n_u, n_i = 150, 200
+    train, test, social = sp.planted_group_lists(np.random.default_rng(5))
     conf = {"emb_size": 32, "batch_size": 256, "lr": 1e-2, "reg_lambda": 1e-4, "max.epoch": 12, "item.ranking.topN": [10, 20],
             "MHCN": {"n_layer": 2, "ss_rate": 0.01}}
     m = MHCNModel(conf, train, test, social, device="cuda", seed=1)

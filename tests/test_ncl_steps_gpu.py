@@ -12,28 +12,27 @@ The e_step (faiss k-means in the reference) is the one stand-in, on both sides: 
 row assigned to its nearest centroid of the current encoder output (the real assignment kernel here).  The generator has
 checked that no row the prototype contrast reads comes near a tie.
 
-Tolerances follow tests/test_gcl_model_gpu.py: a loss term within max(1e-5 rel, 4 x the reference's own |f32 - f64|), a
-final table within 4 x the reference's own f32 slack on it (floored at 1e-7), and that tolerance at most 1/50 of what
-dropping the structure contrast, the prototype contrast or the l2 term would move the table."""
+The rule is tests/step_pins.py's (family "ncl"): terms against the reference's float64 and float32 runs, final tables
+within `atol_floor_1` of the reference's own f32 slack, and that tolerance at most 1/50 of what dropping the structure
+contrast, the prototype contrast or the l2 term would move the table."""
 import io
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import step_pins as sp
+from step_pins import NCL_TERMS as TERMS  # noqa: F401  (tests/test_prepared_models_gpu.py reads it from here)
+
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ncl_steps.npz")
-TERMS = ("rec_loss", "ssl_loss", "proto_loss", "total_loss")
 TABLES = ("user_emb", "item_emb")
-SENSITIVITY = ("ssl_reg", "proto_reg", "reg")
 PATHS = ("autograd", "fused", "graph", "resume_cap_cap", "resume_cap_eager", "resume_eager_cap")
 
 
 @pytest.fixture(scope="module")
 def steps():
-    return np.load(GOLDEN)
+    return sp.load("ncl")
 
 
 def _conf(g, c):
@@ -73,11 +72,9 @@ def fixed_e_step(monkeypatch, steps):
 
 def _model(g, c, **kw):
     from recommendation_amd.ncl import NCLModel
-    train = [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
+    train = sp.triples(g)
     m = NCLModel(_conf(g, c), train, train[:20], device="cuda", **kw)
-    # the fixture's batches and tables are indexed by the reference's dense ids (sorted raw ids, ncl.py:60-61)
-    assert [m.data.id2user[k] for k in range(m.data.user_num)] == g["user_ids"].tolist()
-    assert [m.data.id2item[k] for k in range(m.data.item_num)] == g["item_ids"].tolist()
+    sp.assert_dense_id_order(m, g)                                  # sorted raw ids, ncl.py:60-61
     d = int(g[f"c{c}/d"])
     with torch.no_grad():
         for k in TABLES:
@@ -91,8 +88,7 @@ def _optimizer(g, m, capturable):
 
 
 def _batches(g):
-    return [tuple(torch.from_numpy(g[f"batch{n}_{s}"]).cuda() for s in ("users", "pos", "neg"))
-            for n in range(int(g["steps"]))]
+    return [sp.batch(g, n, ("users", "pos", "neg")) for n in range(int(g["steps"]))]
 
 
 def _run(m, opt, batches, fused):
@@ -161,25 +157,4 @@ def test_ncl_trajectory_matches_reference_float64(steps, fixed_e_step, c, path):
     got = torch.stack(losses).cpu().numpy().astype(np.float64)            # [steps, 4]
     final = {k: m.model.embedding_dict[k].detach().cpu().numpy().astype(np.float64) for k in TABLES}
 
-    report, failures = [f"config {c} {path}:"], []
-    for j, k in enumerate(TERMS):
-        ref, f32 = g[f"c{c}/f64/{k}"], g[f"c{c}/f32/{k}"]
-        tol = np.maximum(1e-5 * np.abs(ref), 4 * np.abs(f32 - ref))
-        err = np.abs(got[:, j] - ref)
-        report.append(f"  {k}: max err {err.max():.3g} ({(err / tol).max():.2f} x tol)")
-        if not np.all(err <= tol):
-            failures.append(f"{k}: got {got[:, j].tolist()} reference {ref.tolist()}")
-    for k in TABLES:
-        ref = g[f"c{c}/f64/final/{k}"]
-        slack = float(g[f"c{c}/slack/{k}"])
-        atol = max(4 * slack, 1e-7)
-        err = float(np.abs(final[k] - ref).max())
-        deltas = {t: float(g[f"c{c}/delta_{t}/{k}"]) for t in SENSITIVITY}
-        report.append(f"  {k}: max err {err:.3g}, reference f32 slack {slack:.3g} ({err / max(slack, 1e-30):.2f}x), "
-                      f"atol {atol:.3g}; a dropped term moves it by " + ", ".join(f"{t} {v:.3g}" for t, v in deltas.items()))
-        # a tolerance that would not see a missing loss term checks nothing
-        assert all(v > 50 * atol for v in deltas.values()), (k, deltas, atol)
-        if err > atol:
-            failures.append(f"{k}: max |final - f64| = {err:.3g} > atol {atol:.3g}")
-    print("\n".join(report))
-    assert not failures, "\n".join(report + failures)
+    sp.check(sp.record("ncl", g, c, path), got, final)

@@ -3,16 +3,16 @@ model is built from the first one's own operators and CSR arrays with the same s
 equal bitwise, and one train_step on the same batch with the same recorded draws gives the same loss terms and parameters.
 
 Data sets, configurations, batches and draws are those of each model's own step test (its golden fixture, configuration 0).
-Tolerances are the constants of those tests (the atomics in the backwards rule out a bitwise claim between two runs):
-  * loss terms: REL = 1e-5, the relative bound of test_{ncl_steps,directau,mhcn_model,buir_model}_gpu.py (DirectAU's `loss`, a
-    difference, against 1e-5 x (|pos_loss| + |neg_loss|) as there); SEPT: REL_SEPT = 1e-6, what test_sept_model_gpu.py
-    asserts between its two passes of the HIP path;
-  * parameters: max(4 x slack, 1e-7) with the fixture's own `slack/<name>`, the `atol` of the same tests."""
+Tolerances are those of tests/step_pins.py (the atomics in the backwards rule out a bitwise claim between two runs):
+  * loss terms: its REL = 1e-5 (DirectAU's `loss`, a difference, against `difference_tol` of pos_loss and neg_loss);
+    SEPT: REL_SEPT = 1e-6, what test_sept_model_gpu.py asserts between its two passes of the HIP path;
+  * parameters: the `atol` of each fixture's own record, in the form of its family."""
 import numpy as np
 import pytest
 import torch
 
 import directau_fixture as dfx
+import step_pins as sp
 import test_buir_model_gpu as tbuir
 import test_mhcn_model_gpu as tmhcn
 import test_ncl_steps_gpu as tncl
@@ -21,15 +21,7 @@ from test_ncl_steps_gpu import fixed_e_step, steps  # noqa: F401  (NCL's fixture
 
 pytestmark = pytest.mark.gpu
 
-REL, REL_SEPT, SEED = 1e-5, 1e-6, 3
-
-
-def _atol(g, name, c=0):
-    return max(4 * float(g[f"c{c}/slack/{name}"]), 1e-7)
-
-
-def _batch(g, n, names, prefix=""):
-    return tuple(torch.from_numpy(g[f"{prefix}batch{n}_{s}"].astype(np.int64)).cuda() for s in names)
+REL, REL_SEPT, SEED = sp.REL, 1e-6, 3
 
 
 def _same_bits(a, b):
@@ -58,7 +50,7 @@ def test_ncl_from_graph(steps, fixed_e_step, fused):  # noqa: F811
     g = steps
     fixed_e_step(0)
     conf = tncl._conf(g, 0)
-    train = [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
+    train = sp.triples(g)
     torch.manual_seed(SEED)                                     # NCLModel draws its tables from the caller's RNG
     a = NCLModel(conf, train, train[:20], device="cuda")
     torch.manual_seed(SEED)
@@ -66,11 +58,11 @@ def test_ncl_from_graph(steps, fixed_e_step, fused):  # noqa: F811
     assert b.data.norm_adj is a.data.norm_adj and b.topN == a.topN == [10] and FusedNCLStep.supported(b)
     params = [list(m.model.embedding_dict.items()) for m in (a, b)]
     _same_bits(*params)
-    batch = _batch(g, 0, ("users", "pos", "neg"))
+    batch = sp.batch(g, 0, ("users", "pos", "neg"))
     out = [m.train_step(batch, tncl._optimizer(g, m, False), check_negatives=False, fused=fused) for m in (a, b)]
     assert (a._fused is not None) == (b._fused is not None) == fused
     _close_terms(*out, REL, tncl.TERMS)
-    _close_params(*params, lambda k: _atol(g, k))
+    _close_params(*params, sp.record("ncl", g, 0).atol.get)
 
 
 def test_directau_from_graph():
@@ -85,38 +77,34 @@ def test_directau_from_graph():
     batch = tuple(torch.from_numpy(np.asarray(t)).cuda() for t in dfx.batches(g)[0])
     out = [m.train_step(batch) for m in (a, b)]
     _close_terms(out[0][:3], out[1][:3], REL, dfx.TERMS[:3])
-    size = abs(float(out[0][0])) + abs(float(out[0][1]))       # `loss` is a difference: held to the size of its parts
-    assert dfx.TERMS[3] == "loss" and abs(float(out[0][3]) - float(out[1][3])) <= REL * size
-    _close_params(*params, lambda k: 4 * max(cf.slack(k), 1e-7))
+    size = sp.difference_tol(float(out[0][0]), float(out[0][1]))       # `loss` is a difference: held to the size of its parts
+    assert dfx.TERMS[3] == "loss" and abs(float(out[0][3]) - float(out[1][3])) <= size
+    _close_params(*params, cf.record().atol.get)
 
 
 def test_mhcn_from_graphs():
     from recommendation_amd.mhcn import MHCNModel
-    g = np.load(tmhcn.GOLDEN)
-    conf = tmhcn._conf(g, 0)
-    train = [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
-    social = [[int(x), int(y), 1.0] for x, y in zip(g["social_follower"], g["social_followee"])]
-    a = MHCNModel(conf, train, train[:10], social, device="cuda", seed=SEED)
+    g = sp.load("mhcn")
+    conf, train = tmhcn._conf(g, 0), sp.triples(g)
+    a = MHCNModel(conf, train, train[:10], sp.social(g), device="cuda", seed=SEED)
     enc = a.model
     b = MHCNModel.from_graphs(conf, enc.H_s, enc.H_j, enc.H_p, enc.R, seed=SEED)
     assert (b.data.user_num, b.data.item_num) == (a.data.user_num, a.data.item_num) and b.model.R is enc.R
     params = [list(m.model.named_parameters()) for m in (a, b)]
     assert len(params[0]) == 20
     _same_bits(*params)
-    batch = _batch(g, 0, ("users", "pos", "neg"))
+    batch = sp.batch(g, 0, ("users", "pos", "neg"))
     perms = [torch.from_numpy(p.astype(np.int64)).cuda() for p in g["c0/perms"][0]]
     out = [m.train_step(batch, perms) for m in (a, b)]
     _close_terms(*out, REL, tmhcn.TERMS)
-    _close_params(*params, lambda k: _atol(g, k))
+    _close_params(*params, sp.record("mhcn", g, 0).atol.get)
 
 
 def test_sept_from_graphs_tri_training_step():
     from recommendation_amd.sept import SEPTModel
-    g = np.load(tsept.GOLDEN)
-    conf = tsept._conf(g, 0)
-    train = [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
-    social = [[int(x), int(y), 1.0] for x, y in zip(g["social_follower"], g["social_followee"])]
-    a = SEPTModel(conf, train, train[:10], social, device="cuda", seed=SEED)
+    g = sp.load("sept")
+    conf, train = tsept._conf(g, 0), sp.triples(g)
+    a = SEPTModel(conf, train, train[:10], sp.social(g), device="cuda", seed=SEED)
     b = SEPTModel.from_graphs(conf, a.norm_adj, a.social_mat, a.sharing_mat, a.data.user_rowptr, a.data.user_items_sorted,
                               seed=SEED)
     assert (b.data.user_num, b.data.item_num) == (a.data.user_num, a.data.item_num)
@@ -124,18 +112,18 @@ def test_sept_from_graphs_tri_training_step():
     params = [[(k, getattr(m, k)) for k in tsept.TABLES] for m in (a, b)]
     _same_bits(*params)
     aug = a.graph_from_kept_pairs(g["kept_user"].astype(np.int64), g["kept_item"].astype(np.int64))
-    batch = _batch(g, int(g["plain_steps"]), ("users", "pos", "neg"), prefix="c0/")      # the first tri-training batch
+    batch = sp.batch(g, int(g["plain_steps"]), ("users", "pos", "neg"), prefix="c0/")      # the first tri-training batch
     out_a = a.train_step(batch, True, aug)
     out_b = b.train_step(batch, True, aug, a.last_positives.clone())        # the label sets `a` drew, replayed
     assert torch.equal(a.last_positives, b.last_positives) and float(out_a[1]) != 0.0
     _close_terms(out_a, out_b, REL_SEPT, tsept.TERMS)
-    _close_params(*params, lambda k: _atol(g, k))
+    _close_params(*params, sp.record("sept", g, 0).atol.get)
 
 
 def test_buir_from_graphs():
     from recommendation_amd.buir import BUIRModel
-    g = np.load(tbuir.GOLDEN)
-    conf, train = tbuir._conf(g, 0), tbuir._triples(g)
+    g = sp.load("buir")
+    conf, train = tbuir._conf(g, 0), sp.triples(g)
     a = BUIRModel(conf, train, train[:10], device="cuda", seed=SEED)
     d = a.data
     b = BUIRModel.from_graphs(conf, d.norm_adj, d.user_num, d.uid_dev, d.iid_dev, d.user_rowptr, d.user_items_sorted, seed=SEED)
@@ -143,8 +131,8 @@ def test_buir_from_graphs():
     params = [[(k, getattr(m, attr)) for k, attr in tbuir.NAMES.items()] for m in (a, b)]
     _same_bits(*params)
     views = tbuir._views(g, 0, a, 0)                            # the reference's recorded dropout draws of step 0
-    batch = _batch(g, 0, ("users", "items"))
+    batch = sp.batch(g, 0, ("users", "items"))
     out = [m.train_step(batch, views=views) for m in (a, b)]
     assert a.step_count == b.step_count == 1
     _close_terms([out[0]], [out[1]], REL, ("loss",))
-    _close_params(*params, lambda k: _atol(g, k))
+    _close_params(*params, sp.record("buir", g, 0).atol.get)

@@ -6,13 +6,15 @@ import os
 import numpy as np
 import pytest
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sept_steps.npz")
-TABLES = ("user_embeddings", "item_embeddings")
+import step_pins as sp
+from step_pins import SEPT_TABLES as TABLES
+
+GOLDEN = os.path.join(sp.GOLDEN, "sept_steps.npz")
 
 
 @pytest.fixture(scope="module")
 def g():
-    return np.load(GOLDEN)
+    return sp.load("sept")
 
 
 def test_fixture_is_small_plain_data_with_the_expected_keys(g):
@@ -49,7 +51,7 @@ def test_the_generators_conditions_hold_in_the_stored_numbers(g):
     assert int(g["tri_epoch"]) > int(g["max_epoch"]) // 3 >= 1
     for c in (0, 1):
         l64, l32 = g[f"c{c}/f64/losses"], g[f"c{c}/f32/losses"]
-        assert np.isfinite(l64).all() and (np.abs(l32 - l64) <= 1e-5 * np.abs(l64)).all()
+        assert np.isfinite(l64).all() and (np.abs(l32 - l64) <= sp.REL * np.abs(l64)).all()
         assert (l64[:2, 1] == 0).all() and (l64[2:, 1] > 0).all()            # two plain steps, six tri-training steps
         ss = float(g["hp/ss_rate"])
         assert np.allclose(l64[:, 2], l64[:, 0] + ss * l64[:, 1], rtol=1e-12)
@@ -57,10 +59,10 @@ def test_the_generators_conditions_hold_in_the_stored_numbers(g):
         assert bool(g[f"c{c}/f32_labels_equal"])
         # no first-step gradient of the size of Adam's eps: the slack measures a step's precision, not one element's lottery
         assert float(g[f"c{c}/first_grad"]) >= 1e-7 and int(g[f"c{c}/table_seed"]) >= 3 + c
+        rec = sp.record("sept", g, c)
+        assert tuple(rec.tables) == TABLES and all(set(rec.dropped[k]) == {"ss", "reg"} for k in TABLES)
+        rec.assert_sensitivity()                                             # either dropped term: more than DROPPED x atol
         for k in TABLES:
-            atol = max(4 * float(g[f"c{c}/slack/{k}"]), 1e-7)
-            for term in ("ss", "reg"):
-                assert float(g[f"c{c}/delta_{term}/{k}"]) > 50 * atol, (c, k, term)
             assert np.abs(g[f"c{c}/f64/delta/{k}"]).max() > 1e-3
 
 

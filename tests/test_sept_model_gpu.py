@@ -3,27 +3,24 @@ tests/golden/sept_steps.npz, written by scripts/gen_golden_sept_steps.py.  Eight
 fixture's initial tables, two plain steps and six tri-training steps on the fixture's dropped interaction matrix, two
 configurations (2 layers, d = 64, 10 labels; 3 layers, d = 32, 5 labels).
 
-Tolerances are those of tests/test_mhcn_model_gpu.py: a term within max(1e-5 rel, 4 x the reference's own |f32 - f64|), each
-final table within 4 x the reference's own f32 slack on it (floored at 1e-7), that tolerance at most 1/50 of what dropping
-the tri-training term or the regulariser moves the table.  The kernel's label sets equal the reference's float64 sets (the
+The rule is tests/step_pins.py's (family "sept"): terms against the reference's float64 and float32 runs, each final table
+within `atol_floor_1` of the reference's own f32 slack, that tolerance at most 1/50 of what dropping the tri-training term
+or the regulariser moves the table.  The kernel's label sets equal the reference's float64 sets (the
 generator kept a sampler seed at which every set is decided by a relative gap of at least 1e-5, and a table seed at which no
 first-step gradient is of the size of Adam's eps, where one element's rounding would be the whole slack)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+import step_pins as sp
+from step_pins import SEPT_TABLES as TABLES, SEPT_TERMS as TERMS  # noqa: F401  (read by tests/test_prepared_models_gpu.py)
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sept_steps.npz")
-TERMS = ("rec_loss", "neighbor_dis_loss", "total_loss")
-TABLES = ("user_embeddings", "item_embeddings")
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def steps():
-    return np.load(GOLDEN)
+    return sp.load("sept")
 
 
 def _conf(g, c, max_epoch=None):
@@ -36,11 +33,9 @@ def _conf(g, c, max_epoch=None):
 
 def _model(g, c):
     from recommendation_amd.sept import SEPTModel
-    train = [[int(u), int(i), 1.0] for u, i in zip(g["train_user"], g["train_item"])]
-    social = [[int(a), int(b), 1.0] for a, b in zip(g["social_follower"], g["social_followee"])]
-    m = SEPTModel(_conf(g, c), train, train[:10], social, device="cuda")
-    assert [m.data.id2user[k] for k in range(m.data.user_num)] == g["user_ids"].tolist()
-    assert [m.data.id2item[k] for k in range(m.data.item_num)] == g["item_ids"].tolist()
+    train = sp.triples(g)
+    m = SEPTModel(_conf(g, c), train, train[:10], sp.social(g), device="cuda")
+    sp.assert_dense_id_order(m, g)
     with torch.no_grad():
         for k in TABLES:
             getattr(m, k).copy_(torch.from_numpy(g[f"c{c}/init/{k}"]))
@@ -54,7 +49,7 @@ def _run(g, c, replay=None):
     plain = int(g["plain_steps"])
     got, labels = [], []
     for n in range(int(g["steps"])):
-        batch = tuple(torch.from_numpy(g[f"c{c}/batch{n}_{s}"].astype(np.int64)).cuda() for s in ("users", "pos", "neg"))
+        batch = sp.batch(g, n, ("users", "pos", "neg"), prefix=f"c{c}/")
         tri = n >= plain
         pos = replay[n - plain] if (replay is not None and tri) else None
         got.append(torch.stack([t.reshape(()) for t in m.train_step(batch, tri, aug if tri else None, pos)]))
@@ -67,36 +62,14 @@ def _run(g, c, replay=None):
 def test_sept_trajectory_matches_reference_float64(steps, c):
     g = steps
     got, labels, m = _run(g, c)
-    report, failures = [f"config {c}:"], []
-    ref, f32 = g[f"c{c}/f64/losses"], g[f"c{c}/f32/losses"]
-    for j, k in enumerate(TERMS):
-        tol = np.maximum(1e-5 * np.abs(ref[:, j]), 4 * np.abs(f32[:, j] - ref[:, j]))
-        err = np.abs(got[:, j] - ref[:, j])
-        report.append(f"  {k}: max err {err.max():.3g} (max rel {np.max(err / np.maximum(np.abs(ref[:, j]), 1e-300)):.3g})")
-        if not np.all(err <= tol):
-            failures.append(f"{k}: got {got[:, j].tolist()} reference {ref[:, j].tolist()}")
+    failures = []
     for n, lab in enumerate(labels):                            # the kernel's own label sets are the reference's
         want = g[f"c{c}/labels{n}"].astype(np.int64)
         have = np.sort(lab.cpu().numpy(), axis=2)
         assert have.shape == want.shape, (n, have.shape, want.shape)
         if not np.array_equal(have, want):
             failures.append(f"step {n + 2}: {int((have != want).any(axis=2).sum())} label sets differ from the float64 run's")
-    for k in TABLES:
-        final = getattr(m, k).detach().cpu().numpy().astype(np.float64)
-        assert np.isfinite(final).all(), k
-        want = g[f"c{c}/init/{k}"].astype(np.float64) + g[f"c{c}/f64/delta/{k}"].astype(np.float64)
-        slack = float(g[f"c{c}/slack/{k}"])
-        atol = max(4 * slack, 1e-7)
-        err = float(np.abs(final - want).max())
-        deltas = {t: float(g[f"c{c}/delta_{t}/{k}"]) for t in ("ss", "reg")}
-        report.append(f"  {k}: max err {err:.3g} ({err / atol:.2f} x atol {atol:.3g}, reference f32 slack {slack:.3g}); a dropped "
-                      "term moves it by " + ", ".join(f"{t} {v:.3g}" for t, v in deltas.items()))
-        for t, v in deltas.items():                             # a tolerance that would not see a missing term checks nothing
-            assert v > 50 * atol, (k, t, v, atol)
-        if err > atol:
-            failures.append(f"{k}: max |final - f64| = {err:.3g} > atol {atol:.3g}")
-    print("\n".join(report))
-    assert not failures, "\n".join(report + failures)
+    sp.check(sp.record("sept", g, c), got, {k: getattr(m, k).detach().cpu().numpy() for k in TABLES}, failures)
 
     # a second pass that replays the recorded label sets gives the same losses
     again, labels2, _ = _run(g, c, replay=labels)
@@ -133,17 +106,8 @@ def test_operators_built_from_the_raw_lists_equal_the_references(steps):
 def test_train_end_to_end_on_a_planted_group_graph():
     from recommendation_amd.evaluate import ranking_evaluation, test as rank_test
     from recommendation_amd.sept import SEPTModel
-    rng = np.random.default_rng(5)
-    n_u, n_i, groups = 150, 200, 5
-    train, test, social = [], [], []
-    for u in range(n_u):
-        own = rng.permutation(np.arange(u % groups, n_i, groups))[:15]          # items of the user's group
-        train += [[f"u{u:03d}", f"i{int(i):03d}", 1.0] for i in own[:12]]
-        test += [[f"u{u:03d}", f"i{int(i):03d}", 1.0] for i in own[12:]]
-        for v in rng.choice(np.arange(u % groups, n_u, groups), 6, replace=False):
-            if v != u:
-                social.append([f"u{u:03d}", f"u{int(v):03d}", 1.0])
-    social += [[b, a, w] for a, b, w in social[:300]] + [["nobody", "u001", 1.0]]
+    n_u, n_i = 150, 200
+    train, test, social = sp.planted_group_lists(np.random.default_rng(5))
     conf = {"emb_size": 32, "batch_size": 300, "lr": 1e-2, "reg_lambda": 1e-4, "max.epoch": 6, "item.ranking.topN": [10, 20],
             "SEPT": {"n_layer": 2, "ss_rate": 0.005, "drop_rate": 0.3, "ins_cnt": 10}}
     # 1800 pairs in batches of 300: no ragged last batch with fewer distinct users than ins_cnt (there the reference's topk

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import ssl4rec_fixture as fx
+import step_pins as sp
 
 
 @pytest.fixture(scope="module")
@@ -28,31 +29,29 @@ def test_reference_float32_losses_agree_with_float64(fixture):
     the GPU test's rtol of 1e-5 against float64 is not asking for more than float32 arithmetic gives."""
     _, configs = fixture
     for c in configs:
-        for term in fx.TERMS:
-            a, b = c.losses("f32", term), c.losses("f64", term)
-            assert a.shape == b.shape == (6,)
-            assert np.max(np.abs(a - b) / np.abs(b)) <= 2.5e-6, (c.pre, term)
+        rec = c.record()
+        assert rec.f32.shape == rec.f64.shape == (6, len(fx.TERMS))
+        assert np.max(np.abs(rec.f32 - rec.f64) / np.abs(rec.f64)) <= 2.5e-6, c.pre
 
 
 def test_tolerance_would_see_a_dropped_term(fixture):
     """For each loss term that can be dropped (alpha = 0; reg.weight = 0 where reg.weight >= 1e-3), some parameter's final
-    value moves by at least 10 x the GPU test's tolerance 4 x max(slack, 1e-7)."""
+    value moves by at least DROPPED_CPU = 10 x the GPU test's tolerance (tests/step_pins.py, `atol_floor_4`)."""
     _, configs = fixture
     for c in configs:
+        rec = c.record()
         for term in fx.SENSITIVITY:
             if term == "reg_weight" and c.reg_weight < 1e-3:
                 continue          # at the default 1e-4 the regulariser moves less than the tolerance: no claim made
-            ratio = max(c.delta(term, k) / (4 * max(c.slack(k), 1e-7)) for k in c.names)
-            assert ratio >= 10, (c.pre, term, ratio)
+            ratio = max(rec.dropped[k][term] / rec.atol[k] for k in c.names)
+            assert ratio >= sp.DROPPED_CPU, (c.pre, term, ratio)
     assert any(c.reg_weight >= 1e-3 for c in configs)
 
 
 def test_every_parameter_moves_far_more_than_the_slack(fixture):
     _, configs = fixture
     for c in configs:
-        for k in c.names:
-            moved = np.abs(c.final(k) - c.at(k, c.init(k))).max()
-            assert moved > 100 * c.slack(k), (c.pre, k, moved, c.slack(k))
+        c.record().assert_sensitivity()                     # the MOVED rule, on the reference's own finals
 
 
 def test_recorded_masks_keep_the_expected_share(fixture):
@@ -79,10 +78,10 @@ def test_stored_tensors_have_the_declared_shapes(fixture):
             if c.sampled(k):
                 idx = c.index(k)
                 assert idx.shape == (fx.SAMPLE,) and len(np.unique(idx)) == fx.SAMPLE and idx.max() < n
-                assert c.final(k).shape == (fx.SAMPLE,)
+                assert c.record().tables[k].shape == (fx.SAMPLE,)
             else:
-                assert c.final(k).shape == c.shapes[k]
-            assert c.final(k).dtype == np.float64
+                assert c.record().tables[k].shape == c.shapes[k]
+            assert c.record().tables[k].dtype == np.float64
             # initial values sit on the 2^-12 grid
             assert np.array_equal(np.round(c.init(k) / fx.GRID) * fx.GRID, c.init(k))
     for n in range(int(g["steps"])):

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import ssl4rec_fixture as fx
+import step_pins as sp
 
 pytestmark = pytest.mark.gpu
 
@@ -298,10 +299,10 @@ def _train_list(g):
 
 @pytest.mark.parametrize("c", [0, 1, 2])
 def test_trajectory_matches_reference_float64(c):
-    """Six train_steps from the fixture's state on its batches and recorded masks: every loss term at rtol 1e-5 of the
-    reference's float64 run; every parameter within 4 x max(slack, 1e-7) of its float64 final, slack being the drift of
-    the reference's own float32 run (the rule tests/test_gcl_model_gpu.py uses and explains); every parameter moved by
-    more than 100 x slack.  Matrices with a 1024-wide side are compared at the fixture's seeded sample of entries.
+    """Six train_steps from the fixture's state on its batches and recorded masks, by the rule of tests/step_pins.py
+    (family "ssl4rec"): every loss term at rtol 1e-5 of the reference's float64 run; every parameter within
+    4 x max(slack, 1e-7) (`atol_floor_4`) of its float64 final, slack being the drift of the reference's own float32 run;
+    every parameter moved by more than 100 x slack.  Matrices with a 1024-wide side are compared at the fixture's seeded sample of entries.
 
     The fixture runs at learning.rate 1e-5, the smallest value of the reference's grid (why: the comment at `LR` in
     scripts/gen_golden_ssl4rec_steps.py — an Adam step turns a relative gradient error rho into lr x rho, and at 1e-3
@@ -313,35 +314,17 @@ def test_trajectory_matches_reference_float64(c):
     cf = configs[c]
     model = SSL4RecModel(cf.conf(), _train_list(g), [], device="cuda")
     # first-seen dense ids (ssl4rec.py:69-75): the fixture's batches index these rows
-    assert [model.data.id2user[k] for k in range(model.data.user_num)] == [str(s) for s in g["user_ids"]]
-    assert [model.data.id2item[k] for k in range(model.data.item_num)] == [str(s) for s in g["item_ids"]]
+    sp.assert_dense_id_order(model, g)
     assert list(model.model.state_dict()) == cf.names
     model.model.load_state_dict({k: torch.from_numpy(cf.init(k)) for k in cf.names})
-    got = {k: [] for k in fx.TERMS}
+    got = []
     model.model.train()
     for n in range(int(g["steps"])):
-        u, i = (torch.from_numpy(g[f"batch{n}_{s}"]).cuda() for s in ("users", "items"))
-        out = model.train_step(u, i, keep_bits=torch.from_numpy(cf.keep_bits[n]).cuda())
-        for k, v in zip(fx.TERMS, out):
-            assert not v.requires_grad
-            got[k].append(v)
-    for k in fx.TERMS:
-        vals = torch.stack(got[k]).cpu().numpy().astype(np.float64)
-        rel = np.abs(vals - cf.losses("f64", k)) / np.abs(cf.losses("f64", k))
-        print(f"config {c} {k}: max rel err {rel.max():.3g}")
-    final = {k: cf.at(k, v.detach().cpu().numpy().astype(np.float64)) for k, v in model.model.state_dict().items()}
-    report = []
-    for k in cf.names:
-        err, slack = float(np.abs(final[k] - cf.final(k)).max()), max(cf.slack(k), 1e-7)
-        report.append(f"{k}: max err {err:.3g}, reference f32 slack {slack:.3g} ({err / slack:.2f}x)")
-    print("\n".join(report))
-    for k in fx.TERMS:
-        vals = torch.stack(got[k]).cpu().numpy().astype(np.float64)
-        np.testing.assert_allclose(vals, cf.losses("f64", k), rtol=1e-5, err_msg=k)
-    for k in cf.names:
-        assert np.abs(final[k] - cf.at(k, cf.init(k))).max() > 100 * cf.slack(k), k
-        np.testing.assert_allclose(final[k], cf.final(k), rtol=0, atol=4 * max(cf.slack(k), 1e-7),
-                                   err_msg=k + "\n" + "\n".join(report))
+        out = model.train_step(*sp.batch(g, n, ("users", "items")), keep_bits=torch.from_numpy(cf.keep_bits[n]).cuda())
+        assert not any(v.requires_grad for v in out)
+        got.append(torch.stack([v.reshape(()) for v in out]))
+    final = {k: cf.at(k, v.detach().cpu().numpy()) for k, v in model.model.state_dict().items()}
+    sp.check(cf.record(), torch.stack(got).cpu().numpy(), final)
 
 
 def test_seeded_steps_draw_new_masks_and_need_no_recorded_bits():
