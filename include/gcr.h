@@ -643,7 +643,9 @@ int32_t gcr_score_rows_f32(const float* user_emb, const int64_t* user_ids, int64
                            const float* item_emb, int64_t n_items, int32_t d, float* scores, void* stream);
 /* Per query row: scores[q, training items of the user] = -inf (in place), then the k largest scores
  * in descending order, ties -> smaller item id; rows with fewer than k finite items are padded with
- * (-1, -inf).  replaces `scores_user[list(known_pos)] = -np.inf; np.argsort(-scores_user)[:k]`
+ * (-1, -inf): a masked training positive is never returned, with any score.  A query whose user id
+ * (user_ids[q], or q itself when user_ids == NULL) is outside [0, n_users) gets an all-padding row; its
+ * scores are not read.  replaces `scores_user[list(known_pos)] = -np.inf; np.argsort(-scores_user)[:k]`
  * lightgcn.py:55-57, gcl.py:93-96 and `candidates[...] = -1e8; torch.topk(candidates, max_N)`
  * ncl.py:257-261.  user_rowptr / user_items_sorted (CSR of training positives) may both be NULL.
  * k <= 256. */
@@ -658,6 +660,7 @@ int32_t gcr_topk_masked_f32(float* scores, int64_t n_query, int64_t n_items, con
  * bf16 MFMA, f32-accurate) and keeps only (score >= threshold, item not a training positive) candidates —
  * about k * n_items / 4096 per user; a per-user bitonic sort finishes.  status[q] = 1 marks a user whose
  * candidate list overflowed or came up short (re-rank those through the two-call path); 0 = row q is final.
+ * A query whose user id is outside [0, n_users) gets an all-padding row, (-1, -inf) k times, with status 0.
  * Supported (gcr_rank_fused_supported): d in {32, 64, 128}, n_items >= 16384, k <= 256.
  * replaces lightgcn.py:48-57, gcl.py:87-96, ncl.py:253-264,390-394 (as gcr_topk_masked_f32).
  */

@@ -11,7 +11,8 @@
 // topk_masked: one 256-thread block per user row: scatter -inf over the user's training items,
 //   3-pass radix select (11 + 11 + 10 bits) of the k-th largest key over the L2-resident row, gather
 //   the winners, bitonic sort by (score desc, item id asc).  Ties at the threshold are resolved
-//   towards the smaller item id (deterministic).
+//   towards the smaller item id (deterministic).  A row with fewer than k eligible items ends in the padding
+//   (-1, -inf), never in its masked training items; a user id outside [0, n_users) gets an all-padding row.
 #include "gcr_b3.h"   // the f32 tile engine (gcr_tile.h) and the split-operand bf16 MFMA helpers
 
 namespace {
@@ -281,6 +282,33 @@ __device__ int pick_bin(const uint32_t* hist, int nbins, uint32_t want, uint32_t
   return bin;
 }
 
+// Position i of a ranked row from the sorted candidates: (item, score), or the padding (-1, -inf) past the kk selected
+// entries and for a selected entry whose score is -inf (a masked training positive of a row with fewer than k
+// eligible items: the sort puts those last, so the padding is one tail)
+__device__ __forceinline__ void write_ranked(const unsigned long long* cand, const float* __restrict__ row, int i, int kk,
+                                             int64_t* __restrict__ items_out, float* __restrict__ scores_out) {
+  int64_t item = -1;
+  float score = -INFINITY;
+  if (i < kk) {
+    const uint32_t j = 0xFFFFFFFFu - (uint32_t)(cand[i] & 0xFFFFFFFFull);
+    const float v = row[j];
+    if (v != -INFINITY) {
+      item = j;
+      score = v;
+    }
+  }
+  items_out[i] = item;
+  scores_out[i] = score;
+}
+
+// all-padding row of a query whose user id is outside [0, n_users)
+__device__ __forceinline__ void write_padding_row(int k, int64_t* __restrict__ items_out, float* __restrict__ scores_out) {
+  for (int i = threadIdx.x; i < k; i += kTopThreads) {
+    items_out[i] = -1;
+    scores_out[i] = -INFINITY;
+  }
+}
+
 // Exact top-k of one row by a 3-pass radix select (11 + 11 + 10 bits) over the whole row + gather + bitonic
 // sort; ties at the threshold go to the smaller item id.  Used for short rows and as the fallback of the
 // candidate filter below.
@@ -373,16 +401,7 @@ __device__ void topk_row_full(const float* __restrict__ row, int64_t n_items, in
       __syncthreads();
     }
   }
-  for (int i = tid; i < k; i += kTopThreads) {
-    if (i < kk) {
-      const uint32_t item = 0xFFFFFFFFu - (uint32_t)(cand[i] & 0xFFFFFFFFull);
-      top_items[q * k + i] = item;
-      top_scores[q * k + i] = row[item];
-    } else {
-      top_items[q * k + i] = -1;
-      top_scores[q * k + i] = -INFINITY;
-    }
-  }
+  for (int i = tid; i < k; i += kTopThreads) write_ranked(cand, row, i, kk, top_items + q * k, top_scores + q * k);
 }
 
 
@@ -454,6 +473,12 @@ __global__ __launch_bounds__(kTopThreads) void rank_finish_kernel(const unsigned
   __shared__ int s_total, s_bad, s_masked;
   const int tid = threadIdx.x;
   for (int64_t q = blockIdx.x; q < n_query; q += gridDim.x) {
+    const int64_t uid = user_ids != nullptr ? user_ids[q] : q;
+    if (uid < 0 || uid >= n_users) {                  // (block-uniform) no such user: an all-padding row, final
+      write_padding_row(k, top_items + q * k, top_scores + q * k);
+      if (tid == 0) status[q] = 0;
+      continue;
+    }
     if (tid == 0) {
       int total = 0, bad = 0;
       for (int r = 0; r < n_regions; ++r) {
@@ -483,8 +508,7 @@ __global__ __launch_bounds__(kTopThreads) void rank_finish_kernel(const unsigned
     }
     __syncthreads();
     // training positives among the candidates sink to the end (key 0 is below every real score)
-    const int64_t uid = user_ids != nullptr ? user_ids[q] : q;
-    if (user_rowptr != nullptr && uid >= 0 && uid < n_users) {
+    if (user_rowptr != nullptr) {
       const int64_t t0 = user_rowptr[uid], t1 = user_rowptr[uid + 1];
       const int n_train = (int)(t1 - t0);
       if (n_train <= kEqCap * 2) {
@@ -621,7 +645,11 @@ __global__ __launch_bounds__(kTopThreads) void topk_masked_kernel(float* __restr
   for (int64_t q = blockIdx.x; q < n_query; q += gridDim.x) {
     float* row = scores + q * n_items;
     const int64_t uid = user_ids != nullptr ? user_ids[q] : q;
-    if (user_rowptr != nullptr && uid >= 0 && uid < n_users) {
+    if (uid < 0 || uid >= n_users) {                  // (block-uniform) no such user: nothing is ranked
+      write_padding_row(k, top_items + q * k, top_scores + q * k);
+      continue;
+    }
+    if (user_rowptr != nullptr) {
       for (int64_t e = user_rowptr[uid] + tid; e < user_rowptr[uid + 1]; e += kTopThreads) {
         const int32_t it = user_items[e];
         if (it >= 0 && it < n_items) row[it] = -INFINITY;
@@ -708,16 +736,7 @@ __global__ __launch_bounds__(kTopThreads) void topk_masked_kernel(float* __restr
             __syncthreads();
           }
         }
-        for (int i = tid; i < k; i += kTopThreads) {
-          if (i < kk) {
-            const uint32_t item = 0xFFFFFFFFu - (uint32_t)(cand[i] & 0xFFFFFFFFull);
-            top_items[q * k + i] = item;
-            top_scores[q * k + i] = row[item];
-          } else {
-            top_items[q * k + i] = -1;
-            top_scores[q * k + i] = -INFINITY;
-          }
-        }
+        for (int i = tid; i < k; i += kTopThreads) write_ranked(cand, row, i, kk, top_items + q * k, top_scores + q * k);
         done = true;
       }
       __syncthreads();

@@ -62,9 +62,10 @@ def test_fused_rank_zero_queries_and_unsupported_shapes():
     ue, ie = torch.randn(10, 64, device=DEV), torch.randn(20000, 64, device=DEV)
     items, scores = rank_topk(ue, ie, torch.zeros(0, dtype=torch.int64), None, None, 10)
     assert items.shape == (0, 10)
-    # an out-of-range user id is never dereferenced: its row comes back through the exact fallback, all padding
+    # an out-of-range user id is never dereferenced: its row is all padding (include/gcr.h), final on the fused path
     items, scores = rank_topk(ue, ie, torch.tensor([3, 99, -1]), None, None, 10)
     assert int(items[0].min()) >= 0
+    assert bool((items[1:] == -1).all()) and bool((scores[1:] == float("-inf")).all())
     ref = torch.topk(ue[3] @ ie.T, 10).indices
     assert torch.equal(items[0].cpu(), ref.cpu())
 
