@@ -940,6 +940,32 @@ int32_t gcr_bt_bwd_f32(const float* h1, const float* h2, int64_t n, int32_t d, f
                        const float* stats, const float* c, const float* g_loss, float* g_h1, float* g_h2, void* workspace,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * DiffNet: one social-diffusion layer, fused (csrc/gcr_diffuse.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * replaces  DiffNet.forward's layer body  univariate/diffnet.py:1127-1130  (sparse.mm, cat, matmul, relu):
+ *   h = relu(Z W_top + x W_bot),   w = [W_top; W_bot] [2 d, d] row-major,   x, h [n, d] row-major float32,
+ *   Z = z when z != NULL, else Z = S x gathered inside the kernel from the CSR S [n, n] (rowptr int64 [n + 1], col int32,
+ *   val float32 or NULL = ones), a row's entries summed in stored order.  A validated CSR is trusted (as in the SpMM).
+ *   h must not alias x.
+ * gcr_diffuse_bwd_f32: with m = g where h > 0 and 0 elsewhere,
+ *   p = m W_top^T,  q = m W_bot^T  ([n, d] each; the caller finishes dx = S^T p + q with the SpMM),
+ *   dw [2 d, d] = [Z | x]^T m   with Z rebuilt as in the forward (it is never saved).
+ *   A row of h that is all zero gives an exactly zero row of p and q.
+ * No atomics; dw's per-workgroup partials are folded in workgroup order: every output is bitwise reproducible.
+ * Supported (gcr_diffuse_supported): d in {32, 64, 128}.  An unsupported d, n < 0, a pointer that is not 16-B aligned
+ * or h == x: GCR_EINVAL.  n == 0 launches nothing (the backward zeroes dw).  workspace (backward only):
+ * gcr_diffuse_workspace_bytes(n, d) bytes, 16-B aligned.  One launch forward, three backward.
+ */
+int32_t gcr_diffuse_supported(int32_t d);
+int64_t gcr_diffuse_workspace_bytes(int64_t n, int32_t d);
+int32_t gcr_diffuse_fwd_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* x,
+                            const float* z, const float* w, int32_t d, float* h, void* stream);
+int32_t gcr_diffuse_bwd_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* x,
+                            const float* z, const float* w, const float* h, const float* g, int32_t d, float* p, float* q,
+                            float* dw, void* workspace, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

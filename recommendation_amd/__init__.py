@@ -7,5 +7,13 @@ from . import _lib
 from .graph import CsrGraph, SpmmPlan
 from . import functional
 
-__all__ = ["CsrGraph", "SpmmPlan", "functional", "_lib"]
+__all__ = ["CsrGraph", "SpmmPlan", "functional", "_lib", "DiffNetEncoder", "DiffNetModel"]
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    """The DiffNet classes, imported on first use (their module pulls in the model base, the sampler and the optimiser)."""
+    if name in ("DiffNetEncoder", "DiffNetModel"):
+        from . import diffnet
+        return getattr(diffnet, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

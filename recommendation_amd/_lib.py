@@ -149,6 +149,10 @@ SIGNATURES = {
     "gcr_bt_workspace_bytes": (c_int64, [c_int64, c_int32]),
     "gcr_bt_fwd_f32": (c_int32, [_P, _P, c_int64, c_int32, c_float, c_float, c_int32, _P, _P, _P, _P, _P]),
     "gcr_bt_bwd_f32": (c_int32, [_P, _P, c_int64, c_int32, c_float, c_float, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "gcr_diffuse_supported": (c_int32, [c_int32]),
+    "gcr_diffuse_workspace_bytes": (c_int64, [c_int64, c_int32]),
+    "gcr_diffuse_fwd_f32": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P, c_int32, _P, _P]),
+    "gcr_diffuse_bwd_f32": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, _P]),
     "gcr_mask_columns_f32":(c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "gcr_spgemm_expand_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_csr_lookup_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P]),
@@ -170,7 +174,7 @@ _exports = {}   # name -> (converter without a stream, converter with one, is th
 # int32 is libgcr's status code, except for these exports, whose int32 is the answer
 INT32_ANSWERS = ("gcr_version", "gcr_infonce_engine", "gcr_infonce_fwd_o_supported", "gcr_channel_mix_supported",
                  "gcr_mim_supported", "gcr_bce_fwd_o_supported", "gcr_rank_fused_supported", "gcr_tri_supported",
-                 "gcr_buir_supported", "gcr_bt_supported")
+                 "gcr_buir_supported", "gcr_bt_supported", "gcr_diffuse_supported")
 
 
 class GcrError(RuntimeError):

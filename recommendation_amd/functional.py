@@ -1702,6 +1702,120 @@ def ema_rows_(target, online, idx, momentum):
 
 
 # ---------------------------------------------------------------------------------------------
+# DiffNet's social-diffusion layer (univariate/diffnet.py:1127-1130)
+# ---------------------------------------------------------------------------------------------
+# `diffuse_layer(gather=None)` sums S x inside the layer kernel only when no row of S has more entries than this.  Measured
+# (scripts/perf_diffnet_step.py; EXPERIMENTS.md, "DiffNet: the fused social-diffusion layer"): at 1M users the in-kernel gather
+# loses to the tuned SpMM + scratch z already at ten entries per row (4.03 against 2.69 ms per layer, forward + backward),
+# and by more with a 20 000-entry row (8.69 against 2.51), so the rule keeps it for a graph without entries.
+DIFFUSE_GATHER_MAX_DEGREE = 0
+
+
+def diffuse_supported(d):
+    """True when the fused kernels (gcr_diffuse_*) serve rows of width d: 32, 64 or 128."""
+    return bool(_lib.call("gcr_diffuse_supported", int(d)))
+
+
+def _diffuse_args(graph, x, w):
+    if x.dim() != 2 or w.dim() != 2 or tuple(w.shape) != (2 * x.shape[1], x.shape[1]) or w.dtype != x.dtype:
+        raise ValueError("x must be [n, d] and w [2 d, d] of one dtype")
+    if graph.n_rows != x.shape[0] or graph.n_cols != x.shape[0]:
+        raise ValueError("the graph must be [n, n] for x [n, d]")
+
+
+def _sparse_mm_host(graph, x):
+    """S x for a CPU tensor of any float dtype: torch's own sparse product on the graph's entries (duplicates sum)."""
+    rows = torch.repeat_interleave(torch.arange(graph.n_rows), graph.rowptr.cpu()[1:] - graph.rowptr.cpu()[:-1])
+    val = torch.ones(graph.nnz) if graph.val is None else graph.val.cpu()
+    s = torch.sparse_coo_tensor(torch.stack([rows, graph.col.cpu().to(torch.int64)]), val.to(x.dtype),
+                                (graph.n_rows, graph.n_cols))
+    return torch.sparse.mm(s, x)
+
+
+def diffuse_layer_composed(graph, x, w):
+    """One DiffNet layer as the reference writes it (diffnet.py:1127-1130): sparse.mm, cat, matmul, relu, the product
+    through `spmm` on the device; a CPU tensor (float64 too) takes torch's sparse product."""
+    _diffuse_args(graph, x, w)
+    z = spmm(graph, x) if x.is_cuda else _sparse_mm_host(graph, x)
+    return torch.relu(torch.matmul(torch.cat([z, x], dim=1), w))
+
+
+class _DiffuseLayer(torch.autograd.Function):
+    """gcr_diffuse_fwd_f32 / gcr_diffuse_bwd_f32: saves x, w and h only; the backward rebuilds S x (inside the kernel, or
+    by the SpMM into a scratch z when not `gather`) and finishes dx = S^T p + q with the SpMM on S^T."""
+
+    @staticmethod
+    def _z(graph, x, gather):
+        return None if gather else spmm_into(graph, x, y=torch.empty_like(x))
+
+    @staticmethod
+    def forward(ctx, x, w, graph, gather):
+        x, w = x.contiguous(), w.contiguous()
+        n, d = x.shape
+        h = torch.empty_like(x)
+        _lib.call("gcr_diffuse_fwd_f32", graph.rowptr, graph.col, graph.val, n, x, _DiffuseLayer._z(graph, x, gather), w, d, h,
+                  on=x)
+        ctx.save_for_backward(x, w, h)
+        ctx.graph, ctx.gather = graph, gather
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, h = ctx.saved_tensors
+        graph = ctx.graph
+        n, d = x.shape
+        p, q, dw = torch.empty_like(x), torch.empty_like(x), torch.empty_like(w)
+        ws = _lib.workspace("gcr_diffuse_workspace_bytes", n, d, device=x.device)
+        _lib.call("gcr_diffuse_bwd_f32", graph.rowptr, graph.col, graph.val, n, x, _DiffuseLayer._z(graph, x, ctx.gather), w, h,
+                  g.contiguous(), d, p, q, dw, ws, on=x)
+        dx = spmm_into(graph.t, p, acc_in=q, acc_out=torch.empty_like(x)) if ctx.needs_input_grad[0] else None
+        return dx, dw, None, None
+
+
+class _SpmmAdd(torch.autograd.Function):
+    """acc + A x as one launch (the SpMM's fused addend); backward: g to acc, A^T g to x."""
+
+    @staticmethod
+    def forward(ctx, x, acc, graph):
+        ctx.graph = graph
+        acc = acc.contiguous()
+        return spmm_into(graph, x, acc_in=acc, acc_out=torch.empty_like(acc))
+
+    @staticmethod
+    def backward(ctx, g):
+        return (_spmm_t(ctx.graph, g) if ctx.needs_input_grad[0] else None), (g if ctx.needs_input_grad[1] else None), None
+
+
+def spmm_add(graph: CsrGraph, x, acc):
+    """`acc + torch.sparse.mm(A, x)` (diffnet.py:1131) in one launch, differentiable in x and acc."""
+    return _SpmmAdd.apply(x, acc, graph)
+
+
+def diffuse_max_degree(graph):
+    """The largest number of entries in a row of the graph (cached on it)."""
+    m = getattr(graph, "_max_degree", None)
+    if m is None:
+        rp = graph.rowptr_host
+        m = graph._max_degree = int((rp[1:] - rp[:-1]).max()) if graph.n_rows else 0
+    return m
+
+
+def diffuse_layer(graph, x, w, gather=None):
+    """relu([S x | x] w), one layer of DiffNet.forward (diffnet.py:1127-1130), for S = `graph` [n, n], x [n, d], w [2 d, d]:
+    one autograd node over the fused kernels, differentiable in x and w, which keeps x, w and the output only (the
+    composition keeps S x and the [n, 2 d] concatenation as well).  gather=True sums S x inside the kernel (a row's entries
+    in stored order); gather=False runs the tuned SpMM into a scratch z first, forward and backward; None takes the first
+    when no row has more than DIFFUSE_GATHER_MAX_DEGREE entries (measured: SpMM + z wins on every graph with an entry).  Bitwise reproducible.  Widths outside
+    `diffuse_supported(d)`, other dtypes than float32, CPU tensors and n = 0 run `diffuse_layer_composed`."""
+    _diffuse_args(graph, x, w)
+    if not (x.is_cuda and x.dtype == torch.float32 and x.shape[0] > 0 and diffuse_supported(x.shape[1])):
+        return diffuse_layer_composed(graph, x, w)
+    if gather is None:
+        gather = diffuse_max_degree(graph) <= DIFFUSE_GATHER_MAX_DEGREE
+    return _DiffuseLayer.apply(x, w, graph, bool(gather))
+
+
+# ---------------------------------------------------------------------------------------------
 # Barlow Twins: redundancy reduction over two full-batch views (univariate/gbt.py:203-228, 386-395)
 # ---------------------------------------------------------------------------------------------
 BT_WIDTHS = (32, 64, 96, 128, 256)
