@@ -948,7 +948,8 @@ int32_t gcr_bt_bwd_f32(const float* h1, const float* h2, int64_t n, int32_t d, f
  *   h = relu(Z W_top + x W_bot),   w = [W_top; W_bot] [2 d, d] row-major,   x, h [n, d] row-major float32,
  *   Z = z when z != NULL, else Z = S x gathered inside the kernel from the CSR S [n, n] (rowptr int64 [n + 1], col int32,
  *   val float32 or NULL = ones), a row's entries summed in stored order.  A validated CSR is trusted (as in the SpMM).
- *   h must not alias x.
+ *   h must not alias x.  Without z, a NULL rowptr or col is GCR_EINVAL, also for a CSR without entries, whose col is never
+ *   read: the caller passes any non-NULL pointer there (functional.diffuse_layer does).
  * gcr_diffuse_bwd_f32: with m = g where h > 0 and 0 elsewhere,
  *   p = m W_top^T,  q = m W_bot^T  ([n, d] each; the caller finishes dx = S^T p + q with the SpMM),
  *   dw [2 d, d] = [Z | x]^T m   with Z rebuilt as in the forward (it is never saved).

@@ -1723,20 +1723,23 @@ def _diffuse_args(graph, x, w):
         raise ValueError("the graph must be [n, n] for x [n, d]")
 
 
-def _sparse_mm_host(graph, x):
-    """S x for a CPU tensor of any float dtype: torch's own sparse product on the graph's entries (duplicates sum)."""
-    rows = torch.repeat_interleave(torch.arange(graph.n_rows), graph.rowptr.cpu()[1:] - graph.rowptr.cpu()[:-1])
-    val = torch.ones(graph.nnz) if graph.val is None else graph.val.cpu()
-    s = torch.sparse_coo_tensor(torch.stack([rows, graph.col.cpu().to(torch.int64)]), val.to(x.dtype),
+def _sparse_mm_torch(graph, x):
+    """S x where libgcr has no kernel (a CPU tensor, or a dtype other than float32): torch's own sparse product on the
+    graph's entries (duplicates sum), on x's device and in its dtype."""
+    rowptr = graph.rowptr.to(x.device)
+    rows = torch.repeat_interleave(torch.arange(graph.n_rows, device=x.device), rowptr[1:] - rowptr[:-1])
+    val = torch.ones(graph.nnz, device=x.device) if graph.val is None else graph.val.to(x.device)
+    s = torch.sparse_coo_tensor(torch.stack([rows, graph.col.to(device=x.device, dtype=torch.int64)]), val.to(x.dtype),
                                 (graph.n_rows, graph.n_cols))
     return torch.sparse.mm(s, x)
 
 
 def diffuse_layer_composed(graph, x, w):
     """One DiffNet layer as the reference writes it (diffnet.py:1127-1130): sparse.mm, cat, matmul, relu, the product
-    through `spmm` on the device; a CPU tensor (float64 too) takes torch's sparse product."""
+    through `spmm` for float32 on the device; a CPU tensor and any other dtype (float64 on either side) take torch's
+    sparse product, as the reference does."""
     _diffuse_args(graph, x, w)
-    z = spmm(graph, x) if x.is_cuda else _sparse_mm_host(graph, x)
+    z = spmm(graph, x) if x.is_cuda and x.dtype == torch.float32 else _sparse_mm_torch(graph, x)
     return torch.relu(torch.matmul(torch.cat([z, x], dim=1), w))
 
 
@@ -1749,12 +1752,18 @@ class _DiffuseLayer(torch.autograd.Function):
         return None if gather else spmm_into(graph, x, y=torch.empty_like(x))
 
     @staticmethod
+    def _col(graph):
+        """graph.col, or a one-element stand-in for a graph without entries: an empty tensor's pointer is NULL, which the
+        kernels refuse when they gather (gcr.h), and no row reads it."""
+        return graph.col if graph.nnz else torch.zeros(1, dtype=torch.int32, device=graph.col.device)
+
+    @staticmethod
     def forward(ctx, x, w, graph, gather):
         x, w = x.contiguous(), w.contiguous()
         n, d = x.shape
         h = torch.empty_like(x)
-        _lib.call("gcr_diffuse_fwd_f32", graph.rowptr, graph.col, graph.val, n, x, _DiffuseLayer._z(graph, x, gather), w, d, h,
-                  on=x)
+        _lib.call("gcr_diffuse_fwd_f32", graph.rowptr, _DiffuseLayer._col(graph), graph.val, n, x,
+                  _DiffuseLayer._z(graph, x, gather), w, d, h, on=x)
         ctx.save_for_backward(x, w, h)
         ctx.graph, ctx.gather = graph, gather
         return h
@@ -1766,8 +1775,8 @@ class _DiffuseLayer(torch.autograd.Function):
         n, d = x.shape
         p, q, dw = torch.empty_like(x), torch.empty_like(x), torch.empty_like(w)
         ws = _lib.workspace("gcr_diffuse_workspace_bytes", n, d, device=x.device)
-        _lib.call("gcr_diffuse_bwd_f32", graph.rowptr, graph.col, graph.val, n, x, _DiffuseLayer._z(graph, x, ctx.gather), w, h,
-                  g.contiguous(), d, p, q, dw, ws, on=x)
+        _lib.call("gcr_diffuse_bwd_f32", graph.rowptr, _DiffuseLayer._col(graph), graph.val, n, x,
+                  _DiffuseLayer._z(graph, x, ctx.gather), w, h, g.contiguous(), d, p, q, dw, ws, on=x)
         dx = spmm_into(graph.t, p, acc_in=q, acc_out=torch.empty_like(x)) if ctx.needs_input_grad[0] else None
         return dx, dw, None, None
 

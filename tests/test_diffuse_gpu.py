@@ -2,56 +2,26 @@
 float64, in both `gather` modes.
 
 The component cases are the reference's own statements (diffnet.py:1127-1130) run under float64 autograd
-(tests/golden/diffnet_steps.npz, comp<d>/); the launch-shape sweep uses a float64 torch restatement on the CPU.  One rule,
-the project's (restated from tests/test_buir_gpu.py):  err / S <= max(4 x drift, 2^-20)  and  err / S <= 1e-5,
-S = max |f64|, drift = the float32 error of the SAME float64 source (stored for the component cases, computed here for
-the restatement).  Inputs of the sweep are drawn until the float64 pre-activations keep a margin of 8 x their float32 error
-from zero, as the fixture's are: a gradient pin must not compare two different ReLU masks."""
+(tests/golden/diffnet_steps.npz, comp<d>/); the launch-shape sweep uses a float64 torch restatement on the CPU, with the
+values of S and with S all ones (`val == nullptr`) at every shape.  One rule, tests/diffuse_rules.py's `check`, with the
+drift stored for the component cases and computed from the restatement for the sweep.  Inputs of the sweep are drawn until
+the float64 pre-activations keep a margin of 8 x their float32 error from zero, as the fixture's are
+(diffuse_rules.margin_case).  The launch paths these shapes do not reach are in tests/test_diffuse_paths_gpu.py."""
 import numpy as np
 import pytest
 import torch
 
 import diffnet_fixture as dfx
+from diffuse_rules import check as _check, device_graph as _graph, fused_layer as _layer, margin_case
 
 pytestmark = pytest.mark.gpu
 
-FLOOR, NORTH_STAR = 2.0 ** -20, 1e-5
 EINVAL = "code -1"
 
 
 @pytest.fixture(scope="module")
 def golden():
     return dfx.load()
-
-
-def _graph(row, col, val, n):
-    import recommendation_amd as ra
-    return ra.CsrGraph.from_coo(row, col, val, n, n, "cuda")
-
-
-def _layer(graph, x, w, g, gather):
-    from recommendation_amd import functional as Fn
-    xt = torch.from_numpy(x).cuda().requires_grad_(True)
-    wt = torch.from_numpy(w).cuda().requires_grad_(True)
-    h = Fn.diffuse_layer(graph, xt, wt, gather=gather)
-    assert h.grad_fn is not None and type(h.grad_fn).__name__.startswith("_DiffuseLayer"), "the fused node must run"
-    h.backward(torch.from_numpy(g).cuda())
-    torch.cuda.synchronize()
-    return dict(h=h.detach().cpu().numpy(), dx=xt.grad.cpu().numpy(), dw=wt.grad.cpu().numpy())
-
-
-def _check(got, ref, drift, tag):
-    """drift: relative to the scale, per key."""
-    lines, bad = [], []
-    for k, want in ref.items():
-        scale = float(np.abs(want).max())
-        err = float(np.abs(got[k].astype(np.float64) - want).max()) / scale
-        bound = max(4.0 * drift[k], FLOOR)
-        lines.append(f"DIFFUSE {tag} {k}: err/S {err:.3g} bound {bound:.3g} (drift {drift[k]:.3g}, S {scale:.3g})")
-        if not (np.isfinite(got[k]).all() and err <= bound and err <= NORTH_STAR):
-            bad.append(lines[-1])
-    print("\n".join(lines))
-    assert not bad, "\n".join(bad)
 
 
 @pytest.mark.parametrize("d", dfx.COMP_WIDTHS)
@@ -64,20 +34,10 @@ def test_component_case_matches_the_reference_in_float64(golden, d):
         _check(_layer(graph, c["x"], c["w"], c["g"], gather), ref, drift, f"component d={d} gather={gather}")
 
 
-def _restatement(row, col, val, n, x, w, g, dtype):
-    s = torch.zeros(n, n, dtype=dtype)
-    v = torch.ones(len(row), dtype=dtype) if val is None else torch.from_numpy(val).to(dtype)
-    s.index_put_((torch.from_numpy(row), torch.from_numpy(col)), v, accumulate=True)
-    xt, wt = torch.from_numpy(x).to(dtype).requires_grad_(True), torch.from_numpy(w).to(dtype).requires_grad_(True)
-    pre = torch.cat([s @ xt, xt], 1) @ wt
-    h = torch.relu(pre)
-    h.backward(torch.from_numpy(g).to(dtype))
-    return dict(h=h.detach().double().numpy(), dx=xt.grad.double().numpy(), dw=wt.grad.double().numpy()), pre.detach().double().numpy()
-
-
-def _sweep_case(n, d):
-    """Random S (a few entries per row, repeats allowed, an empty row when there is room), x, w, g with a ReLU margin."""
-    for seed in range(50):
+def _sweep_case(n, d, ones):
+    """Random S (a few entries per row, repeats allowed, an empty row when there is room; all-ones when `ones`), x, w, g
+    with a ReLU margin."""
+    def draw(seed):
         rng = np.random.default_rng([n, d, seed])
         deg = rng.integers(0, 9, n)
         deg[-1] = max(deg[-1], 1)
@@ -85,23 +45,20 @@ def _sweep_case(n, d):
             deg[1] = 0
         row = np.repeat(np.arange(n, dtype=np.int64), deg)
         col = rng.integers(0, n, row.size).astype(np.int64)
-        val = None if n == 33 else rng.uniform(0.1, 1.0, row.size).astype(np.float32)
-        x, w, g = dfx.component_inputs(d, 1000 + seed, n=n)
-        ref, pre64 = _restatement(row, col, val, n, x, w, g, torch.float64)
-        f32, pre32 = _restatement(row, col, val, n, x, w, g, torch.float32)
-        if np.abs(pre64).min() >= 8.0 * np.abs(pre32 - pre64).max():
-            drift = {k: float(np.abs(f32[k] - ref[k]).max()) / float(np.abs(ref[k]).max()) for k in ref}
-            return row, col, val, x, w, g, ref, drift
-    raise AssertionError("no seed with a ReLU margin")
+        val = None if ones else rng.uniform(0.1, 1.0, row.size).astype(np.float32)
+        return (row, col, val, n) + dfx.component_inputs(d, 1000 + seed, n=n)
+
+    return margin_case(draw)
 
 
 @pytest.mark.parametrize("d", dfx.COMP_WIDTHS)
-@pytest.mark.parametrize("n", [1, 33, 64, 257])
-def test_launch_shapes(n, d):
-    row, col, val, x, w, g, ref, drift = _sweep_case(n, d)
+@pytest.mark.parametrize("n,ones", [pytest.param(n, ones, id=f"{n}-ones" if ones else str(n))
+                                    for n in (1, 33, 64, 257) for ones in (False, True)])
+def test_launch_shapes(n, ones, d):
+    row, col, val, x, w, g, ref, drift = _sweep_case(n, d, ones)
     graph = _graph(row, col, val, n)
     for gather in (True, False):
-        _check(_layer(graph, x, w, g, gather), ref, drift, f"n={n} d={d} gather={gather}")
+        _check(_layer(graph, x, w, g, gather), ref, drift, f"n={n} d={d} ones={ones} gather={gather}")
 
 
 @pytest.mark.parametrize("d", dfx.COMP_WIDTHS)
