@@ -286,6 +286,28 @@ def call(name, *args, on=None):
     return rc
 
 
+def call_on(handle):
+    """`call` for another handle than the package's own (the A/B tools time other builds of libgcr.so; a test binds a
+    recording stand-in): the same conversions and the same reading of the return, over the exports of SIGNATURES that
+    `handle` has.  `.has(name)` tells whether it has one; calling one it lacks is a KeyError."""
+    exports = _bind(handle, {name: sig for name, sig in SIGNATURES.items() if hasattr(handle, name)})
+
+    def call(name, *args, on=None):
+        plain, streamed, status = exports[name]
+        if on is None:
+            conv = plain(*args)
+        else:
+            conv = streamed(*args, on if isinstance(on, c_void_p) else cur_stream(on.device if isinstance(on, _Tensor) else on))
+        rc = getattr(handle, name)(*conv)
+        if status:
+            check(rc, name)
+            return None
+        return rc
+
+    call.has = exports.__contains__
+    return call
+
+
 _SIZE_UNIT = {"_bytes": 1, "_floats": 4, "_words": 4}     # what a size export counts, by its name's ending
 
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, spmm_launch
 from .graph import CsrGraph
 
 SPMM_ROW_L2NORM = 1
@@ -25,11 +25,6 @@ def _check_dense(x, n_rows, name):
         raise ValueError(f"{name} must be float32 [{n_rows}, d], got {tuple(x.shape)} {x.dtype}")
     if not (1 <= x.shape[1] <= 256):
         raise ValueError("embedding dim must be in [1, 256]")
-
-
-def _plan_head(graph, plan):
-    """The eight arguments every SpMM entry point of gcr.h starts with: a launch plan and the CSR it partitions."""
-    return (plan.desc, plan.n_parts, plan.long_row, plan.long_slot0, plan.n_long, graph.rowptr, graph.col, graph.val)
 
 
 def _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, **outputs):
@@ -75,27 +70,24 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
     stream = _lib.cur_stream(x.device)
     # the heaviest rows by column window (graph.HubPlan): plain launches only
     hub = graph.hub if plain and graph.hub is not None and graph.hub.eligible(d) else None
+    out = dict(y=y, acc_in=acc_in, acc_out=acc_out, acc_scale=acc_scale, val_scale=val_scale)    # every route's epilogue
     if hub is not None and d <= WINDOWED_MAX_D:
         # both walks in one grid, both plans' split rows in another, then the hub reduction: the words of the branch below
         H = hub.H
-        _lib.call("gcr_spmm_windowed_f32", *_plan_head(H, H.plan), H.workspace(d), *_plan_head(graph, hub.main), ws,
-                  hub.hub_row, hub.n_hub, hub.n_windows, hub.partials(d), x, d, val_scale, y, acc_in, acc_out, acc_scale,
-                  hub.main_first, graph.n_rows, graph.n_cols, on=stream)
+        spmm_launch.windowed(H, H.plan, graph, hub.main, hub, hub_split=H.workspace(d), partials=ws, hub_partials=hub.partials(d),
+                             x=x, d=d, main_first=hub.main_first, on=stream, **out)
     else:
         if hub is not None:               # d > 64: the companion through the generic kernel, the reduction, then `main`
             H, part = hub.H, hub.partials(d)
-            _lib.call("gcr_spmm_csr_acc2_f32", *_plan_head(H, H.plan), None, 1.0, x, d, part, None, None, 0.0, None, 1.0, 0,
-                      None, H.workspace(d), H.n_rows, H.n_cols, None, on=stream)
-            _lib.call("gcr_spmm_hub_reduce_f32", hub.hub_row, hub.n_hub, hub.n_windows, part, d, val_scale, y, acc_in, acc_out,
-                      acc_scale, graph.n_rows, on=stream)
+            spmm_launch.csr_acc2(H, H.plan, x=x, d=d, y=part, acc_in2_scale=0.0, partials=H.workspace(d), on=stream)
+            spmm_launch.hub_reduce(hub, partials=part, d=d, n_rows=graph.n_rows, on=stream, **out)
             p = hub.main                  # every other row: the classic walk with the hub rows skipped
         if plain and d <= ROWS_MAX_D:     # the plain launch's own kernel: the same words on another schedule
-            _lib.call("gcr_spmm_rows_f32", *_plan_head(graph, p), val_scale, x, d, y, acc_in, acc_out, acc_scale, ws,
-                      graph.n_rows, graph.n_cols, on=stream)
+            spmm_launch.rows(graph, p, x=x, d=d, partials=ws, on=stream, **out)
         else:
-            _lib.call("gcr_spmm_csr_acc2_f32", *_plan_head(graph, p), keep_bits, val_scale, x, d, y, acc_in, acc_in2,
-                      acc_in2_scale, acc_out, acc_scale, SPMM_ROW_L2NORM if l2norm else 0, inv_norm_out, ws, graph.n_rows,
-                      graph.n_cols, col_active_bits, on=stream)
+            spmm_launch.csr_acc2(graph, p, x=x, d=d, partials=ws, keep_bits=keep_bits, acc_in2=acc_in2, acc_in2_scale=acc_in2_scale,
+                                 flags=SPMM_ROW_L2NORM if l2norm else 0, inv_norm_out=inv_norm_out,
+                                 col_active_bits=col_active_bits, on=stream, **out)
     if sink is not None:
         ev1.record()
         sink.append((ev0, ev1))
@@ -530,8 +522,8 @@ def spmm_dual_into(graph: CsrGraph, x, y_raw, y_norm, inv_norm_out=None, keep_bi
     _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, y_raw=y_raw, y_norm=y_norm)
     if y_raw.data_ptr() == y_norm.data_ptr():
         raise ValueError("y_raw and y_norm must be different buffers")
-    _lib.call("gcr_spmm_csr_dual_f32", *_plan_head(graph, graph.plan), keep_bits, val_scale, x, d, y_raw, y_norm, inv_norm_out,
-              graph.workspace(d), graph.n_rows, graph.n_cols, on=x)
+    spmm_launch.csr_dual(graph, graph.plan, x=x, d=d, y_raw=y_raw, y_norm=y_norm, inv_norm_out=inv_norm_out, keep_bits=keep_bits,
+                         val_scale=val_scale, partials=graph.workspace(d), on=x)
     return y_raw, y_norm
 
 
@@ -547,8 +539,9 @@ def spmm_dual_acc_into(graph: CsrGraph, x, y_raw, acc_in, acc_out, inv_norm_out,
     _check_spmm_outputs(graph, d, keep_bits, inv_norm_out, y_raw=y_raw, acc_out=acc_out, acc_in=acc_in, y_norm=y_norm)
     if y_raw.data_ptr() == acc_out.data_ptr() or (y_norm is not None and y_norm.data_ptr() == y_raw.data_ptr()):
         raise ValueError("y_raw, y_norm and acc_out must be different buffers")
-    _lib.call("gcr_spmm_csr_dual_acc_f32", *_plan_head(graph, graph.plan), keep_bits, val_scale, x, d, y_raw, y_norm, acc_in,
-              acc_out, inv_norm_out, graph.workspace(d), graph.n_rows, graph.n_cols, on=x)
+    spmm_launch.csr_dual_acc(graph, graph.plan, x=x, d=d, y_raw=y_raw, y_norm=y_norm, acc_in=acc_in, acc_out=acc_out,
+                             inv_norm_out=inv_norm_out, keep_bits=keep_bits, val_scale=val_scale, partials=graph.workspace(d),
+                             on=x)
     return y_raw, acc_out
 
 

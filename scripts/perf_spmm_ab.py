@@ -57,39 +57,29 @@ def child(args):
     x0 = torch.empty(n, d, device=dev)
     torch.nn.init.xavier_uniform_(x0, generator=torch.Generator(device=dev).manual_seed(0))
     p, ws = graph.plan, graph.workspace(d)
-    res, argt = _lib.SIGNATURES["gcr_spmm_csr_acc2_f32"]
+    from recommendation_amd import spmm_launch as L
     from recommendation_amd.graph import HubPlan, long_rows_first_order
     libs, plans, orders = [], {}, {}
     for path in args.lib:
-        h = ctypes.CDLL(os.path.abspath(path))
-        fn = h.gcr_spmm_csr_acc2_f32
-        fn.restype, fn.argtypes = res, argt
-        rows = getattr(h, "gcr_spmm_rows_f32", None) if d <= 64 and not args.acc2 else None
-        if rows is not None:
-            rows.restype, rows.argtypes = _lib.SIGNATURES["gcr_spmm_rows_f32"]
-        red = getattr(h, "gcr_spmm_hub_reduce_f32", None)
-        if red is None or args.acc2:                       # the second-addend form never takes the windowed plan
-            libs.append((path, fn, None, None, None, rows, None, None))
+        call = _lib.call_on(ctypes.CDLL(os.path.abspath(path)))             # the exports this library has, and no others
+        rows = d <= 64 and not args.acc2 and call.has("gcr_spmm_rows_f32")
+        if not call.has("gcr_spmm_hub_reduce_f32") or args.acc2:           # the second-addend form never takes the windowed plan
+            libs.append((path, call, None, False, rows, None))
             continue
-        red.restype, red.argtypes = _lib.SIGNATURES["gcr_spmm_hub_reduce_f32"]
-        own = getattr(h, "gcr_spmm_hub_parts_f32", None) if d <= 64 else None
-        if own is not None:
-            own.restype, own.argtypes = _lib.SIGNATURES["gcr_spmm_hub_parts_f32"]
-        fused = getattr(h, "gcr_spmm_windowed_f32", None) if d <= 64 and not args.five_launch else None
-        if fused is not None:
-            fused.restype, fused.argtypes = _lib.SIGNATURES["gcr_spmm_windowed_f32"]
+        own = d <= 64 and call.has("gcr_spmm_hub_parts_f32")
+        fused = d <= 64 and not args.five_launch and call.has("gcr_spmm_windowed_f32")
 
         def add(name, hub):
-            if fused is None or hub is None or not args.order:
-                cell = None if fused is None or hub is None else (int(hub.main_first), hub.main)
-                libs.append((name, fn, red, hub, own, rows, fused, cell))
+            if not fused or hub is None or not args.order:
+                cell = None if not fused or hub is None else (int(hub.main_first), hub.main)
+                libs.append((name, call, hub, own, rows, cell))
                 return
             for c in args.order:                           # one entry per order of the work, the same plans
                 first, _, desc_order = c.partition(":")
                 if (first, desc_order) not in orders:
                     orders[first, desc_order] = (["hub_first", "main_first", "two_walks"].index(first), hub.main if not desc_order else
                                                  hub.main.permuted(long_rows_first_order(hub.main.desc_host)))
-                libs.append((f"{name} [{c}]", fn, red, hub, own, rows, fused, orders[first, desc_order]))
+                libs.append((f"{name} [{c}]", call, hub, own, rows, orders[first, desc_order]))
 
         if not args.hub_config:
             add(path, graph.hub if graph.hub is not None and graph.hub.eligible(d) else None)
@@ -106,43 +96,27 @@ def child(args):
     in2_scale = 0.25 if args.acc2 else 0.0
 
     def launch(lib, x, out):
-        _, fn, red, hub, own, rows, fused, cell = lib
+        _, call, hub, own, rows, cell = lib
+        layer = dict(x=x, d=d, acc_in=x0, acc_out=out, on=stream, call=call)         # the Horner layer: one acc_out, no y
         q = p
         if cell is not None:
             main_first, q = cell
-            H, hp = hub.H, hub.H.plan
-            _lib.check(fused(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
-                             _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(H.workspace(d)),
-                             _lib.dptr(q.desc), q.n_parts, _lib.dptr(q.long_row), _lib.dptr(q.long_slot0), q.n_long,
-                             _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), _lib.dptr(ws),
-                             _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(hub.partials(d)), _lib.dptr(x), d,
-                             1.0, None, _lib.dptr(x0), _lib.dptr(out), 1.0, main_first, graph.n_rows, graph.n_cols, stream),
-                       "gcr_spmm_windowed_f32")
+            H = hub.H
+            L.windowed(H, H.plan, graph, q, hub, hub_split=H.workspace(d), partials=ws, hub_partials=hub.partials(d),
+                       main_first=main_first, **layer)
             return
         if hub is not None:
-            H, hp, part = hub.H, hub.H.plan, hub.partials(d)
-            if own is not None:
-                _lib.check(own(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
-                               _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(x), d, _lib.dptr(part),
-                               _lib.dptr(H.workspace(d)), H.n_rows, H.n_cols, stream), "gcr_spmm_hub_parts_f32")
+            H, part = hub.H, hub.partials(d)
+            if own:
+                L.hub_parts(H, H.plan, x=x, d=d, y=part, partials=H.workspace(d), on=stream, call=call)
             else:
-                _lib.check(fn(_lib.dptr(hp.desc), hp.n_parts, _lib.dptr(hp.long_row), _lib.dptr(hp.long_slot0), hp.n_long,
-                              _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), None, 1.0, _lib.dptr(x), d,
-                              _lib.dptr(part), None, None, 0.0, None, 1.0, 0, None, _lib.dptr(H.workspace(d)), H.n_rows,
-                              H.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
-            _lib.check(red(_lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, 1.0, None, _lib.dptr(x0),
-                           _lib.dptr(out), 1.0, graph.n_rows, stream), "gcr_spmm_hub_reduce_f32")
+                L.csr_acc2(H, H.plan, x=x, d=d, y=part, acc_in2_scale=0.0, partials=H.workspace(d), on=stream, call=call)
+            L.hub_reduce(hub, partials=part, d=d, n_rows=graph.n_rows, acc_in=x0, acc_out=out, on=stream, call=call)
             q = hub.main
-        if rows is not None:
-            _lib.check(rows(_lib.dptr(q.desc), q.n_parts, _lib.dptr(q.long_row), _lib.dptr(q.long_slot0), q.n_long,
-                            _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), 1.0, _lib.dptr(x), d, None,
-                            _lib.dptr(x0), _lib.dptr(out), 1.0, _lib.dptr(ws), graph.n_rows, graph.n_cols, stream),
-                       "gcr_spmm_rows_f32")
+        if rows:
+            L.rows(graph, q, partials=ws, **layer)
             return
-        _lib.check(fn(_lib.dptr(q.desc), q.n_parts, _lib.dptr(q.long_row), _lib.dptr(q.long_slot0), q.n_long,
-                      _lib.dptr(graph.rowptr), _lib.dptr(graph.col), _lib.dptr(graph.val), None, 1.0, _lib.dptr(x), d, None,
-                      _lib.dptr(x0), _lib.dptr(in2), in2_scale, _lib.dptr(out), 1.0, 0, None, _lib.dptr(ws), graph.n_rows,
-                      graph.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
+        L.csr_acc2(graph, q, partials=ws, acc_in2=in2, acc_in2_scale=in2_scale, **layer)
 
     z = torch.empty_like(x0)
     launch(libs[0], x0, z)                         # layer 1 of the base: the input of the timed (second) layer
@@ -172,13 +146,13 @@ def child(args):
         outs = snaps
     report = {"workload": args.workload, "acc2": bool(args.acc2), "d": d, "nnz": graph.nnz, "n_parts": p.n_parts, "n_long": p.n_long,
               "alternations": args.alternations, "launches": args.launches, "libs": []}
-    for k, (path, _, _, hub, _, rows, _, cell) in enumerate(libs):
+    for k, (path, _, hub, _, rows, cell) in enumerate(libs):
         m = sum(ms[k]) / len(ms[k])
         ent = {"lib": path, "ms_per_layer": [round(v, 5) for v in ms[k]], "mean": round(m, 5),
                "spread": round(max(ms[k]) - min(ms[k]), 5), "equal_to_base": bool(torch.equal(outs[k], outs[0])),
                "max_diff_over_max": float((outs[k] - outs[0]).abs().max() / outs[0].abs().max()),
                "main_entry": "gcr_spmm_windowed_f32" if cell is not None else
-                             "gcr_spmm_csr_acc2_f32" if rows is None else "gcr_spmm_rows_f32",
+                             "gcr_spmm_csr_acc2_f32" if not rows else "gcr_spmm_rows_f32",
                "windowed": None if hub is None else {"window_rows": hub.window_rows, "windows": hub.n_windows,
                                                       "n_hub": hub.n_hub, "hub_nnz": hub.hub_nnz,
                                                       "nnz_per_part": hub.H.plan.nnz_per_part}}

@@ -60,12 +60,10 @@ def run(args):
     idx[1::2] = torch.randint(0, n_cold, (n_idx // 2,), device=dev, dtype=torch.int32, generator=g)
     stream_in = torch.rand(n_idx // 16, 64, 4, device=dev, generator=g)
     outs = {flags: torch.full((n_idx // 16, 64), float("nan"), device=dev) for flags in sorted({f for _, f in CELLS})}
-    L, stream = _lib.lib(), _lib.cur_stream(dev)
+    stream = _lib.cur_stream(dev)
 
     def launch(flags):
-        _lib.check(L.gcr_probe_policy_rows_f32(_lib.dptr(hot), n_hot, _lib.dptr(cold), n_cold, _lib.dptr(idx), n_idx,
-                                               _lib.dptr(stream_in), _lib.dptr(outs[flags]), flags, stream),
-                   "gcr_probe_policy_rows_f32")
+        _lib.call("gcr_probe_policy_rows_f32", hot, n_hot, cold, n_cold, idx, n_idx, stream_in, outs[flags], flags, on=stream)
 
     cells = [{"cell": label, "nt_flags": flags} for label, flags in CELLS]
     if args.counters:

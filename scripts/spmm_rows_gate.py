@@ -44,7 +44,9 @@ def run(args):
     import torch
     import bench
     import recommendation_amd as ra
+    import copy
     from recommendation_amd import _lib
+    from recommendation_amd import spmm_launch as L
 
     dev = torch.device("cuda", 0)
     wl = bench.WORKLOADS[args.workload]
@@ -60,7 +62,7 @@ def run(args):
     hub = graph.hub if graph.hub is not None and graph.hub.eligible(d) else None
     p = graph.plan if hub is None else hub.main
     ws = graph.workspace(d)
-    L, stream = _lib.lib(), _lib.cur_stream(dev)
+    stream = _lib.cur_stream(dev)
     desc_host = p.desc_host
     row0 = desc_host[:, 2] & 0xFFFFFFFF
     split = int((row0 < n_u).sum())                       # partitions are in row order: [0, split) start at a user row
@@ -92,20 +94,16 @@ def run(args):
         print(json.dumps(ent), flush=True)
 
     for entry in args.entry:
-        if entry == "rows" and not hasattr(L, "gcr_spmm_rows_f32"):
+        if entry == "rows" and not hasattr(_lib.lib(), "gcr_spmm_rows_f32"):
             sys.exit("this library has no gcr_spmm_rows_f32")
         for label, a, b, n_long in segments:
-            dsc = p.desc[a:b]
-            head = (_lib.dptr(dsc), b - a, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), n_long, _lib.dptr(graph.rowptr),
-                    _lib.dptr(graph.col), _lib.dptr(graph.val))
+            part = copy.copy(p)                           # a run of the plan's partitions, with or without its split rows
+            part.desc, part.n_parts, part.n_long = p.desc[a:b], b - a, n_long
+            layer = dict(x=x, d=d, acc_in=x0, acc_out=out, partials=ws, on=stream)
             if entry == "rows":
-                fn = lambda head=head: _lib.check(L.gcr_spmm_rows_f32(
-                    *head, 1.0, _lib.dptr(x), d, None, _lib.dptr(x0), _lib.dptr(out), 1.0, _lib.dptr(ws), graph.n_rows,
-                    graph.n_cols, stream), "gcr_spmm_rows_f32")
+                fn = lambda part=part, layer=layer: L.rows(graph, part, **layer)
             else:
-                fn = lambda head=head: _lib.check(L.gcr_spmm_csr_acc2_f32(
-                    *head, None, 1.0, _lib.dptr(x), d, None, _lib.dptr(x0), None, 0.0, _lib.dptr(out), 1.0, 0, None,
-                    _lib.dptr(ws), graph.n_rows, graph.n_cols, None, stream), "gcr_spmm_csr_acc2_f32")
+                fn = lambda part=part, layer=layer: L.csr_acc2(graph, part, acc_in2_scale=0.0, **layer)
             rows_written = int((desc_host[a:b, 2][desc_host[a:b, 3] < 0] >> 32).sum())
             timed(f"{label}, {entry}", fn, {"entry": entry, "n_parts": b - a, "nnz": nnz_of(a, b), "rows_written": rows_written,
                                             "kernel": "spmm_" + entry})
@@ -117,8 +115,8 @@ def run(args):
             n_idx = max(64, n_idx // 64 * 64)
             idx = torch.randint(0, table.shape[0], (n_idx,), device=dev, dtype=torch.int32, generator=g)
             sink = torch.empty(n_idx // 64, 64, device=dev)
-            fn = lambda table=table, idx=idx, sink=sink: _lib.check(L.gcr_probe_gather_rows_f32(
-                _lib.dptr(table), table.shape[0], _lib.dptr(idx), idx.numel(), _lib.dptr(sink), stream), "gcr_probe_gather_rows_f32")
+            fn = lambda table=table, idx=idx, sink=sink: _lib.call("gcr_probe_gather_rows_f32", table, table.shape[0], idx,
+                                                                   idx.numel(), sink, on=stream)
             timed(label, fn, {"entry": "probe", "nnz": n_idx, "table_bytes": int(table.shape[0]) * d * 4, "kernel": "probe_gather"})
             if not args.counters:
                 cases[-1]["gathered_TB_per_s"] = round(n_idx * 256 / cases[-1]["ms_per_launch"] / 1e9, 3)

@@ -18,17 +18,19 @@ import torch
 
 from oracle import oracle_np as O
 from spmm_fused_common import CASES, build_graph, case_matrix, companion_plan
+from spmm_raw import Out, assert_words_equal, nan
 from spmm_window_common import F32, N_COLS
 
 pytestmark = pytest.mark.gpu
 
-# (y, acc_in, acc_out, val_scale, acc_scale): the forms of test_spmm_window_gpu.test_windowed_order_is_pinned
+# (y, acc_in: None | 'given' | 'inplace', acc_out, val_scale, acc_scale): the forms of
+# test_spmm_window_gpu.test_windowed_order_is_pinned
 FORMS = {
-    "y_only": (True, False, False, 1.0, 1.0),
-    "acc_out_only": (False, True, True, 1.0, 1.0),
-    "both_scaled": (True, True, True, 1.0 / 0.65, 0.25),
-    "in_place": (False, "same", True, 1.0, 0.5),
-    "acc_in_none": (False, False, True, 0.7, 3.0),
+    "y_only": (True, None, False, 1.0, 1.0),
+    "acc_out_only": (False, "given", True, 1.0, 1.0),
+    "both_scaled": (True, "given", True, 1.0 / 0.65, 0.25),
+    "in_place": (False, "inplace", True, 1.0, 0.5),
+    "acc_in_none": (False, None, True, 0.7, 3.0),
 }
 CELLS = {"hub_first": (0, False), "main_first": (1, False), "hub_first_long_rows_first": (0, True),
          "main_first_long_rows_first": (1, True)}
@@ -40,52 +42,32 @@ def _graph(case, has_val):
     return g, companion_plan(g, case)
 
 
-def _head(plan, csr):
-    from recommendation_amd import _lib
-    return (_lib.dptr(plan.desc), plan.n_parts, _lib.dptr(plan.long_row), _lib.dptr(plan.long_slot0), plan.n_long,
-            _lib.dptr(csr.rowptr), _lib.dptr(csr.col), _lib.dptr(csr.val))
-
-
-class _Buffers:
+class _Buffers(Out):
     """One launch's outputs and workspaces, NaN-filled; acc_in is a copy the launch may overwrite (in place)."""
 
     def __init__(self, g, hp, main, d, form, acc_in):
-        want_y, a_in, want_acc, self.val_scale, self.acc_scale = FORMS[form]
-        nan = lambda r: torch.full((max(r, 1), d), float("nan"), device="cuda")
-        self.y = nan(g.n_rows) if want_y else None
-        self.acc_out = nan(g.n_rows) if want_acc else None
-        self.acc_in = acc_in.clone() if a_in else None
-        if a_in == "same":
-            self.acc_out = self.acc_in
-        self.part, self.h_ws, self.m_ws = nan(g.hub.H.n_rows), nan(hp.n_slots), nan(main.n_slots)
+        super().__init__(g.n_rows, d, FORMS[form], acc_in)
+        self.part, self.h_ws, self.m_ws = nan(g.hub.H.n_rows, d), nan(hp.n_slots, d), nan(main.n_slots, d)
 
     def words(self):
         named = (("y", self.y), ("acc_out", self.acc_out), ("hub partials", self.part),
                  ("companion workspace", self.h_ws), ("main workspace", self.m_ws))
-        return {k: t.cpu().numpy().view(np.uint32) for k, t in named if t is not None}
+        return {k: t for k, t in named if t is not None}
 
 
 def _old_entries(g, hp, main, xt, d, b):
     """Today's order: the companion and its split segments, the hub reduction, the main plan and its split rows."""
-    from recommendation_amd import _lib
-    L, hub, H, s = _lib.lib(), g.hub, g.hub.H, _lib.cur_stream(xt.device)
-    _lib.check(L.gcr_spmm_hub_parts_f32(*_head(hp, H), _lib.dptr(xt), d, _lib.dptr(b.part), _lib.dptr(b.h_ws), H.n_rows,
-                                        H.n_cols, s), "gcr_spmm_hub_parts_f32")
-    _lib.check(L.gcr_spmm_hub_reduce_f32(_lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(b.part), d, b.val_scale,
-                                         _lib.dptr(b.y), _lib.dptr(b.acc_in), _lib.dptr(b.acc_out), b.acc_scale, g.n_rows, s),
-               "gcr_spmm_hub_reduce_f32")
-    _lib.check(L.gcr_spmm_rows_f32(*_head(main, g), b.val_scale, _lib.dptr(xt), d, _lib.dptr(b.y), _lib.dptr(b.acc_in),
-                                   _lib.dptr(b.acc_out), b.acc_scale, _lib.dptr(b.m_ws), g.n_rows, g.n_cols, s),
-               "gcr_spmm_rows_f32")
+    from recommendation_amd import spmm_launch as L
+    hub, H = g.hub, g.hub.H
+    L.hub_parts(H, hp, x=xt, d=d, y=b.part, partials=b.h_ws, on=xt)
+    L.hub_reduce(hub, partials=b.part, d=d, n_rows=g.n_rows, on=xt, **b.kw())
+    L.rows(g, main, x=xt, d=d, partials=b.m_ws, on=xt, **b.kw())
 
 
 def _new_entry(g, hp, main, xt, d, b, main_first):
-    from recommendation_amd import _lib
-    L, hub, H, s = _lib.lib(), g.hub, g.hub.H, _lib.cur_stream(xt.device)
-    return L.gcr_spmm_windowed_f32(*_head(hp, H), _lib.dptr(b.h_ws), *_head(main, g), _lib.dptr(b.m_ws),
-                                   _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(b.part), _lib.dptr(xt), d,
-                                   b.val_scale, _lib.dptr(b.y), _lib.dptr(b.acc_in), _lib.dptr(b.acc_out), b.acc_scale,
-                                   main_first, g.n_rows, g.n_cols, s)
+    from recommendation_amd import spmm_launch as L
+    L.windowed(g.hub.H, hp, g, main, g.hub, hub_split=b.h_ws, partials=b.m_ws, hub_partials=b.part, x=xt, d=d,
+               main_first=main_first, on=xt, **b.kw())
 
 
 @functools.lru_cache(maxsize=None)
@@ -113,8 +95,7 @@ def _reference(case, d, has_val):
 def _same(got, want, what):
     assert got.keys() == want.keys()
     for k in want:
-        same = got[k] == want[k]
-        assert same.all(), f"{what}, {k}: {int((~same).sum())} of {same.size} words differ, first at {np.argwhere(~same)[0]}"
+        assert_words_equal(got[k], want[k], f"{what}, {k}")
 
 
 def _assert_counts(case, g, hp):
@@ -136,7 +117,6 @@ def _assert_counts(case, g, hp):
 @pytest.mark.parametrize("d", [64, 48])
 @pytest.mark.parametrize("case", CASES)
 def test_every_word_is_the_three_entries(case, d, has_val, cell):
-    from recommendation_amd import _lib
     from recommendation_amd.graph import long_rows_first_order
     g, hp = _graph(case, has_val)
     _assert_counts(case, g, hp)
@@ -150,26 +130,25 @@ def test_every_word_is_the_three_entries(case, d, has_val, cell):
     _, xt, a_in = _inputs(case, d, has_val)
     ref = _reference(case, d, has_val)
     for form in FORMS:
-        assert not any(np.isnan(w.view(F32)).any() for k, w in ref[form].items() if k in ("y", "acc_out", "hub partials")), \
+        assert not any(bool(torch.isnan(w).any()) for k, w in ref[form].items() if k in ("y", "acc_out", "hub partials")), \
             f"{form}: the old entries left a word unwritten"
         first = _Buffers(g, hp, main, d, form, a_in)
-        _lib.check(_new_entry(g, hp, main, xt, d, first, main_first), "gcr_spmm_windowed_f32")
+        _new_entry(g, hp, main, xt, d, first, main_first)
         _same(first.words(), ref[form], f"{case} {form}")
         second = _Buffers(g, hp, main, d, form, a_in)
-        _lib.check(_new_entry(g, hp, main, xt, d, second, main_first), "gcr_spmm_windowed_f32")
+        _new_entry(g, hp, main, xt, d, second, main_first)
         _same(second.words(), first.words(), f"{case} {form}, second launch")
 
 
 @pytest.mark.parametrize("main_first", [0, 1], ids=["hub_first", "main_first"])
 def test_output_matches_the_float64_oracle(main_first):
-    from recommendation_amd import _lib
     case, d = "base", 64
     rowptr, col, val, _ = case_matrix(case)
     g, hp = _graph(case, True)
     x, xt, a_in = _inputs(case, d, True)
     ref64 = O.spmm_csr(rowptr, col, val, x, keep=None, scale=1.0)
     b = _Buffers(g, hp, g.hub.main, d, "both_scaled", a_in)
-    _lib.check(_new_entry(g, hp, g.hub.main, xt, d, b, main_first), "gcr_spmm_windowed_f32")
+    _new_entry(g, hp, g.hub.main, xt, d, b, main_first)
     acc_in = a_in.cpu().numpy()
     yref = ref64 / 0.65
     for got, ref, extra in ((b.y, yref, 0.0), (b.acc_out, (acc_in + yref) * 0.25, np.abs(acc_in).max())):
@@ -195,9 +174,8 @@ def test_spmm_into_takes_the_new_entry_and_wider_launches_do_not():
         Fn.spmm_into(g, xt, acc_in=a_in, acc_out=out)
         assert calls == [64]
         want = _reference("dup", 64, True)["acc_out_only"]
-        _same({"acc_out": out.cpu().numpy().view(np.uint32)}, {"acc_out": want["acc_out"]}, "spmm_into")
-        _same({"hub partials": g.hub.partials(64).cpu().numpy().view(np.uint32)}, {"hub partials": want["hub partials"]},
-              "spmm_into")
+        assert_words_equal(out, want["acc_out"], "spmm_into, acc_out")
+        assert_words_equal(g.hub.partials(64), want["hub partials"], "spmm_into, hub partials")
         keep = torch.full(((g.nnz + 31) // 32,), -1, dtype=torch.int32, device="cuda")
         Fn.spmm_into(g, xt, y=torch.empty(g.n_rows, 64, device="cuda"), keep_bits=keep)
         assert calls == [64], "a masked launch keeps the classic plan"
@@ -209,6 +187,7 @@ def test_spmm_into_takes_the_new_entry_and_wider_launches_do_not():
     # called directly, a wider launch is refused before anything is launched
     b = _Buffers(g, hp, g.hub.main, 128, "y_only", None)
     b.y.fill_(7.0), b.part.fill_(7.0)
-    assert _new_entry(g, hp, g.hub.main, x128, 128, b, 0) == -2      # GCR_EUNSUPPORTED
+    with pytest.raises(_lib.GcrError, match="code -2"):              # GCR_EUNSUPPORTED
+        _new_entry(g, hp, g.hub.main, x128, 128, b, 0)
     torch.cuda.synchronize()
     assert bool((b.y == 7.0).all()) and bool((b.part == 7.0).all()), "a refused call launched something"

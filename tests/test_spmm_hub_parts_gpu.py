@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from spmm_raw import nan
 from spmm_window_common import F32, HUB_MIN_DEGREE, N_COLS, WINDOW_ROWS, make_matrix, replay_windowed
 
 pytestmark = pytest.mark.gpu
@@ -36,7 +37,7 @@ def build(rowptr, col, val):
 def generic_partials(hub, xt):
     """H x by the launch the new kernel replaces (`spmm_parts`), before the hub reduction."""
     from recommendation_amd import functional as Fn
-    ref = torch.full((hub.H.n_rows, xt.shape[1]), float("nan"), device="cuda")
+    ref = nan(hub.H.n_rows, xt.shape[1])
     assert hub.H.hub is None
     Fn.spmm_into(hub.H, xt, y=ref)
     return ref
@@ -63,7 +64,7 @@ def check(g, rowptr, col, w, d, seed):
         torch.from_numpy((acc_in + raw) * F32(0.5)).cuda()
     ref = generic_partials(hub, xt)
     assert bool(torch.isfinite(ref).all())
-    empty = lambda: torch.full((n_rows, d), float("nan"), device="cuda")
+    empty = lambda: nan(n_rows, d)
     nan_workspaces(hub, d)
     y = empty()
     Fn.spmm_into(g, xt, y=y)                                                             # y only
@@ -114,7 +115,7 @@ def test_stacked_matrices(kind, d, has_val):
 
 
 def test_wider_launches_keep_the_generic_companion():
-    from recommendation_amd import _lib
+    from recommendation_amd import _lib, spmm_launch
     from recommendation_amd import functional as Fn
     d = 128
     rowptr, col, val, _ = make_matrix("dup")
@@ -123,15 +124,12 @@ def test_wider_launches_keep_the_generic_companion():
     x = np.random.default_rng(5).standard_normal((N_COLS, d)).astype(F32)
     xt = torch.from_numpy(x).cuda()
     part = hub.partials(d).fill_(7.0)
-    rc = _lib.lib().gcr_spmm_hub_parts_f32(
-        _lib.dptr(H.plan.desc), H.plan.n_parts, _lib.dptr(H.plan.long_row), _lib.dptr(H.plan.long_slot0), H.plan.n_long,
-        _lib.dptr(H.rowptr), _lib.dptr(H.col), _lib.dptr(H.val), _lib.dptr(xt), d, _lib.dptr(part), _lib.dptr(H.workspace(d)),
-        H.n_rows, H.n_cols, _lib.cur_stream(xt.device))
-    assert rc == -2                                                  # GCR_EUNSUPPORTED
+    with pytest.raises(_lib.GcrError, match="code -2"):              # GCR_EUNSUPPORTED
+        spmm_launch.hub_parts(H, H.plan, x=xt, d=d, y=part, partials=H.workspace(d), on=xt)
     torch.cuda.synchronize()
     assert bool((part == 7.0).all()), "a refused call launched something"
     nan_workspaces(hub, d)
-    y = torch.full((rowptr.size - 1, d), float("nan"), device="cuda")
+    y = nan(rowptr.size - 1, d)
     Fn.spmm_into(g, xt, y=y)
     assert torch.equal(hub.partials(d), generic_partials(hub, xt))
     assert torch.equal(y, torch.from_numpy(replay_windowed(g, rowptr, col, val, x)).cuda())

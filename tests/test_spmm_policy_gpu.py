@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 import torch
 
+from spmm_raw import Out, assert_words_equal as _equal, generic, nan as _nan
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
@@ -71,60 +73,21 @@ def _inputs(shape, d):
             torch.from_numpy(rng.standard_normal((n, d)).astype(F32)).cuda())
 
 
-def _head(plan, csr):
-    from recommendation_amd import _lib
-    return (_lib.dptr(plan.desc), plan.n_parts, _lib.dptr(plan.long_row), _lib.dptr(plan.long_slot0), plan.n_long,
-            _lib.dptr(csr.rowptr), _lib.dptr(csr.col), _lib.dptr(csr.val))
-
-
-def _nan(rows, d):
-    return torch.full((max(int(rows), 1), d), float("nan"), device="cuda")
-
-
-class _Out:
-    def __init__(self, g, d, form, acc_in):
-        want_y, a_in, want_acc, self.val_scale, self.acc_scale = FORMS[form]
-        self.y = _nan(g.n_rows, d) if want_y else None
-        self.acc_out = _nan(g.n_rows, d) if want_acc else None
-        self.acc_in = acc_in.clone() if a_in else None
-        if a_in == "inplace":
-            self.acc_out = self.acc_in
-
-
-def _generic(plan, csr, xt, d, o, ws, val_scale=None):
-    """`spmm_parts` over `plan`: the reference.  Rows the plan skips stay as they were."""
-    from recommendation_amd import _lib
-    _lib.check(_lib.lib().gcr_spmm_csr_acc2_f32(
-        *_head(plan, csr), None, o.val_scale if val_scale is None else val_scale, _lib.dptr(xt), d, _lib.dptr(o.y),
-        _lib.dptr(o.acc_in), None, 0.0, _lib.dptr(o.acc_out), o.acc_scale, 0, None, _lib.dptr(ws), csr.n_rows, csr.n_cols, None,
-        _lib.cur_stream(xt.device)), "gcr_spmm_csr_acc2_f32")
-    torch.cuda.synchronize()
-
-
-def _equal(got, want, what):
-    assert (got is None) == (want is None), what
-    if got is not None:
-        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), \
-            f"{what}: {int((got.view(torch.int32) != want.view(torch.int32)).sum())} of {got.numel()} words differ"
-
-
 @pytest.mark.parametrize("has_val", [True, False], ids=["val", "ones"])
 @pytest.mark.parametrize("d", [64, 48, 4])
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 def test_plain_launch_equals_the_generic_kernel(shape, d, has_val):
-    from recommendation_amd import _lib
+    from recommendation_amd import spmm_launch as L
     g = _graph(shape, has_val, False)
     xt, a_in = _inputs(shape, d)
     for form in FORMS:
-        ref, ref_ws = _Out(g, d, form, a_in), _nan(g.plan.n_slots, d)
-        _generic(g.plan, g, xt, d, ref, ref_ws)
+        ref, ref_ws = Out(g.n_rows, d, FORMS[form], a_in), _nan(g.plan.n_slots, d)
+        generic(g, g.plan, xt, d, ref_ws, **ref.kw())
         assert not any(bool(torch.isnan(t).any()) for t in (ref.y, ref.acc_out) if t is not None), "the reference left a word unwritten"
         runs = []
         for _ in range(2):
-            o, ws = _Out(g, d, form, a_in), _nan(g.plan.n_slots, d)
-            _lib.check(_lib.lib().gcr_spmm_rows_f32(*_head(g.plan, g), o.val_scale, _lib.dptr(xt), d, _lib.dptr(o.y),
-                                                    _lib.dptr(o.acc_in), _lib.dptr(o.acc_out), o.acc_scale, _lib.dptr(ws), g.n_rows,
-                                                    g.n_cols, _lib.cur_stream(xt.device)), "gcr_spmm_rows_f32")
+            o, ws = Out(g.n_rows, d, FORMS[form], a_in), _nan(g.plan.n_slots, d)
+            L.rows(g, g.plan, x=xt, d=d, partials=ws, on=xt, **o.kw())
             torch.cuda.synchronize()
             runs.append((o.y, o.acc_out, ws))
         for k, what in enumerate(("y", "acc_out", "workspace")):
@@ -151,7 +114,7 @@ def _hub_rows_f32(part, n_hub, n_win, val_scale, acc_in_rows, acc_scale):
 @pytest.mark.parametrize("d", [64, 48, 4])
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 def test_windowed_launch_equals_the_generic_kernel(shape, d, has_val):
-    from recommendation_amd import _lib
+    from recommendation_amd import spmm_launch as L
     g = _graph(shape, has_val, True)
     hub, H, main = g.hub, g.hub.H, g.hub.main
     xt, a_in = _inputs(shape, d)
@@ -160,23 +123,18 @@ def test_windowed_launch_equals_the_generic_kernel(shape, d, has_val):
     rest[hub_rows] = False
     # the window partials are H x as the generic kernel writes it with y only and a val_scale of 1
     ref_part, ref_hws = _nan(H.n_rows, d), _nan(H.plan.n_slots, d)
-    href = _Out(H, d, "y_only", None)
-    href.y = ref_part
-    _generic(H.plan, H, xt, d, href, ref_hws, val_scale=1.0)
+    generic(H, H.plan, xt, d, ref_hws, y=ref_part)
     assert not bool(torch.isnan(ref_part).any())
     for form in FORMS:
-        ref, ref_mws = _Out(g, d, form, a_in), _nan(main.n_slots, d)
-        _generic(main, g, xt, d, ref, ref_mws)
+        ref, ref_mws = Out(g.n_rows, d, FORMS[form], a_in), _nan(main.n_slots, d)
+        generic(g, main, xt, d, ref_mws, **ref.kw())
         acc_rows = None if FORMS[form][1] is None else a_in[hub_rows].cpu().numpy()
         hub_y, hub_acc = _hub_rows_f32(ref_part, hub.n_hub, hub.n_windows, ref.val_scale, acc_rows, ref.acc_scale)
         runs = []
         for _ in range(2):
-            o, part, hws, mws = _Out(g, d, form, a_in), _nan(H.n_rows, d), _nan(H.plan.n_slots, d), _nan(main.n_slots, d)
-            _lib.check(_lib.lib().gcr_spmm_windowed_f32(
-                *_head(H.plan, H), _lib.dptr(hws), *_head(main, g), _lib.dptr(mws), _lib.dptr(hub.hub_row), hub.n_hub,
-                hub.n_windows, _lib.dptr(part), _lib.dptr(xt), d, o.val_scale, _lib.dptr(o.y), _lib.dptr(o.acc_in),
-                _lib.dptr(o.acc_out), o.acc_scale, int(hub.main_first), g.n_rows, g.n_cols, _lib.cur_stream(xt.device)),
-                "gcr_spmm_windowed_f32")
+            o, part, hws, mws = Out(g.n_rows, d, FORMS[form], a_in), _nan(H.n_rows, d), _nan(H.plan.n_slots, d), _nan(main.n_slots, d)
+            L.windowed(H, H.plan, g, main, hub, hub_split=hws, partials=mws, hub_partials=part, x=xt, d=d,
+                       main_first=int(hub.main_first), on=xt, **o.kw())
             torch.cuda.synchronize()
             runs.append((o.y, o.acc_out, part, hws, mws))
         y, acc_out, part, hws, mws = runs[0]
@@ -208,9 +166,7 @@ def test_policy_probe_sums_what_it_says(n_idx):
     first = None
     for flags in range(8):
         out = _nan(n_idx // 16, 64)
-        _lib.check(_lib.lib().gcr_probe_policy_rows_f32(_lib.dptr(hot), n_hot, _lib.dptr(cold), n_cold, _lib.dptr(idx), n_idx,
-                                                        _lib.dptr(stream_in), _lib.dptr(out), flags,
-                                                        _lib.cur_stream(out.device)), "gcr_probe_policy_rows_f32")
+        _lib.call("gcr_probe_policy_rows_f32", hot, n_hot, cold, n_cold, idx, n_idx, stream_in, out, flags, on=out)
         torch.cuda.synchronize()
         # 20 addends in [0, 1): every partial sum is below 32, so an addition rounds by at most 2^-20, in either order
         assert torch.allclose(out, want, rtol=0.0, atol=2 * 20 * 2.0 ** -20), f"nt_flags {flags}"

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from oracle import oracle_np as O
+from spmm_raw import Out, assert_words_equal as _same_words, generic, nan
 
 pytestmark = pytest.mark.gpu
 
@@ -72,62 +73,31 @@ class _Case:
         self.xt = torch.from_numpy(self.x).cuda()
         self.acc_t = torch.from_numpy(self.acc_in).cuda()
 
-    def launch(self, entry, y, acc_in, acc_out, val_scale, acc_scale):
-        """One raw launch of `entry` ('rows' | 'parts') on NaN-filled split-row workspace; returns a copy of the workspace."""
-        from recommendation_amd import _lib
-        g, p, d = self.g, self.g.plan, self.d
-        ws = g.workspace(d)
-        if ws is not None:
-            ws.fill_(float("nan"))
-        L, s = _lib.lib(), _lib.cur_stream(self.xt.device)
-        head = (_lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long, _lib.dptr(g.rowptr),
-                _lib.dptr(g.col), _lib.dptr(g.val))
-        if entry == "rows":
-            rc = L.gcr_spmm_rows_f32(*head, float(val_scale), _lib.dptr(self.xt), d, _lib.dptr(y), _lib.dptr(acc_in),
-                                     _lib.dptr(acc_out), float(acc_scale), _lib.dptr(ws), g.n_rows, g.n_cols, s)
-        else:
-            rc = L.gcr_spmm_csr_acc2_f32(*head, None, float(val_scale), _lib.dptr(self.xt), d, _lib.dptr(y), _lib.dptr(acc_in),
-                                         None, 0.0, _lib.dptr(acc_out), float(acc_scale), 0, None, _lib.dptr(ws), g.n_rows,
-                                         g.n_cols, None, s)
-        assert rc == 0, f"{entry}: status {rc}"
-        torch.cuda.synchronize()
-        return None if ws is None else ws.clone()
 
-
-def _same_words(a, b, what):
-    if a is None and b is None:
-        return
-    same = a.view(torch.int32) == b.view(torch.int32)
-    assert bool(same.all()), f"{what}: {int((~same).sum())} of {same.numel()} words differ, first at {same.logical_not().nonzero()[0].tolist()}"
-
-
-# (name, y?, acc_out?, acc_in: None | 'given' | 'inplace', val_scale, acc_scale)
-FORMS = [
-    ("y", True, False, None, 1.0, 1.0),
-    ("y_scaled", True, False, None, 1.0 / 0.65, 1.0),
-    ("acc", False, True, "given", 1.0, 1.0),
-    ("acc_scaled", False, True, "given", 0.75, 0.25),
-    ("both", True, True, "given", 1.0 / 0.65, 1.0 / 3.0),
-    ("acc_null_in", False, True, None, -1.5, 0.5),
-    ("both_null_in", True, True, None, 1.0, 1.0),
-    ("inplace", False, True, "inplace", 1.0, 0.5),
-    ("both_inplace", True, True, "inplace", 0.3, 1.0),
-]
+# name -> (y?, acc_in: None | 'given' | 'inplace', acc_out?, val_scale, acc_scale)
+FORMS = {
+    "y": (True, None, False, 1.0, 1.0),
+    "y_scaled": (True, None, False, 1.0 / 0.65, 1.0),
+    "acc": (False, "given", True, 1.0, 1.0),
+    "acc_scaled": (False, "given", True, 0.75, 0.25),
+    "both": (True, "given", True, 1.0 / 0.65, 1.0 / 3.0),
+    "acc_null_in": (False, None, True, -1.5, 0.5),
+    "both_null_in": (True, None, True, 1.0, 1.0),
+    "inplace": (False, "inplace", True, 1.0, 0.5),
+    "both_inplace": (True, "inplace", True, 0.3, 1.0),
+}
 
 
 def _run(c, entry, form):
-    _, has_y, has_acc, acc_in, val_scale, acc_scale = form
-    nan = float("nan")
-    y = torch.full((c.n_rows, c.d), nan, device="cuda") if has_y else None
-    out = ain = None
-    if has_acc:
-        if acc_in == "inplace":
-            out = ain = c.acc_t.clone()
-        else:
-            out = torch.full((c.n_rows, c.d), nan, device="cuda")
-            ain = c.acc_t if acc_in == "given" else None
-    ws = c.launch(entry, y, ain, out, val_scale, acc_scale)
-    return y, out, ws
+    """One raw launch of `entry` ('rows' | 'parts') on a NaN-filled split-row workspace: (y, acc_out, workspace)."""
+    from recommendation_amd import spmm_launch as L
+    o, ws = Out(c.n_rows, c.d, FORMS[form], c.acc_t), nan(c.g.plan.n_slots, c.d)
+    if entry == "rows":
+        L.rows(c.g, c.g.plan, x=c.xt, d=c.d, partials=ws, on=c.xt, **o.kw())
+    else:
+        generic(c.g, c.g.plan, c.xt, c.d, ws, **o.kw())
+    torch.cuda.synchronize()
+    return o.y, o.acc_out, ws
 
 
 def _check_geometry(c):
@@ -158,11 +128,10 @@ def test_every_word_equals_the_generic_launch(kind, d, has_val):
     ref64 = None
     if d == 64 and has_val:
         ref64 = O.spmm_csr(c.rowptr, c.col, c.w, c.x, keep=None, scale=1.0)
-    for form in FORMS:
-        name = form[0]
-        y0, out0, ws0 = _run(c, "parts", form)
-        y1, out1, ws1 = _run(c, "rows", form)
-        y2, out2, ws2 = _run(c, "rows", form)
+    for name in FORMS:
+        y0, out0, ws0 = _run(c, "parts", name)
+        y1, out1, ws1 = _run(c, "rows", name)
+        y2, out2, ws2 = _run(c, "rows", name)
         for got, want, again, what in ((y1, y0, y2, "y"), (out1, out0, out2, "acc_out")):
             if want is None:
                 assert got is None
@@ -173,7 +142,7 @@ def test_every_word_equals_the_generic_launch(kind, d, has_val):
         _same_words(ws1, ws0, f"{kind} {name} workspace")
         _same_words(ws2, ws1, f"{kind} {name} workspace, second launch")
         if ref64 is not None:
-            _, _, _, acc_in, val_scale, acc_scale = form
+            _, acc_in, _, val_scale, acc_scale = FORMS[name]
             yref = ref64 * val_scale
             prev = 0.0 if acc_in is None else c.acc_in
             amax = 0.0 if acc_in is None else np.abs(c.acc_in).max()
@@ -184,7 +153,7 @@ def test_every_word_equals_the_generic_launch(kind, d, has_val):
 
 
 def test_spmm_into_takes_the_new_entry_and_wider_launches_do_not():
-    from recommendation_amd import _lib
+    from recommendation_amd import _lib, spmm_launch
     from recommendation_amd import functional as Fn
     c = _Case("ladder", 64, True)
     L = _lib.lib()
@@ -210,10 +179,7 @@ def test_spmm_into_takes_the_new_entry_and_wider_launches_do_not():
         L.gcr_spmm_rows_f32 = real
     # called directly, a wider launch is refused before anything is launched
     out = torch.full((c.n_rows, 128), 7.0, device="cuda")
-    g, p = c.g, c.g.plan
-    rc = L.gcr_spmm_rows_f32(_lib.dptr(p.desc), p.n_parts, _lib.dptr(p.long_row), _lib.dptr(p.long_slot0), p.n_long,
-                             _lib.dptr(g.rowptr), _lib.dptr(g.col), _lib.dptr(g.val), 1.0, _lib.dptr(x128), 128, _lib.dptr(out),
-                             None, None, 1.0, _lib.dptr(g.workspace(128)), g.n_rows, g.n_cols, _lib.cur_stream(out.device))
-    assert rc == -2                                                  # GCR_EUNSUPPORTED
+    with pytest.raises(_lib.GcrError, match="code -2"):              # GCR_EUNSUPPORTED
+        spmm_launch.rows(c.g, c.g.plan, x=x128, d=128, y=out, partials=c.g.workspace(128), on=out)
     torch.cuda.synchronize()
     assert bool((out == 7.0).all()), "a refused call launched something"

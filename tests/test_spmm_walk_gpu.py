@@ -20,6 +20,8 @@ import numpy as np
 import pytest
 import torch
 
+from spmm_raw import Out, assert_words_equal, generic, nan as _nan
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
@@ -100,71 +102,37 @@ def _inputs(name, d):
             torch.from_numpy(rng.standard_normal((g.n_rows, d)).astype(F32)).cuda())
 
 
-def _head(plan, csr):
-    from recommendation_amd import _lib
-    return (_lib.dptr(plan.desc), plan.n_parts, _lib.dptr(plan.long_row), _lib.dptr(plan.long_slot0), plan.n_long,
-            _lib.dptr(csr.rowptr), _lib.dptr(csr.col), _lib.dptr(csr.val))
-
-
-def _nan(rows, d):
-    return torch.full((max(int(rows), 1), d), float("nan"), device="cuda")
-
-
-class _Out:
-    def __init__(self, g, d, form, acc_in):
-        want_y, a_in, want_acc, self.val_scale, self.acc_scale = FORMS[form]
-        self.y = _nan(g.n_rows, d) if want_y else None
-        self.acc_out = _nan(g.n_rows, d) if want_acc else None
-        self.acc_in = acc_in.clone() if a_in else None
-        if a_in == "inplace":
-            self.acc_out = self.acc_in
-
-
-def _generic(plan, csr, xt, d, y, acc_in, acc_out, val_scale, acc_scale, ws):
-    """`spmm_parts` over `plan`.  Rows the plan skips stay as they were."""
-    from recommendation_amd import _lib
-    _lib.check(_lib.lib().gcr_spmm_csr_acc2_f32(
-        *_head(plan, csr), None, val_scale, _lib.dptr(xt), d, _lib.dptr(y), _lib.dptr(acc_in), None, 0.0, _lib.dptr(acc_out),
-        acc_scale, 0, None, _lib.dptr(ws), csr.n_rows, csr.n_cols, None, _lib.cur_stream(xt.device)), "gcr_spmm_csr_acc2_f32")
-
-
 def _reference(g, xt, d, form, a_in):
     """[y, acc_out, main workspace, hub partials, companion workspace] by the generic route; None where there is none."""
-    from recommendation_amd import _lib
-    o = _Out(g, d, form, a_in)
+    from recommendation_amd import spmm_launch as L
+    o = Out(g.n_rows, d, FORMS[form], a_in)
     if g.hub is None:
         ws = _nan(g.plan.n_slots, d)
-        _generic(g.plan, g, xt, d, o.y, o.acc_in, o.acc_out, o.val_scale, o.acc_scale, ws)
+        generic(g, g.plan, xt, d, ws, **o.kw())
         torch.cuda.synchronize()
         return [o.y, o.acc_out, ws, None, None]
     hub, H, main = g.hub, g.hub.H, g.hub.main
     part, hws, mws = _nan(H.n_rows, d), _nan(H.plan.n_slots, d), _nan(main.n_slots, d)
-    _generic(H.plan, H, xt, d, part, None, None, 1.0, 1.0, hws)
-    _generic(main, g, xt, d, o.y, o.acc_in, o.acc_out, o.val_scale, o.acc_scale, mws)
-    _lib.check(_lib.lib().gcr_spmm_hub_reduce_f32(_lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows, _lib.dptr(part), d, o.val_scale,
-                                                  _lib.dptr(o.y), _lib.dptr(o.acc_in), _lib.dptr(o.acc_out), o.acc_scale, g.n_rows,
-                                                  _lib.cur_stream(xt.device)), "gcr_spmm_hub_reduce_f32")
+    generic(H, H.plan, xt, d, hws, y=part)
+    generic(g, main, xt, d, mws, **o.kw())
+    L.hub_reduce(hub, partials=part, d=d, n_rows=g.n_rows, on=xt, **o.kw())
     torch.cuda.synchronize()
     return [o.y, o.acc_out, mws, part, hws]
 
 
 def _walk(g, xt, d, form, a_in):
     """The same five arrays by the entry that runs `walk_partition`."""
-    from recommendation_amd import _lib
-    L, s = _lib.lib(), _lib.cur_stream(xt.device)
-    o = _Out(g, d, form, a_in)
+    from recommendation_amd import spmm_launch as L
+    o = Out(g.n_rows, d, FORMS[form], a_in)
     if g.hub is None:
         ws = _nan(g.plan.n_slots, d)
-        _lib.check(L.gcr_spmm_rows_f32(*_head(g.plan, g), o.val_scale, _lib.dptr(xt), d, _lib.dptr(o.y), _lib.dptr(o.acc_in),
-                                       _lib.dptr(o.acc_out), o.acc_scale, _lib.dptr(ws), g.n_rows, g.n_cols, s), "gcr_spmm_rows_f32")
+        L.rows(g, g.plan, x=xt, d=d, partials=ws, on=xt, **o.kw())
         torch.cuda.synchronize()
         return [o.y, o.acc_out, ws, None, None]
     hub, H, main = g.hub, g.hub.H, g.hub.main
     part, hws, mws = _nan(H.n_rows, d), _nan(H.plan.n_slots, d), _nan(main.n_slots, d)
-    _lib.check(L.gcr_spmm_windowed_f32(
-        *_head(H.plan, H), _lib.dptr(hws), *_head(main, g), _lib.dptr(mws), _lib.dptr(hub.hub_row), hub.n_hub, hub.n_windows,
-        _lib.dptr(part), _lib.dptr(xt), d, o.val_scale, _lib.dptr(o.y), _lib.dptr(o.acc_in), _lib.dptr(o.acc_out), o.acc_scale,
-        int(hub.main_first), g.n_rows, g.n_cols, s), "gcr_spmm_windowed_f32")
+    L.windowed(H, H.plan, g, main, hub, hub_split=hws, partials=mws, hub_partials=part, x=xt, d=d,
+               main_first=int(hub.main_first), on=xt, **o.kw())
     torch.cuda.synchronize()
     return [o.y, o.acc_out, mws, part, hws]
 
@@ -174,10 +142,7 @@ WHAT = ("y", "acc_out", "main workspace", "hub partials", "companion workspace")
 
 def _equal(got, want, what):
     for g, w, name in zip(got, want, WHAT):
-        assert (g is None) == (w is None), f"{what} {name}"
-        if g is not None:
-            gi, wi = g.view(torch.int32), w.view(torch.int32)
-            assert torch.equal(gi, wi), f"{what} {name}: {int((gi != wi).sum())} of {gi.numel()} words differ"
+        assert_words_equal(g, w, f"{what} {name}")
 
 
 @pytest.mark.parametrize("has_val", [True, False], ids=["val", "ones"])
