@@ -967,6 +967,55 @@ int32_t gcr_diffuse_bwd_f32(const int64_t* rowptr, const int32_t* col, const flo
                             const float* z, const float* w, const float* h, const float* g, int32_t d, float* p, float* q,
                             float* dw, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GAT: one graph-attention aggregation, fused (csrc/gcr_gat.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * replaces  the message passing of torch_geometric's GATConv as gat.py:20-23 configures it and gat.py:34, 37 call it
+ *           (concat = True, add_self_loops = True): the edge softmax, its dropout and the weighted gather-sum, which PyG
+ *           holds per edge (alpha [E, H], messages [E, H, C], forward and again for autograd).
+ * Graph: CSR [n, n] without values, rows = targets, cols = sources (rowptr int64 [n + 1], col int32), which stores NO
+ * diagonal entry (the caller strips them); the kernel adds node i's own row as the self-loop term, first in the row's
+ * order.  Duplicate entries are separate softmax terms.  A validated CSR is trusted (as in the SpMM).
+ * h [n, heads * c], a_src, a_dst, lse [n, heads], bias [heads * c] or NULL, row-major float32.  Per head, for target i:
+ *   z_ij = a_src[j] + a_dst[i],  e_ij = leaky_relu(z_ij, negative_slope),
+ *   alpha_ij = exp(e_ij - max_i) / (sum_i + 1e-16)  over j in {i} + row i,   lse[i] = max_i + log(sum_i),
+ *   alpha~_ij = alpha_ij * keep_ij * keep_scale,   out_i = sum_j alpha~_ij h_j + bias.
+ * An isolated node gets out_i = h_i + bias with alpha = 1 exactly.  Nothing is written per edge; lse is all the backward
+ * needs beside the inputs.
+ * keep_bits: NULL = no dropout (keep = 1, keep_scale ignored); else ONE little-endian bitmap of 32-bit words in the
+ * FORWARD entry order: bit (e * heads + head) for entry e in [0, nnz + n), node i's self loop being entry nnz + i
+ * (nnz = rowptr[n], read on the device); keep_scale = 1 / (1 - p).  A row whose every term is dropped gives out_i = bias.
+ * gcr_gat_bwd_f32, for the upstream g [n, heads * c], with l'_ij = (z_ij > 0 ? 1 : negative_slope) and
+ * q_ij = keep_ij * keep_scale * <g_i, h_j> (the head's c columns):
+ *   row pass over the CSR:       D_i = sum_j alpha_ij q_ij,  A_i = sum_j l'_ij alpha_ij q_ij,  B_i = sum_j l'_ij alpha_ij,
+ *                                da_dst[i] = A_i - D_i B_i;   D and r [n, heads] go to the workspace;
+ *   pass over the transpose:     dh[j] = sum_i alpha~_ij g_i,   da_src[j] = sum_i l'_ij alpha_ij (q_ij - D_i),
+ *   with alpha_ij = exp(e_ij - lse[i]) r_i rebuilt, r_i = 1 / sum_j exp(e_ij - lse[i]): lse is a rounded float32, which
+ *   alone would scale a whole row's alpha by exp(its rounding error); the row pass sums the weights it rebuilds anyway,
+ *   applies r_i to its own sums at the row's end (they are linear in alpha) and leaves r [n, heads] beside D.  rowptr_t / col_t: the CSR of the transpose (rows = sources), perm_t
+ *   int64 [nnz]: entry e of the transpose is entry perm_t[e] of the forward CSR, which is where its keep bit is (NULL
+ *   is allowed without keep_bits).  dbias = column sums of g is the caller's.
+ * A row of at most 512 entries is walked by one wave, a longer one by a whole workgroup whose waves' (max, sum),
+ * accumulators and scalar sums are merged in wave order: correct at any length, no atomics, one writer per output row,
+ * every output bitwise reproducible.
+ * Supported (gcr_gat_supported): c in {32, 64, 128}, heads in {1, 2, 4}, heads * c <= 256; GCR_EUNSUPPORTED otherwise.
+ * n < 0, n >= 2^31, a NULL or not 16-B aligned pointer (bias, keep_bits and perm_t excepted as said), out == h, dh == h or
+ * dh == g: GCR_EINVAL.  col is never read for a CSR without entries but must not be NULL.  n == 0 launches nothing.
+ * workspace: gcr_gat_workspace_bytes(n, nnz, heads, c) bytes, 16-B aligned, backward only (the forward ignores it and
+ * takes NULL).  Two launches forward (short rows, long rows), four backward.
+ */
+int32_t gcr_gat_supported(int32_t heads, int32_t c);
+int64_t gcr_gat_workspace_bytes(int64_t n, int64_t nnz, int32_t heads, int32_t c);
+int32_t gcr_gat_fwd_f32(const int64_t* rowptr, const int32_t* col, int64_t n, const float* h, const float* a_src,
+                        const float* a_dst, int32_t heads, int32_t c, float negative_slope, const uint32_t* keep_bits,
+                        float keep_scale, const float* bias, float* out, float* lse, void* workspace, void* stream);
+int32_t gcr_gat_bwd_f32(const int64_t* rowptr, const int32_t* col, const int64_t* rowptr_t, const int32_t* col_t,
+                        const int64_t* perm_t, int64_t n, const float* h, const float* a_src, const float* a_dst,
+                        const float* lse, const float* g, int32_t heads, int32_t c, float negative_slope,
+                        const uint32_t* keep_bits, float keep_scale, float* dh, float* da_src, float* da_dst,
+                        void* workspace, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

@@ -7,13 +7,18 @@ from . import _lib
 from .graph import CsrGraph, SpmmPlan
 from . import functional
 
-__all__ = ["CsrGraph", "SpmmPlan", "functional", "_lib", "DiffNetEncoder", "DiffNetModel"]
+__all__ = ["CsrGraph", "SpmmPlan", "functional", "_lib", "DiffNetEncoder", "DiffNetModel", "GATConv", "GATRec",
+           "GATRecModel"]
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """The DiffNet classes, imported on first use (their module pulls in the model base, the sampler and the optimiser)."""
+    """The DiffNet and GAT classes, imported on first use (their modules pull in the model base, the sampler and the
+    optimiser)."""
     if name in ("DiffNetEncoder", "DiffNetModel"):
         from . import diffnet
         return getattr(diffnet, name)
+    if name in ("GATConv", "GATRec", "GATRecModel"):
+        from . import gat
+        return getattr(gat, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

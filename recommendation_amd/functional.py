@@ -1818,6 +1818,121 @@ def diffuse_layer(graph, x, w, gather=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# GAT: the attention aggregation of torch_geometric's GATConv (gat.py:20-23, 34, 37)
+# ---------------------------------------------------------------------------------------------
+def gat_supported(heads, c):
+    """True when the fused kernels (gcr_gat_*) serve `heads` heads of `c` columns: c in {32, 64, 128}, heads in {1, 2, 4},
+    heads * c <= 256."""
+    return bool(_lib.call("gcr_gat_supported", int(heads), int(c)))
+
+
+def _gat_args(graph, h, a_src, a_dst, heads, keep_bits, p, bias):
+    n = graph.n_rows
+    if graph.n_cols != n or h.dim() != 2 or h.shape[0] != n or h.shape[1] % heads:
+        raise ValueError("the graph must be [n, n] and h [n, heads * c]")
+    if tuple(a_src.shape) != (n, heads) or tuple(a_dst.shape) != (n, heads):
+        raise ValueError("a_src and a_dst must be [n, heads]")
+    if bias is not None and tuple(bias.shape) != (h.shape[1],):
+        raise ValueError("bias must be [heads * c]")
+    if not 0.0 <= p < 1.0:
+        raise ValueError("p must be in [0, 1)")
+    if keep_bits is not None and (keep_bits.dtype != torch.int32 or keep_bits.numel() < ((graph.nnz + n) * heads + 31) // 32):
+        raise ValueError("keep_bits must be int32 words covering (nnz + n) * heads bits")
+
+
+def unpack_bits(bits, count):
+    """bool [count] of an int32 little-endian bitmap (`pack_bits`' inverse), on the bitmap's device."""
+    idx = torch.arange(count, device=bits.device)
+    return ((bits[idx >> 5] >> (idx & 31)) & 1).bool()
+
+
+def gat_edges(graph, device):
+    """(src, dst) int64 [nnz + n] of the aggregation's terms in the bitmap's order: the graph's entries (rows = targets,
+    cols = sources) in CSR order, then one self loop per node."""
+    rowptr = graph.rowptr.to(device)
+    loops = torch.arange(graph.n_rows, device=device)
+    dst = torch.repeat_interleave(loops, rowptr[1:] - rowptr[:-1])
+    return torch.cat([graph.col.to(device=device, dtype=torch.int64), loops]), torch.cat([dst, loops])
+
+
+def gat_aggregate_composed(graph, h, a_src, a_dst, heads, negative_slope=0.2, keep_bits=None, p=0.0, bias=None):
+    """`gat_aggregate` as torch_geometric's GATConv composes it, statement by statement in torch (alpha [E, heads] and the
+    messages [E, heads, c] are materialised), on any device and dtype: the path of shapes outside `gat_supported`, the
+    baseline of scripts/perf_gat_layer.py, and the float64 reference on CPU tensors."""
+    _gat_args(graph, h, a_src, a_dst, heads, keep_bits, p, bias)
+    n, c = h.shape[0], h.shape[1] // heads
+    src, dst = gat_edges(graph, h.device)
+    alpha = torch.nn.functional.leaky_relu(a_src[src] + a_dst[dst], negative_slope)
+    index = dst[:, None].expand(-1, heads)
+    amax = torch.zeros_like(a_dst).scatter_reduce(0, index, alpha.detach(), "amax", include_self=False)
+    alpha = (alpha - amax[dst]).exp()
+    alpha = alpha / (torch.zeros_like(a_dst).index_add_(0, dst, alpha) + 1e-16)[dst]
+    if keep_bits is not None:
+        keep = unpack_bits(keep_bits.to(h.device), src.numel() * heads).view(-1, heads)
+        alpha = alpha * keep.to(h.dtype) * (1.0 / (1.0 - p))
+    out = torch.zeros(n, heads, c, dtype=h.dtype, device=h.device).index_add_(0, dst, h.view(n, heads, c)[src] * alpha[:, :, None])
+    out = out.view(n, heads * c)
+    return out if bias is None else out + bias
+
+
+class _GatAggregate(torch.autograd.Function):
+    """gcr_gat_fwd_f32 / gcr_gat_bwd_f32: beside the inputs and the bitmap only lse [n, heads] is saved."""
+
+    @staticmethod
+    def _col(graph):
+        return graph.col if graph.nnz else torch.zeros(4, dtype=torch.int32, device=graph.col.device)
+
+    @staticmethod
+    def forward(ctx, h, a_src, a_dst, bias, graph, heads, slope, keep_bits, keep_scale):
+        h, a_src, a_dst = h.contiguous(), a_src.contiguous(), a_dst.contiguous()
+        n, c = h.shape[0], h.shape[1] // heads
+        out = torch.empty_like(h)
+        lse = torch.empty_like(a_src)
+        _lib.call("gcr_gat_fwd_f32", graph.rowptr, _GatAggregate._col(graph), n, h, a_src, a_dst, heads, c, slope, keep_bits,
+                  keep_scale, None if bias is None else bias.contiguous(), out, lse, None, on=h)
+        ctx.save_for_backward(h, a_src, a_dst, lse)
+        ctx.graph, ctx.hp, ctx.keep_bits = graph, (heads, c, slope, keep_scale), keep_bits
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        h, a_src, a_dst, lse = ctx.saved_tensors
+        graph, keep_bits = ctx.graph, ctx.keep_bits
+        heads, c, slope, keep_scale = ctx.hp
+        n = h.shape[0]
+        g = g.contiguous()
+        gt = graph.t
+        perm = None
+        if keep_bits is not None:
+            perm = graph.mirror_perm() if graph.symmetric else gt.perm_from_transpose
+            if perm.numel() == 0:             # no entries: never read, but not NULL beside a bitmap (gcr.h)
+                perm = torch.zeros(2, dtype=torch.int64, device=h.device)
+        dh, da_src, da_dst = torch.empty_like(h), torch.empty_like(a_src), torch.empty_like(a_dst)
+        ws = _lib.workspace("gcr_gat_workspace_bytes", n, graph.nnz, heads, c, device=h.device)
+        _lib.call("gcr_gat_bwd_f32", graph.rowptr, _GatAggregate._col(graph), gt.rowptr, _GatAggregate._col(gt), perm, n, h,
+                  a_src, a_dst, lse, g, heads, c, slope, keep_bits, keep_scale, dh, da_src, da_dst, ws, on=h)
+        dbias = g.sum(dim=0) if ctx.needs_input_grad[3] else None
+        return dh, da_src, da_dst, dbias, None, None, None, None, None
+
+
+def gat_aggregate(graph, h, a_src, a_dst, heads, negative_slope=0.2, keep_bits=None, p=0.0, bias=None):
+    """The message passing of GATConv (concat=True, add_self_loops=True) for `graph` [n, n] WITHOUT values and WITHOUT
+    diagonal entries (rows = targets, cols = sources; duplicates are separate terms), h [n, heads * c], a_src / a_dst
+    [n, heads]: per head, alpha = softmax over {i} + row i of leaky_relu(a_src[j] + a_dst[i]), dropped by `keep_bits`
+    (bit (e * heads + head) of `edge_mask_bits((nnz + n) * heads, p, seed, device)`, e in CSR order, the self loop of node
+    i at nnz + i) and scaled by 1 / (1 - p), out_i = sum_j alpha_ij h_j + bias.  One autograd node over gcr_gat_fwd_f32 /
+    gcr_gat_bwd_f32 (include/gcr.h), differentiable in h, a_src, a_dst and bias, which writes nothing per edge and saves
+    lse [n, heads] only; bitwise reproducible.  Shapes outside `gat_supported`, other dtypes than float32, CPU tensors
+    and n = 0 run `gat_aggregate_composed`."""
+    _gat_args(graph, h, a_src, a_dst, heads, keep_bits, p, bias)
+    c = h.shape[1] // heads
+    if not (h.is_cuda and h.dtype == torch.float32 and h.shape[0] > 0 and gat_supported(heads, c)):
+        return gat_aggregate_composed(graph, h, a_src, a_dst, heads, negative_slope, keep_bits, p, bias)
+    keep_bits = None if keep_bits is None else keep_bits.contiguous()
+    return _GatAggregate.apply(h, a_src, a_dst, bias, graph, int(heads), float(negative_slope), keep_bits, 1.0 / (1.0 - p))
+
+
+# ---------------------------------------------------------------------------------------------
 # Barlow Twins: redundancy reduction over two full-batch views (univariate/gbt.py:203-228, 386-395)
 # ---------------------------------------------------------------------------------------------
 BT_WIDTHS = (32, 64, 96, 128, 256)
