@@ -111,6 +111,9 @@ __device__ __forceinline__ void gat_row(const GatArgs& a, const int64_t row, con
   const int64_t e0 = a.rowptr[row];
   const int64_t nterm = a.rowptr[row + 1] - e0 + 1;
   const int64_t nnz = a.rowptr_fwd[a.n];
+  // A node without in-edges: its softmax has one term, the self loop, whose logit gets no gradient (alpha = 1 whatever
+  // the logit).  Computed, that zero is D_i's float32 rounding in da_src and the two float64 sums' in da_dst.
+  const bool lone = MODE != FWD && a.rowptr_fwd[row + 1] == a.rowptr_fwd[row];
   const float* __restrict__ tab = MODE == BWD_T ? a.g : a.h;      // the gathered table
 
   float rs[H], rl[H];               // the row's own logit half, and its lse (BWD_ROW)
@@ -227,8 +230,10 @@ __device__ __forceinline__ void gat_row(const GatArgs& a, const int64_t row, con
         } else {
           const float al = expf(e - a.lse_in[nk]) * a.rinv_in[nk];
           wa[k] = al * mk;
-          wb[k] = lp * wa[k];
-          sc[k] += (double)(lp * al) * (double)a.dd_in[nk];
+          if (!(lone && p == 0)) {              // the self loop of a lone node: no part in da_src
+            wb[k] = lp * wa[k];
+            sc[k] += (double)(lp * al) * (double)a.dd_in[nk];
+          }
         }
       }
     }
@@ -317,7 +322,7 @@ __device__ __forceinline__ void gat_row(const GatArgs& a, const int64_t row, con
         // lse is rounded to float32, which would scale the whole row's alpha by exp(rounding): renormalise by their sum
         const double rinv = 1. / tss;
         ta *= rinv; td *= rinv; tsc *= rinv;
-        a.ds[row * H + head] = (float)(ta - td * tsc);
+        a.ds[row * H + head] = lone ? 0.f : (float)(ta - td * tsc);
         a.dd_out[row * H + head] = (float)td;
         a.rinv_out[row * H + head] = (float)rinv;
       } else {

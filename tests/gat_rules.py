@@ -13,6 +13,9 @@ j -> i; no diagonal) followed by one self loop per node:
 `restatement` runs these in a given dtype under autograd.  LeakyReLU has a kink at zero, so a case is drawn until every
 float64 z keeps 8 x its float32 error from zero (`margin_case`): a gradient pin must not compare two different slopes.
 
+Two graph builders: `sweep_graph` (the DEGREES cycle, uniform sources, one optional long row 0) and `shaped_graph`
+(prescribed row and column lengths, for the paths a uniform draw never reaches: tests/test_gat_paths_gpu.py).
+
 A component case's inputs are functions of a seed (`inputs`, `keep_mask`: numpy's PCG64 streams); the fixture stores the
 seed and a checksum of what the writer drew, and `component` re-checks it."""
 import functools
@@ -32,6 +35,14 @@ PAIRS = tuple((h, c) for h in (1, 2, 4) for c in (32, 64, 128) if h * c <= 256)
 DEGREES = (0, 1, 7, 8, 9, 15, 16, 17, 24, 41)
 LONG_ROW = 512                      # csrc/gcr_gat.hip: a row with more entries is walked by a whole workgroup
 SLOPE = 0.2
+# `shaped_graph`'s dictionaries of tests/test_gat_paths_gpu.py (n, rows, hubs), which tests/test_gat_cpu.py holds to the
+# builder's guarantees: second 64-term batches of a one-wave row (64, 65, 128, 129 terms with the self loop), both sides
+# of LONG_ROW in the CSR and in the transpose, long rows whose waves get no term (513, 600), one batch each (1023) and
+# one wave a second batch (1024); n = 1200 gives the long launch two workgroups, each with two or more long rows
+PATHS = (1200, {2: 63, 3: 64, 4: 65, 6: 127, 8: 128, 9: 200, 12: 511, 13: 512, 0: 513, 7: 1023, 700: 1024, 701: 600, 1199: 1100},
+         {20: 513, 21: 512, 640: 1100, 1198: 600})
+FAR = (257, {0: 513, 5: 600}, {9: 513})                        # embedded behind 2^20 isolated nodes
+MIRRORED = (300, {0: 513}, {})                                 # symmetrised: node 0 is long as a row and as a column
 COMP_N, COMP_PE = 8, (0.0, 0.5)    # the fixture's component cases
 CONV_PAIR, CONV_IN, CONV_N, CONV_PE = (2, 64), 64, 12, 0.5
 STEP_CASES = ("A", "B", "C")
@@ -134,9 +145,49 @@ def sweep_graph(n, seed=0, long_row=0):
     return dst, src
 
 
-def margin_case(dst, src, n, heads, c, p, seed0=0, seeds=200, big_dst=False, with_bias=True):
-    """The first seed's inputs whose z keep the margin: dict of dst, src, n, heads, c, p, h, a_src, a_dst, g, bias, keep,
-    seed, ref (float64) and drift."""
+def shaped_graph(n, rows, hubs, seed=0):
+    """(dst, src) int64, dst ascending, no diagonal entry, with prescribed row AND column lengths: row r has exactly
+    rows[r] entries (the other rows follow `sweep_graph`'s DEGREES cycle, row 1 empty), source s appears exactly hubs[s]
+    times, no other source more than LONG_ROW times, and every row of two or more entries has a repeated column (its
+    first two entries).  A hub takes the place of one entry per row, round by round over the rows that still have an
+    entry to give (never a row's first two, never its own row), so a hub longer than the graph has rows gets several
+    entries in the longest rows; nothing is appended, so no row length changes."""
+    rng = np.random.default_rng([n, seed, len(rows), len(hubs)])
+    deg = np.array([DEGREES[r % len(DEGREES)] for r in range(n)])
+    if n > 1:
+        deg[1] = 0
+    for r, k in rows.items():
+        deg[r] = k
+    dst = np.repeat(np.arange(n, dtype=np.int64), deg)
+    start = np.concatenate([[0], np.cumsum(deg)])
+    # the plain sources: non-hub nodes, uniformly, without the row's own
+    pool = np.array([s for s in range(n) if s not in hubs], dtype=np.int64)
+    where = np.full(n, -1, dtype=np.int64)
+    where[pool] = np.arange(pool.size)
+    own = where[dst]
+    k = (rng.random(dst.size) * (pool.size - (own >= 0))).astype(np.int64)
+    src = pool[k + ((own >= 0) & (k >= own))]
+    for r in np.flatnonzero(deg >= 2):
+        src[start[r] + 1] = src[start[r]]
+    free = np.where(deg == 1, 0, 2)                             # the next entry a row can give to a hub
+    for s in sorted(hubs):
+        left = hubs[s]
+        while left:
+            cand = np.flatnonzero((free < deg) & (np.arange(n) != s))
+            assert cand.size, f"hub {s}: no row has an entry left for it"
+            take = rng.permutation(cand)[:left]
+            src[start[take] + free[take]] = s
+            free[take] += 1
+            left -= take.size
+    count = np.bincount(src, minlength=n)
+    assert (dst != src).all() and all(count[s] == hubs[s] for s in hubs)
+    assert count[pool].max(initial=0) <= LONG_ROW, "a plain source became a long row of the transpose"
+    return dst, src
+
+
+def margin_case(dst, src, n, heads, c, p, seed0=0, seeds=200, big_dst=False, with_bias=True, slope=SLOPE):
+    """The first seed's inputs whose z keep the margin: dict of dst, src, n, heads, c, p, slope, h, a_src, a_dst, g, bias,
+    keep, seed, ref (float64) and drift."""
     for seed in range(seed0, seed0 + seeds):
         h, a_src, a_dst, g, bias = inputs(n, heads, c, seed, big_dst)
         z64 = a_src.astype(np.float64)[terms_of(dst, src, n)[0]] + a_dst.astype(np.float64)[terms_of(dst, src, n)[1]]
@@ -144,11 +195,11 @@ def margin_case(dst, src, n, heads, c, p, seed0=0, seeds=200, big_dst=False, wit
         if not has_margin(z64, z32):
             continue
         keep = keep_mask(dst.size + n, heads, p, seed)
-        kw = dict(keep=keep, p=p, bias=bias if with_bias else None)
+        kw = dict(keep=keep, p=p, bias=bias if with_bias else None, slope=slope)
         ref, _ = restatement(dst, src, n, h, a_src, a_dst, g, heads, torch.float64, **kw)
         f32, _ = restatement(dst, src, n, h, a_src, a_dst, g, heads, torch.float32, **kw)
-        return dict(dst=dst, src=src, n=n, heads=heads, c=c, p=p, h=h, a_src=a_src, a_dst=a_dst, g=g, bias=kw["bias"],
-                    keep=keep, seed=seed, ref=ref, drift=drift_of(f32, ref))
+        return dict(dst=dst, src=src, n=n, heads=heads, c=c, p=p, slope=slope, h=h, a_src=a_src, a_dst=a_dst, g=g,
+                    bias=kw["bias"], keep=keep, seed=seed, ref=ref, drift=drift_of(f32, ref))
     raise AssertionError("no seed with a LeakyReLU margin")
 
 
@@ -157,6 +208,17 @@ def sweep_case(n, heads, c, p, long_row=0, big_dst=False):
     """A `margin_case` on `sweep_graph`, shared among the tests that need it and never written to."""
     dst, src = sweep_graph(n, long_row=long_row)
     return margin_case(dst, src, n, heads, c, p, big_dst=big_dst)
+
+
+@functools.lru_cache(maxsize=None)
+def _shaped_case(n, rows, hubs, heads, c, p, slope):
+    dst, src = shaped_graph(n, dict(rows), dict(hubs))
+    return margin_case(dst, src, n, heads, c, p, slope=slope)
+
+
+def shaped_case(n, rows, hubs, heads, c, p, slope=SLOPE):
+    """A `margin_case` on `shaped_graph(n, rows, hubs)` (dicts), shared among the tests that need it and never written to."""
+    return _shaped_case(n, tuple(sorted(rows.items())), tuple(sorted(hubs.items())), heads, c, p, slope)
 
 
 def checksum(*arrays):
@@ -202,13 +264,14 @@ def packed(keep, device="cuda"):
     return None if keep is None else Fn.pack_bits(torch.from_numpy(keep.reshape(-1))).to(device)
 
 
-def aggregate(graph, case, device="cuda", fused=True, fn=None):
+def aggregate(graph, case, device="cuda", fused=True, fn=None, slope=None):
     """out, dh, da_src, da_dst (and dbias) of functional.gat_aggregate (or `fn`) for a case, as arrays; with `fused` the
-    node must be the fused one."""
+    node must be the fused one.  slope: None = the case's own, SLOPE where it names none."""
     from recommendation_amd import functional as Fn
+    slope = case.get("slope", SLOPE) if slope is None else slope
     t = {k: torch.from_numpy(case[k]).to(device).requires_grad_(True) for k in ("h", "a_src", "a_dst")}
     bias = None if case["bias"] is None else torch.from_numpy(case["bias"]).to(device).requires_grad_(True)
-    out = (fn or Fn.gat_aggregate)(graph, t["h"], t["a_src"], t["a_dst"], case["heads"], SLOPE, packed(case["keep"], device),
+    out = (fn or Fn.gat_aggregate)(graph, t["h"], t["a_src"], t["a_dst"], case["heads"], slope, packed(case["keep"], device),
                                    case["p"], bias)
     if fused:
         assert out.grad_fn is not None and type(out.grad_fn).__name__.startswith("_GatAggregate"), "the fused node must run"

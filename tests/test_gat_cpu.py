@@ -1,8 +1,9 @@
 """The GAT fixture and what can be checked of the GAT path without a GPU: tests/golden/gat_steps.npz's size and schema,
 gat_rules' float64 restatement against the reference stand-in's stored runs, functional.gat_aggregate_composed (the path of
 CPU tensors and unsupported shapes) under the component rule, GATConv's composition against the whole-layer case, the
-operator GATRec.prepare builds, and GATRec's float64 forward and step-0 gradients against the step cases (recorded masks
-included)."""
+operator GATRec.prepare builds, GATRec's float64 forward and step-0 gradients against the step cases (recorded masks
+included), and gat_rules.shaped_graph's guarantees with the two float64 statements on the graph tests/test_gat_paths_gpu.py
+runs."""
 import os
 
 import numpy as np
@@ -58,6 +59,50 @@ def test_composed_on_cpu_tensors_meets_the_rule(golden, heads, c, pe):
     got = gr.aggregate(graph, case, device="cpu", fused=False)
     gr.check(got, case["ref"], case["drift"], f"composed cpu heads={heads} c={c} pe={pe}")
     assert Fn.gat_aggregate is not Fn.gat_aggregate_composed
+
+
+@pytest.mark.parametrize("name", ("PATHS", "FAR", "MIRRORED"))
+def test_shaped_graph_keeps_its_guarantees(name):
+    """The graphs of tests/test_gat_paths_gpu.py: exact row lengths, exact hub lengths, no other long column, a repeated
+    column in every row of two or more entries, no diagonal entry, and `sweep_graph`'s cycle elsewhere."""
+    n, rows, hubs = getattr(gr, name)
+    dst, src = gr.shaped_graph(n, rows, hubs)
+    assert dst.dtype == src.dtype == np.int64 and (np.diff(dst) >= 0).all() and (dst != src).all()
+    assert src.min() >= 0 and src.max() < n
+    deg, cnt = np.bincount(dst, minlength=n), np.bincount(src, minlength=n)
+    want = np.array([gr.DEGREES[r % len(gr.DEGREES)] for r in range(n)])
+    want[1] = 0
+    for r, k in rows.items():
+        want[r] = k
+    assert np.array_equal(deg, want)
+    assert all(cnt[s] == k for s, k in hubs.items())
+    assert np.delete(cnt, list(hubs)).max() <= gr.LONG_ROW
+    start = np.concatenate([[0], np.cumsum(deg)])
+    for r in np.flatnonzero(deg >= 2):
+        row = src[start[r]:start[r + 1]]
+        assert np.unique(row).size < row.size, r
+    d2, s2 = gr.shaped_graph(n, rows, hubs)
+    assert np.array_equal(dst, d2) and np.array_equal(src, s2)              # a function of its arguments
+
+
+def test_composed_float64_agrees_with_the_restatement_on_the_paths_graph():
+    """The references of tests/test_gat_paths_gpu.py rest on two independent statements: gat_rules.restatement and
+    functional.gat_aggregate_composed, both in float64, agree to rounding on the graph with the long rows and columns."""
+    import recommendation_amd as ra
+    n, rows, hubs = gr.PATHS
+    for heads, c, p in ((2, 64, 0.5), (1, 32, 0.0)):
+        case = gr.shaped_case(n, rows, hubs, heads, c, p)
+        graph = ra.CsrGraph.from_coo(case["dst"], case["src"], None, n, n, "cpu")
+        t = {k: torch.from_numpy(case[k]).double().requires_grad_(True) for k in ("h", "a_src", "a_dst", "bias")}
+        from recommendation_amd import functional as Fn
+        out = Fn.gat_aggregate_composed(graph, t["h"], t["a_src"], t["a_dst"], heads, gr.SLOPE, gr.packed(case["keep"], "cpu"), p,
+                                        t["bias"])
+        out.backward(torch.from_numpy(case["g"]).double())
+        got = dict(out=out.detach(), dh=t["h"].grad, da_src=t["a_src"].grad, da_dst=t["a_dst"].grad, dbias=t["bias"].grad)
+        for k, want in case["ref"].items():
+            err = np.abs(got[k].numpy() - want).max() / np.abs(want).max()
+            print(f"GAT composed f64 against the restatement, heads={heads} c={c} pe={p} {k}: err/S {err:.3g}")
+            assert err <= 1e-12, k                                         # 1100-term sums in float64: 1e3 x 2^-53 and room
 
 
 def test_gatconv_composition_matches_the_whole_layer_case(golden):
