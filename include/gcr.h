@@ -1016,6 +1016,38 @@ int32_t gcr_gat_bwd_f32(const int64_t* rowptr, const int32_t* col, const int64_t
                         const uint32_t* keep_bits, float keep_scale, float* dh, float* da_src, float* da_dst,
                         void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GraphSAGE: one SAGEConv layer with its activation and dropout, fused (csrc/gcr_sage.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * replaces  graphsage.py:28-30  (conv(x, edge_index) of torch_geometric's SAGEConv with mean aggregation, root weight and
+ *           bias; self.activation; F.dropout) behind the mean aggregation, which the caller runs as the SpMM:
+ *   h = keep * keep_scale * act(z wl^T + x wr^T + bias),   x, z [n, din], wl, wr [dout, din], bias [dout] or NULL,
+ *   h [n, dout], all row-major float32;  z = mean_j x_j.  act: 0 none, 1 relu, 2 exact (erf) gelu.
+ *   keep_bits: packed bitmap, bit r * dout + c (an int64 index; bit b of word b / 32 is 1 << (b % 32)) keeps element
+ *   (r, c); NULL keeps everything.  keep_scale > 0 multiplies every kept element (1 / (1 - p); 1 without dropout).  The
+ *   kernel draws nothing and stores no mask.
+ *   pre [n, dout] receives the pre-activation for act == gelu (the backward reads it) and must be NULL otherwise.
+ * gcr_sage_bwd_f32: with m = g * keep * keep_scale * act'(pre)  (relu: g * keep_scale where h > 0, from the saved h),
+ *   p = m wl,  q = m wr  ([n, din] each; the caller finishes dx = A^T p + q with the SpMM); p == q == NULL skips both
+ *   (the first layer's input takes no gradient),
+ *   dwl = m^T z,  dwr = m^T x  ([dout, din]),  dbias = column sums of m (NULL: not wanted).
+ * No atomics; the per-workgroup partials are folded in workgroup order: every output is bitwise reproducible.
+ * Supported (gcr_sage_supported): din, dout each in {32, 64, 128}.  An unsupported pair, n < 0, an act outside 0..2, a
+ * pointer that is not 16-B aligned, h == x, pre present when act != gelu or absent when act == gelu, exactly one of p, q
+ * NULL: GCR_EINVAL.  n == 0 launches nothing (the backward zeroes dwl, dwr and dbias).  workspace:
+ * gcr_sage_workspace_bytes(n, din, dout) bytes, 16-B aligned, for either call.  Two launches forward, two backward.
+ */
+int32_t gcr_sage_supported(int32_t din, int32_t dout);
+int64_t gcr_sage_workspace_bytes(int64_t n, int32_t din, int32_t dout);
+int32_t gcr_sage_fwd_f32(int64_t n, const float* x, const float* z, const float* wl, const float* wr, const float* bias,
+                         int32_t din, int32_t dout, int32_t act, const uint32_t* keep_bits, float keep_scale, float* h,
+                         float* pre, void* workspace, void* stream);
+int32_t gcr_sage_bwd_f32(int64_t n, const float* x, const float* z, const float* wl, const float* wr, const float* h,
+                         const float* pre, const float* g, int32_t din, int32_t dout, int32_t act,
+                         const uint32_t* keep_bits, float keep_scale, float* p, float* q, float* dwl, float* dwr,
+                         float* dbias, void* workspace, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

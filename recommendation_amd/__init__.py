@@ -8,17 +8,20 @@ from .graph import CsrGraph, SpmmPlan
 from . import functional
 
 __all__ = ["CsrGraph", "SpmmPlan", "functional", "_lib", "DiffNetEncoder", "DiffNetModel", "GATConv", "GATRec",
-           "GATRecModel"]
+           "GATRecModel", "SAGEConv", "GraphSAGE", "GraphSAGEModel"]
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """The DiffNet and GAT classes, imported on first use (their modules pull in the model base, the sampler and the
-    optimiser)."""
+    """The DiffNet, GAT and GraphSAGE classes, imported on first use (their modules pull in the model base, the sampler
+    and the optimiser)."""
     if name in ("DiffNetEncoder", "DiffNetModel"):
         from . import diffnet
         return getattr(diffnet, name)
     if name in ("GATConv", "GATRec", "GATRecModel"):
         from . import gat
         return getattr(gat, name)
+    if name in ("SAGEConv", "GraphSAGE", "GraphSAGEModel"):
+        from . import graphsage
+        return getattr(graphsage, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

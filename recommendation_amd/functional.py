@@ -1933,6 +1933,143 @@ def gat_aggregate(graph, h, a_src, a_dst, heads, negative_slope=0.2, keep_bits=N
 
 
 # ---------------------------------------------------------------------------------------------
+# GraphSAGE: one SAGEConv layer with its activation and dropout (graphsage.py:28-30)
+# ---------------------------------------------------------------------------------------------
+SAGE_ACTS = {"none": 0, "relu": 1, "gelu": 2}          # gcr_sage_*'s `act`; gelu is the exact (erf) form, F.gelu's default
+
+# (din, dout) pairs that `sage_layer` hands to `sage_layer_composed` although the kernels serve them: a pair belongs here
+# when scripts/perf_sage_layer.py does not show the fused layer's p10 - p90 band disjoint from, and below, the composed
+# one's.  Measured (EXPERIMENTS.md, "GraphSAGE: the fused SAGEConv layer"; 1.1M nodes, 20M entries, forward + backward): the
+# bands are disjoint in the fused layer's favour at all nine pairs, from 2.18 against 5.81 ms at (32, 32) to 7.14 against
+# 9.96 ms at (128, 128), so the set is empty.  It was not always: with one backward workgroup per CU (64, 128) under gelu took
+# 6.74 against 6.58 ms and would have been listed here.
+SAGE_COMPOSED_PAIRS = frozenset()
+
+
+def sage_supported(din, dout):
+    """True when the fused kernels (gcr_sage_*) serve a layer [n, din] -> [n, dout]: each width 32, 64 or 128."""
+    return bool(_lib.call("gcr_sage_supported", int(din), int(dout)))
+
+
+def sage_mean_graph(edge_index, num_nodes, device):
+    """The [n, n] operator of torch_geometric's mean aggregation for `edge_index` int64 [2, E] (edge j -> i =
+    (edge_index[0], edge_index[1])): CSR with rows = edge_index[1], cols = edge_index[0], a row's entries in edge_index
+    order, duplicates kept (a duplicated edge counts twice in the mean), self loops kept (SAGEConv adds or removes none),
+    val = 1 / (entries of the row); a node without in-edges has an empty row, so its mean is 0.  The transpose is built
+    with it (`graph.t`, which the backward's dx = A^T p + q walks)."""
+    import numpy as np
+    ei = torch.as_tensor(edge_index).detach().to(torch.int64).cpu().numpy()
+    deg = np.bincount(ei[1], minlength=num_nodes)
+    val = (1.0 / deg[ei[1]]).astype(np.float32)
+    graph = CsrGraph.from_coo(ei[1], ei[0], val, num_nodes, num_nodes, device)
+    graph.t                                       # noqa: B018  (built now, not inside the first backward)
+    graph.mean_counts = torch.from_numpy(deg)     # the rows' entry counts: `_sage_mean_torch` divides by them exactly
+    return graph
+
+
+def _sage_mean_torch(graph, x):
+    """The mean aggregation where libgcr has no kernel (a CPU tensor, or a dtype other than float32), in x's dtype: the
+    rows' sums divided by their counts (the stored float32 reciprocals would put 2^-24 on a float64 run)."""
+    counts = getattr(graph, "mean_counts", None)
+    if counts is None:
+        return _sparse_mm_torch(graph, x)
+    rowptr = graph.rowptr.to(x.device)
+    rows = torch.repeat_interleave(torch.arange(graph.n_rows, device=x.device), rowptr[1:] - rowptr[:-1])
+    sums = torch.zeros_like(x).index_add_(0, rows, x[graph.col.to(device=x.device, dtype=torch.int64)])
+    return sums / counts.to(device=x.device, dtype=x.dtype).clamp(min=1)[:, None]
+
+
+def _sage_args(graph, x, wl, wr, bias, keep_bits, p):
+    if x.dim() != 2 or wl.dim() != 2 or wl.shape[1] != x.shape[1] or wr.shape != wl.shape:
+        raise ValueError("x must be [n, din] and wl, wr [dout, din]")
+    if graph.n_rows != x.shape[0] or graph.n_cols != x.shape[0]:
+        raise ValueError("the graph must be [n, n] for x [n, din]")
+    if bias is not None and tuple(bias.shape) != (wl.shape[0],):
+        raise ValueError("bias must be [dout]")
+    if not 0.0 <= p < 1.0:
+        raise ValueError("p must be in [0, 1)")
+    if keep_bits is not None and (keep_bits.dtype != torch.int32 or keep_bits.numel() < (x.shape[0] * wl.shape[0] + 31) // 32):
+        raise ValueError("keep_bits must be int32 words covering n * dout bits")
+
+
+def sage_layer_composed(graph, x, wl, wr, bias, act, keep_bits=None, p=0.0):
+    """`sage_layer` as torch_geometric and graphsage.py:28-30 compose it, statement by statement in torch: the mean
+    aggregation (through `spmm` for float32 on the device, torch's sparse product otherwise), lin_l(z) + lin_r(x), the
+    activation, the dropout.  Any dtype, CPU tensors, any widths; `act` may also be a callable (another F function)."""
+    _sage_args(graph, x, wl, wr, bias, keep_bits, p)
+    z = spmm(graph, x) if x.is_cuda and x.dtype == torch.float32 else _sage_mean_torch(graph, x)
+    out = torch.nn.functional.linear(z, wl, bias) + torch.nn.functional.linear(x, wr)
+    if callable(act):
+        out = act(out)
+    elif SAGE_ACTS[act] == 1:
+        out = torch.relu(out)
+    elif SAGE_ACTS[act] == 2:
+        out = torch.nn.functional.gelu(out)
+    if keep_bits is not None:
+        keep = unpack_bits(keep_bits.to(out.device), out.numel()).view_as(out)
+        out = out * keep.to(out.dtype) * (1.0 / (1.0 - p))
+    return out
+
+
+class _SageLayer(torch.autograd.Function):
+    """gcr_sage_fwd_f32 / gcr_sage_bwd_f32: saves x, wl, wr, h, and the pre-activation only under gelu; the backward re-runs
+    the SpMM for z and finishes dx = A^T p + q with the SpMM on A^T."""
+
+    @staticmethod
+    def forward(ctx, x, wl, wr, bias, graph, act, keep_bits, keep_scale):
+        x, wl, wr = x.contiguous(), wl.contiguous(), wr.contiguous()
+        n, din = x.shape
+        dout = wl.shape[0]
+        z = spmm_into(graph, x, y=torch.empty_like(x))
+        h = torch.empty(n, dout, dtype=x.dtype, device=x.device)
+        pre = torch.empty_like(h) if act == 2 else None
+        ws = _lib.workspace("gcr_sage_workspace_bytes", n, din, dout, device=x.device)
+        _lib.call("gcr_sage_fwd_f32", n, x, z, wl, wr, None if bias is None else bias.contiguous(), din, dout, act, keep_bits,
+                  keep_scale, h, pre, ws, on=x)
+        ctx.save_for_backward(*((x, wl, wr, h) + (() if pre is None else (pre,))))
+        ctx.graph, ctx.hp, ctx.keep_bits, ctx.has_bias = graph, (act, keep_scale), keep_bits, bias is not None
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wl, wr, h = ctx.saved_tensors[:4]
+        pre = ctx.saved_tensors[4] if len(ctx.saved_tensors) == 5 else None
+        graph = ctx.graph
+        act, keep_scale = ctx.hp
+        n, din = x.shape
+        dout = wl.shape[0]
+        z = spmm_into(graph, x, y=torch.empty_like(x))
+        want_dx = ctx.needs_input_grad[0]
+        p, q = (torch.empty_like(x), torch.empty_like(x)) if want_dx else (None, None)
+        dwl, dwr = torch.empty_like(wl), torch.empty_like(wr)
+        dbias = torch.empty(dout, dtype=x.dtype, device=x.device) if ctx.has_bias else None
+        ws = _lib.workspace("gcr_sage_workspace_bytes", n, din, dout, device=x.device)
+        _lib.call("gcr_sage_bwd_f32", n, x, z, wl, wr, h, pre, g.contiguous(), din, dout, act, ctx.keep_bits, keep_scale, p, q,
+                  dwl, dwr, dbias, ws, on=x)
+        dx = spmm_into(graph.t, p, acc_in=q, acc_out=torch.empty_like(x)) if want_dx else None
+        return dx, dwl, dwr, dbias, None, None, None, None
+
+
+def sage_layer(graph, x, wl, wr, bias=None, act="relu", keep_bits=None, p=0.0):
+    """One hidden layer of GraphSAGE.forward (graphsage.py:28-30) behind one autograd node:
+    keep / (1 - p) * act(lin_l(mean_j x_j) + lin_r(x)) for `graph` = `sage_mean_graph(...)` [n, n], x [n, din], wl
+    (lin_l.weight), wr (lin_r.weight) [dout, din], bias (lin_l.bias) [dout] or None, act 'none', 'relu' or 'gelu' (exact).
+    keep_bits: the dropout's keep bitmap, bit r * dout + c (`pack_bits` / `edge_mask_bits(n * dout, p, seed, device)`
+    order); None = no dropout, whatever p.  Differentiable in x, wl, wr and bias; the mean runs as the tuned SpMM into a
+    scratch z, forward and again in the backward; x, wl, wr, the output and (gelu only) the pre-activation are kept, where
+    the composition keeps z, the pre-activation, the activation's output and a mask.  Bitwise reproducible.  Widths
+    outside `sage_supported`, pairs in SAGE_COMPOSED_PAIRS, a callable act, other dtypes than float32, CPU tensors and
+    n = 0 run `sage_layer_composed`."""
+    _sage_args(graph, x, wl, wr, bias, keep_bits, p)
+    pair = (x.shape[1], wl.shape[0])
+    if not (x.is_cuda and x.dtype == torch.float32 and x.shape[0] > 0 and not callable(act) and sage_supported(*pair)
+            and pair not in SAGE_COMPOSED_PAIRS):
+        return sage_layer_composed(graph, x, wl, wr, bias, act, keep_bits, p)
+    keep_bits = None if keep_bits is None else keep_bits.contiguous()
+    return _SageLayer.apply(x, wl, wr, bias, graph, SAGE_ACTS[act], keep_bits, 1.0 / (1.0 - p) if keep_bits is not None else 1.0)
+
+
+# ---------------------------------------------------------------------------------------------
 # Barlow Twins: redundancy reduction over two full-batch views (univariate/gbt.py:203-228, 386-395)
 # ---------------------------------------------------------------------------------------------
 BT_WIDTHS = (32, 64, 96, 128, 256)
