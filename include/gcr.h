@@ -155,6 +155,28 @@ int32_t gcr_spmm_windowed_f32(const int64_t* hub_desc, int64_t hub_n_parts, cons
                               float* hub_partials, const float* x, int32_t d, float val_scale, float* y,
                               const float* acc_in, float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows,
                               int64_t n_cols, void* stream);
+/*
+ * The two launches above on a row-ordered plan (one-off plan: recommendation_amd/graph.py RowOrder).  rowptr / col / val
+ * are a row-permuted copy P of the rows the plan covers (a row keeps its non-zeros in stored order), desc partitions P,
+ * row_id[r] (int32, one per row of P) is the row of y / acc_in / acc_out that row r of P stands for, and long_row holds
+ * rows of those arrays already.  n_rows counts the rows of y / acc_in / acc_out.  Only the order in which rows are walked
+ * differs: every word written equals the unmapped launch's on the caller's own CSR, bit for bit.
+ */
+int32_t gcr_spmm_rows_mapped_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0,
+                                 int64_t n_long_rows, const int64_t* rowptr, const int32_t* col, const float* val,
+                                 const int32_t* row_id, float val_scale, const float* x, int32_t d, float* y,
+                                 const float* acc_in, float* acc_out, float acc_scale, float* partials, int64_t n_rows,
+                                 int64_t n_cols, void* stream);
+int32_t gcr_spmm_windowed_mapped_f32(const int64_t* hub_desc, int64_t hub_n_parts, const int32_t* hub_long_row,
+                                     const int32_t* hub_long_slot0, int64_t hub_n_long_rows, const int64_t* hub_rowptr,
+                                     const int32_t* hub_col, const float* hub_val, float* hub_split,
+                                     const int64_t* desc, int64_t n_parts, const int32_t* long_row,
+                                     const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
+                                     const int32_t* col, const float* val, const int32_t* row_id, float* partials,
+                                     const int32_t* hub_row, int64_t n_hub, int32_t n_windows, float* hub_partials,
+                                     const float* x, int32_t d, float val_scale, float* y, const float* acc_in,
+                                     float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows, int64_t n_cols,
+                                     void* stream);
 /* bits[idx[i] >> 5] |= 1 << (idx[i] & 31) for every idx[i] in [0, n_bits) (atomic OR; the caller zeroes `bits`). */
 int32_t gcr_bitmap_set(const int64_t* idx, int64_t n, int64_t n_bits, uint32_t* bits, void* stream);
 

@@ -33,6 +33,11 @@ SIGNATURES = {
     "gcr_spmm_windowed_f32": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P, _P, _P,
                                         _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, _P,
                                         _P, c_int32, c_float, _P, _P, _P, c_float, c_int32, c_int64, c_int64, _P]),
+    "gcr_spmm_rows_mapped_f32": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_float, _P, c_int32, _P, _P, _P,
+                                           c_float, _P, c_int64, c_int64, _P]),
+    "gcr_spmm_windowed_mapped_f32": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P, _P, _P,
+                                               _P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, _P, _P, c_int64, c_int32, _P,
+                                               _P, c_int32, c_float, _P, _P, _P, c_float, c_int32, c_int64, c_int64, _P]),
     "gcr_spmm_csr_f32": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_float, _P, c_int32,
                                    _P, _P, _P, c_float, c_uint32, _P, _P, c_int64, c_int64, _P]),
     "gcr_spmm_csr_acc2_f32": (c_int32, [_P, c_int64, _P, _P, c_int64, _P, _P, _P, _P, c_float, _P, c_int32,

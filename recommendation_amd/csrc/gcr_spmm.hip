@@ -409,11 +409,16 @@ __device__ __forceinline__ int64_t wave_partition(unsigned block0) {
 // front of every batch of gathers (n rows of the partition have not ended yet; n = 0 in a chunk), sink.flush(acc) at every
 // row end, in row order.  The rows of a partition are consecutive, so a sink steps its row addresses from one flush to the
 // next and multiplies a row by d once per partition, in begin().
+// A mapped sink (Sink::mapped, the row-ordered plan of graph.py RowOrder): the partition's rows are rows of a row-permuted
+// copy P of the CSR, and row_id[P row] names the row of the caller's arrays each of them stands for.  The ids of the
+// partition's (<= 64) rows are loaded one per lane beside ends_v and handed to the sink once (begin_mapped); refill and flush
+// get the local index of the row that ends next, and the sink reads that row's id, and the next one's, by v_readlane.
 template <bool D64, bool HAS_VAL, class Sink>
 __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t* __restrict__ desc, int64_t n_parts,
                                                const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                const float* __restrict__ val, const float* __restrict__ x, int d,
-                                               float* __restrict__ partials, Sink& sink) {
+                                               float* __restrict__ partials, Sink& sink,
+                                               const int32_t* __restrict__ row_id = nullptr) {
   constexpr int UNR = 16;
   const int lane = threadIdx.x & 63;
   if (part >= n_parts) return;
@@ -433,10 +438,20 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
   int cur_end = whole_rows ? gcr_readlane_i(ends_v, 0) : 0x7fffffff;
 
   float acc = 0.f;
-  sink.begin((int64_t)row0);
-  auto refill = [&]() { sink.refill(whole_rows ? nrows - cur : 0); };
+  if constexpr (Sink::mapped) {
+    int rid_v = 0;
+    if (whole_rows && lane < nrows) rid_v = stream_load(row_id + row0 + lane);
+    sink.begin_mapped(rid_v);
+  } else {
+    sink.begin((int64_t)row0);
+  }
+  auto refill = [&]() {
+    if constexpr (Sink::mapped) sink.refill(whole_rows ? nrows - cur : 0, cur);
+    else sink.refill(whole_rows ? nrows - cur : 0);
+  };
   auto flush = [&]() {
-    sink.flush(acc);
+    if constexpr (Sink::mapped) sink.flush(acc, cur);
+    else sink.flush(acc);
     acc = 0.f;
     ++cur;
     cur_end = cur < nrows ? gcr_readlane_i(ends_v, cur) : 0x7fffffff;
@@ -520,6 +535,7 @@ __device__ __forceinline__ void walk_partition(const int64_t part, const int64_t
 template <bool D64>
 struct StoreSink {
   static constexpr bool queued = false;
+  static constexpr bool mapped = false;
   float* __restrict__ y;
   int d, lane;
   __device__ __forceinline__ void begin(int64_t row0) { y += row0 * d; }
@@ -541,9 +557,14 @@ struct StoreSink {
 // `y`, `acc_in` and `acc_out` are wave-uniform row pointers once begin() has run: y and acc_out the row of the next flush,
 // acc_in the row of the next load, which is the row of the next flush + nq whichever arm loads it (acc_in is read only
 // when rows are queued).  Each moves on by d floats with one 64-bit scalar add; a NULL pointer is never moved.
-template <bool D64, bool HORNER>
+// MAPPED: the rows of a partition are not consecutive in y / acc_in / acc_out (walk_partition's row map).  The pointers
+// stay at the arrays' bases; `rid_v` holds the ids of the partition's rows, one per lane, and a row's offset is its id by
+// v_readlane times d: the row of the next flush is local row `cur`, the queue's q0 is row cur and q1 row cur + 1, which is
+// what the stepped pointer visits (the row of the next load is cur + nq).  Same loads, same stores, same roundings.
+template <bool D64, bool HORNER, bool MAPPED = false>
 struct CombineSink {
   static constexpr bool queued = true;
+  static constexpr bool mapped = MAPPED;
   float val_scale, acc_scale;
   float* y;
   const float* acc_in;
@@ -551,6 +572,7 @@ struct CombineSink {
   int d, lane;
   float q0 = 0.f, q1 = 0.f;
   int nq = 0;
+  int rid_v = 0;
   const bool has_y = !HORNER && y != nullptr;
   const bool has_out = HORNER || acc_out != nullptr;
   const bool queues = HORNER || (acc_in != nullptr && acc_out != nullptr);
@@ -592,6 +614,37 @@ struct CombineSink {
       acc_out += d;
     }
   }
+  // the mapped forms: `cur` is the local index of the row that ends next
+  __device__ __forceinline__ void begin_mapped(int ids) { rid_v = ids; }
+  __device__ __forceinline__ int64_t row_offset(int k) const { return (int64_t)gcr_readlane_i(rid_v, k) * d; }
+  __device__ __forceinline__ float load_row(int k) const {
+    return (D64 || lane < d) ? stream_load(acc_in + row_offset(k) + lane) : 0.f;
+  }
+  __device__ __forceinline__ void refill(int n, int cur) {
+    if (!queues) n = 0;
+    if (nq < 1 && 0 < n) q0 = load_row(cur);
+    if (nq < 2 && 1 < n) q1 = load_row(cur + 1);
+    nq = max(nq, min(2, n));
+  }
+  __device__ __forceinline__ void flush(float acc, int cur) {
+#pragma clang fp contract(off)
+    const bool on = D64 || lane < d;
+    const float yv = acc * val_scale;
+    const int64_t ro = row_offset(cur);
+    if (has_y) {
+      if (on) stream_store(y + ro + lane, yv);
+    }
+    if (has_out) {
+      if (nq > 0) {
+        if (on) stream_store(acc_out + ro + lane, (q0 + yv) * acc_scale);
+        q0 = q1;
+        --nq;
+      } else {
+        const float prev = queues ? load_row(cur) : 0.f;
+        if (on) stream_store(acc_out + ro + lane, (prev + yv) * acc_scale);
+      }
+    }
+  }
 };
 
 // What one arm of `spmm_layer` walks: a plan's descriptors, the CSR they partition and the split rows' workspace.
@@ -605,12 +658,12 @@ struct WalkSet {
 };
 
 // The plain launch's walk of partition `part`, for `spmm_rows` and the main arm of `spmm_layer`.
-template <bool D64, bool HAS_VAL, bool HORNER>
+template <bool D64, bool HAS_VAL, bool HORNER, bool MAPPED>
 __device__ __forceinline__ void walk_combine(int64_t part, const WalkSet& w, const float* __restrict__ x, int d,
                                              float val_scale, float* y, const float* acc_in, float* acc_out,
-                                             float acc_scale) {
-  CombineSink<D64, HORNER> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
-  walk_partition<D64, HAS_VAL>(part, w.desc, w.n_parts, w.rowptr, w.col, w.val, x, d, w.partials, sink);
+                                             float acc_scale, const int32_t* __restrict__ row_id) {
+  CombineSink<D64, HORNER, MAPPED> sink{val_scale, acc_scale, y, acc_in, acc_out, d, (int)(threadIdx.x & 63)};
+  walk_partition<D64, HAS_VAL>(part, w.desc, w.n_parts, w.rowptr, w.col, w.val, x, d, w.partials, sink, row_id);
 }
 
 // The windowed companion's own kernel (graph.py HubPlan, step 1 of a windowed launch: partials = H x, nothing else), d <= 64:
@@ -631,14 +684,17 @@ __global__ __launch_bounds__(256) void spmm_hub_parts(const int64_t* __restrict_
 // SIMD without an SGPR cap and without lane spills (`spmm_parts`: 63 / 94 capped, 18 scalars in VGPR lanes).
 // Measurements: EXPERIMENTS.md "SpMM: spmm_rows" and "SpMM: the walk's scalar work".
 // HORNER: the host entry saw acc_in and acc_out and no y (is_horner), the compile-time form of CombineSink.
-template <bool D64, bool HAS_VAL, bool HORNER>
+// MAPPED (gcr_spmm_rows_mapped_f32): the CSR is a row-permuted copy and row_id names each of its rows in y / acc_in / acc_out;
+// the last argument, unused and not loaded otherwise, so the unmapped instantiations keep their code.
+template <bool D64, bool HAS_VAL, bool HORNER, bool MAPPED = false>
 __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ desc, int64_t n_parts,
                                                  const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                  const float* __restrict__ val, const float* __restrict__ x, int d,
                                                  float val_scale, float* y, const float* acc_in, float* acc_out,
-                                                 float acc_scale, float* __restrict__ partials) {
-  walk_combine<D64, HAS_VAL, HORNER>(wave_partition(0u), WalkSet{desc, n_parts, rowptr, col, val, partials}, x, d,
-                                     val_scale, y, acc_in, acc_out, acc_scale);
+                                                 float acc_scale, float* __restrict__ partials,
+                                                 const int32_t* __restrict__ row_id) {
+  walk_combine<D64, HAS_VAL, HORNER, MAPPED>(wave_partition(0u), WalkSet{desc, n_parts, rowptr, col, val, partials}, x, d,
+                                             val_scale, y, acc_in, acc_out, acc_scale, row_id);
 }
 
 // The windowed launch's two walks in one grid (gcr_spmm_windowed_f32), d <= 64: blocks [hub_block0, hub_block0 +
@@ -655,17 +711,20 @@ __global__ __launch_bounds__(256) void spmm_rows(const int64_t* __restrict__ des
 // layer, which ate the whole gain of the one grid.  Capped it was 94 (96 allocated, 8 waves) with two scalars written to
 // VGPR lanes once in the prologue.  With the stepped row addresses the Horner form takes 79 SGPRs and 46 VGPRs and the
 // other forms 94 and 46, neither with a scalar in a VGPR lane; the cap stays for the other forms.
-template <bool D64, bool HAS_VAL, bool HORNER>
+// MAPPED (gcr_spmm_windowed_mapped_f32): the main arm walks a row-ordered copy with its row map, as `spmm_rows`.
+template <bool D64, bool HAS_VAL, bool HORNER, bool MAPPED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void spmm_layer(WalkSet hub, WalkSet rest, unsigned hub_block0, unsigned hub_blocks,
                                                   unsigned main_block0, const float* __restrict__ x, int d,
                                                   float* __restrict__ hub_y, float val_scale, float* y,
-                                                  const float* acc_in, float* acc_out, float acc_scale) {
+                                                  const float* acc_in, float* acc_out, float acc_scale,
+                                                  const int32_t* __restrict__ row_id) {
   if (blockIdx.x - hub_block0 < hub_blocks) {
     StoreSink<D64> sink{hub_y, d, (int)(threadIdx.x & 63)};
     walk_partition<D64, HAS_VAL>(wave_partition(hub_block0), hub.desc, hub.n_parts, hub.rowptr, hub.col, hub.val, x, d,
                                  hub.partials, sink);
   } else {
-    walk_combine<D64, HAS_VAL, HORNER>(wave_partition(main_block0), rest, x, d, val_scale, y, acc_in, acc_out, acc_scale);
+    walk_combine<D64, HAS_VAL, HORNER, MAPPED>(wave_partition(main_block0), rest, x, d, val_scale, y, acc_in, acc_out,
+                                               acc_scale, row_id);
   }
 }
 
@@ -934,12 +993,10 @@ extern "C" int32_t gcr_spmm_hub_parts_f32(const int64_t* desc, int64_t n_parts, 
 // The plain launch at d <= 64 (no mask, no second addend, no row normalise): `spmm_rows` on the partitions, then the split
 // rows through `spmm_long_rows` with the same epilogue, exactly as gcr_spmm_csr_f32 runs them.  Every word written equals
 // that launch's.  d > 64: GCR_EUNSUPPORTED (the caller keeps gcr_spmm_csr_f32).
-extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
-                                     const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
-                                     const int32_t* col, const float* val, float val_scale, const float* x, int32_t d,
-                                     float* y, const float* acc_in, float* acc_out, float acc_scale, float* partials,
-                                     int64_t n_rows, int64_t n_cols, void* stream) {
-  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+// row_id: NULL, or the row map of a row-ordered plan (gcr_spmm_rows_mapped_f32), the MAPPED instantiations.
+namespace {
+int32_t spmm_rows_entry(const Plan& p, const int32_t* row_id, float val_scale, const float* x, int32_t d, float* y,
+                        const float* acc_in, float* acc_out, float acc_scale, int64_t n_rows, int64_t n_cols, void* stream) {
   const int32_t st = check_plan(p, n_rows, n_cols, d, 64);
   if (st != GCR_LAUNCH) return st;
   GCR_CHECK_ARG(x != nullptr && (y != nullptr || acc_out != nullptr));
@@ -947,11 +1004,39 @@ extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const
   return launch_walk(p, d, make_epilogue(val_scale, y, acc_in, acc_out, acc_scale), s,
                      [&](auto d64, auto hv, dim3 blocks) {
                        dispatch_bool(is_horner(y, acc_in, acc_out), [&](auto horner) {
-                         hipLaunchKernelGGL((spmm_rows<decltype(d64)::value, decltype(hv)::value, decltype(horner)::value>),
-                                            blocks, dim3(256), 0, s, desc, n_parts, rowptr, col, val, x, d, val_scale, y,
-                                            acc_in, acc_out, acc_scale, partials);
+                         dispatch_bool(row_id != nullptr, [&](auto mapped) {
+                           hipLaunchKernelGGL((spmm_rows<decltype(d64)::value, decltype(hv)::value, decltype(horner)::value,
+                                                         decltype(mapped)::value>),
+                                              blocks, dim3(256), 0, s, p.desc, p.n_parts, p.rowptr, p.col, p.val, x, d,
+                                              val_scale, y, acc_in, acc_out, acc_scale, p.partials, row_id);
+                         });
                        });
                      });
+}
+}  // namespace
+
+extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
+                                     const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
+                                     const int32_t* col, const float* val, float val_scale, const float* x, int32_t d,
+                                     float* y, const float* acc_in, float* acc_out, float acc_scale, float* partials,
+                                     int64_t n_rows, int64_t n_cols, void* stream) {
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  return spmm_rows_entry(p, nullptr, val_scale, x, d, y, acc_in, acc_out, acc_scale, n_rows, n_cols, stream);
+}
+
+// gcr_spmm_rows_f32 on a row-ordered plan (graph.py RowOrder): rowptr / col / val are the row-permuted copy P the plan
+// partitions, row_id[P row] is the row of y / acc_in / acc_out that P row stands for, long_row holds such rows already.
+// n_rows: of y / acc_in / acc_out.  Every row keeps its non-zeros in stored order, so every word written equals the
+// unmapped launch's on the caller's own CSR.
+extern "C" int32_t gcr_spmm_rows_mapped_f32(const int64_t* desc, int64_t n_parts, const int32_t* long_row,
+                                            const int32_t* long_slot0, int64_t n_long_rows, const int64_t* rowptr,
+                                            const int32_t* col, const float* val, const int32_t* row_id, float val_scale,
+                                            const float* x, int32_t d, float* y, const float* acc_in, float* acc_out,
+                                            float acc_scale, float* partials, int64_t n_rows, int64_t n_cols,
+                                            void* stream) {
+  GCR_CHECK_ARG(row_id != nullptr || n_parts == 0);
+  const Plan p{desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, partials};
+  return spmm_rows_entry(p, row_id, val_scale, x, d, y, acc_in, acc_out, acc_scale, n_rows, n_cols, stream);
 }
 
 // A whole windowed launch at d <= 64 (graph.py HubPlan) in three launches instead of five: `spmm_layer` walks the companion
@@ -959,13 +1044,16 @@ extern "C" int32_t gcr_spmm_rows_f32(const int64_t* desc, int64_t n_parts, const
 // partials.  Every word written -- outputs, hub partials, both split-row workspaces -- equals what gcr_spmm_hub_parts_f32,
 // gcr_spmm_hub_reduce_f32 and gcr_spmm_rows_f32 write when called in that order.  main_first: the main plan's blocks come
 // first in the grid and the companion's start at the next multiple of 8 blocks; otherwise the companion's come first.
-extern "C" int32_t gcr_spmm_windowed_f32(
+// row_id: NULL, or the row map of a row-ordered main plan (gcr_spmm_windowed_mapped_f32), the MAPPED instantiations.
+namespace {
+int32_t spmm_windowed_entry(
     const int64_t* hub_desc, int64_t hub_n_parts, const int32_t* hub_long_row, const int32_t* hub_long_slot0,
     int64_t hub_n_long_rows, const int64_t* hub_rowptr, const int32_t* hub_col, const float* hub_val, float* hub_split,
     const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0, int64_t n_long_rows,
-    const int64_t* rowptr, const int32_t* col, const float* val, float* partials, const int32_t* hub_row, int64_t n_hub,
-    int32_t n_windows, float* hub_partials, const float* x, int32_t d, float val_scale, float* y, const float* acc_in,
-    float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows, int64_t n_cols, void* stream) {
+    const int64_t* rowptr, const int32_t* col, const float* val, const int32_t* row_id, float* partials,
+    const int32_t* hub_row, int64_t n_hub, int32_t n_windows, float* hub_partials, const float* x, int32_t d,
+    float val_scale, float* y, const float* acc_in, float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows,
+    int64_t n_cols, void* stream) {
   GCR_CHECK_ARG(n_hub >= 0 && n_windows >= 1 && n_rows >= 0 && n_rows < (1ll << 31));
   GCR_CHECK_ARG(n_hub <= n_rows && n_hub * (int64_t)n_windows < (1ll << 31));
   GCR_CHECK_ARG(main_first >= 0 && main_first <= 2);
@@ -999,12 +1087,15 @@ extern "C" int32_t gcr_spmm_windowed_f32(
       if (n_blocks == 0) return (int32_t)GCR_OK;
       dispatch_bool(is_horner(y, acc_in, acc_out), [&](auto horner) {
         constexpr bool HORNER = decltype(horner)::value;
-        if (has_val)
-          hipLaunchKernelGGL((spmm_layer<D64, true, HORNER>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
-                             hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
-        else
-          hipLaunchKernelGGL((spmm_layer<D64, false, HORNER>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0, x, d,
-                             hub_partials, val_scale, y, acc_in, acc_out, acc_scale);
+        dispatch_bool(row_id != nullptr, [&](auto mapped) {
+          constexpr bool MAPPED = decltype(mapped)::value;
+          if (has_val)
+            hipLaunchKernelGGL((spmm_layer<D64, true, HORNER, MAPPED>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0,
+                               x, d, hub_partials, val_scale, y, acc_in, acc_out, acc_scale, row_id);
+          else
+            hipLaunchKernelGGL((spmm_layer<D64, false, HORNER, MAPPED>), dim3(n_blocks), dim3(256), 0, s, wh, wm, hb0, hb, mb0,
+                               x, d, hub_partials, val_scale, y, acc_in, acc_out, acc_scale, row_id);
+        });
       });
       return (int32_t)GCR_LAUNCH_STATUS();
     };
@@ -1024,6 +1115,39 @@ extern "C" int32_t gcr_spmm_windowed_f32(
     return (int32_t)GCR_LAUNCH_STATUS();
   };
   return d == 64 ? go(std::true_type{}) : go(std::false_type{});
+}
+}  // namespace
+
+extern "C" int32_t gcr_spmm_windowed_f32(
+    const int64_t* hub_desc, int64_t hub_n_parts, const int32_t* hub_long_row, const int32_t* hub_long_slot0,
+    int64_t hub_n_long_rows, const int64_t* hub_rowptr, const int32_t* hub_col, const float* hub_val, float* hub_split,
+    const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0, int64_t n_long_rows,
+    const int64_t* rowptr, const int32_t* col, const float* val, float* partials, const int32_t* hub_row, int64_t n_hub,
+    int32_t n_windows, float* hub_partials, const float* x, int32_t d, float val_scale, float* y, const float* acc_in,
+    float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows, int64_t n_cols, void* stream) {
+  return spmm_windowed_entry(hub_desc, hub_n_parts, hub_long_row, hub_long_slot0, hub_n_long_rows, hub_rowptr, hub_col,
+                             hub_val, hub_split, desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val,
+                             nullptr, partials, hub_row, n_hub, n_windows, hub_partials, x, d, val_scale, y, acc_in,
+                             acc_out, acc_scale, main_first, n_rows, n_cols, stream);
+}
+
+// gcr_spmm_windowed_f32 with a row-ordered main plan (graph.py RowOrder): rowptr / col / val are the row-permuted copy of
+// the non-hub rows the main plan partitions, row_id its row map, long_row rows of the caller's arrays, as for
+// gcr_spmm_rows_mapped_f32; the companion and the hub reduction are untouched.  Every word written equals the unmapped
+// launch's.
+extern "C" int32_t gcr_spmm_windowed_mapped_f32(
+    const int64_t* hub_desc, int64_t hub_n_parts, const int32_t* hub_long_row, const int32_t* hub_long_slot0,
+    int64_t hub_n_long_rows, const int64_t* hub_rowptr, const int32_t* hub_col, const float* hub_val, float* hub_split,
+    const int64_t* desc, int64_t n_parts, const int32_t* long_row, const int32_t* long_slot0, int64_t n_long_rows,
+    const int64_t* rowptr, const int32_t* col, const float* val, const int32_t* row_id, float* partials,
+    const int32_t* hub_row, int64_t n_hub, int32_t n_windows, float* hub_partials, const float* x, int32_t d,
+    float val_scale, float* y, const float* acc_in, float* acc_out, float acc_scale, int32_t main_first, int64_t n_rows,
+    int64_t n_cols, void* stream) {
+  GCR_CHECK_ARG(row_id != nullptr || n_parts == 0);
+  return spmm_windowed_entry(hub_desc, hub_n_parts, hub_long_row, hub_long_slot0, hub_n_long_rows, hub_rowptr, hub_col,
+                             hub_val, hub_split, desc, n_parts, long_row, long_slot0, n_long_rows, rowptr, col, val, row_id,
+                             partials, hub_row, n_hub, n_windows, hub_partials, x, d, val_scale, y, acc_in, acc_out,
+                             acc_scale, main_first, n_rows, n_cols, stream);
 }
 
 extern "C" int32_t gcr_csr_validate(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_cols,

@@ -71,11 +71,22 @@ def spmm_into(graph: CsrGraph, x, *, y=None, acc_in=None, acc_out=None, acc_scal
     # the heaviest rows by column window (graph.HubPlan): plain launches only
     hub = graph.hub if plain and graph.hub is not None and graph.hub.eligible(d) else None
     out = dict(y=y, acc_in=acc_in, acc_out=acc_out, acc_scale=acc_scale, val_scale=val_scale)    # every route's epilogue
+    # a row order (graph.RowOrder) stands in for the plan it was built beside: the hub plan's `main`, or the classic plan
+    # when the graph has no hub plan.  Plain launches at d <= 64 only; the same words in another order of the rows
+    rp = graph.rows_p if plain and d <= ROWS_MAX_D and (hub is not None or graph.hub is None) else None
+    if rp is not None and not rp.eligible(d):
+        rp = None
     if hub is not None and d <= WINDOWED_MAX_D:
         # both walks in one grid, both plans' split rows in another, then the hub reduction: the words of the branch below
         H = hub.H
-        spmm_launch.windowed(H, H.plan, graph, hub.main, hub, hub_split=H.workspace(d), partials=ws, hub_partials=hub.partials(d),
-                             x=x, d=d, main_first=hub.main_first, on=stream, **out)
+        win = dict(hub_split=H.workspace(d), partials=ws, hub_partials=hub.partials(d), x=x, d=d, main_first=hub.main_first,
+                   on=stream, **out)
+        if rp is not None:
+            spmm_launch.windowed_mapped(H, H.plan, rp, rp.plan, hub, **win)
+        else:
+            spmm_launch.windowed(H, H.plan, graph, hub.main, hub, **win)
+    elif rp is not None:
+        spmm_launch.rows_mapped(rp, rp.plan, x=x, d=d, partials=ws, on=stream, **out)
     else:
         if hub is not None:               # d > 64: the companion through the generic kernel, the reduction, then `main`
             H, part = hub.H, hub.partials(d)

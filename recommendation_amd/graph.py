@@ -30,6 +30,7 @@ HUB_WINDOW_ROWS = 16384
 HUB_NNZ_PER_PART = 128
 HUB_MIN_TABLE_BYTES = 16 << 20        # the gathered table is at least 4 x one XCD's 4 MiB L2, or the rows hit anyway
 HUB_MAX_WINDOW_BYTES = 4 << 20        # one window of the table is at most one XCD's L2 (d <= 64 at the default window)
+ROW_ORDER_MAX_D = 64                  # the mapped kernels (RowOrder) are the d <= 64 ones
 
 
 # The order of the work inside the one grid that walks the companion and the main plan (gcr_spmm_windowed_f32); both are
@@ -86,6 +87,7 @@ class SpmmPlan:
             desc = np.where((order >= 0)[:, None], desc[np.maximum(order, 0)], pad[None, :])
             self.n_parts = int(order.size)
         self.desc_host = desc[: self.n_parts]
+        self.long_row_host, self.long_slot0_host = long_row[: self.n_long], long_slot0
         self.desc = torch.from_numpy(desc).to(device)
         self.long_row = torch.from_numpy(long_row).to(device)
         self.long_slot0 = torch.from_numpy(long_slot0).to(device)
@@ -191,13 +193,108 @@ class HubPlan:
         return ws
 
 
+def coldest_column_key(rowptr, col, n_cols, lo, hi):
+    """int64 [hi - lo]: the sort key of rows lo .. hi - 1 of a CSR (torch tensors, any device): degree * n_cols + id of the
+    row's least-referenced column -- the degree of a column is its count in the whole `col` (bincount), ties go to the
+    smaller id.  An empty row gets the largest int64, so it sorts last."""
+    rowptr, col = rowptr.to(torch.int64), col.to(torch.int64)
+    cnt = torch.bincount(col, minlength=n_cols)
+    e0, e1 = int(rowptr[lo]), int(rowptr[hi])
+    c = col[e0:e1]
+    key = torch.full((hi - lo,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=col.device)
+    rows = torch.repeat_interleave(torch.arange(hi - lo, device=col.device), rowptr[lo + 1: hi + 1] - rowptr[lo:hi])
+    return key.scatter_reduce_(0, rows, cnt[c] * int(n_cols) + c, "amin")
+
+
+def coldest_column_order(rowptr, col, n_rows, n_cols, lo, hi):
+    """int64 [n_rows], a permutation of the rows: rows lo .. hi - 1 sorted stably by `coldest_column_key`, every other row
+    in place.  Rows that share an unpopular column become neighbours, so one wave walks them one after another and the
+    column's row of the gathered table is fetched once instead of once per row (EXPERIMENTS.md "SpMM: user rows in
+    order of their coldest column")."""
+    order = torch.arange(n_rows, dtype=torch.int64, device=col.device)
+    if hi > lo:
+        order[lo:hi] = lo + torch.argsort(coldest_column_key(rowptr, col, n_cols, lo, hi), stable=True)
+    return order
+
+
+class RowOrder:
+    """A row-ordered plan: the rows of a graph walked in another order than they are stored in, through a row-permuted
+    copy `P` of the CSR and a row map, so that nothing the caller sees is renumbered.
+
+    `order` (int64 [n_rows], a permutation of the rows) with the rows in `skip` (the hub rows of the graph's HubPlan) left
+    out gives row_id (int32 [n_p]): row r of P is row row_id[r] of the graph, with its col / val sequence copied as it
+    stands (rowptr_p int64 [n_p + 1], col_p, val_p).  `plan` is an ordinary SpmmPlan over rowptr_p; its whole-row
+    partitions hold consecutive rows of P, which is all `walk_partition` needs, and the mapped kernels
+    (gcr_spmm_rows_mapped_f32, gcr_spmm_windowed_mapped_f32) take the row of a flush and of an acc_in load from row_id.
+    Split rows keep the slots and the long_row / long_slot0 tables of `base` (the graph's classic plan, or its HubPlan's
+    `main`): only the chunk descriptors of P are renumbered to those slots, so the split rows' workspace and its reducer
+    see what they see without a row order.  This object is the `graph` of spmm_launch.rows_mapped: rowptr / col / val are
+    P's, n_rows / n_cols the graph's.
+    Memory: 8 B per non-hub non-zero (col_p, val_p) plus 12 B per row (rowptr_p, row_id) beside the graph's own CSR: about
+    0.13 GB on the cfg2 benchmark graph and 1.5 GB on cfg4."""
+
+    def __init__(self, graph, order, base, skip=None, forced=False, table_rows=None):
+        dev = graph.device
+        order = torch.as_tensor(order).to(device=dev, dtype=torch.int64)
+        if order.shape != (graph.n_rows,) or not bool((torch.sort(order).values == torch.arange(graph.n_rows, device=dev)).all()):
+            raise ValueError("row_order must be a permutation of the graph's rows")
+        if skip is not None:
+            order = order[~torch.as_tensor(skip, dtype=torch.bool, device=dev)[order]]
+        self.forced = bool(forced)
+        self.table_rows = graph.n_cols if table_rows is None else int(table_rows)
+        self.n_rows, self.n_cols, self.n_p = graph.n_rows, graph.n_cols, int(order.numel())
+        self.order_host = order.cpu().numpy()
+        self.row_id = order.to(torch.int32)
+        deg = (graph.rowptr[1:] - graph.rowptr[:-1])[order]
+        self.rowptr = torch.zeros(self.n_p + 1, dtype=torch.int64, device=dev)
+        self.rowptr[1:] = torch.cumsum(deg, 0)
+        self.rowptr_host = self.rowptr.cpu().numpy()
+        nnz_p = int(self.rowptr_host[-1])
+        rid = torch.repeat_interleave(torch.arange(self.n_p, device=dev), deg)           # P row of every non-zero of P
+        src = graph.rowptr[order][rid] + (torch.arange(nnz_p, device=dev) - self.rowptr[rid])
+        del rid
+        self.col = graph.col[src]
+        self.val = None if graph.val is None else graph.val[src]
+        del src
+        self.plan = SpmmPlan(self.rowptr_host, dev, base.nnz_per_part)
+        # split rows: base's tables (the graph's own rows) and base's slots
+        p = self.plan
+        if p.n_slots != base.n_slots or p.n_long != base.n_long:
+            raise RuntimeError("the row-ordered plan and its base disagree on the split rows")
+        if p.n_long:
+            slot0_of = np.full(graph.n_rows, -1, dtype=np.int64)
+            slot0_of[base.long_row_host] = base.long_slot0_host[:-1]
+            own0_of = np.zeros(self.n_p, dtype=np.int64)
+            own0_of[p.long_row_host] = p.long_slot0_host[:-1]
+            desc = p.desc_host.copy()
+            chunk = desc[:, 3] >= 0
+            prow = desc[chunk, 2] & 0xFFFFFFFF
+            desc[chunk, 3] += slot0_of[self.order_host[prow]] - own0_of[prow]
+            if bool((desc[chunk, 3] < 0).any()):
+                raise RuntimeError("a split row of the row-ordered plan is not a split row of its base")
+            p.desc_host = desc
+            p.desc = torch.from_numpy(desc).to(dev)
+        p.long_row_host, p.long_slot0_host = base.long_row_host, base.long_slot0_host
+        p.long_row, p.long_slot0 = base.long_row, base.long_slot0
+
+    def eligible(self, d: int) -> bool:
+        """The table the ordered rows gather from is large enough to miss in L2; a forced order waives it."""
+        return self.forced or self.table_rows * 4 * d >= HUB_MIN_TABLE_BYTES
+
+
 class CsrGraph:
     """A sparse operator A [n_rows, n_cols] resident on one GPU, ready for `functional.spmm`."""
 
     def __init__(self, rowptr, col, val, n_rows, n_cols, device, symmetric=False,
                  nnz_per_part=DEFAULT_NNZ_PER_PART, validate=True, transpose=None, row_group=None,
-                 hub_window_rows=None, hub_min_degree=None):
-        """hub_window_rows: None = the windowed companion of the hub rows (HubPlan) is built with HUB_WINDOW_ROWS when the
+                 hub_window_rows=None, hub_min_degree=None, row_order=None, _default_row_range=None):
+        """row_order: the order in which plain launches at d <= 64 walk the rows (RowOrder; results do not depend on it).
+        None = the constructors of bipartite operators (`bipartite_sym_norm`, `bipartite_raw`) order the user rows by their
+        coldest column (`coldest_column_order`) when the gathered table is large enough to miss in L2, every other
+        constructor keeps the stored order; a (lo, hi) range = that order on rows lo .. hi - 1 at any size; an int64
+        permutation of the rows = that order at any size; False = the stored order.  A graph with a `row_group` keeps its
+        grouped plan.  The transpose inherits the keyword (a range or a permutation only when it has as many rows).
+        hub_window_rows: None = the windowed companion of the hub rows (HubPlan) is built with HUB_WINDOW_ROWS when the
         table is large enough for it to matter and used by the launches whose sizes qualify; an int > 0 forces it with that
         window at any size; 0 disables it.  hub_min_degree: None = max(HUB_NNZ_PER_PART, 8 W); an int = rows with a larger
         degree are hubs.  A graph with a `row_group` (XCD-grouped classic plan) keeps the classic plan."""
@@ -227,6 +324,34 @@ class CsrGraph:
                 self.hub = HubPlan.build(self, HUB_WINDOW_ROWS, hub_min_degree)
         elif int(hub_window_rows) > 0:
             self.hub = HubPlan.build(self, hub_window_rows, hub_min_degree, forced=True)
+        self._row_order_kw = row_order
+        self.rows_p = None
+        if row_group is None and row_order is not False:
+            self.rows_p = self._build_row_order(row_order, _default_row_range)
+
+    def _build_row_order(self, row_order, default_range):
+        """The RowOrder the keyword asks for, or None (see __init__)."""
+        forced = row_order is not None
+        table_rows = None
+        if not forced:
+            if default_range is None:
+                return None
+            lo, hi = default_range
+            table_rows = self.n_cols - (hi - lo)        # a bipartite operator: the ordered block gathers from the other one
+            if table_rows * 4 * ROW_ORDER_MAX_D < HUB_MIN_TABLE_BYTES:
+                return None                              # no launch the mapped kernels take (d <= 64) could qualify
+            row_order = default_range
+        if isinstance(row_order, tuple) and len(row_order) == 2:
+            lo, hi = int(row_order[0]), int(row_order[1])
+            if not 0 <= lo <= hi <= self.n_rows:
+                raise ValueError("row_order range must lie inside the graph's rows")
+            row_order = coldest_column_order(self.rowptr, self.col, self.n_rows, self.n_cols, lo, hi)
+        skip = None
+        if self.hub is not None:
+            skip = torch.zeros(self.n_rows, dtype=torch.bool)
+            skip[torch.from_numpy(self.hub.hub_row_host)] = True
+        base = self.plan if self.hub is None else self.hub.main
+        return RowOrder(self, row_order, base, skip=skip, forced=forced, table_rows=table_rows)
 
     # -- checks ---------------------------------------------------------------------------
     def validate(self):
@@ -258,7 +383,7 @@ class CsrGraph:
             rp, c, v, perm = coo_to_csr_device(self.col.to(torch.int64), rows, self.val, self.n_cols, self.n_rows,
                                                self.device, want_perm=True)
             self._t = CsrGraph(rp, c, v, self.n_cols, self.n_rows, self.device, symmetric=False,
-                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self, **self._hub_kw)
+                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self, **self._t_kw())
             self._t.perm_from_transpose = perm     # non-zero e of A^T is non-zero perm[e] of A (shared edge masks)
         if self._t is None:
             col_host = self.col.cpu().numpy().astype(np.int64)
@@ -266,8 +391,16 @@ class CsrGraph:
             val_host = None if self.val is None else self.val.cpu().numpy()
             rp, c, v, _ = _coo_to_csr_host(col_host, rows, val_host, self.n_cols)
             self._t = CsrGraph(rp, c, v, self.n_cols, self.n_rows, self.device, symmetric=False,
-                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self, **self._hub_kw)
+                               nnz_per_part=self.plan.nnz_per_part, validate=False, transpose=self, **self._t_kw())
         return self._t
+
+    def _t_kw(self):
+        """Constructor keywords the transpose inherits: the hub plan's, and the row order's -- None and False as they are,
+        a range or a permutation only when the transpose has as many rows as this operator."""
+        ro = self._row_order_kw
+        if ro is not None and ro is not False and self.n_cols != self.n_rows:
+            ro = False
+        return dict(self._hub_kw, row_order=ro)
 
     def row_degrees(self):
         """Non-zeros per row, float32 [n_rows] (cached)."""
@@ -287,6 +420,8 @@ class CsrGraph:
         g.val = val.contiguous()
         g._t = None
         g.hub = None                       # the companion holds a copy of the old values: this view runs the classic plan
+        g.rows_p = None                    # and so does the row-ordered copy: never walk stale values
+        g._row_order_kw = False
         return g
 
     def user_major_edges(self, n_users):
@@ -373,6 +508,7 @@ class CsrGraph:
     def bipartite_raw(cls, uid, iid, num_users, num_items, device, **kw):
         """ncl.py:74-85: rows/cols [(u, i+U), (i+U, u)] per interaction, value 1, duplicates kept (Q1)."""
         n = num_users + num_items
+        kw.setdefault("_default_row_range", (0, num_users))
         if torch.device(device).type == "cuda":
             u, i = _dev_i64(uid, device), _dev_i64(iid, device) + num_users
             row = torch.stack([u, i], 1).reshape(-1)      # (u, i+U) then (i+U, u) per interaction
@@ -390,6 +526,7 @@ class CsrGraph:
         """selfcf.py:291-306 + 240-255 (ssl4rec.py:79-88): A = R~ + R~^T with duplicate interactions
         summed, then D^-1/2 A D^-1/2 with 1/sqrt(0) -> 0, float32."""
         n = num_users + num_items
+        kw.setdefault("_default_row_range", (0, num_users))
         if torch.device(device).type == "cuda":
             u, i = _dev_i64(uid, device), _dev_i64(iid, device) + num_users
             rp, c, v, _ = coo_to_csr_device(torch.cat([u, i]), torch.cat([i, u]), None, n, n, device, coalesce=True)

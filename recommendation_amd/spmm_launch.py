@@ -38,6 +38,14 @@ def rows(graph, plan, *, x, d, partials, on, y=None, acc_in=None, acc_out=None, 
          graph.n_cols, on=on)
 
 
+def rows_mapped(graph, plan, *, x, d, partials, on, y=None, acc_in=None, acc_out=None, acc_scale=1.0, val_scale=1.0,
+                call=_lib.call):
+    """`graph`: a row-ordered copy (graph.RowOrder: rowptr, col, val of P, row_id, and the n_rows / n_cols of the graph it
+    was made from); `plan`: its plan, long_row in the graph's own rows."""
+    call("gcr_spmm_rows_mapped_f32", *_plan_head(graph, plan), graph.row_id, val_scale, x, d, y, acc_in, acc_out, acc_scale,
+         partials, graph.n_rows, graph.n_cols, on=on)
+
+
 def hub_parts(graph, plan, *, x, d, y, partials, on, call=_lib.call):
     call("gcr_spmm_hub_parts_f32", *_plan_head(graph, plan), x, d, y, partials, graph.n_rows, graph.n_cols, on=on)
 
@@ -55,3 +63,11 @@ def windowed(hub_graph, hub_plan, graph, plan, hub, *, hub_split, partials, hub_
     call("gcr_spmm_windowed_f32", *_plan_head(hub_graph, hub_plan), hub_split, *_plan_head(graph, plan), partials, hub.hub_row,
          hub.n_hub, hub.n_windows, hub_partials, x, d, val_scale, y, acc_in, acc_out, acc_scale, main_first, graph.n_rows,
          graph.n_cols, on=on)
+
+
+def windowed_mapped(hub_graph, hub_plan, graph, plan, hub, *, hub_split, partials, hub_partials, x, d, main_first, on, y=None,
+                    acc_in=None, acc_out=None, acc_scale=1.0, val_scale=1.0, call=_lib.call):
+    """`windowed` with a row-ordered main pair: (graph, plan) as `rows_mapped` takes them, over the non-hub rows."""
+    call("gcr_spmm_windowed_mapped_f32", *_plan_head(hub_graph, hub_plan), hub_split, *_plan_head(graph, plan), graph.row_id,
+         partials, hub.hub_row, hub.n_hub, hub.n_windows, hub_partials, x, d, val_scale, y, acc_in, acc_out, acc_scale,
+         main_first, graph.n_rows, graph.n_cols, on=on)

@@ -24,7 +24,9 @@ windowed layer (d <= 64, not --acc2) through it, three launches, again as functi
 (repeatable; hub_first or main_first, optionally followed by :long_rows_first) times such a library once per cell instead
 of the graph's own order: which range of blocks leads the one grid, and whether the main plan's descriptors keep plan
 order or graph.long_rows_first_order's; two_walks launches the two ranges one after the other (the merged split-row launch
-without the one grid).  --five-launch keeps such a library on the three older entries.  --shared-output makes every
+without the one grid).  A library that exports gcr_spmm_windowed_mapped_f32 runs the graph's own windowed layer with
+the graph's row order (graph.RowOrder) when it has one, once more as functional.spmm_into does; --no-row-order keeps every
+library on the stored order.  --five-launch keeps such a library on the three older entries.  --shared-output makes every
 library write the same output array: with an array of its own per library, a library's place in the list moved its time by
 1-4 % (other addresses), more than most differences this script is asked about; give a library twice to see what is left.
 
@@ -71,14 +73,18 @@ def child(args):
 
         def add(name, hub):
             if not fused or hub is None or not args.order:
-                cell = None if not fused or hub is None else (int(hub.main_first), hub.main)
+                cell = None if not fused or hub is None else (int(hub.main_first), hub.main, None)
+                rp = graph.rows_p
+                if (cell is not None and hub is graph.hub and rp is not None and rp.eligible(d) and not args.no_row_order
+                        and call.has("gcr_spmm_windowed_mapped_f32")):
+                    cell = (int(hub.main_first), rp.plan, rp)
                 libs.append((name, call, hub, own, rows, cell))
                 return
             for c in args.order:                           # one entry per order of the work, the same plans
                 first, _, desc_order = c.partition(":")
                 if (first, desc_order) not in orders:
                     orders[first, desc_order] = (["hub_first", "main_first", "two_walks"].index(first), hub.main if not desc_order else
-                                                 hub.main.permuted(long_rows_first_order(hub.main.desc_host)))
+                                                 hub.main.permuted(long_rows_first_order(hub.main.desc_host)), None)
                 libs.append((f"{name} [{c}]", call, hub, own, rows, orders[first, desc_order]))
 
         if not args.hub_config:
@@ -100,10 +106,13 @@ def child(args):
         layer = dict(x=x, d=d, acc_in=x0, acc_out=out, on=stream, call=call)         # the Horner layer: one acc_out, no y
         q = p
         if cell is not None:
-            main_first, q = cell
+            main_first, q, rp = cell
             H = hub.H
-            L.windowed(H, H.plan, graph, q, hub, hub_split=H.workspace(d), partials=ws, hub_partials=hub.partials(d),
-                       main_first=main_first, **layer)
+            win = dict(hub_split=H.workspace(d), partials=ws, hub_partials=hub.partials(d), main_first=main_first, **layer)
+            if rp is not None:
+                L.windowed_mapped(H, H.plan, rp, q, hub, **win)
+            else:
+                L.windowed(H, H.plan, graph, q, hub, **win)
             return
         if hub is not None:
             H, part = hub.H, hub.partials(d)
@@ -151,7 +160,8 @@ def child(args):
         ent = {"lib": path, "ms_per_layer": [round(v, 5) for v in ms[k]], "mean": round(m, 5),
                "spread": round(max(ms[k]) - min(ms[k]), 5), "equal_to_base": bool(torch.equal(outs[k], outs[0])),
                "max_diff_over_max": float((outs[k] - outs[0]).abs().max() / outs[0].abs().max()),
-               "main_entry": "gcr_spmm_windowed_f32" if cell is not None else
+               "main_entry": "gcr_spmm_windowed_mapped_f32" if cell is not None and cell[2] is not None else
+                             "gcr_spmm_windowed_f32" if cell is not None else
                              "gcr_spmm_csr_acc2_f32" if not rows else "gcr_spmm_rows_f32",
                "windowed": None if hub is None else {"window_rows": hub.window_rows, "windows": hub.n_windows,
                                                       "n_hub": hub.n_hub, "hub_nnz": hub.hub_nnz,
@@ -188,6 +198,7 @@ def main():
                     choices=["hub_first", "main_first", "hub_first:long_rows_first", "main_first:long_rows_first", "two_walks"],
                     help="time a library with gcr_spmm_windowed_f32 once per order of the work (default: the graph's own)")
     ap.add_argument("--shared-output", action="store_true", help="every library writes the same output array")
+    ap.add_argument("--no-row-order", action="store_true", help="keep every library on the stored order of the rows")
     ap.add_argument("--five-launch", action="store_true", help="keep every library on the three older windowed entries")
     ap.add_argument("--timeout", type=int, default=300, help="seconds per workload (child process)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -215,6 +226,8 @@ def main():
             cmd += ["--order", c]
         if args.five_launch:
             cmd.append("--five-launch")
+        if args.no_row_order:
+            cmd.append("--no-row-order")
         if args.shared_output:
             cmd.append("--shared-output")
         try:

@@ -52,7 +52,7 @@ def run(args):
     wl = bench.WORKLOADS[args.workload]
     n_u, n_i = wl["users"], wl["items"]
     users, items = bench.synth_interactions_device(n_u, n_i, wl["edges"], bench.SEED, dev)
-    graph = ra.CsrGraph.bipartite_sym_norm(users, items, n_u, n_i, dev)
+    graph = ra.CsrGraph.bipartite_sym_norm(users, items, n_u, n_i, dev, row_order=False if args.row_order == "off" else None)
     del users, items
     n, d = n_u + n_i, args.d
     x0 = torch.empty(n, d, device=dev)
@@ -61,6 +61,12 @@ def run(args):
     out = torch.empty_like(x0)
     hub = graph.hub if graph.hub is not None and graph.hub.eligible(d) else None
     p = graph.plan if hub is None else hub.main
+    # the graph's row order (graph.RowOrder), when it has one: its plan stands in for `p` and only --entry rows can walk it.
+    # P keeps the user rows in front of the item rows, so the segments below are cut in the same way
+    rp = graph.rows_p if graph.rows_p is not None and graph.rows_p.eligible(d) and (hub is not None or graph.hub is None) else None
+    if rp is not None:
+        p = rp.plan
+        args.entry = [e for e in args.entry if e == "rows"] or sys.exit("a row-ordered plan runs through --entry rows only")
     ws = graph.workspace(d)
     stream = _lib.cur_stream(dev)
     desc_host = p.desc_host
@@ -100,7 +106,9 @@ def run(args):
             part = copy.copy(p)                           # a run of the plan's partitions, with or without its split rows
             part.desc, part.n_parts, part.n_long = p.desc[a:b], b - a, n_long
             layer = dict(x=x, d=d, acc_in=x0, acc_out=out, partials=ws, on=stream)
-            if entry == "rows":
+            if entry == "rows" and rp is not None:
+                fn = lambda part=part, layer=layer: L.rows_mapped(rp, part, **layer)
+            elif entry == "rows":
                 fn = lambda part=part, layer=layer: L.rows(graph, part, **layer)
             else:
                 fn = lambda part=part, layer=layer: L.csr_acc2(graph, part, acc_in2_scale=0.0, **layer)
@@ -120,7 +128,7 @@ def run(args):
             timed(label, fn, {"entry": "probe", "nnz": n_idx, "table_bytes": int(table.shape[0]) * d * 4, "kernel": "probe_gather"})
             if not args.counters:
                 cases[-1]["gathered_TB_per_s"] = round(n_idx * 256 / cases[-1]["ms_per_launch"] / 1e9, 3)
-    info = {"workload": args.workload, "d": d, "nnz": graph.nnz, "n": n, "n_users": n_u, "hub_plan": hub is not None,
+    info = {"row_order": rp is not None, "workload": args.workload, "d": d, "nnz": graph.nnz, "n": n, "n_users": n_u, "hub_plan": hub is not None,
             "hub_nnz": None if hub is None else hub.hub_nnz, "mean_degree_users": float(deg[:n_u].mean()), "cases": cases}
     name = "rows_gate_%s%s.json" % (args.workload, "_counters" if args.counters else "")
     with open(os.path.join(out_dir(args), name), "w") as f:
@@ -190,6 +198,7 @@ if __name__ == "__main__":
     ap.add_argument("--entry", action="append", choices=["parts", "rows"], help="default: both")
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--row-order", default="on", choices=["on", "off"], help="off: build the graph with row_order=False")
     ap.add_argument("--counters", action="store_true", help="two dispatches per case, no timing: for a rocprofv3 --pmc run")
     ap.add_argument("--summarize", metavar="DIR", nargs="+", help="pair the counter runs' traces under each DIR with the case list")
     ap.add_argument("--tag", help="name of the summary written by --summarize")
