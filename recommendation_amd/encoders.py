@@ -298,10 +298,13 @@ class LightGCN(nn.Module):
         self.num_layers = num_layers
         nn.init.xavier_uniform_(self.user_embedding.weight)
         nn.init.xavier_uniform_(self.item_embedding.weight)
-        self._graph_key, self._graph = None, None
+        self._graph_key, self._graph, self._graph_src = None, None, None
 
     def prepare(self, edge_index, symmetric=None):
-        """Builds (or returns the cached) operator for `edge_index` int64 [2, nnz]."""
+        """Builds (or returns the cached) operator for `edge_index` int64 [2, nnz].  The cache is keyed on the tensor's
+        address, shape and version counter and holds the tensor, so a new tensor or an in-place edit rebuilds the
+        operator.  An edit through `.data` or a numpy alias moves neither the address nor the version and is NOT seen:
+        pass a new tensor (or edit in place through torch) instead."""
         key = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version)
         if self._graph_key != key:
             n = self.user_embedding.num_embeddings + self.item_embedding.num_embeddings
@@ -312,6 +315,7 @@ class LightGCN(nn.Module):
                     np.array_equal(ei[1, :half], ei[0, half:])
             self._graph = CsrGraph.from_edge_index_gcn_norm(ei, n, self.user_embedding.weight.device, symmetric=symmetric)
             self._graph_key = key
+            self._graph_src = edge_index            # holding edge_index keeps the pointer from being recycled
         return self._graph
 
     def forward(self, edge_index):

@@ -128,19 +128,23 @@ class GATRec(nn.Module):
                             negative_slope=neg_slope, seed=2 * seed + 2)
         self.dropout = dropout
         self.init_weights()
-        self._graph_key, self._graph = None, None
+        self._graph_key, self._graph, self._graph_src = None, None, None
 
     def init_weights(self):
         nn.init.xavier_uniform_(self.user_embedding.weight)
         nn.init.xavier_uniform_(self.item_embedding.weight)
 
     def prepare(self, edge_index):
-        """Builds (or returns the cached) `gat_graph` of `edge_index` int64 [2, E]."""
+        """Builds (or returns the cached) `gat_graph` of `edge_index` int64 [2, E].  The cache is keyed on the tensor's
+        address, shape and version counter and holds the tensor, so a new tensor or an in-place edit rebuilds the graph.
+        An edit through `.data` or a numpy alias moves neither the address nor the version and is NOT seen: pass a new
+        tensor (or edit in place through torch) instead."""
         key = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version)
         if self._graph_key != key:
             n = self.user_embedding.num_embeddings + self.item_embedding.num_embeddings
             self._graph = gat_graph(edge_index, n, self.user_embedding.weight.device)
             self._graph_key = key
+            self._graph_src = edge_index            # holding edge_index keeps the pointer from being recycled
         return self._graph
 
     def _feature_dropout(self, x, keep):

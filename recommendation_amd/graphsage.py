@@ -93,14 +93,18 @@ class GraphSAGE(nn.Module):
             self.layers.append(SAGEConv(hidden_channels, hidden_channels))
         self.layers.append(SAGEConv(hidden_channels, out_channels))
         self.seed, self.calls = int(seed), 0
-        self._graph_key, self._graph = None, None
+        self._graph_key, self._graph, self._graph_src = None, None, None
 
     def prepare(self, edge_index, num_nodes):
-        """Builds (or returns the cached) `functional.sage_mean_graph` of `edge_index` int64 [2, E]."""
+        """Builds (or returns the cached) `functional.sage_mean_graph` of `edge_index` int64 [2, E].  The cache is keyed
+        on the tensor's address, shape and version counter (and num_nodes) and holds the tensor, so a new tensor or an
+        in-place edit rebuilds the graph.  An edit through `.data` or a numpy alias moves neither the address nor the
+        version and is NOT seen: pass a new tensor (or edit in place through torch) instead."""
         key = (edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, int(num_nodes))
         if self._graph_key != key:
             self._graph = Fn.sage_mean_graph(edge_index, num_nodes, self.layers[0].lin_l.weight.device)
             self._graph_key = key
+            self._graph_src = edge_index            # holding edge_index keeps the pointer from being recycled
         return self._graph
 
     def draw_keep_bits(self, count, device):

@@ -14,7 +14,11 @@ The layer, graphsage.py:28-30 over torch_geometric's SAGEConv (mean aggregation,
 float64 pre-activation keeps 8 x the float32 error from zero (`margin_case`, `has_margin`: gat_rules.has_margin's rule).
 With millions of pre-activations no seed does that, so `large_case` makes the mask irrelevant where it is ambiguous
 instead (diffuse_rules.large_case's method): g = 0 wherever |pre64| < 8 x max |pre32 - pre64|; g is an input, so every
-element of every output is still compared, and the share of g zeroed this way must stay <= MAX_ZEROED_SHARE."""
+element of every output is still compared, and the share of g zeroed this way must stay <= MAX_ZEROED_SHARE.
+
+For tests/test_sage_paths_gpu.py: `hub_graph` (long rows in A and in A^T, for the SpMM's windowed route), `exact_case`
+(integers, where float32 is exact and equality is owed; `assert_exact`), `tail_case` (gelu far from zero), `Raw` (the raw
+exports' arguments, with sentinels for the bounds tests).  tests/test_sage_cpu.py asserts each builder's conditions."""
 import functools
 import os
 
@@ -41,6 +45,15 @@ DEGREES = (0, 1, 3, 8, 2, 17, 5, 1, 41, 4)
 # One pair per (forward tile rows, W in LDS) class: (32, 32) 64 / yes, (64, 128) 64 / no, (128, 64) 32 / no, (128, 32) 32 / yes.
 FWD_CAP = BWD_CAP = 1024
 MULTI_TRIP_SHAPES = ((65537, 32, 32), (65537, 64, 128), (32769, 128, 64), (32769, 128, 32))
+# Hub rows: the smallest width at which the SpMM's windowed hub plan (graph.HubPlan) both exists and is used, for z = A x
+# and for dx = A^T p + q, at the multi-trip n (one row above the smallest table that qualifies).  The plan is eligible when
+# the gathered table is at least 16 MiB and one 16384-row window at most 4 MiB: at d = 64, 65537 x 256 B >= 16 MiB and
+# 16384 x 256 B = 4 MiB; at d = 32 the table is too small, at d = 128 the window too large.  A hub row has more than max(128, 8 x 5 windows) entries.  (64, 32): W in LDS; (64, 128): W through the
+# caches.
+HUB_N, HUB_EXTRA, HUB_PAIRS = 65537, 3000, ((64, 32), (64, 128))
+# Exact cases: in-degrees whose reciprocals are powers of two, 70 rows = a partial tile for 32- and for 64-row tiles
+EXACT_N, EXACT_DEGREES = 70, (0, 1, 2, 4, 8)
+SENTINEL = -1.2345678e30                     # no kernel output: what the bounds tests fill with and look for
 COMP_N, COMP_P = 12, 0.5                     # the fixture's layer cases
 COMP_CASES = ((32, 64, "gelu"), (64, 32, "relu"), (32, 32, "none"))
 STEP_CASES = ("A", "B", "C")
@@ -178,9 +191,34 @@ def margin_case(n, din, dout, act, p, with_bias=True, seeds=200):
     raise AssertionError("no seed with a ReLU margin")
 
 
-def zeroed_share(n, din, dout, seed=0):
+def hub_nodes(n):
+    return n // 3, 2 * (n // 3) + 1
+
+
+@functools.lru_cache(maxsize=None)
+def hub_graph(n, seed=0):
+    """`sweep_graph(n)` plus two hub nodes (`hub_nodes`), each with HUB_EXTRA more in-edges from uniform sources and
+    HUB_EXTRA more out-edges to distinct targets, stable-sorted by dst: a popular node is a long row of A (values 1 / its
+    in-degree) and a long row of A^T (the unequal values 1 / deg(dst) of its targets).  The hubs' own rows list their
+    sources in ascending order, which the windowed plan asks of a hub row (graph.HubPlan.build); A^T's rows do by
+    construction."""
+    src, dst = sweep_graph(n, seed)
+    rng = np.random.default_rng([n, seed, HUB_EXTRA])
+    assert n > HUB_EXTRA
+    for hub in hub_nodes(n):
+        src = np.concatenate([src, rng.integers(0, n, HUB_EXTRA), np.full(HUB_EXTRA, hub)]).astype(np.int64)
+        dst = np.concatenate([dst, np.full(HUB_EXTRA, hub), rng.choice(n, HUB_EXTRA, replace=False)]).astype(np.int64)
+    order = np.argsort(dst, kind="stable")
+    src, dst = src[order], dst[order]
+    for hub in hub_nodes(n):
+        lo, hi = np.searchsorted(dst, [hub, hub + 1])
+        src[lo:hi] = np.sort(src[lo:hi])
+    return src, dst
+
+
+def zeroed_share(n, din, dout, seed=0, graph=sweep_graph):
     """(share of g that `large_case` zeroes for relu, the ambiguous mask), from the restatement alone."""
-    src, dst = sweep_graph(n)
+    src, dst = graph(n)
     x, wl, wr, bias, _ = inputs(n, din, dout, seed)
     pre64 = forward_pre(src, dst, n, x, wl, wr, bias, torch.float64)
     pre32 = forward_pre(src, dst, n, x, wl, wr, bias, torch.float32)
@@ -189,17 +227,82 @@ def zeroed_share(n, din, dout, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
-def large_case(n, din, dout, act, p):
-    """A case too large for a margin scan (module docstring): for relu, g is zeroed where the mask is ambiguous."""
-    src, dst = sweep_graph(n)
+def large_case(n, din, dout, act, p, graph=sweep_graph):
+    """A case too large for a margin scan (module docstring): for relu, g is zeroed where the mask is ambiguous.  graph:
+    `sweep_graph` or `hub_graph`."""
+    src, dst = graph(n)
     x, wl, wr, bias, g = inputs(n, din, dout, 0)
     share = 0.0
     if act == "relu":
-        share, ambiguous = zeroed_share(n, din, dout)
+        share, ambiguous = zeroed_share(n, din, dout, graph=graph)
         assert share <= MAX_ZEROED_SHARE, f"n={n} ({din}, {dout}): {share:.3g} of g would be zeroed"
         g[ambiguous] = 0.0
     case = _case(src, dst, n, din, dout, act, p, 0, True, x, wl, wr, bias, g, keep_mask(n, dout, p, 0))
     case["share"] = share
+    return case
+
+
+def out_isolated(src, n):
+    """The nodes without an out-edge: empty rows of A^T, whose dx is q alone."""
+    return np.flatnonzero(np.bincount(src, minlength=n) == 0)
+
+
+@functools.lru_cache(maxsize=None)
+def exact_case(din, dout, act, with_bias):
+    """A case in which float32 is exact, so that the kernels owe float64's every bit: x in -2 .. 2, weights in {-1, 0, 1},
+    bias in -2 .. 2, g in {-2, -1, 1, 2} (never zero), in-degrees from EXACT_DEGREES (1 / deg a power of two), keep masks
+    with p = 0.5 (with a bias; scale 2) or 0.75 (without; scale 4).  Every z is a multiple of 1/8 below 2 in size, every
+    pre-activation a multiple of 1/8 below 2 * 2 * 128 + 2, every gradient a multiple of 1/8 far below 2^21: each product
+    and each partial sum, in any order, is a float32.  Column `zero_col` of the pre-activations is exactly 0 (zero rows of
+    wl and wr, zero bias entry) and, without a bias, so is row `zero_row` (a node without in-edges whose x row is zero),
+    both under non-zero g: torch's ReLU gives such an element gradient 0.  Also carries `f32`, the float32 restatement."""
+    assert act in ("none", "relu")
+    n = EXACT_N
+    rng = np.random.default_rng([n, din, dout, ACTS.index(act), int(with_bias)])
+    deg = np.array([EXACT_DEGREES[r % len(EXACT_DEGREES)] for r in range(n)])
+    dst = np.repeat(np.arange(n, dtype=np.int64), deg)
+    src = rng.integers(0, n, dst.size).astype(np.int64)
+    x = rng.integers(-2, 3, (n, din)).astype(np.float32)
+    wl, wr = (rng.integers(-1, 2, (dout, din)).astype(np.float32) for _ in range(2))
+    bias = rng.integers(-2, 3, dout).astype(np.float32)
+    g = rng.choice(np.float32([-2, -1, 1, 2]), (n, dout))
+    zero_col, zero_row = dout // 2 + 1, 35                     # 35 % 5 == 0: no in-edge; in the second 32-row tile
+    wl[zero_col], wr[zero_col], bias[zero_col] = 0.0, 0.0, 0.0
+    if not with_bias:
+        assert deg[zero_row] == 0
+        x[zero_row] = 0.0
+    p = 0.5 if with_bias else 0.75
+    keep = keep_mask(n, dout, p, 0)
+    case = _case(src, dst, n, din, dout, act, p, 0, with_bias, x, wl, wr, bias, g, keep)
+    case["f32"], _ = restatement(src, dst, n, x, wl, wr, case["bias"], g, act, torch.float32, keep, p)
+    _, case["pre"] = restatement(src, dst, n, x, wl, wr, case["bias"], g, act, torch.float64, keep, p)
+    case["zero_col"], case["zero_row"] = zero_col, zero_row if not with_bias else None
+    return case
+
+
+def assert_exact(got, ref, tag):
+    """Every element equal; the first differing index otherwise."""
+    for k, want in ref.items():
+        have = np.asarray(got[k], dtype=np.float64)
+        assert have.shape == want.shape, (tag, k, have.shape, want.shape)
+        if not np.array_equal(have, want):
+            at = tuple(int(v) for v in np.argwhere(have != want)[0])
+            raise AssertionError(f"SAGE exact {tag} {k}: {int((have != want).sum())} of {want.size} elements differ, the first "
+                                 f"at {at}: got {have[at]!r}, float64 {want[at]!r}")
+
+
+TAIL_SCALE = 8.0
+
+
+@functools.lru_cache(maxsize=None)
+def tail_case(n, din, dout, p=0.5):
+    """gelu far from zero: `inputs` with x scaled by TAIL_SCALE, which puts pre-activations past +-10, where erf has
+    saturated in float32 and exp(-pre^2 / 2) is below 2e-22.  Carries `pre`, the float64 pre-activations."""
+    src, dst = sweep_graph(n)
+    x, wl, wr, bias, g = inputs(n, din, dout, 0)
+    x *= np.float32(TAIL_SCALE)
+    case = _case(src, dst, n, din, dout, "gelu", p, 0, True, x, wl, wr, bias, g, keep_mask(n, dout, p, 0))
+    case["pre"] = forward_pre(src, dst, n, x, wl, wr, bias, torch.float64)
     return case
 
 
@@ -219,22 +322,85 @@ def packed(keep, device="cuda"):
     return None if keep is None else Fn.pack_bits(torch.from_numpy(keep.reshape(-1))).to(device)
 
 
-def layer(graph, case, device="cuda", fused=True, fn=None, dtype=torch.float32, want_dx=True):
+def is_fused(h):
+    return h.grad_fn is not None and type(h.grad_fn).__name__.startswith("_SageLayer")
+
+
+def no_fused_node_below(h):
+    """Walks the autograd graph under h: the fused node is nowhere in it."""
+    todo, seen = [h.grad_fn], set()
+    while todo:
+        f = todo.pop()
+        if f is not None and f not in seen:
+            seen.add(f)
+            if type(f).__name__.startswith("_SageLayer"):
+                return False
+            todo += [nf for nf, _ in f.next_functions]
+    return h.grad_fn is not None
+
+
+def layer(graph, case, device="cuda", fused=True, fn=None, dtype=torch.float32, want_dx=True, act=None, frozen=()):
     """h, dx, dwl, dwr (and dbias) of functional.sage_layer (or `fn`) for a case, as arrays; with `fused` the node must be
-    the fused one."""
+    the fused one, without it the node must be nowhere below h.  act: given instead of the case's (a callable with the
+    same meaning); frozen: the parameters among wl, wr, bias without requires_grad."""
     from recommendation_amd import functional as Fn
-    t = {k: torch.from_numpy(case[k]).to(device=device, dtype=dtype).requires_grad_(k != "x" or want_dx) for k in ("x", "wl", "wr")}
-    bias = None if case["bias"] is None else torch.from_numpy(case["bias"]).to(device=device, dtype=dtype).requires_grad_(True)
-    h = (fn or Fn.sage_layer)(graph, t["x"], t["wl"], t["wr"], bias, case["act"], packed(case["keep"], device), case["p"])
+    t = {k: torch.from_numpy(case[k]).to(device=device, dtype=dtype).requires_grad_((k != "x" or want_dx) and k not in frozen)
+         for k in ("x", "wl", "wr")}
+    bias = None if case["bias"] is None else \
+        torch.from_numpy(case["bias"]).to(device=device, dtype=dtype).requires_grad_("bias" not in frozen)
+    h = (fn or Fn.sage_layer)(graph, t["x"], t["wl"], t["wr"], bias, act or case["act"], packed(case["keep"], device), case["p"])
     if fused:
-        assert h.grad_fn is not None and type(h.grad_fn).__name__.startswith("_SageLayer"), "the fused node must run"
+        assert is_fused(h), "the fused node must run"
+    elif fn is None:
+        assert no_fused_node_below(h), "the composed layer must run"
     h.backward(torch.from_numpy(case["g"]).to(device=device, dtype=dtype))
+    if frozen:
+        res = dict(h=h.detach(), dx=t["x"].grad, dwl=t["wl"].grad, dwr=t["wr"].grad, dbias=None if bias is None else bias.grad)
+        return {k: v.cpu().numpy() for k, v in res.items() if v is not None}
     res = dict(h=h.detach(), dwl=t["wl"].grad, dwr=t["wr"].grad)
     if want_dx:
         res["dx"] = t["x"].grad
     if bias is not None:
         res["dbias"] = bias.grad
     return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+class Raw:
+    """The arguments of gcr_sage_fwd_f32 / gcr_sage_bwd_f32 for n rows of (din, dout), every buffer its own, the workspace
+    of the size gcr_sage_workspace_bytes gives for (n, din, dout).  fill (the bounds tests): every output and the workspace
+    hold that value, h, pre, p, q over pad_rows more rows and the workspace over pad_words more words than the call is told
+    of; the kernels get the same pointers and the same n."""
+
+    def __init__(self, n=40, din=64, dout=64, act=1, fill=None, pad_rows=0, pad_words=0):
+        from recommendation_amd import _lib
+        self.lib, self.n, self.din, self.dout, self.act = _lib, n, din, dout, act
+        f = functools.partial(torch.randn, device="cuda")
+        self.x, self.z, self.g = f(n, din), f(n, din), f(n, dout)
+        self.wl, self.wr, self.bias = f(dout, din), f(dout, din), f(dout)
+        out = functools.partial(torch.full, fill_value=0.0 if fill is None else fill, device="cuda")
+        self.h, self.pre = out((n + pad_rows, dout)), out((n + pad_rows, dout))
+        self.p, self.q = out((n + pad_rows, din)), out((n + pad_rows, din))
+        grad = functools.partial(torch.full, fill_value=1.0 if fill is None else fill, device="cuda")
+        self.dwl, self.dwr, self.dbias = grad((dout, din)), grad((dout, din)), grad((dout,))
+        self.ws_words = int(_lib.call("gcr_sage_workspace_bytes", max(n, 1), din, dout)) // 4
+        self.ws = torch.empty(max(self.ws_words, 1) + pad_words, device="cuda")
+        if fill is not None:
+            self.ws.fill_(fill)
+
+    def fwd(self, **kw):
+        a = dict(n=self.n, x=self.x, z=self.z, wl=self.wl, wr=self.wr, bias=self.bias, din=self.din, dout=self.dout, act=self.act,
+                 keep=None, scale=1.0, h=self.h, pre=self.pre if self.act == 2 else None, ws=self.ws)
+        a.update(kw)
+        self.lib.call("gcr_sage_fwd_f32", a["n"], a["x"], a["z"], a["wl"], a["wr"], a["bias"], a["din"], a["dout"], a["act"],
+                      a["keep"], a["scale"], a["h"], a["pre"], a["ws"], on=self.g)
+
+    def bwd(self, **kw):
+        a = dict(n=self.n, x=self.x, z=self.z, wl=self.wl, wr=self.wr, h=self.h, pre=self.pre if self.act == 2 else None, g=self.g,
+                 din=self.din, dout=self.dout, act=self.act, keep=None, scale=1.0, p=self.p, q=self.q, dwl=self.dwl, dwr=self.dwr,
+                 dbias=self.dbias, ws=self.ws)
+        a.update(kw)
+        self.lib.call("gcr_sage_bwd_f32", a["n"], a["x"], a["z"], a["wl"], a["wr"], a["h"], a["pre"], a["g"], a["din"], a["dout"],
+                      a["act"], a["keep"], a["scale"], a["p"], a["q"], a["dwl"], a["dwr"], a["dbias"], a["ws"], on=self.g)
 
 
 # ---- the fixture's layout ----

@@ -140,6 +140,14 @@ def test_prepare_strips_the_diagonal_and_keeps_duplicates():
     assert np.asarray(g.coo_perm).tolist() == [1, 4, 0, 2, 3, 5]           # positions among the kept edges
 
 
+def test_prepare_holds_its_edge_index_so_that_a_recycled_address_is_not_a_hit():
+    """GATRec.prepare on CPU tensors (tests/prepare_cache.py)."""
+    from prepare_cache import check_prepare_cache
+    from recommendation_amd.gat import GATRec, gat_graph
+    model = GATRec(30, 20, 8, 4, 4, 2, 0.0, 0.0, 0.2)
+    check_prepare_cache(model.prepare, lambda e: gat_graph(e, 50, "cpu"), 50)
+
+
 @pytest.mark.parametrize("case", gr.STEP_CASES)
 def test_gatrec_float64_forward_and_gradients_match_the_reference(golden, case):
     """GATRec on CPU tensors in float64 (the composition), one step: the loss of gat.py:111-117 and the step-0 gradients."""

@@ -60,6 +60,16 @@ def test_lightgcn_module_cfg1():
     assert model.user_embedding.weight.grad is not None and torch.isfinite(model.user_embedding.weight.grad).all()
 
 
+def test_lightgcn_prepare_holds_its_edge_index_so_that_a_recycled_address_is_not_a_hit():
+    """LightGCN.prepare on device tensors (tests/prepare_cache.py): the caching allocator hands a just-freed block of the
+    same size out again as a matter of course."""
+    from prepare_cache import check_prepare_cache
+    from recommendation_amd import CsrGraph
+    from recommendation_amd.encoders import LightGCN
+    model = LightGCN(30, 20, 32, 1).cuda()
+    check_prepare_cache(model.prepare, lambda e: CsrGraph.from_edge_index_gcn_norm(e, 50, "cuda"), 50, device="cuda")
+
+
 def test_next_batch_pairwise_contract(golden):
     from recommendation_amd.encoders import Interaction
     from recommendation_amd.sampler import next_batch_pairwise, randint_negatives

@@ -1,6 +1,7 @@
 """GraphSAGE without a device: the float64 restatement (tests/sage_rules.py) and functional.sage_layer_composed against the
 fixture's layer cases and step trajectories (tests/golden/sage_steps.npz, written from graphsage.py itself), the fixture's
-stored conditions, the mean operator, the module's shapes and quirks, and the ABI table."""
+stored conditions, the mean operator, the module's shapes and quirks, the ABI table, the conditions of the builders that
+tests/test_sage_paths_gpu.py runs on the device, and `GraphSAGE.prepare`'s cache."""
 import os
 
 import numpy as np
@@ -218,3 +219,99 @@ def test_every_sage_declaration_has_its_binding():
     assert _lib.call("gcr_sage_workspace_bytes", 0, 64, 64) == 0 and _lib.call("gcr_sage_workspace_bytes", 10, 48, 64) == 0
     # [wl^T; wr^T], then one partial of [dwl | dwr] and dbias per workgroup of the backward
     assert _lib.call("gcr_sage_workspace_bytes", 33, 64, 32) == 4 * (2 * 64 * 32 + 2 * (2 * 64 * 32 + 32))
+
+
+# ---- the builders of tests/test_sage_paths_gpu.py: their conditions, from the restatement alone ----
+
+def test_hub_graph_has_two_hub_rows_in_both_operators_and_out_isolated_nodes():
+    from recommendation_amd import functional as Fn
+    n = sr.HUB_N
+    src, dst = sr.hub_graph(n)
+    base_src, base_dst = sr.sweep_graph(n)
+    assert np.all(np.diff(dst) >= 0) and src.size == base_src.size + 4 * sr.HUB_EXTRA
+    indeg, outdeg = np.bincount(dst, minlength=n), np.bincount(src, minlength=n)
+    base_in = np.bincount(base_dst, minlength=n)
+    hubs = list(sr.hub_nodes(n))
+    others = np.setdiff1d(np.arange(n), hubs)
+    for hub in hubs:
+        assert indeg[hub] >= base_in[hub] + sr.HUB_EXTRA and outdeg[hub] >= sr.HUB_EXTRA
+        row = src[dst == hub]
+        assert np.all(np.diff(row) >= 0)                                # what the windowed plan asks of a hub row
+        targets = dst[src == hub]
+        assert np.unique(targets).size >= sr.HUB_EXTRA                  # distinct targets: unequal values 1 / deg(dst) in A^T
+        assert np.unique(indeg[targets]).size > 3
+    assert indeg[others].max() <= max(sr.DEGREES) + len(hubs) and outdeg[others].max() < 128      # nobody else is a hub
+    # every other row keeps sweep_graph's entries in their order, then the hubs' edges
+    r = 7
+    assert src[dst == r][:base_in[r]].tolist() == base_src[base_dst == r].tolist()
+    lonely = sr.out_isolated(src, n)
+    print(f"SAGE hub graph: {lonely.size} nodes without out-edges, in-degrees {indeg[hubs]}, out-degrees {outdeg[hubs]}")
+    assert lonely.size >= 1
+    # the plan's own conditions, on the operator functional.sage_mean_graph builds (a CPU graph plans the same way)
+    graph = sr.device_graph(src, dst, n, "cpu")
+    for g in (graph, graph.t):
+        assert g.hub is not None and g.hub.n_hub == 2 and not g.hub.forced
+        assert g.hub.eligible(64) and not g.hub.eligible(32) and not g.hub.eligible(128)
+        assert g.rows_p is None
+    assert sorted(graph.hub.hub_row_host.tolist()) == hubs == sorted(graph.t.hub.hub_row_host.tolist())
+    from recommendation_amd import graph as G
+    assert (n - 2) * 4 * 64 < G.HUB_MIN_TABLE_BYTES <= (n - 1) * 4 * 64   # one row above the smallest table that qualifies
+    assert Fn.WINDOWED_MAX_D >= 64
+
+
+@pytest.mark.parametrize("din,dout", sr.HUB_PAIRS)
+def test_hub_relu_cases_zero_little_of_g(din, dout):
+    share, _ = sr.zeroed_share(sr.HUB_N, din, dout, graph=sr.hub_graph)
+    print(f"SAGE hub zeroed share n={sr.HUB_N} ({din}, {dout}): {share:.3g}")
+    assert share <= sr.MAX_ZEROED_SHARE
+
+
+@pytest.mark.parametrize("with_bias", (True, False))
+@pytest.mark.parametrize("act", ("none", "relu"))
+@pytest.mark.parametrize("din,dout", sr.PAIRS)
+def test_exact_cases_are_exact_in_float32(din, dout, act, with_bias):
+    case = sr.exact_case(din, dout, act, with_bias)
+    assert case["n"] == 70 and case["n"] % 32 and case["n"] % 64
+    assert set(np.bincount(case["dst"], minlength=case["n"]).tolist()) == set(sr.EXACT_DEGREES)
+    assert case["p"] in (0.5, 0.75) and set(case["ref"]) == set(sr.KEYS if with_bias else sr.KEYS[:-1])
+    for k, want in case["ref"].items():
+        assert np.array_equal(case["f32"][k], want), k                  # float32 is exact here
+    for k in ("dx", "dwl", "dwr"):
+        assert np.abs(case["ref"][k]).max() > 0, k
+    for k in ("x", "wl", "wr", "g"):
+        assert np.array_equal(case[k], np.rint(case[k]))
+    pre, g, keep, c = case["pre"], case["g"], case["keep"], case["zero_col"]
+    assert np.all(g != 0)
+    assert np.all(pre[:, c] == 0) and keep[:, c].any() and not keep[:, c].all()
+    if act == "relu":
+        assert (pre == 0).mean() > 0.005 and (pre > 0).any() and (pre < 0).any()   # zeros beyond the planted ones, too
+        # torch's convention: no gradient at 0, which the column's parameters show
+        assert np.all(case["ref"]["dwl"][c] == 0) and np.all(case["ref"]["dwr"][c] == 0)
+        if with_bias:
+            assert case["ref"]["dbias"][c] == 0
+            # ... and `>=` in its place would show: the column's kept g does not sum to 0
+            assert (g[:, c] * keep[:, c]).sum() != 0
+    if with_bias:
+        assert case["zero_row"] is None
+    else:
+        r = case["zero_row"]
+        assert np.all(pre[r] == 0) and keep[r].any() and case["bias"] is None
+        assert not np.any(case["dst"] == r) and not np.any(case["x"][r])
+
+
+@pytest.mark.parametrize("din,dout", ((64, 64), (128, 32)))
+def test_tail_cases_reach_past_ten(din, dout):
+    case = sr.tail_case(257, din, dout)
+    print(f"SAGE tail ({din}, {dout}): pre in [{case['pre'].min():.3g}, {case['pre'].max():.3g}]")
+    assert case["pre"].max() >= 10.0 and case["pre"].min() <= -10.0 and case["act"] == "gelu" and case["p"] == 0.5
+
+
+def test_prepare_holds_its_edge_index_so_that_a_recycled_address_is_not_a_hit():
+    """GraphSAGE.prepare on CPU tensors (tests/prepare_cache.py)."""
+    from prepare_cache import check_prepare_cache
+    from recommendation_amd import functional as Fn
+    from recommendation_amd.graphsage import GraphSAGE
+    model, n = GraphSAGE(64, 32, 64, 2), 50
+    check_prepare_cache(lambda e: model.prepare(e, n), lambda e: Fn.sage_mean_graph(e, n, "cpu"), n)
+    e = torch.randint(0, n, (2, 400))
+    assert model.prepare(e, n + 1) is not model.prepare(e, n)           # num_nodes is part of the key

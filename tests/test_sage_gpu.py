@@ -101,34 +101,7 @@ def test_two_runs_are_bitwise_equal(din, dout, act, p):
 
 # ---- the ABI's contract, through the raw exports ----
 
-class Raw:
-    """The arguments of gcr_sage_fwd_f32 / gcr_sage_bwd_f32 for n rows of (din, dout), every buffer its own."""
-
-    def __init__(self, n=40, din=64, dout=64, act=1):
-        from recommendation_amd import _lib
-        self.lib, self.n, self.din, self.dout, self.act = _lib, n, din, dout, act
-        f = functools.partial(torch.randn, device="cuda")
-        self.x, self.z, self.g = f(n, din), f(n, din), f(n, dout)
-        self.wl, self.wr, self.bias = f(dout, din), f(dout, din), f(dout)
-        self.h, self.pre = torch.zeros(n, dout, device="cuda"), torch.zeros(n, dout, device="cuda")
-        self.p, self.q = torch.zeros(n, din, device="cuda"), torch.zeros(n, din, device="cuda")
-        self.dwl, self.dwr, self.dbias = torch.ones(dout, din, device="cuda"), torch.ones(dout, din, device="cuda"), torch.ones(dout, device="cuda")
-        self.ws = torch.empty(max(int(_lib.call("gcr_sage_workspace_bytes", max(n, 1), 64, 64)) // 4, 1), device="cuda")
-
-    def fwd(self, **kw):
-        a = dict(n=self.n, x=self.x, z=self.z, wl=self.wl, wr=self.wr, bias=self.bias, din=self.din, dout=self.dout, act=self.act,
-                 keep=None, scale=1.0, h=self.h, pre=self.pre if self.act == 2 else None, ws=self.ws)
-        a.update(kw)
-        self.lib.call("gcr_sage_fwd_f32", a["n"], a["x"], a["z"], a["wl"], a["wr"], a["bias"], a["din"], a["dout"], a["act"],
-                      a["keep"], a["scale"], a["h"], a["pre"], a["ws"], on=self.g)
-
-    def bwd(self, **kw):
-        a = dict(n=self.n, x=self.x, z=self.z, wl=self.wl, wr=self.wr, h=self.h, pre=self.pre if self.act == 2 else None, g=self.g,
-                 din=self.din, dout=self.dout, act=self.act, keep=None, scale=1.0, p=self.p, q=self.q, dwl=self.dwl, dwr=self.dwr,
-                 dbias=self.dbias, ws=self.ws)
-        a.update(kw)
-        self.lib.call("gcr_sage_bwd_f32", a["n"], a["x"], a["z"], a["wl"], a["wr"], a["h"], a["pre"], a["g"], a["din"], a["dout"],
-                      a["act"], a["keep"], a["scale"], a["p"], a["q"], a["dwl"], a["dwr"], a["dbias"], a["ws"], on=self.g)
+Raw = sr.Raw                # the arguments of the raw exports (tests/sage_rules.py), shared with test_sage_paths_gpu.py
 
 
 def test_contract_refusals():
