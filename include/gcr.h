@@ -759,15 +759,18 @@ int32_t gcr_edge_mask_exact_bits(int64_t nnz, int64_t n_keep, uint64_t seed, uin
  * it: no amsgrad, L2 weight_decay added to the gradient): g = grad_scale * (grad + grad2 + grad3) + weight_decay * p;
  * m += (1 - beta1) (g - m); v = beta2 v + (1 - beta2) g^2; p -= lr / (1 - beta1^step) * m / (sqrt(v / (1 - beta2^step)) + eps).
  * grad2 / grad3 are optional further gradient pieces of the same parameter (summed on the way in instead of by
- * separate element-wise adds).  Pointers 16-B aligned; step counts from 1.
+ * separate element-wise adds).  Pointers must be 4-B aligned (GCR_EINVAL otherwise); 16-B alignment of all of them is
+ * fast (16-B accesses), any other takes a one-float-per-thread route with the same arithmetic.  Step counts from 1.
+ * The betas are doubles: 1 - beta is rounded to float32 once, as torch rounds its lerp weight and its `1 - beta2`
+ * (1.0f - 0.999f is 1.3e-5 off 0.001, which exp_avg_sq would carry; 1.0f - 0.9f is 2.4e-7 off 0.1, which exp_avg would).
  */
 int32_t gcr_adam_step_f32(float* param, const float* grad, const float* grad2, const float* grad3, float* exp_avg,
-                          float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float* exp_avg_sq, int64_t n, float lr, double beta1, double beta2, float eps,
                           float weight_decay, int64_t step, float grad_scale, void* stream);
 /* The same step with the step count read from device memory (*step_dev >= 1, incremented by the caller on the same
  * stream): a training step captured in a hipGraph replays with the current count instead of the captured one. */
 int32_t gcr_adam_step_dev_f32(float* param, const float* grad, const float* grad2, const float* grad3, float* exp_avg,
-                              float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps,
+                              float* exp_avg_sq, int64_t n, float lr, double beta1, double beta2, float eps,
                               float weight_decay, const int64_t* step_dev, float grad_scale, void* stream);
 
 /* out[r, c] = keep bit c ? x[r, c] : 0 — PyGCL's FeatureMasking / drop_feature (univariate/grace.py:261-278): whole
@@ -789,7 +792,8 @@ int32_t gcr_spgemm_expand_f32(const int64_t* a_rowptr, const int32_t* a_col, con
 
 /* One torch.optim.SGD step with momentum (directau.py:214: dampening 0, no nesterov): g = grad + weight_decay * p;
  * buf = first_step ? g : momentum * buf + g; p -= lr * buf.  One streaming pass (reads p, g, buf; writes p, buf).
- * momentum_buf may be NULL when momentum == 0 (plain SGD).  Pointers 16-B aligned. */
+ * momentum_buf may be NULL when momentum == 0 (plain SGD).  Pointers must be 4-B aligned (GCR_EINVAL otherwise); 16-B
+ * alignment of all of them is fast, any other takes a one-float-per-thread route with the same arithmetic. */
 int32_t gcr_sgd_momentum_step_f32(float* param, const float* grad, float* momentum_buf, int64_t n, float lr,
                                   float momentum, float weight_decay, int32_t first_step, void* stream);
 

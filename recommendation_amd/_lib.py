@@ -125,9 +125,9 @@ SIGNATURES = {
     "gcr_csr_row_norm_f32": (c_int32, [_P, _P, _P, c_int64, _P, _P, _P]),
     "gcr_edge_mask_exact_workspace_bytes": (c_int64, [c_int64]),
     "gcr_edge_mask_exact_bits": (c_int32, [c_int64, c_int64, c_uint64, _P, _P, _P]),
-    "gcr_adam_step_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, c_int64,
+    "gcr_adam_step_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_float, c_double, c_double, c_float, c_float, c_int64,
                                     c_float, _P]),
-    "gcr_adam_step_dev_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float, _P,
+    "gcr_adam_step_dev_f32": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_float, c_double, c_double, c_float, c_float, _P,
                                         c_float, _P]),
     "gcr_sgd_momentum_step_f32": (c_int32, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_int32, _P]),
     "gcr_directau_workspace_bytes": (c_int64, [c_int64, c_int32]),

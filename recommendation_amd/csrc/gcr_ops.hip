@@ -13,14 +13,15 @@ namespace {
 __global__ __launch_bounds__(256) void adam_step_kernel(float4* __restrict__ p, const float4* __restrict__ g1,
                                                         const float4* __restrict__ g2, const float4* __restrict__ g3,
                                                         float4* __restrict__ m, float4* __restrict__ v, int64_t n4,
-                                                        int tail, float lr_over_bc1, float beta1, float beta2, float eps,
+                                                        int tail, float lr_over_bc1, double beta1d, double beta2d, float eps,
                                                         float inv_sqrt_bc2, float weight_decay, float grad_scale,
                                                         const int64_t* __restrict__ step_dev, float lr) {
-  const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2;
+  // 1 - beta is rounded once, from the double, as torch rounds its `value=1 - beta2`: 1.0f - 0.999f is 1.3e-5 off 0.001
+  const float beta2 = (float)beta2d, omb1 = (float)(1.0 - beta1d), omb2 = (float)(1.0 - beta2d);
   if (step_dev != nullptr) {      // step count kept on the device (a captured graph replays with the CURRENT count)
     const double st = (double)*step_dev;
-    lr_over_bc1 = (float)((double)lr / (1.0 - pow((double)beta1, st)));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, st)));
+    lr_over_bc1 = (float)((double)lr / (1.0 - pow(beta1d, st)));
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(beta2d, st)));
   }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4 pp = p[i], gg = g1[i], mm = m[i], vv = v[i];
@@ -63,6 +64,34 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float4* __restrict__ p, 
   }
 }
 
+// The same step one float per thread: the route of a pointer that is 4-B but not 16-B aligned (the item block of a stacked
+// [U + I, d] table whose U * d is no multiple of four).  Same operations in the same order as adam_step_kernel's.
+__global__ __launch_bounds__(256) void adam_step_scalar_kernel(float* __restrict__ p, const float* __restrict__ g1,
+                                                               const float* __restrict__ g2, const float* __restrict__ g3,
+                                                               float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                               float lr_over_bc1, double beta1d, double beta2d, float eps,
+                                                               float inv_sqrt_bc2, float weight_decay, float grad_scale,
+                                                               const int64_t* __restrict__ step_dev, float lr) {
+  // 1 - beta is rounded once, from the double, as torch rounds its `value=1 - beta2`: 1.0f - 0.999f is 1.3e-5 off 0.001
+  const float beta2 = (float)beta2d, omb1 = (float)(1.0 - beta1d), omb2 = (float)(1.0 - beta2d);
+  if (step_dev != nullptr) {
+    const double st = (double)*step_dev;
+    lr_over_bc1 = (float)((double)lr / (1.0 - pow(beta1d, st)));
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(beta2d, st)));
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float g = g1[i];
+    if (g2 != nullptr) g += g2[i];
+    if (g3 != nullptr) g += g3[i];
+    g = fmaf(weight_decay, p[i], g * grad_scale);
+    const float mm = fmaf(omb1, g - m[i], m[i]);
+    const float vv = fmaf(beta2, v[i], omb2 * g * g);
+    p[i] -= lr_over_bc1 * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
+    m[i] = mm;
+    v[i] = vv;
+  }
+}
+
 // torch.optim.SGD(momentum, dampening = 0, nesterov = False): g = grad + wd p; buf = first ? g : mu buf + g; p -= lr buf
 __device__ __forceinline__ void sgd_point(float& p, float g, float* buf, float lr, float mu, float wd, bool first) {
   g = fmaf(wd, p, g);
@@ -98,6 +127,19 @@ __global__ __launch_bounds__(256) void sgd_momentum_step_kernel(float4* __restri
     sgd_point(pv, reinterpret_cast<const float*>(g)[i], bs != nullptr ? &bv : nullptr, lr, mu, wd, first);
     ps[i] = pv;
     if (bs != nullptr) bs[i] = bv;
+  }
+}
+
+// one float per thread: the route of a pointer that is 4-B but not 16-B aligned (see adam_step_scalar_kernel)
+__global__ __launch_bounds__(256) void sgd_momentum_step_scalar_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                       float* __restrict__ buf, int64_t n, float lr, float mu,
+                                                                       float wd, int first) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float pv = p[i];
+    float bv = (buf != nullptr && !first) ? buf[i] : 0.f;
+    sgd_point(pv, g[i], buf != nullptr ? &bv : nullptr, lr, mu, wd, first);
+    p[i] = pv;
+    if (buf != nullptr) buf[i] = bv;
   }
 }
 
@@ -175,18 +217,27 @@ int ops_grid(int64_t n, int per_block) {
   return (int)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
 }
 
+// the low `bits` address bits of every pointer, OR-ed (a NULL contributes none)
+template <class... P>
+uintptr_t low_bits(int bits, P... ptr) { return (((uintptr_t)ptr) | ...) & (((uintptr_t)1 << bits) - 1); }
+
 }  // namespace
 
 extern "C" int32_t gcr_adam_step_f32(float* param, const float* grad, const float* grad2, const float* grad3,
-                                     float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                                     float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1, double beta2,
                                      float eps, float weight_decay, int64_t step, float grad_scale, void* stream) {
   GCR_CHECK_ARG(n >= 0 && step >= 1);
-  GCR_CHECK_ARG(lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f);
+  GCR_CHECK_ARG(lr >= 0.f && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f);
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(param && grad && exp_avg && exp_avg_sq);
-  GCR_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)grad2 | (uintptr_t)grad3 | (uintptr_t)exp_avg |
-                  (uintptr_t)exp_avg_sq) & 15) == 0);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  GCR_CHECK_ARG(low_bits(2, param, grad, grad2, grad3, exp_avg, exp_avg_sq) == 0);
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  if (low_bits(4, param, grad, grad2, grad3, exp_avg, exp_avg_sq) != 0) {
+    hipLaunchKernelGGL(adam_step_scalar_kernel, dim3(ops_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, grad2,
+                       grad3, exp_avg, exp_avg_sq, n, (float)((double)lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)),
+                       weight_decay, grad_scale, (const int64_t*)nullptr, lr);
+    return GCR_LAUNCH_STATUS();
+  }
   hipLaunchKernelGGL(adam_step_kernel, dim3(ops_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, (float4*)param,
                      (const float4*)grad, (const float4*)grad2, (const float4*)grad3, (float4*)exp_avg, (float4*)exp_avg_sq,
                      n / 4, (int)(n & 3), (float)((double)lr / bc1), beta1, beta2, eps, (float)(1.0 / sqrt(bc2)), weight_decay, grad_scale,
@@ -195,15 +246,19 @@ extern "C" int32_t gcr_adam_step_f32(float* param, const float* grad, const floa
 }
 
 extern "C" int32_t gcr_adam_step_dev_f32(float* param, const float* grad, const float* grad2, const float* grad3,
-                                         float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                                         float* exp_avg, float* exp_avg_sq, int64_t n, float lr, double beta1, double beta2,
                                          float eps, float weight_decay, const int64_t* step_dev, float grad_scale,
                                          void* stream) {
   GCR_CHECK_ARG(n >= 0 && step_dev != nullptr);
-  GCR_CHECK_ARG(lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f);
+  GCR_CHECK_ARG(lr >= 0.f && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f);
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(param && grad && exp_avg && exp_avg_sq);
-  GCR_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)grad2 | (uintptr_t)grad3 | (uintptr_t)exp_avg |
-                  (uintptr_t)exp_avg_sq) & 15) == 0);
+  GCR_CHECK_ARG(low_bits(2, param, grad, grad2, grad3, exp_avg, exp_avg_sq) == 0);
+  if (low_bits(4, param, grad, grad2, grad3, exp_avg, exp_avg_sq) != 0) {
+    hipLaunchKernelGGL(adam_step_scalar_kernel, dim3(ops_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, grad2,
+                       grad3, exp_avg, exp_avg_sq, n, 0.f, beta1, beta2, eps, 0.f, weight_decay, grad_scale, step_dev, lr);
+    return GCR_LAUNCH_STATUS();
+  }
   hipLaunchKernelGGL(adam_step_kernel, dim3(ops_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, (float4*)param,
                      (const float4*)grad, (const float4*)grad2, (const float4*)grad3, (float4*)exp_avg, (float4*)exp_avg_sq,
                      n / 4, (int)(n & 3), 0.f, beta1, beta2, eps, 0.f, weight_decay, grad_scale, step_dev, lr);
@@ -215,7 +270,12 @@ extern "C" int32_t gcr_sgd_momentum_step_f32(float* param, const float* grad, fl
   GCR_CHECK_ARG(n >= 0 && lr >= 0.f && momentum >= 0.f && weight_decay >= 0.f);
   if (n == 0) return GCR_OK;
   GCR_CHECK_ARG(param && grad && (momentum_buf != nullptr || momentum == 0.f));
-  GCR_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)momentum_buf) & 15) == 0);
+  GCR_CHECK_ARG(low_bits(2, param, grad, momentum_buf) == 0);
+  if (low_bits(4, param, grad, momentum_buf) != 0) {
+    hipLaunchKernelGGL(sgd_momentum_step_scalar_kernel, dim3(ops_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, param,
+                       grad, momentum_buf, n, lr, momentum, weight_decay, (int)(first_step != 0));
+    return GCR_LAUNCH_STATUS();
+  }
   hipLaunchKernelGGL(sgd_momentum_step_kernel, dim3(ops_grid(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream,
                      (float4*)param, (const float4*)grad, (float4*)momentum_buf, n / 4, (int)(n & 3), lr, momentum,
                      weight_decay, (int)(first_step != 0));
