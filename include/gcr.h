@@ -1074,6 +1074,39 @@ int32_t gcr_sage_bwd_f32(int64_t n, const float* x, const float* z, const float*
                          const uint32_t* keep_bits, float keep_scale, float* p, float* q, float* dwl, float* dwr,
                          float* dbias, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * BGRL: one GINConv layer (Linear, ReLU, Linear) with the ReLU and dropout behind it, fused (csrc/gcr_gin.hip).
+ * --------------------------------------------------------------------------------------------- */
+/*
+ * replaces  bgrl_g2l.py:500-505, 527-529  (conv(z, edge_index) of torch_geometric's GINConv over
+ *           Sequential(Linear, ReLU, Linear); self.activation = ReLU; F.dropout) behind the sum aggregation, which the
+ *           caller runs as the SpMM:  s = (1 + eps) x + sum_j x_j  [n, din];
+ *   t = relu(s w1^T + b1),   h = keep * keep_scale * relu(t w2^T + b2),
+ *   w1 [dout, din], b1 [dout], w2 [dout, dout], b2 [dout], h [n, dout], all row-major float32.  t [n, dout] lives in LDS
+ *   only and is never written to memory.
+ *   keep_bits: packed bitmap, bit r * dout + c (an int64 index; bit b of word b / 32 is 1 << (b % 32)) keeps element
+ *   (r, c); NULL keeps everything.  keep_scale > 0 multiplies every kept element (1 / (1 - p); 1 without dropout).  The
+ *   kernel draws nothing and stores no mask.
+ * gcr_gin_bwd_f32: t is recomputed from s by the forward's own loop (the same bits, so the inner ReLU's mask is the
+ *   forward's); with m = g * keep_scale where h > 0 (the saved h: a dropped element is 0) and u = (m w2) where t > 0,
+ *   dw2 = m^T t,  db2 = column sums of m,  dw1 = u^T s,  db1 = column sums of u,
+ *   ds = u w1  [n, din] (the caller finishes dx = (1 + eps) ds + A^T ds with the SpMM); ds == NULL skips it (the first
+ *   layer's input is a fixed table).
+ * No atomics; the per-workgroup partials are folded in workgroup order: every output is bitwise reproducible.
+ * Supported (gcr_gin_supported): din, dout each in {32, 64, 128}.  An unsupported pair, n < 0, a NULL pointer (keep_bits
+ * and ds excepted), a pointer that is not 16-B aligned, h == s, ds == s, ds == h or ds == g: GCR_EINVAL.  n == 0 launches
+ * nothing (the backward zeroes dw1, db1, dw2 and db2).  workspace: gcr_gin_workspace_bytes(n, din, dout) bytes, 16-B
+ * aligned, for either call.  Two launches forward, three backward.
+ */
+int32_t gcr_gin_supported(int32_t din, int32_t dout);
+int64_t gcr_gin_workspace_bytes(int64_t n, int32_t din, int32_t dout);
+int32_t gcr_gin_fwd_f32(int64_t n, const float* s, const float* w1, const float* b1, const float* w2, const float* b2,
+                        int32_t din, int32_t dout, const uint32_t* keep_bits, float keep_scale, float* h, void* workspace,
+                        void* stream);
+int32_t gcr_gin_bwd_f32(int64_t n, const float* s, const float* w1, const float* b1, const float* w2, const float* h,
+                        const float* g, int32_t din, int32_t dout, float keep_scale, float* ds, float* dw1, float* db1,
+                        float* dw2, float* db2, void* workspace, void* stream);
+
 /* out[e] = value of (row_of[e], col[e]) in the CSR m (columns ascending inside a row; m_val NULL = ones), 0 when it
  * is not stored: the sparse element-wise products `.multiply(U.T)` / `.multiply(B)` of mhcn.py:340-368. */
 int32_t gcr_csr_lookup_f32(const int32_t* row_of, const int32_t* col, int64_t nnz, const int64_t* m_rowptr,

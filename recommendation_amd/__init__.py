@@ -8,12 +8,13 @@ from .graph import CsrGraph, SpmmPlan
 from . import functional
 
 __all__ = ["CsrGraph", "SpmmPlan", "functional", "_lib", "DiffNetEncoder", "DiffNetModel", "GATConv", "GATRec",
-           "GATRecModel", "SAGEConv", "GraphSAGE", "GraphSAGEModel"]
+           "GATRecModel", "SAGEConv", "GraphSAGE", "GraphSAGEModel", "GINConv", "GConv", "Encoder", "BootstrapLatent",
+           "BootstrapContrast", "BGRLModel"]
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    """The DiffNet, GAT and GraphSAGE classes, imported on first use (their modules pull in the model base, the sampler
+    """The DiffNet, GAT, GraphSAGE and BGRL classes, imported on first use (their modules pull in the model base, the sampler
     and the optimiser)."""
     if name in ("DiffNetEncoder", "DiffNetModel"):
         from . import diffnet
@@ -24,4 +25,7 @@ def __getattr__(name):
     if name in ("SAGEConv", "GraphSAGE", "GraphSAGEModel"):
         from . import graphsage
         return getattr(graphsage, name)
+    if name in ("GINConv", "GConv", "Encoder", "BootstrapLatent", "BootstrapContrast", "BGRLModel"):
+        from . import bgrl
+        return getattr(bgrl, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -168,6 +168,10 @@ SIGNATURES = {
     "gcr_sage_fwd_f32": (c_int32, [c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float, _P, _P, _P, _P]),
     "gcr_sage_bwd_f32": (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float, _P, _P, _P,
                                    _P, _P, _P, _P]),
+    "gcr_gin_supported": (c_int32, [c_int32, c_int32]),
+    "gcr_gin_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "gcr_gin_fwd_f32": (c_int32, [c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, _P, c_float, _P, _P, _P]),
+    "gcr_gin_bwd_f32": (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_mask_columns_f32":(c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
     "gcr_spgemm_expand_f32": (c_int32, [_P, _P, _P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gcr_csr_lookup_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, _P, _P]),
@@ -190,7 +194,7 @@ _exports = {}   # name -> (converter without a stream, converter with one, is th
 INT32_ANSWERS = ("gcr_version", "gcr_infonce_engine", "gcr_infonce_fwd_o_supported", "gcr_channel_mix_supported",
                  "gcr_mim_supported", "gcr_bce_fwd_o_supported", "gcr_rank_fused_supported", "gcr_tri_supported",
                  "gcr_buir_supported", "gcr_bt_supported", "gcr_diffuse_supported", "gcr_gat_supported",
-                 "gcr_sage_supported")
+                 "gcr_sage_supported", "gcr_gin_supported")
 
 
 class GcrError(RuntimeError):

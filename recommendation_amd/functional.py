@@ -2081,6 +2081,155 @@ def sage_layer(graph, x, wl, wr, bias=None, act="relu", keep_bits=None, p=0.0):
 
 
 # ---------------------------------------------------------------------------------------------
+# BGRL: one GINConv layer (Linear, ReLU, Linear) with the ReLU and dropout behind it (bgrl_g2l.py:500-505, 525-529)
+# ---------------------------------------------------------------------------------------------
+# (din, dout) pairs that `gin_layer` hands to `gin_layer_composed` although the kernels serve them: a pair belongs here
+# when scripts/perf_gin_layer.py does not show the fused layer's p10 - p90 band disjoint from, and below, the composed
+# one's.  Measured (EXPERIMENTS.md, "BGRL: the fused GINConv layer"; 1.1M nodes, 20M entries, forward + backward): the bands
+# are disjoint in the fused layer's favour at all nine pairs, from 1.51 against 5.32 ms at (32, 32) to 6.44 against 10.87 ms
+# at (128, 128), so the set is empty.
+GIN_COMPOSED_PAIRS = frozenset()
+
+
+def gin_supported(din, dout):
+    """True when the fused kernels (gcr_gin_*) serve a layer [n, din] -> [n, dout]: each width 32, 64 or 128."""
+    return bool(_lib.call("gcr_gin_supported", int(din), int(dout)))
+
+
+def gin_sum_graph(edge_index, num_nodes, device):
+    """The [n, n] operator of torch_geometric's sum aggregation for `edge_index` int64 [2, E] (edge j -> i =
+    (edge_index[0], edge_index[1])): CSR WITHOUT values, rows = edge_index[1], cols = edge_index[0], a row's entries in
+    edge_index order, duplicates kept (a duplicated edge counts twice), self loops kept (GINConv adds or removes none).
+    The transpose is built with it (`graph.t`, which the backward's dx walks), and so are `graph.edge_of_entry` and
+    `graph.t.edge_of_entry` (int64 [E] on the graph's device: entry e of the CSR is edge edge_of_entry[e]), with which
+    `gin_edge_keep_bits` brings a per-edge mask in edge_index order into both entry orders."""
+    import numpy as np
+    ei = torch.as_tensor(edge_index).detach().to(torch.int64).cpu().numpy()
+    graph = CsrGraph.from_coo(ei[1], ei[0], None, num_nodes, num_nodes, device, want_perm=True)
+    gt = graph.t
+    perm = graph.coo_perm.to(graph.device)
+    graph.edge_of_entry = perm
+    perm_t = getattr(gt, "perm_from_transpose", None)          # the device build keeps it; the host build sorts stably by column
+    if perm_t is None:
+        perm_t = torch.from_numpy(np.argsort(graph.col.cpu().numpy(), kind="stable"))
+    gt.edge_of_entry = perm[perm_t.to(graph.device)]
+    return graph
+
+
+def gin_edge_keep_bits(graph, keep_edges):
+    """(keep_bits, keep_bits_t) of `gin_layer` for a per-edge keep mask, bool [E] in the order of the edge_index that
+    `gin_sum_graph` was built from (dropout_adj's `rand >= p` mask: EdgeRemoving, bgrl_g2l.py:448-456)."""
+    keep_edges = torch.as_tensor(keep_edges).reshape(-1).to(graph.device)
+    return tuple(pack_bits(keep_edges[g.edge_of_entry]) for g in (graph, graph.t))
+
+
+def _gin_sum_torch(graph, x, edge_keep_bits):
+    """sum_j x_j over the (kept) entries where libgcr has no kernel (a CPU tensor, or a dtype other than float32)."""
+    rowptr = graph.rowptr.to(x.device)
+    rows = torch.repeat_interleave(torch.arange(graph.n_rows, device=x.device), rowptr[1:] - rowptr[:-1])
+    msg = x[graph.col.to(device=x.device, dtype=torch.int64)]
+    if edge_keep_bits is not None:
+        msg = msg * unpack_bits(edge_keep_bits.to(x.device), graph.nnz).to(x.dtype)[:, None]
+    return torch.zeros_like(x).index_add_(0, rows, msg)
+
+
+def _gin_args(graph, x, w1, b1, w2, b2, keep_bits, p, edge_keep_bits):
+    if x.dim() != 2 or w1.dim() != 2 or w1.shape[1] != x.shape[1] or tuple(w2.shape) != (w1.shape[0], w1.shape[0]):
+        raise ValueError("x must be [n, din], w1 [dout, din] and w2 [dout, dout]")
+    if tuple(b1.shape) != (w1.shape[0],) or tuple(b2.shape) != (w1.shape[0],):
+        raise ValueError("b1 and b2 must be [dout]")
+    if graph.n_rows != x.shape[0] or graph.n_cols != x.shape[0]:
+        raise ValueError("the graph must be [n, n] for x [n, din]")
+    if not 0.0 <= p < 1.0:
+        raise ValueError("p must be in [0, 1)")
+    if keep_bits is not None and (keep_bits.dtype != torch.int32 or keep_bits.numel() < (x.shape[0] * w1.shape[0] + 31) // 32):
+        raise ValueError("keep_bits must be int32 words covering n * dout bits")
+    if edge_keep_bits is not None and (edge_keep_bits.dtype != torch.int32 or edge_keep_bits.numel() * 32 < graph.nnz):
+        raise ValueError("edge_keep_bits must be int32 words covering the graph's entries")
+
+
+def gin_layer_composed(graph, x, w1, b1, w2, b2, eps=0.0, keep_bits=None, p=0.0, edge_keep_bits=None, edge_keep_bits_t=None):
+    """`gin_layer` as torch_geometric and bgrl_g2l.py:525-529 compose it, statement by statement in torch: the sum
+    aggregation over the kept edges (through `spmm` for float32 on the device, an index_add otherwise), out + (1 + eps) x,
+    Linear, ReLU, Linear, the ReLU, the dropout.  Any dtype, CPU tensors, any widths."""
+    _gin_args(graph, x, w1, b1, w2, b2, keep_bits, p, edge_keep_bits)
+    if x.is_cuda and x.dtype == torch.float32 and x.shape[0] > 0:
+        out = spmm(graph, x, keep_bits=edge_keep_bits, keep_bits_t=edge_keep_bits_t)
+    else:
+        out = _gin_sum_torch(graph, x, edge_keep_bits)
+    out = out + (1.0 + eps) * x
+    out = torch.nn.functional.linear(out, w1, b1)
+    out = torch.relu(out)
+    out = torch.nn.functional.linear(out, w2, b2)
+    out = torch.relu(out)
+    if keep_bits is not None:
+        keep = unpack_bits(keep_bits.to(out.device), out.numel()).view_as(out)
+        out = out * keep.to(out.dtype) * (1.0 / (1.0 - p))
+    return out
+
+
+class _GinLayer(torch.autograd.Function):
+    """gcr_gin_fwd_f32 / gcr_gin_bwd_f32: saves s = (1 + eps) x + A x, h and the weights (w1, b1, w2: the backward
+    recomputes the hidden activation from them), nothing else; the backward finishes dx = (1 + eps) ds + A^T ds with the
+    SpMM on A^T."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, graph, eps, keep_bits, keep_scale, edge_keep_bits, edge_keep_bits_t):
+        x, w1, b1, w2, b2 = (t.contiguous() for t in (x, w1, b1, w2, b2))
+        n, din = x.shape
+        dout = w1.shape[0]
+        root = x if eps == 0.0 else x * (1.0 + eps)
+        s = spmm_into(graph, x, acc_in=root, acc_out=torch.empty_like(x), keep_bits=edge_keep_bits)
+        h = torch.empty(n, dout, dtype=x.dtype, device=x.device)
+        ws = _lib.workspace("gcr_gin_workspace_bytes", n, din, dout, device=x.device)
+        _lib.call("gcr_gin_fwd_f32", n, s, w1, b1, w2, b2, din, dout, keep_bits, keep_scale, h, ws, on=x)
+        ctx.save_for_backward(s, h, w1, b1, w2)
+        ctx.graph, ctx.hp, ctx.edge_keep_bits_t = graph, (eps, keep_scale), edge_keep_bits_t
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        s, h, w1, b1, w2 = ctx.saved_tensors
+        eps, keep_scale = ctx.hp
+        n, din = s.shape
+        dout = w1.shape[0]
+        want_dx = ctx.needs_input_grad[0]
+        ds = torch.empty_like(s) if want_dx else None
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        db1, db2 = torch.empty_like(b1), torch.empty_like(b1)
+        ws = _lib.workspace("gcr_gin_workspace_bytes", n, din, dout, device=s.device)
+        _lib.call("gcr_gin_bwd_f32", n, s, w1, b1, w2, h, g.contiguous(), din, dout, keep_scale, ds, dw1, db1, dw2, db2, ws,
+                  on=s)
+        dx = None
+        if want_dx:
+            root = ds if eps == 0.0 else ds * (1.0 + eps)
+            dx = spmm_into(ctx.graph.t, ds, acc_in=root, acc_out=torch.empty_like(ds), keep_bits=ctx.edge_keep_bits_t)
+        return dx, dw1, db1, dw2, db2, None, None, None, None, None, None
+
+
+def gin_layer(graph, x, w1, b1, w2, b2, eps=0.0, keep_bits=None, p=0.0, edge_keep_bits=None, edge_keep_bits_t=None):
+    """One layer of BGRL's GConv.forward (bgrl_g2l.py:525-529) behind one autograd node:
+    keep / (1 - p) * relu(relu(s w1^T + b1) w2^T + b2),  s = (1 + eps) x + sum over the kept edges into i of x_j,
+    for `graph` = `gin_sum_graph(...)` [n, n], x [n, din], w1 / b1 (nn.0) [dout, din] / [dout], w2 / b2 (nn.2)
+    [dout, dout] / [dout].  keep_bits: the dropout's keep bitmap, bit r * dout + c (`pack_bits` /
+    `edge_mask_bits(n * dout, p, seed, device)` order); None = no dropout, whatever p.  edge_keep_bits / edge_keep_bits_t:
+    EdgeRemoving's mask in the entry order of `graph` and of `graph.t` (`gin_edge_keep_bits`); the second is needed when x
+    takes a gradient.  Differentiable in x and the four parameters; s runs as the tuned SpMM with x as its `acc_in`; s, the
+    output and the weights are kept, where the composition keeps the aggregate, s, both pre-activations, the hidden
+    activation, the output before the dropout and a mask.  Bitwise reproducible.  Widths outside `gin_supported`, pairs in
+    GIN_COMPOSED_PAIRS, other dtypes than float32, CPU tensors and n = 0 run `gin_layer_composed`."""
+    _gin_args(graph, x, w1, b1, w2, b2, keep_bits, p, edge_keep_bits)
+    pair = (x.shape[1], w1.shape[0])
+    if not (x.is_cuda and x.dtype == torch.float32 and x.shape[0] > 0 and gin_supported(*pair) and pair not in GIN_COMPOSED_PAIRS):
+        return gin_layer_composed(graph, x, w1, b1, w2, b2, eps, keep_bits, p, edge_keep_bits, edge_keep_bits_t)
+    if edge_keep_bits is not None and edge_keep_bits_t is None:
+        _need_mask_t(x)
+    keep_bits = None if keep_bits is None else keep_bits.contiguous()
+    return _GinLayer.apply(x, w1, b1, w2, b2, graph, float(eps), keep_bits, 1.0 / (1.0 - p) if keep_bits is not None else 1.0,
+                           edge_keep_bits, edge_keep_bits_t)
+
+
+# ---------------------------------------------------------------------------------------------
 # Barlow Twins: redundancy reduction over two full-batch views (univariate/gbt.py:203-228, 386-395)
 # ---------------------------------------------------------------------------------------------
 BT_WIDTHS = (32, 64, 96, 128, 256)
